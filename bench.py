@@ -5,11 +5,20 @@
     python bench.py --gpus N --steps K --warmup W          (N = 1: plain python; N > 1: either under torchrun - RANK / WORLD_SIZE in
                                                             the environment - or plain: it then starts its own N ranks, self_launch)
 
+    python bench.py ... --full                              (also every other leg, below)
+    python bench.py ... --dump-outputs DIR                  (also DIR/<name>.npy: what the last timed step returned)
+
 One STEP = one pass of the hot path over one batch of synthetic input = one `TCGNN.forward` call
 (fp16 staging pass + the SpMM kernel) on the Reddit-shaped graph at D = 64, inputs resident in HBM.
-`value` = traversed edges per second of the whole job in GTEPS (E * K * N / t).  The other
+`value` = traversed edges per second of the whole job in GTEPS (E * K * N / t); `ms_per_step` = t / K.
+A plain run sets up, warms up, times the K steps and prints the line.  With --full the other
 quantities the metric names are measured in the same run and reported under `extra`
-(SDDMM and SpMM-AGNN GTEPS, GCN / AGNN ms per epoch, host and device SGT times).
+(SDDMM and SpMM-AGNN GTEPS, GCN / AGNN ms per epoch, host and device SGT times), with `datasets`,
+the reference's artifact shapes and `cpu_baseline` next to them.
+
+--dump-outputs DIR: Y = A X of the last timed step as DIR/spmm_out.npy (N > 1: each rank's rows as
+spmm_out_rank<r>.npy), float32; beyond 64 MB in all, a fixed seeded sample of its rows.  The graph and X
+are seeded (--seed), so the same arguments give the same inputs on every run.
 
 workload (config.workload): BASELINE.json configs[2] "Reddit GCN 2-layer hidden=64" -
 N = 232 965 nodes, nnz = 114 615 892, seeded synthetic symmetric graph (no dataset
@@ -18,7 +27,7 @@ or network on the box), features randn, labels ones (dataset.py:115,122).
 N > 1 (weak scaling): the papers100M pattern of configs[4] in miniature - the graph has N x 232 965
 nodes, rank p owns the rows of its 232 965 nodes (114.6 M nnz with columns over ALL N x 232 965
 nodes), a step = all-gather of the X row blocks over RCCL + the local SpMM (the replicated-X variant, no collective in the
-step, is timed next to it and reported under `extra`).  Per-GPU work is fixed.
+step, is timed next to it with --full and reported under `extra`).  Per-GPU work is fixed.
 
 roofline: the SpMM kernel is HBM-bound by its algorithmic bytes B = 4(N+1) + 4E + 8ND
 (SURVEY.md 8d); `achieved` = B / (mean kernel time from HIP events on the launch stream, recorded
@@ -31,7 +40,7 @@ sources this process runs (tcgnn_capi.build_id(), tools/collect_profiles.py) - e
 `datasets` repeats those figures per dataset: the headline graph, its R-MAT and community (SBM) variants, and the ogbn-products
 shape at D = 128 (BASELINE.json configs[3]).
 
-cpu_baseline: the row-parallel CSR gather-add (the DGL-CPU-style aggregation) of oracle/cpu_baseline.c, built on the box with
+cpu_baseline (--full): the row-parallel CSR gather-add (the DGL-CPU-style aggregation) of oracle/cpu_baseline.c, built on the box with
 -march=native, and torch.sparse.mm next to it, on the host cores, same graph and D, rank 0, N = 1 only.
 """
 import argparse
@@ -72,9 +81,16 @@ def parse():
                         "calibrated to real Reddit's TC-block count (13.63 M 16x8 blocks against 13.57 M, /root/reference/logs/reduce_blocks.csv:18); "
                         "r01-r04 reported the uniform graph, whose figures stay in `summary` (uniform_*)")
     p.add_argument("--scale", type=float, default=1.0, help="shrink the graph (debug only; the reported config is scale 1)")
-    p.add_argument("--epochs", type=int, default=10, help="timed epochs of the GCN / AGNN legs")
-    p.add_argument("--no-extra", action="store_true", help="skip SDDMM / epoch / CPU legs (profiling runs)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--epochs", type=int, default=10, help="timed epochs of the GCN / AGNN legs (--full)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline steps, every other leg: host / device SGT timings, SDDMM, edge-valued SpMM, fused AGNN pair, "
+                        "other widths, the skewed graph, GCN / AGNN epochs, the per-dataset list, the reference's artifact shapes and the "
+                        "CPU baseline (N = 1); the exchange variants, the sharded GCN epoch and strong scaling (N > 1)")
+    p.add_argument("--no-extra", action="store_true", help="with --full: skip SDDMM / epoch / dataset legs (profiling runs)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step returned as DIR/<name>.npy (float32, at most 64 MB in all: a "
+                        "fixed, seeded row sample of a larger output)")
     p.add_argument("--exchange", choices=["auto", "always", "never"], default="always",
                    help="N > 1: all-gather X inside every step (always: the sharded-GCN step - the SpMM input is the previous layer's "
                         "row-sharded output, so a step without the gather is not the workload), replicate X and time the local SpMM "
@@ -87,7 +103,12 @@ def parse():
     p.add_argument("--shard-files", default=None,
                    help="--plan-only: template of the shard files written by tools/convert_dataset.py --shards (\"g.rank{rank}of{world}.npz\"): rows and "
                         "edges per rank are read from them instead of assumed even")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 LEG_SETTLE_S = 0.06   # untimed calls in front of every secondary kernel leg (timed_leg)
@@ -121,6 +142,36 @@ def sync_time(fn, steps, warmup, barrier):
         fn()
     torch.cuda.synchronize(); barrier()
     return time.perf_counter() - t0
+
+
+def time_steps(fn, steps, barrier):
+    """The K timed steps of the headline, as sync_time times them: -> (seconds, what the last step returned).  Only the last
+    step's result is kept, so every earlier step allocates and frees its output exactly as an untimed call does."""
+    barrier(); torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps - 1):
+        fn()
+    last = fn()
+    torch.cuda.synchronize(); barrier()
+    return time.perf_counter() - t0, last
+
+
+DUMP_LIMIT = 64 * 10 ** 6   # bytes of --dump-outputs arrays in all
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT):
+    """--dump-outputs: {name: device tensor} -> dirname/<name>.npy as float32.  An array whose rows do not fit its share of
+    `limit` is cut to a fixed row sample (numpy default_rng(0), sorted row ids), the same on every run of the same shape."""
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // max(1, len(arrays)) - 4096     # (room for the .npy header)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.dim() >= 1 and t.numel() * 4 > share:
+            row_bytes = 4 * max(1, t.numel() // max(1, t.shape[0]))
+            k = max(1, share // row_bytes)
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=k, replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 def spmm_bytes(n, e, d):
@@ -331,27 +382,29 @@ def single_gpu(args):
     E = col_d.numel()
     nw = (n + 15) // 16
 
-    # ---- sparse-graph translation: host (as main_tcgnn.py:51 does) and device, timed once each
-    rp_h, col_h = rp_d.cpu(), col_d.cpu()
-    bp_h = torch.zeros(nw, dtype=torch.int32); e2c_h = torch.zeros(E, dtype=torch.int32); e2r_h = torch.zeros(E, dtype=torch.int32)
-    e2c_h.fill_(1); e2r_h.fill_(1)  # touch the pages before timing
-    devnull = os.open(os.devnull, os.O_WRONLY); saved = os.dup(1); sys.stdout.flush(); os.dup2(devnull, 1)
-    try:
-        t0 = time.perf_counter()
-        TCGNN.preprocess(col_h, rp_h, n, 16, 8, bp_h, e2c_h, e2r_h)
-        host_sgt_ms = (time.perf_counter() - t0) * 1e3
+    # ---- sparse-graph translation on the device: the metadata the steps read.  --full also times the host translation (as
+    #      main_tcgnn.py:51 does) and the device one, and checks that the two agree
+    if args.full:
+        rp_h, col_h = rp_d.cpu(), col_d.cpu()
+        bp_h = torch.zeros(nw, dtype=torch.int32); e2c_h = torch.zeros(E, dtype=torch.int32); e2r_h = torch.zeros(E, dtype=torch.int32)
+        e2c_h.fill_(1); e2r_h.fill_(1)  # touch the pages before timing
+    with quiet_stdout():
+        if args.full:
+            t0 = time.perf_counter()
+            TCGNN.preprocess(col_h, rp_h, n, 16, 8, bp_h, e2c_h, e2r_h)
+            host_sgt_ms = (time.perf_counter() - t0) * 1e3
         bp = torch.zeros(nw, dtype=torch.int32, device=dev); e2c = torch.zeros(E, dtype=torch.int32, device=dev); e2r = torch.zeros(E, dtype=torch.int32, device=dev)
         TCGNN.preprocess_gpu(col_d, rp_d, n, 16, 8, bp, e2c, e2r)  # warm (rocPRIM temp allocation)
-        dev_sgt_runs = []
-        for _ in range(3):   # (r06: the scratch comes from torch's caching allocator - tcgnn_preprocess_gpu_ws allocates nothing - so the MEDIAN of three is
-            #  reported and all three are recorded; r05 took the best of three because one run in a dozen read 95 ms against 5: ~10 hipMalloc / hipFree per call)
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            TCGNN.preprocess_gpu(col_d, rp_d, n, 16, 8, bp, e2c, e2r)
-            torch.cuda.synchronize(); dev_sgt_runs.append((time.perf_counter() - t0) * 1e3)
-        dev_sgt_ms = float(np.median(dev_sgt_runs))
-    finally:
-        sys.stdout.flush(); os.dup2(saved, 1); os.close(saved); os.close(devnull)
-    sgt_equal = bool(torch.equal(bp.cpu(), bp_h) and torch.equal(e2c.cpu(), e2c_h) and torch.equal(e2r.cpu(), e2r_h))
+        if args.full:
+            dev_sgt_runs = []
+            for _ in range(3):   # (r06: the scratch comes from torch's caching allocator - tcgnn_preprocess_gpu_ws allocates nothing - so the MEDIAN of three is
+                #  reported and all three are recorded; r05 took the best of three because one run in a dozen read 95 ms against 5: ~10 hipMalloc / hipFree per call)
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                TCGNN.preprocess_gpu(col_d, rp_d, n, 16, 8, bp, e2c, e2r)
+                torch.cuda.synchronize(); dev_sgt_runs.append((time.perf_counter() - t0) * 1e3)
+            dev_sgt_ms = float(np.median(dev_sgt_runs))
+    if args.full:
+        sgt_equal = bool(torch.equal(bp.cpu(), bp_h) and torch.equal(e2c.cpu(), e2c_h) and torch.equal(e2r.cpu(), e2r_h))
     meta = (rp_d, col_d, bp, e2c, e2r)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     info = TCGNN.plan_info(*meta)   # first sight of the five arrays: packs the tile stream (+ the cell stream of dense graphs)
@@ -367,7 +420,10 @@ def single_gpu(args):
     settle(step)
     for _ in range(args.warmup):
         step()
-    elapsed = sync_time(step, args.steps, 0, noop)
+    elapsed, last = time_steps(step, args.steps, noop)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"spmm_out": last[0]})   # Y = A X of the last timed step
+    del last
     kernel_ms_all = TCGNN.kernel_timing(*meta)
     kernel_ms = kernel_ms_all[-args.steps:]                                  # the K timed steps
     TCGNN.kernel_timing(*meta, max_calls=0)
@@ -402,9 +458,12 @@ def single_gpu(args):
                      "kernel_ms_mean_all_launches": round(float(np.mean(kernel_ms_all)), 4) if kernel_ms_all else None,
                      "kernel_launches_all": len(kernel_ms_all)},
     }
-    extra = {"graph_gen_s": round(gen_s, 2), "host_sgt_ms": round(host_sgt_ms, 1), "host_sgt_ns_per_edge": round(host_sgt_ms * 1e6 / E, 2),
-             "device_sgt_ms": round(dev_sgt_ms, 1), "device_sgt_ms_runs": [round(x, 1) for x in dev_sgt_runs], "device_sgt_equals_host_sgt": sgt_equal, "plan_create_ms": round(plan_ms, 1), "plan_bytes": info["plan_bytes"],
+    extra = {"graph_gen_s": round(gen_s, 2), "plan_create_ms": round(plan_ms, 1), "plan_bytes": info["plan_bytes"],
              "staging_plus_launch_ms_per_step": round(ms_per_step - k_mean, 4)}
+    if args.full:
+        extra.update({"host_sgt_ms": round(host_sgt_ms, 1), "host_sgt_ns_per_edge": round(host_sgt_ms * 1e6 / E, 2), "device_sgt_ms": round(dev_sgt_ms, 1),
+                      "device_sgt_ms_runs": [round(x, 1) for x in dev_sgt_runs], "device_sgt_equals_host_sgt": sgt_equal})
+    extras = args.full and not args.no_extra
 
     def timed_leg(meta_, E_, fn, bytes_, reps=20):
         # (r05: every leg settles like the headline step - ~60 ms of untimed calls.  Three warm-up calls left the 10-20 timed ones inside
@@ -484,7 +543,7 @@ def single_gpu(args):
         TCGNN.clear_plan_cache()
         return row
 
-    if not args.no_extra:
+    if extras:
         kernel_leg = lambda fn, bytes_, reps=20: timed_leg(meta, E, fn, bytes_, reps)
         att = torch.randn(1, E, device=dev, generator=g)
         extra["sddmm_d%d" % D] = kernel_leg(lambda: TCGNN.forward_ef(X, *meta), sddmm_bytes(n, E, D))
@@ -555,7 +614,7 @@ def single_gpu(args):
                  "N": n, "nnz": int(E), "D": D, "tc_blocks_16x8": info["tc_blocks"],
                  "spmm": {"kernel": kname, "kernel_ms": round(k_mean, 4), "gteps": round(gteps, 3), "hbm_frac": out["roofline"]["frac"],
                           **{k: out["roofline"][k] for k in ("traffic", "mfma_busy", "mfma_useful_frac", "mfma_useful_tflops", "mfma_peak_frac")}}}]
-    if not args.no_extra:
+    if extras:
         # (r06, VERDICT r05 item 7: the headline graph's row carries every operator with its PMC figures, not the SpMM alone - the legs
         #  were timed above, the counters come from the same profile file)
         wl0 = datasets[0]["workload"]
@@ -565,7 +624,7 @@ def single_gpu(args):
             if isinstance(leg, dict) and leg.get("kernel"):
                 datasets[0][key] = dict(leg, **profile_fields(leg["kernel"], wl0, fl * E * D, leg["kernel_ms"], val=val_, bwd=bwd_))
         datasets[0]["gcn_ms_per_epoch"] = extra.get("gcn_ms_per_epoch"); datasets[0]["agnn_ms_per_epoch"] = extra.get("agnn_ms_per_epoch")
-    if not args.no_extra and args.scale == 1.0:
+    if extras and args.scale == 1.0:
         TCGNN.clear_plan_cache()
         every = ("spmm", "spmm_val", "sddmm", "agnn")
         # (the three generators SURVEY.md 8d names, plus the community graph calibrated to real Reddit's TC-block count -
@@ -584,7 +643,7 @@ def single_gpu(args):
                 datasets.append({"dataset": "%s shape, %s generator" % (shape, gen), "error": str(exc)[:300]})
             torch.cuda.empty_cache()
     out["datasets"] = datasets
-    if not args.no_extra and args.scale == 1.0:
+    if extras and args.scale == 1.0:
         # ---- row (g): the reference's published RTX 3090 tables, same harness flow, same-size graphs
         shapes = artifact_shapes(args.seed)
         extra["artifact_shapes"] = shapes
@@ -599,7 +658,7 @@ def single_gpu(args):
             # (vs_baseline stays null: BASELINE.md publishes no GTEPS and nothing at Reddit size.  The one published number for a named
             #  config is the reference's single-kernel time on citeseer, 0.040 ms on an RTX 3090, logs/profile.csv:2)
             extra["citeseer_spmm_d16_speedup_vs_rtx3090"] = cs[0]["spmm_speedup_vs_rtx3090"]
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(rp_h.numpy(), col_h.numpy(), n, E, D, args.seed)
     out["extra"] = extra
     return out
@@ -610,7 +669,11 @@ def cpu_baseline(rp, col, n, E, D, seed):
     built on this machine with -march=native (equal-nnz static row blocks, parallel first touch, prefetch) - the number used -
     and torch's own sparse-CSR product next to it.  Rank 0, N = 1 only; a reported baseline, never the target."""
     from oracle import cpu_baseline as CB
-    threads = os.cpu_count() or 1
+    # the cores this process may use (its CPU affinity, and OMP_NUM_THREADS where the environment caps it): more threads than
+    # that only oversubscribe them
+    threads = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        threads = min(threads, int(os.environ["OMP_NUM_THREADS"]))
     X = np.random.default_rng(seed).standard_normal((n, D)).astype(np.float32)
     _, probe = CB.csr_spmm(X, rp, col, threads=threads, reps=1)                       # build + place pages + cost probe
     reps = int(max(2, min(20, 12.0 / max(probe[0], 1e-3))))
@@ -712,74 +775,77 @@ def multi_gpu(args):
     for _ in range(args.warmup):
         step()
     shard.ops.set_timing(args.steps)
-    elapsed = sync_time(step, args.steps, 0, barrier)
+    elapsed, last = time_steps(step, args.steps, barrier)
+    if args.dump_outputs:   # this rank's rows of Y = A X from the last timed step
+        dump_outputs(args.dump_outputs, {"spmm_out_rank%d" % rank: last}, limit=DUMP_LIMIT // world)
+    del last
     kernel_ms = shard.ops.read_timing()
-    # the other variant, for the exchange fraction
-    other = (lambda: shard.ops.spmm(xg)) if exchange else (lambda: shard.spmm(x_local))
-    t_other = sync_time(other, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
+    # ---- --full: the other variant (the exchange fraction), the other exchanges, a sharded GCN epoch and strong scaling.  Every
+    #      rank takes the same branch (same arguments), so the collectives inside the legs still match up
+    t_other = t_wire16 = t_chunk = t_overlap = gcn_ms = t_strong = float("nan")
+    e_strong, strong_kernel = 0.0, ""
+    if args.full:
+        # the other variant, for the exchange fraction
+        other = (lambda: shard.ops.spmm(xg)) if exchange else (lambda: shard.spmm(x_local))
+        t_other = sync_time(other, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
+        # ---- the exchange with fp16 on the wire (each rank converts its own rows; the kernels' image, not fp32 X, is gathered)
+        try:
+            w16 = lambda: shard.spmm(x_local, wire="fp16")
+            t_wire16 = sync_time(w16, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
+        except Exception as exc:   # an extra: must never take the headline down
+            if rank == 0:
+                print("fp16-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
+        # ---- the exchange in 32-column chunks through a ring of two buffers (RowShard.spmm_chunked: what config 5 needs to fit)
+        try:
+            wc = lambda: shard.spmm_chunked(x_local, chunk=32, wire="fp32")
+            t_chunk = sync_time(wc, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
+        except Exception as exc:   # an extra: must never take the headline down
+            if rank == 0:
+                print("chunked-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
+        # ---- the exchange overlapped with the own-block product (RowShard.spmm_overlapped: the gather on a side stream)
+        try:
+            wo = lambda: shard.spmm_overlapped(x_local)
+            t_overlap = sync_time(wo, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
+        except Exception as exc:   # an extra: must never take the headline down
+            if rank == 0:
+                print("overlapped-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
+        # ---- one sharded GCN training epoch (2 layers, hidden D, main_tcgnn.py:146-181 on the shard): X W locally, all-gather +
+        #      local SpMM forward and backward in both layers, one all-reduce of the weight gradients
+        try:
+            _, _, in_dim, classes = G.SHAPES[args.shape]
+            feats = torch.randn(n0, in_dim, device=dev, generator=g)
+            labels = torch.ones(n0, dtype=torch.long, device=dev)
+            model = S.ShardedGCN(in_dim, D, classes, num_layers=2, seed=args.seed).to(dev)
+            opt = H.make_adam(model.parameters())
+            ep = lambda: S.sharded_train_step(model, shard, feats, labels, opt, n_global)
+            gcn_ms = sync_time(ep, max(2, args.epochs // 2), 3, barrier) * 1e3 / max(2, args.epochs // 2)
+            del feats, model, opt
+        except Exception as exc:   # the extra leg must never take the headline down
+            if rank == 0:
+                print("sharded GCN leg failed: %s" % str(exc)[:300], file=sys.stderr)
+        # ---- STRONG scaling next to the weak line above (r06): the single-GPU headline graph itself - args.graph at the
+        #      shape's own size, every rank builds the same seeded CSR - cut into N row blocks balanced by nnz (tcgnn_shard.partition_rows); X is
+        #      replicated (it fits one GPU: no collective in the step), a step is every rank's SpMM over its block, the time is
+        #      the slowest rank's.  value_strong = the WHOLE graph's edges over that time: N = 1 would read the single-GPU headline.
+        try:
+            rp_g, col_g = G.GENERATORS[args.graph](n0, nnz0, seed=args.seed, device=dev)
+            shard_s = S.RowShard(rp_g.cpu().numpy(), col_g.cpu().numpy(), rank=rank, world_size=world, device=dev, always_collective=False)
+            del rp_g, col_g
+            xs = torch.randn(n0, D, device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed))   # (the same matrix on every rank)
+            xg_s = shard_s.place_replicated(xs)
+            step_s = lambda: shard_s.ops.spmm(xg_s)
+            for _ in range(n_settle):
+                step_s()
+            torch.cuda.synchronize()
+            t_strong = sync_time(step_s, args.steps, args.warmup, barrier)
+            e_strong = float(shard_s.ops.nnz)
+            strong_kernel = str(_c.lib.tcgnn_plan_last_kernel(shard_s.ops.plan).decode()) if hasattr(_c.lib, "tcgnn_plan_last_kernel") else ""
+            del shard_s, xs, xg_s
+        except Exception as exc:   # an extra: must never take the headline down
+            if rank == 0:
+                print("strong-scaling leg failed: %s" % str(exc)[:300], file=sys.stderr)
     t_nox = t_other if exchange else elapsed
     t_withx = elapsed if exchange else t_other
-    # ---- the exchange with fp16 on the wire (each rank converts its own rows; the kernels' image, not fp32 X, is gathered)
-    t_wire16 = float("nan")
-    try:
-        w16 = lambda: shard.spmm(x_local, wire="fp16")
-        t_wire16 = sync_time(w16, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
-    except Exception as exc:   # an extra: must never take the headline down
-        if rank == 0:
-            print("fp16-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
-    # ---- the exchange in 32-column chunks through a ring of two buffers (RowShard.spmm_chunked: what config 5 needs to fit)
-    t_chunk = float("nan")
-    try:
-        wc = lambda: shard.spmm_chunked(x_local, chunk=32, wire="fp32")
-        t_chunk = sync_time(wc, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
-    except Exception as exc:   # an extra: must never take the headline down
-        if rank == 0:
-            print("chunked-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
-    # ---- the exchange overlapped with the own-block product (RowShard.spmm_overlapped: the gather on a side stream)
-    t_overlap = float("nan")
-    try:
-        wo = lambda: shard.spmm_overlapped(x_local)
-        t_overlap = sync_time(wo, max(3, args.steps // 5), 2, barrier) * args.steps / max(3, args.steps // 5)
-    except Exception as exc:   # an extra: must never take the headline down
-        if rank == 0:
-            print("overlapped-exchange leg failed: %s" % str(exc)[:300], file=sys.stderr)
-    # ---- one sharded GCN training epoch (2 layers, hidden D, main_tcgnn.py:146-181 on the shard): X W locally, all-gather +
-    #      local SpMM forward and backward in both layers, one all-reduce of the weight gradients
-    gcn_ms = float("nan")
-    try:
-        _, _, in_dim, classes = G.SHAPES[args.shape]
-        feats = torch.randn(n0, in_dim, device=dev, generator=g)
-        labels = torch.ones(n0, dtype=torch.long, device=dev)
-        model = S.ShardedGCN(in_dim, D, classes, num_layers=2, seed=args.seed).to(dev)
-        opt = H.make_adam(model.parameters())
-        ep = lambda: S.sharded_train_step(model, shard, feats, labels, opt, n_global)
-        gcn_ms = sync_time(ep, max(2, args.epochs // 2), 3, barrier) * 1e3 / max(2, args.epochs // 2)
-        del feats, model, opt
-    except Exception as exc:   # the extra leg must never take the headline down
-        if rank == 0:
-            print("sharded GCN leg failed: %s" % str(exc)[:300], file=sys.stderr)
-    # ---- STRONG scaling next to the weak line above (r06): the single-GPU headline graph itself - args.graph at the
-    #      shape's own size, every rank builds the same seeded CSR - cut into N row blocks balanced by nnz (tcgnn_shard.partition_rows); X is
-    #      replicated (it fits one GPU: no collective in the step), a step is every rank's SpMM over its block, the time is
-    #      the slowest rank's.  value_strong = the WHOLE graph's edges over that time: N = 1 would read the single-GPU headline.
-    t_strong, e_strong, strong_kernel = float("nan"), 0.0, ""
-    try:
-        rp_g, col_g = G.GENERATORS[args.graph](n0, nnz0, seed=args.seed, device=dev)
-        shard_s = S.RowShard(rp_g.cpu().numpy(), col_g.cpu().numpy(), rank=rank, world_size=world, device=dev, always_collective=False)
-        del rp_g, col_g
-        xs = torch.randn(n0, D, device=dev, generator=torch.Generator(device=dev).manual_seed(args.seed))   # (the same matrix on every rank)
-        xg_s = shard_s.place_replicated(xs)
-        step_s = lambda: shard_s.ops.spmm(xg_s)
-        for _ in range(n_settle):
-            step_s()
-        torch.cuda.synchronize()
-        t_strong = sync_time(step_s, args.steps, args.warmup, barrier)
-        e_strong = float(shard_s.ops.nnz)
-        strong_kernel = str(_c.lib.tcgnn_plan_last_kernel(shard_s.ops.plan).decode()) if hasattr(_c.lib, "tcgnn_plan_last_kernel") else ""
-        del shard_s, xs, xg_s
-    except Exception as exc:   # an extra: must never take the headline down
-        if rank == 0:
-            print("strong-scaling leg failed: %s" % str(exc)[:300], file=sys.stderr)
     stats = torch.tensor([elapsed, t_nox, float(E_local), float(np.mean(kernel_ms)), t_withx, gcn_ms, t_wire16, t_overlap, t_chunk, t_strong, e_strong], dtype=torch.float64, device=dev)
     mx = stats.clone(); dist.all_reduce(mx, op=dist.ReduceOp.MAX)
     sm = stats.clone(); dist.all_reduce(sm, op=dist.ReduceOp.SUM)
@@ -800,9 +866,10 @@ def multi_gpu(args):
             "roofline": {"bound": "hbm", "kernel": "%s (slowest rank)" % shard_kernel, "achieved": round(roof_b / (k_mean * 1e-3) / 1e9, 2), "peak": HBM_PEAK / 1e9,
                          "unit": "GB/s", "frac": round(roof_b / (k_mean * 1e-3) / HBM_PEAK, 5), "traffic": None, "algorithmic_bytes": roof_b,
                          "kernel_ms_mean": round(k_mean, 4)},
-            "extra": {"exchange_in_timed_step": exchange, "ms_per_step_without_exchange": round(t_local * 1e3 / args.steps, 4),
-                      "ms_per_step_with_exchange": round(t_x * 1e3 / args.steps, 4),
-                      "exchange_fraction_if_exchanged": round(max(0.0, 1.0 - t_local / t_x), 4),
+            # (a plain run times one of the two variants: the other one's figures and the fraction are --full's, null here)
+            "extra": {"exchange_in_timed_step": exchange, "ms_per_step_without_exchange": None if np.isnan(t_local) else round(t_local * 1e3 / args.steps, 4),
+                      "ms_per_step_with_exchange": None if np.isnan(t_x) else round(t_x * 1e3 / args.steps, 4),
+                      "exchange_fraction_if_exchanged": None if np.isnan(t_local / t_x) else round(max(0.0, 1.0 - t_local / t_x), 4),
                       "gathered_X_bytes": int(shard.layout.num_cols) * D * 4,
                       "gcn_ms_per_epoch_sharded": None if np.isnan(float(mx[5])) else round(float(mx[5]), 3),
                       "ms_per_step_with_fp16_exchange": None if np.isnan(float(mx[6])) else round(float(mx[6]) * 1e3 / args.steps, 4),
@@ -810,7 +877,7 @@ def multi_gpu(args):
                       "ms_per_step_with_overlapped_exchange": None if np.isnan(float(mx[7])) else round(float(mx[7]) * 1e3 / args.steps, 4),
                       "exchange_fraction_if_overlapped": None if np.isnan(float(mx[7])) else round(max(0.0, 1.0 - t_local / float(mx[7])), 4),
                       "ms_per_step_with_chunked_exchange_32col_fp32": None if np.isnan(float(mx[8])) else round(float(mx[8]) * 1e3 / args.steps, 4),
-                      "own_block_edge_fraction": round(float(getattr(shard, "_own_frac", float("nan"))), 4),
+                      "own_block_edge_fraction": None if np.isnan(float(getattr(shard, "_own_frac", float("nan")))) else round(float(shard._own_frac), 4),
                       # strong scaling: the single-GPU headline graph split over the N ranks, X replicated (see above)
                       "strong_scaling": None if np.isnan(float(mx[9])) else {
                           "workload": "%s-shape graph from the %s generator, %d nodes, %d nnz in all, rows split over %d GPUs by nnz, X replicated" % (args.shape, args.graph, n0, int(sm[10]), world),

@@ -117,3 +117,33 @@ def test_plan_only_prints_the_per_rank_memory_plan_of_config_5(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     doc = json.loads(r.stdout.strip().splitlines()[-1])
     assert [x["rows"] for x in doc["per_rank"]] == [w[1] for w in written] and [x["edges"] for x in doc["per_rank"]] == [w[2] for w in written]
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_row_sample_past_the_limit(tmp_path):
+    """--dump-outputs: an array within its share is written whole as float32; a larger one is cut to a seeded row sample that is
+    the same on every call, and the files stay within the limit."""
+    import numpy as np
+    import torch
+    y = torch.arange(1000 * 8, dtype=torch.float64).view(1000, 8)
+    bench.dump_outputs(str(tmp_path / "whole"), {"y": y})
+    a = np.load(tmp_path / "whole" / "y.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, y.numpy().astype(np.float32))
+    limit = 4096 + 100 * 8 * 4
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y}, limit=limit)
+    s1, s2 = np.load(tmp_path / "s1" / "y.npy"), np.load(tmp_path / "s2" / "y.npy")
+    assert s1.shape == (100, 8) and np.array_equal(s1, s2) and os.path.getsize(tmp_path / "s1" / "y.npy") <= limit
+    rows = (s1[:, 0] / 8).astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, a[rows])      # distinct rows of the output, in order
+
+
+def test_plain_arguments_leave_the_full_legs_off(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and args.steps == 3 and args.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()

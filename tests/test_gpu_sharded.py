@@ -403,10 +403,10 @@ def test_rccl_world_of_one_executes_every_collective_of_the_n_gpu_step(tmp_path)
     assert flags.size >= 15 and flags.all(), open(os.path.join(tmp_path, "rccl_rank0.txt")).read()
 
 
-def test_bench_gpus_n_starts_its_own_ranks_and_prints_one_json_line_last():
-    """`python bench.py --gpus N` with no launcher (the form the driver uses at N = 1): the sharded path is forced with a
-    world of one, so the self-launch (torch.distributed.run on 127.0.0.1), the RCCL process group and the exchange inside the
-    timed step all execute; the last stdout line is the JSON line."""
+def test_bench_gpus_n_starts_its_own_ranks_and_prints_one_json_line_last(tmp_path):
+    """`python bench.py --gpus N --full` with no launcher (the form the driver uses at N = 1): the sharded path is forced with a
+    world of one, so the self-launch (torch.distributed.run on 127.0.0.1), the RCCL process group, the exchange inside the
+    timed step and the --full legs all execute; the last stdout line is the JSON line."""
     import json
     import subprocess
     import sys
@@ -414,8 +414,8 @@ def test_bench_gpus_n_starts_its_own_ranks_and_prints_one_json_line_last():
     env = dict(os.environ, TCGNN_BENCH_FORCE_SHARDED="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--scale", "0.05", "--steps", "5", "--warmup", "2", "--epochs", "4"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--scale", "0.05", "--steps", "5", "--warmup", "2", "--epochs", "4", "--full",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines[-1]) < 4096, len(lines[-1])          # (the driver parses this line; r03's 20 KB object came back unparsed)
@@ -430,11 +430,13 @@ def test_bench_gpus_n_starts_its_own_ranks_and_prints_one_json_line_last():
     assert ex["ms_per_step_with_exchange"] > 0 and ex["ms_per_step_with_fp16_exchange"] is not None
     assert ex["gcn_ms_per_epoch_sharded"] is not None
     assert ex["ms_per_step_with_overlapped_exchange"] is not None and 0.0 <= ex["exchange_fraction_if_overlapped"] < 1.0
+    y = np.load(tmp_path / "out" / "spmm_out_rank0.npy")      # --dump-outputs: the rank's rows of the last timed step
+    assert y.dtype == np.float32 and y.shape == (int(232965 * 0.05), 64) and np.isfinite(y).all() and np.abs(y).max() > 0
 
 
 @pytest.mark.gpu
 def test_bench_single_gpu_line_is_bounded_and_carries_roofline_and_cpu_baseline():
-    """The N = 1 form the driver runs (scaled down): last stdout line < 4 KB, parses, holds `roofline` and `cpu_baseline`."""
+    """The N = 1 form the driver runs with --full (scaled down): last stdout line < 4 KB, parses, holds `roofline` and `cpu_baseline`."""
     import json
     import subprocess
     import sys
@@ -442,7 +444,7 @@ def test_bench_single_gpu_line_is_bounded_and_carries_roofline_and_cpu_baseline(
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TCGNN_BENCH_FORCE_SHARDED"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "5", "--warmup", "2", "--epochs", "3"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "5", "--warmup", "2", "--epochs", "3", "--full"],
                        env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -453,3 +455,44 @@ def test_bench_single_gpu_line_is_bounded_and_carries_roofline_and_cpu_baseline(
     assert line["roofline"]["bound"] == "hbm" and line["roofline"]["frac"] > 0
     assert line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["cores"] >= 1 and line["cpu_baseline"]["kind"] == "port"
     assert line["summary"]["gcn_ms_per_epoch"] > 0 and line["summary"]["agnn_ms_per_epoch"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_k_steps_and_dumps_what_the_last_step_returned(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (scaled down), no --full: the line holds the headline keys and
+    K timed steps and none of the --full legs; DIR/spmm_out.npy is Y = A X of the seeded inputs (graph and X from --seed), so
+    it equals the same product computed here from the same seeds."""
+    import json
+    import subprocess
+    import sys
+    import TCGNN
+    import tcgnn_graph as G
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "TCGNN_BENCH_FORCE_SHARDED"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scale", "0.05", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+        assert k in line, k
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert "cpu_baseline" not in line and "sddmm_d64_ms" not in line["summary"] and "gcn_ms_per_epoch" not in line["summary"]
+    with open(os.path.join(root, line["detail"])) as f:
+        detail = json.load(f)
+    assert detail["roofline"]["kernel_launches_timed"] == 7 and len(detail["datasets"]) == 1
+    got = np.load(tmp_path / "out" / "spmm_out.npy")
+    n, nnz, _, _ = G.SHAPES["reddit"]
+    n, nnz = int(n * 0.05), int(nnz * 0.05 * 0.05)
+    dev = torch.device("cuda:0")
+    rp, col = G.GENERATORS["sbm_reddit"](n, nnz, seed=0, device=dev)
+    E = col.numel()
+    bp = torch.zeros((n + 15) // 16, dtype=torch.int32, device=dev)
+    e2c = torch.zeros(E, dtype=torch.int32, device=dev); e2r = torch.zeros(E, dtype=torch.int32, device=dev)
+    TCGNN.preprocess_gpu(col, rp, n, 16, 8, bp, e2c, e2r)
+    X = torch.randn(n, 64, device=dev, generator=torch.Generator(device=dev).manual_seed(0))
+    want = TCGNN.forward(X, rp, col, bp, e2c, e2r)[0].cpu().numpy()
+    TCGNN.clear_plan_cache()
+    assert got.dtype == np.float32 and got.shape == want.shape == (n, 64)
+    assert np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want))) <= 1e-3
