@@ -23,7 +23,8 @@
  *     arrays for its lifetime, see tcgnn_plan_create); outputs are caller-allocated.
  *   - `stream` is a hipStream_t passed as void* (NULL = the legacy default stream).  All device
  *     work is enqueued asynchronously on it.  What synchronises the stream: tcgnn_plan_create (to size its
- *     outputs), tcgnn_preprocess_gpu_ws (ONCE, to read back 24 bytes; it allocates nothing), tcgnn_plan_prepare, and - ONLY for a feature width
+ *     outputs), tcgnn_preprocess_gpu_ws (ONCE, to read back 24 bytes; it allocates nothing), tcgnn_transpose_ws (ONCE, likewise),
+ *     tcgnn_plan_prepare, and - ONLY for a feature width
  *     tcgnn_plan_prepare was not called for - the first tcgnn_spmm / tcgnn_spmm_fused / tcgnn_spmm_gemm
  *     call of that width on a plan whose time model picks the LDS-resident kernel (it builds the
  *     width's cell stream: allocations, a few count-and-place round trips).  Call tcgnn_plan_prepare
@@ -133,6 +134,25 @@ int tcgnn_preprocess_gpu(const int32_t* d_edgeList, const int32_t* d_nodePointer
                          int32_t blockSize_w, int32_t* d_blockPartition, int64_t bp_len,
                          int32_t* d_edgeToColumn, int32_t* d_edgeToRow, int64_t* tc_blocks,
                          void* stream);
+
+/* CSR transpose (no counterpart in the reference, whose layers back-propagate through A, gnn_conv.py:46,80,110,143: right only on
+ * a symmetric graph).  From A's CSR (DEVICE memory) it builds A^T's:
+ *   d_nodePointer_t [num_nodes + 1], d_edgeList_t [num_edges]: row c of A^T lists the rows r of every entry (r, c) of A in increasing
+ *                    CSR position - sorted rows even when A's are not; A's duplicate entries stay, next to each other;
+ *   d_perm [num_edges]: perm[eT] = the CSR position in A of A^T's entry eT (a bijection on [0, num_edges));
+ *   *symmetric      = 1 exactly when (nodePointer_t, edgeList_t) equal (nodePointer, edgeList), else 0 (may be NULL).
+ * The graph must be square: nodePointer[0] = 0, monotone, nodePointer[num_nodes] = num_edges and every id in [0, num_nodes) (the
+ * forward path takes larger ids; a transpose can not), else TCGNN_ERR_BAD_GRAPH.  Until that check every index derived from the
+ * input is clamped to the arrays.  Runs on CALLER scratch (tcgnn_transpose_workspace_bytes, 256-byte aligned: sorted keys, row ids
+ * and rocPRIM's scratch, ~8 num_edges bytes plus the sort's own), allocates nothing and synchronises `stream` ONCE, to read back the
+ * validation words and the symmetry flag.
+ * tcgnn_permute_edge_values: out[eT] = val[perm[eT]] - the edge values of A in A^T's order, for tcgnn_spmm_val on A^T's plan.
+ * Stream-ordered, no allocation, no synchronisation; perm must be one tcgnn_transpose_ws wrote. */
+int tcgnn_transpose_workspace_bytes(int32_t num_nodes, int64_t num_edges, size_t* bytes);
+int tcgnn_transpose_ws(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                       int32_t* d_nodePointer_t, int32_t* d_edgeList_t, int32_t* d_perm, void* d_workspace,
+                       size_t workspace_bytes, int32_t* symmetric, void* stream);
+int tcgnn_permute_edge_values(const float* d_val, const int32_t* d_perm, int64_t num_edges, float* d_out, void* stream);
 
 /* Tile statistics of the translation - what the reference's counting scripts report
  * (3_cnt_TC_blk_SpMM.py:38-94 with 16x8 tiles, 3_cnt_TC_blk_SDDMM.py with 16x16; logs/16x8_reduction.csv,

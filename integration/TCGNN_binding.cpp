@@ -46,22 +46,37 @@ void check_rows(const torch::Tensor& input, const torch::Tensor& nodePointer) {
 // One plan per graph.  The reference hands the same five tensors to every call (gnn_conv.py:31,56), so the packed tile stream
 // is built at first sight and found again by (address, length, in-place version) of each; the entry keeps the tensors alive,
 // so an address cannot be recycled under it.
+// Not in the reference: what transpose=True calls run on (A^T's CSR, metadata and plan - or A's own plan on a symmetric graph - and
+// the permutation of the edge positions), built at first use and kept in A's entry, so it leaves the cache with A's plan.
+struct TransposedEntry {
+  bool built = false, symmetric = false;
+  std::vector<torch::Tensor> keep;   // A^T's five metadata tensors (not symmetric)
+  torch::Tensor perm;
+  tcgnn_plan* own = nullptr;         // A^T's plan when the graph is not symmetric
+};
+
 struct PlanEntry {
   std::vector<std::tuple<const void*, int64_t, int64_t>> key;
   std::vector<torch::Tensor> keep;
   tcgnn_plan* plan = nullptr;
+  TransposedEntry t;
 };
 std::list<PlanEntry>& plan_cache() { static std::list<PlanEntry> c; return c; }
 constexpr size_t kPlanCacheSize = 8;
 
-tcgnn_plan* plan_for(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
+void destroy_entry(PlanEntry& e) {
+  tcgnn_plan_destroy(e.plan);
+  if (e.t.own) tcgnn_plan_destroy(e.t.own);
+}
+
+PlanEntry& entry_for(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
                      const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow) {
   const torch::Tensor* ts[5] = {&nodePointer, &edgeList, &blockPartition, &edgeToColumn, &edgeToRow};
   std::vector<std::tuple<const void*, int64_t, int64_t>> key;
   for (auto* t : ts) key.emplace_back(t->data_ptr(), t->numel(), (int64_t)t->_version());
   auto& cache = plan_cache();
   for (auto it = cache.begin(); it != cache.end(); ++it)
-    if (it->key == key) { cache.splice(cache.begin(), cache, it); return cache.front().plan; }
+    if (it->key == key) { cache.splice(cache.begin(), cache, it); return cache.front(); }
   for (auto* t : ts) TORCH_CHECK(t->scalar_type() == torch::kInt32, "expected scalar type Int");   // what data_ptr<int>() raises in the reference
   TORCH_CHECK(edgeToColumn.numel() >= edgeList.numel() && edgeToRow.numel() >= edgeList.numel(), "edgeToColumn / edgeToRow are shorter than edgeList");
   PlanEntry e;
@@ -74,10 +89,67 @@ tcgnn_plan* plan_for(const torch::Tensor& nodePointer, const torch::Tensor& edge
   cache.push_front(std::move(e));
   while (cache.size() > kPlanCacheSize) {
     (void)hipDeviceSynchronize();   // kernels still reading the evicted plan - on ANY stream - finish first
-    tcgnn_plan_destroy(cache.back().plan);
+    destroy_entry(cache.back());
     cache.pop_back();
   }
-  return cache.front().plan;
+  return cache.front();
+}
+
+tcgnn_plan* plan_for(const torch::Tensor& nodePointer, const torch::Tensor& edgeList, const torch::Tensor& blockPartition,
+                     const torch::Tensor& edgeToColumn, const torch::Tensor& edgeToRow) {
+  return entry_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow).plan;
+}
+
+torch::Tensor aligned_scratch(size_t bytes, const torch::Tensor& like, void** ptr) {
+  torch::Tensor buf = torch::empty({(int64_t)bytes + 256}, like.options().dtype(torch::kUInt8));
+  *ptr = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(buf.data_ptr()) + 255) & ~(uintptr_t)255);
+  return buf;
+}
+
+// A^T of the entry's graph: tcgnn_transpose_ws, then (not symmetric) the device SGT of A^T and its plan - as TCGNN.py does
+TransposedEntry& transposed_for(PlanEntry& e) {
+  TransposedEntry& t = e.t;
+  if (t.built) return t;
+  const torch::Tensor& nodePointer = e.keep[0];
+  const torch::Tensor& edgeList = e.keep[1];
+  const int32_t N = (int32_t)(nodePointer.numel() - 1);
+  const int64_t E = edgeList.numel(), bp_len = e.keep[2].numel();
+  auto opts = nodePointer.options().dtype(torch::kInt32);
+  torch::Tensor rp_t = torch::empty({(int64_t)N + 1}, opts), col_t = torch::empty({E}, opts), perm = torch::empty({E}, opts);
+  size_t need = 0;
+  void* ws = nullptr;
+  tcgnn_check(tcgnn_transpose_workspace_bytes(N, E, &need), "tcgnn_transpose_workspace_bytes");
+  int32_t sym = 0;
+  {
+    torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
+    tcgnn_check(tcgnn_transpose_ws(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, rp_t.data_ptr<int>(), col_t.data_ptr<int>(),
+                                   perm.data_ptr<int>(), ws, need, &sym, current_stream(nodePointer)), "tcgnn_transpose_ws");
+  }
+  if (!sym) {
+    torch::Tensor bp_t = torch::zeros({bp_len}, opts), e2c_t = torch::empty({E}, opts), e2r_t = torch::empty({E}, opts);
+    tcgnn_check(tcgnn_preprocess_gpu_workspace_bytes(N, E, TCGNN_BLK_H, &need), "tcgnn_preprocess_gpu_workspace_bytes");
+    int64_t tc_blocks = 0;
+    {
+      torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
+      tcgnn_check(tcgnn_preprocess_gpu_ws(col_t.data_ptr<int>(), rp_t.data_ptr<int>(), N, E, TCGNN_BLK_H, TCGNN_BLK_W, bp_t.data_ptr<int>(), bp_len,
+                                          e2c_t.data_ptr<int>(), e2r_t.data_ptr<int>(), ws, need, &tc_blocks, current_stream(nodePointer)),
+                  "tcgnn_preprocess_gpu_ws");
+    }
+    tcgnn_check(tcgnn_plan_create(rp_t.data_ptr<int>(), col_t.data_ptr<int>(), bp_t.data_ptr<int>(), e2c_t.data_ptr<int>(), e2r_t.data_ptr<int>(),
+                                  N, E, (int32_t)bp_len, current_stream(nodePointer), &t.own), "tcgnn_plan_create");
+    t.keep = {rp_t, col_t, bp_t, e2c_t, e2r_t};
+  }
+  t.perm = perm;
+  t.symmetric = sym != 0;
+  t.built = true;
+  return t;
+}
+
+// the plan a call runs on: A's, or with transpose the one of A^T (A's own on a symmetric graph)
+tcgnn_plan* plan_of(PlanEntry& e, bool transpose) {
+  if (!transpose) return e.plan;
+  TransposedEntry& t = transposed_for(e);
+  return t.own ? t.own : e.plan;
 }
 
 struct Workspace {
@@ -94,9 +166,9 @@ struct Workspace {
 
 }  // namespace
 
-// TCGNN.cpp:63-86
+// TCGNN.cpp:63-86 (transpose, not in the reference: A^T @ input, the metadata still describing A)
 std::vector<torch::Tensor> spmm_forward(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
-                                        torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow) {
+                                        torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, bool transpose) {
   CHECK_INPUT(input); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
   TORCH_CHECK(input.scalar_type() == torch::kFloat32, "expected scalar type Float");
@@ -104,7 +176,7 @@ std::vector<torch::Tensor> spmm_forward(torch::Tensor input, torch::Tensor nodeP
   DeviceGuard guard(input.device());
   auto output = torch::empty_like(input);                          // fully overwritten by the kernels (every row is a node's)
   if (input.numel() == 0) return {output};
-  auto* plan = plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  auto* plan = plan_of(entry_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose);
   const int D = (int)input.size(1);
   Workspace ws(plan, D, input);
   tcgnn_check(tcgnn_spmm(plan, input.data_ptr<float>(), output.data_ptr<float>(), D, ws.ptr, ws.bytes, current_stream(input)), "tcgnn_spmm");
@@ -114,7 +186,7 @@ std::vector<torch::Tensor> spmm_forward(torch::Tensor input, torch::Tensor nodeP
 // TCGNN.cpp:93-118 (edgeAttention sits between edgeList and blockPartition, call site gnn_conv.py:132)
 std::vector<torch::Tensor> spmm_forward_AGNN(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
                                              torch::Tensor edgeAttention, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
-                                             torch::Tensor edgeToRow) {
+                                             torch::Tensor edgeToRow, bool transpose) {
   CHECK_INPUT(input); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList); CHECK_INPUT(edgeAttention);
   CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
   TORCH_CHECK(input.scalar_type() == torch::kFloat32 && edgeAttention.scalar_type() == torch::kFloat32, "expected scalar type Float");
@@ -123,11 +195,20 @@ std::vector<torch::Tensor> spmm_forward_AGNN(torch::Tensor input, torch::Tensor 
   DeviceGuard guard(input.device());
   auto output = torch::empty_like(input);
   if (input.numel() == 0) return {output};
-  auto* plan = plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  PlanEntry& entry = entry_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  auto* plan = plan_of(entry, transpose);
   const int D = (int)input.size(1);
   Workspace ws(plan, D, input);
   // every "head" launch of the reference reads row 0 of edgeAttention and overwrites the same output (TCGNN_kernel.cu:253-268, :529)
-  tcgnn_check(tcgnn_spmm_val(plan, input.data_ptr<float>(), edgeAttention.data_ptr<float>(), output.data_ptr<float>(), D, ws.ptr, ws.bytes,
+  const float* val = edgeAttention.data_ptr<float>();
+  torch::Tensor val_t;
+  if (transpose) {   // row 0 in A^T's order
+    val_t = torch::empty({std::max<int64_t>(edgeList.numel(), 1)}, input.options());
+    tcgnn_check(tcgnn_permute_edge_values(val, entry.t.perm.data_ptr<int>(), edgeList.numel(), val_t.data_ptr<float>(), current_stream(input)),
+                "tcgnn_permute_edge_values");
+    val = val_t.data_ptr<float>();
+  }
+  tcgnn_check(tcgnn_spmm_val(plan, input.data_ptr<float>(), val, output.data_ptr<float>(), D, ws.ptr, ws.bytes,
                              current_stream(input)), "tcgnn_spmm_val");
   return {output};
 }
@@ -155,7 +236,7 @@ std::vector<torch::Tensor> sddmm_forward(torch::Tensor input, torch::Tensor node
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
                                                torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow,
                                                c10::optional<torch::Tensor> row_scale, c10::optional<torch::Tensor> col_scale,
-                                               c10::optional<torch::Tensor> bias, bool relu, c10::optional<torch::Tensor> gate) {
+                                               c10::optional<torch::Tensor> bias, bool relu, c10::optional<torch::Tensor> gate, bool transpose) {
   CHECK_INPUT(input); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
   TORCH_CHECK(input.scalar_type() == torch::kFloat32, "expected scalar type Float");
@@ -181,7 +262,7 @@ std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tenso
   DeviceGuard guard(input.device());
   auto output = torch::empty_like(input);
   if (input.numel() == 0) return {output};
-  auto* plan = plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  auto* plan = plan_of(entry_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose);
   Workspace ws(plan, (int)D, input);
   tcgnn_check(tcgnn_spmm_scaled(plan, input.data_ptr<float>(), cs, g, rs, b, output.data_ptr<float>(), (int)D, relu ? TCGNN_FUSE_RELU : 0,
                                 ws.ptr, ws.bytes, current_stream(input)), "tcgnn_spmm_scaled");
@@ -231,7 +312,7 @@ void preprocess_gpu(torch::Tensor edgeList, torch::Tensor nodePointer, int num_n
 void clear_plan_cache() {
   for (auto& e : plan_cache()) {
     if (!e.keep.empty() && e.keep[0].is_cuda()) { DeviceGuard guard(e.keep[0].device()); (void)hipDeviceSynchronize(); }   // nothing may still be reading the plan
-    tcgnn_plan_destroy(e.plan);
+    destroy_entry(e);
   }
   plan_cache().clear();
 }
@@ -240,14 +321,18 @@ void clear_plan_cache() {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("preprocess", &preprocess, "Preprocess Step (CPU)");
   m.def("preprocess_gpu", &preprocess_gpu, "Preprocess Step (CUDA)");
-  m.def("forward", &spmm_forward, "TC-GNN SPMM forward (CUDA)");
+  // (transpose: not in the reference - A^T in place of A, the metadata still describing A)
+  m.def("forward", &spmm_forward, "TC-GNN SPMM forward (CUDA)", py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"),
+        py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("transpose") = false);
   m.def("forward_ef", &sddmm_forward, "TC-GNN SDDMM forward (CUDA)");
-  m.def("forward_AGNN", &spmm_forward_AGNN, "TC-GNN SPMM (AGNN) forward (CUDA)");
-  m.def("backward", &spmm_forward, "TC-GNN SPMM backward (CUDA)");
+  m.def("forward_AGNN", &spmm_forward_AGNN, "TC-GNN SPMM (AGNN) forward (CUDA)", py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"),
+        py::arg("edgeAttention"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("transpose") = false);
+  m.def("backward", &spmm_forward, "TC-GNN SPMM backward (CUDA)", py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"),
+        py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("transpose") = false);
   m.def("backward_ef", &sddmm_forward, "TC-GNN SDDMM backward (CUDA)");
   m.def("clear_plan_cache", &clear_plan_cache, "release the device plans (not in the reference)");
   m.def("forward_scaled", &spmm_forward_scaled, "normalised GCN aggregation with scales / bias / ReLU fused (not in the reference)",
         py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"),
         py::arg("row_scale") = py::none(), py::arg("col_scale") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,
-        py::arg("gate") = py::none());
+        py::arg("gate") = py::none(), py::arg("transpose") = false);
 }

@@ -34,13 +34,16 @@ import tcgnn_capi as _c
 
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
-           "forward_fused", "forward_gemm", "forward_scaled", "degree_scales"]
+           "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph"]
 
 _plan_cache_size = max(1, int(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8")))
 _plans = collections.OrderedDict()  # key -> (handle, tensors kept alive, device index)
 _retired = []                       # evicted plans waiting for the kernels that may still read them: (events, handle, tensors)
 _workspaces = {}                    # (device index, stream id) -> uint8 tensor
 _scales = {}                        # (nodePointer, edgeList) key -> (tensors kept alive, {norm: (row_scale, col_scale)}): degree_scales
+_transposed_csr = {}                # (nodePointer, edgeList) key -> (nodePointer, edgeList, nodePointer_t, edgeList_t, perm, symmetric): transpose_graph
+_transposed = {}                    # A's plan key -> dict(plan=, own=, meta=, perm=, symmetric=): what transpose=True calls run on, evicted with A's plan
+_values_t = {}                      # (device index, stream id) -> fp32 buffer: edge values in A^T's order (forward_AGNN(transpose=True))
 
 
 def set_plan_cache_size(n):
@@ -68,8 +71,10 @@ def _reap(block=False):
 
 def _evict():
     while len(_plans) > _plan_cache_size:
-        _, (old, keep, dev_index) = _plans.popitem(last=False)
+        key, (old, keep, dev_index) = _plans.popitem(last=False)
         _drop_scales()
+        tr = _transposed.pop(key, None)
+        _drop_transposed_csr()
         events = []
         for (d, stream_id) in list(_workspaces):
             if d == dev_index:   # the streams this module has launched kernels on, on the EVICTED plan's device
@@ -78,6 +83,8 @@ def _evict():
                     e.record(torch.cuda.ExternalStream(stream_id, device=d) if stream_id else torch.cuda.default_stream(d))
                     events.append(e)
         _retired.append((events, old, keep))
+        if tr is not None and tr["own"] is not None:   # A^T's own plan (a graph that is not symmetric) leaves with A's
+            _retired.append((events, tr["own"], tr["meta"]))
     if _retired:
         _reap()
 
@@ -109,13 +116,17 @@ def _stream_handle(device):
 
 # ---------------------------------------------------------------- plan cache
 
+def _plan_key(tensors):
+    return tuple((t.data_ptr(), t.numel(), t._version) for t in tensors) + (tensors[0].device.index,)
+
+
 def _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
     """The packed tile stream is a pure function of the five metadata tensors; it is built on the
     device the first time they are seen and reused while they are unchanged (storage address,
     length and in-place version counter).  The cache keeps the tensors alive, so an address can not
     be recycled under a live entry."""
     tensors = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    key = tuple((t.data_ptr(), t.numel(), t._version) for t in tensors) + (nodePointer.device.index,)
+    key = _plan_key(tensors)
     hit = _plans.get(key)
     if hit is not None:
         _plans.move_to_end(key)
@@ -149,32 +160,168 @@ def clear_plan_cache():
     while _plans:
         _, (old, _keep, _d) = _plans.popitem()
         _c.lib.tcgnn_plan_destroy(old)
+    for tr in _transposed.values():
+        if tr["own"] is not None:
+            _c.lib.tcgnn_plan_destroy(tr["own"])
+    _transposed.clear()
+    _transposed_csr.clear()
+    _values_t.clear()
     _reap(block=True)
     _workspaces.clear()
     _scales.clear()
 
 
-def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
-    """Not part of the reference API: statistics of the packed tile stream (dict)."""
+# ---------------------------------------------------------------- the transposed graph (A^T)
+
+def _drop_transposed_csr():
+    """Transposed CSRs of graphs no cached plan uses any more leave with their plans (as the scales do)."""
+    live = {k[:2] + (k[-1],) for k in _plans}
+    for k in [k for k in _transposed_csr if k not in live]:
+        del _transposed_csr[k]
+
+
+def _scratch(nbytes, dev):
+    """(tensor kept alive, 256-byte aligned address, usable bytes) of torch-allocator scratch for one library call"""
+    ws = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, int(nbytes)
+
+
+def _transpose_csr(nodePointer, edgeList):
+    """(nodePointer, edgeList, nodePointer_t, edgeList_t, perm, symmetric) - tcgnn_transpose_ws on torch-allocator scratch (one
+    synchronisation), cached per graph like degree_scales."""
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    if edgeList.device != nodePointer.device:
+        raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, nodePointer.device))
+    key = tuple((t.data_ptr(), t.numel(), t._version) for t in (nodePointer, edgeList)) + (nodePointer.device.index,)
+    hit = _transposed_csr.get(key)
+    if hit is not None:
+        return hit
+    N, E = nodePointer.numel() - 1, edgeList.numel()
+    if N < 0:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    dev = nodePointer.device
+    with torch.cuda.device(dev):
+        rp_t = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        col_t = torch.empty(E, dtype=torch.int32, device=dev)
+        perm = torch.empty(E, dtype=torch.int32, device=dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_transpose_workspace_bytes(N, E, _c.ctypes.byref(need)), "tcgnn_transpose_workspace_bytes")
+        ws, ptr, nbytes = _scratch(need.value, dev)
+        sym = _c._i32(0)
+        st = _c.lib.tcgnn_transpose_ws(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(),
+                                       ptr, nbytes, _c.ctypes.byref(sym), _stream_handle(dev))
+        del ws   # (the call synchronised the stream: nothing still reads it)
+    _c.check(st, "tcgnn_transpose_ws")
+    symmetric = bool(sym.value)
+    if symmetric:   # A^T = A: its arrays are A's own
+        rp_t, col_t = nodePointer, edgeList
+    entry = (nodePointer, edgeList, rp_t, col_t, perm, symmetric)
+    _transposed_csr[key] = entry
+    while len(_transposed_csr) > _plan_cache_size:   # (a graph never handed to the kernels has no plan to leave with)
+        _transposed_csr.pop(next(iter(_transposed_csr)))
+    return entry
+
+
+def transpose_graph(nodePointer, edgeList):
+    """Not in the reference module: the CSR of A^T on the device, (nodePointer_t, edgeList_t, perm, symmetric).  Row c of A^T lists
+    the rows r of every entry (r, c) of A in increasing CSR position (sorted; A's duplicates kept); perm[eT] = the CSR position in A
+    of A^T's entry eT; symmetric = A^T has exactly A's arrays (then nodePointer_t / edgeList_t ARE nodePointer / edgeList).  Column
+    ids must lie in [0, num_nodes).  Built on the GPU (tcgnn_transpose_ws) and cached beside the graph's plan: the transpose=True
+    calls use the same entry."""
+    return _transpose_csr(nodePointer, edgeList)[2:]
+
+
+def _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
+    """What transpose=True calls run on, built at first use and kept beside A's plan (and evicted with it): dict(plan = the plan of
+    A^T - A's own when the graph is symmetric -, own = that plan when it is A^T's own else None, meta = A^T's five metadata tensors,
+    perm, symmetric).  A^T's metadata: the transpose, the device SGT on torch-allocator scratch, tcgnn_plan_create."""
+    tensors = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    plan = _plan_for(*tensors)
+    key = _plan_key(tensors)
+    hit = _transposed.get(key)
+    if hit is not None:
+        return hit
+    _, _, rp_t, col_t, perm, symmetric = _transpose_csr(nodePointer, edgeList)
+    if symmetric:
+        entry = dict(plan=plan, own=None, meta=tensors, perm=perm, symmetric=True)
+    else:
+        dev = nodePointer.device
+        N, E, bp_len = nodePointer.numel() - 1, edgeList.numel(), blockPartition.numel()
+        with torch.cuda.device(dev):
+            bp_t = torch.zeros(bp_len, dtype=torch.int32, device=dev)
+            e2c_t = torch.empty(E, dtype=torch.int32, device=dev)
+            e2r_t = torch.empty(E, dtype=torch.int32, device=dev)
+            need = _c._sz(0)
+            _c.check(_c.lib.tcgnn_preprocess_gpu_workspace_bytes(N, E, 16, _c.ctypes.byref(need)), "tcgnn_preprocess_gpu_workspace_bytes")
+            ws, ptr, nbytes = _scratch(need.value, dev)
+            tc = _c._i64(0)
+            st = _c.lib.tcgnn_preprocess_gpu_ws(col_t.data_ptr(), rp_t.data_ptr(), N, E, 16, 8, bp_t.data_ptr(), bp_len, e2c_t.data_ptr(),
+                                                e2r_t.data_ptr(), ptr, nbytes, _c.ctypes.byref(tc), _stream_handle(dev))
+            del ws
+            _c.check(st, "tcgnn_preprocess_gpu_ws")
+            handle = _c._vp()
+            _c.check(_c.lib.tcgnn_plan_create(rp_t.data_ptr(), col_t.data_ptr(), bp_t.data_ptr(), e2c_t.data_ptr(), e2r_t.data_ptr(), N, E, bp_len,
+                                              _stream_handle(dev), _c.ctypes.byref(handle)), "tcgnn_plan_create")
+        entry = dict(plan=handle, own=handle, meta=(rp_t, col_t, bp_t, e2c_t, e2r_t), perm=perm, symmetric=False)
+    _transposed[key] = entry
+    return entry
+
+
+def _plan_of(meta, transpose):
+    return _transposed_for(*meta)["plan"] if transpose else _plan_for(*meta)
+
+
+def _values_buffer(E, device):
+    """fp32 [max(E, 1)] per (device, stream), like the workspace: A's edge values in A^T's order for forward_AGNN(transpose=True)"""
+    key = (device.index, _stream_handle(device))
+    buf = _values_t.get(key)
+    if buf is None or buf.numel() < max(E, 1):
+        buf = torch.empty(max(E, 1), dtype=torch.float32, device=device)
+        _values_t[key] = buf
+    return buf
+
+
+def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, transpose=False):
+    """Not part of the reference API: statistics of the packed tile stream (dict).  transpose=True: of the plan transpose=True calls
+    run on (A's own on a symmetric graph), plus symmetric, shares_plan (no plan of A^T's own) and transpose_bytes (the arrays the
+    transposed entry owns: perm, and A^T's five metadata tensors unless the graph is symmetric)."""
+    meta = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     info = _c.PlanInfo()
-    _c.check(_c.lib.tcgnn_plan_get_info(_plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow),
-                                        _c.ctypes.byref(info)), "tcgnn_plan_get_info")
-    return {f: getattr(info, f) for f, _ in info._fields_}
+    _c.check(_c.lib.tcgnn_plan_get_info(_plan_of(meta, transpose), _c.ctypes.byref(info)), "tcgnn_plan_get_info")
+    out = {f: getattr(info, f) for f, _ in info._fields_}
+    if transpose:
+        tr = _transposed_for(*meta)
+        owned = [tr["perm"]] + ([] if tr["symmetric"] else list(tr["meta"]))
+        out.update(symmetric=tr["symmetric"], shares_plan=tr["own"] is None, transpose_bytes=sum(t.numel() * t.element_size() for t in owned))
+    return out
 
 
-def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False):
+def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
     forward / backward (/ forward_AGNN) call of those widths synchronises or allocates inside the library, and a call captured into
-    a HIP graph takes the walk it would take outside one.  The harness calls it with the model's widths before the dry epochs."""
+    a HIP graph takes the walk it would take outside one.  The harness calls it with the model's widths before the dry epochs.
+    transpose=True (a model with directed=True layers runs both): also A^T's plan - built now if it is not cached - the same way,
+    and with edge_valued=True the buffer forward_AGNN(transpose=True) permutes the edge values into, on the current stream."""
     plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    plans = [plan]
     dev = nodePointer.device
+    if transpose:
+        tr = _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        if tr["own"] is not None:
+            plans.append(tr["own"])
+        if edge_valued:
+            with torch.cuda.device(dev):
+                _values_buffer(edgeList.numel(), dev)
     with torch.cuda.device(dev):
         for d in sorted({int(w) for w in widths if int(w) >= 1}):
-            _c.check(_c.lib.tcgnn_plan_prepare(plan, d, _stream_handle(dev)), "tcgnn_plan_prepare")
-            if edge_valued:
-                _c.check(_c.lib.tcgnn_plan_prepare_val(plan, d, _stream_handle(dev)), "tcgnn_plan_prepare_val")
+            for p in plans:
+                _c.check(_c.lib.tcgnn_plan_prepare(p, d, _stream_handle(dev)), "tcgnn_plan_prepare")
+                if edge_valued:
+                    _c.check(_c.lib.tcgnn_plan_prepare_val(p, d, _stream_handle(dev)), "tcgnn_plan_prepare_val")
 
 
 def set_plan_modes(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, spmm_mode=None, range_guard=None):
@@ -222,9 +369,10 @@ def kernel_timing(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow
     return [buf[i] for i in range(n.value)]
 
 
-def last_kernel(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
-    """Not part of the reference API: name of the main kernel the most recent call on this graph launched."""
-    return _c.lib.tcgnn_plan_last_kernel(_plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)).decode()
+def last_kernel(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, transpose=False):
+    """Not part of the reference API: name of the main kernel the most recent call on this graph launched (transpose=True: on the
+    plan the transposed calls run on)."""
+    return _c.lib.tcgnn_plan_last_kernel(_plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)).decode()
 
 
 def _workspace(plan, D, device):
@@ -320,8 +468,10 @@ def _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
         raise RuntimeError("input and nodePointer are on different devices")
 
 
-def forward(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
-    """SpMM  Y = A_bin @ input  (GCN / GIN / SAG aggregation, forward and backward)."""
+def forward(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, transpose=False):
+    """SpMM  Y = A_bin @ input  (GCN / GIN / SAG aggregation, forward and backward).
+    transpose=True (not in the reference module): Y = A_bin^T @ input - the metadata still describe A; A^T's plan is built at
+    first use and cached beside A's (A's own plan when the graph is symmetric)."""
     _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     dev = input.device
     N, D = input.shape
@@ -329,18 +479,18 @@ def forward(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRo
     if N == 0 or D == 0:
         return [out]
     with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
         ws, ws_bytes = _workspace(plan, D, dev)
         st = _c.lib.tcgnn_spmm(plan, input.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
     _c.check(st, "tcgnn_spmm")
     return [out]
 
 
-def forward_fused(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, relu=False, gate=None):
+def forward_fused(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, relu=False, gate=None, transpose=False):
     """Not in the reference module: `forward` with the layer's element-wise steps fused in.
     relu=True: max(A @ input, 0) - the ReLU the reference applies after the layer (main_tcgnn.py:100-139) runs in the
     kernel's stores.  gate (same shape as input): A @ (input * (gate > 0)) - with gate = the forward output, the ReLU
-    backward mask is applied to dY while it is staged.  Bit-identical to the unfused compositions."""
+    backward mask is applied to dY while it is staged.  Bit-identical to the unfused compositions.  transpose=True: with A^T."""
     _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     if gate is not None:
         _check_input(gate, "gate")
@@ -353,7 +503,7 @@ def forward_fused(input, nodePointer, edgeList, blockPartition, edgeToColumn, ed
     if N == 0 or D == 0:
         return [out]
     with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
         ws, ws_bytes = _workspace(plan, D, dev)
         st = _c.lib.tcgnn_spmm_fused(plan, input.data_ptr(), gate.data_ptr() if gate is not None else None, out.data_ptr(), D,
                                      1 if relu else 0, ws, ws_bytes, _stream_handle(dev))
@@ -371,12 +521,14 @@ def _check_vector(t, name, n, dev):
 
 
 def forward_scaled(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_scale=None, col_scale=None,
-                   bias=None, relu=False, gate=None):
+                   bias=None, relu=False, gate=None, transpose=False):
     """Not in the reference module: the normalised GCN aggregation with its element-wise steps fused in (tcgnn_spmm_scaled),
         Y = act(row_scale[:, None] * (A @ (col_scale[:, None] * X')) + bias),  X' = input * (gate > 0) when gate is given,
     act = ReLU when relu=True.  row_scale / col_scale: fp32 [N], bias: fp32 [D], gate: like input; each may be None.  The
     column scale is applied while the input is staged, the rest where the kernel stores Y: bit-identical to the unfused
-    composition forward(col_scale * X') * row_scale + bias, then ReLU, on every walk.  degree_scales gives DGL's scales."""
+    composition forward(col_scale * X') * row_scale + bias, then ReLU, on every walk.  degree_scales gives DGL's scales.
+    transpose=True: A^T in place of A, act(row_scale * (A^T @ (col_scale * X')) + bias) - the backward aggregation of the normalised
+    layer on a directed graph."""
     # shapes and dtypes of the optional operands first (they do not depend on the device), then the six of forward
     if isinstance(input, torch.Tensor) and input.dim() == 2:
         for t, name, n in ((row_scale, "row_scale", input.size(0)), (col_scale, "col_scale", input.size(0)), (bias, "bias", input.size(1))):
@@ -406,7 +558,7 @@ def forward_scaled(input, nodePointer, edgeList, blockPartition, edgeToColumn, e
         return [out]
     ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
         ws, ws_bytes = _workspace(plan, D, dev)
         st = _c.lib.tcgnn_spmm_scaled(plan, input.data_ptr(), ptr(col_scale), ptr(gate), ptr(row_scale), ptr(bias), out.data_ptr(), D,
                                       1 if relu else 0, ws, ws_bytes, _stream_handle(dev))
@@ -507,8 +659,10 @@ def forward_gemm(input, weights, nodePointer, edgeList, blockPartition, edgeToCo
     return [out]
 
 
-def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, edgeToColumn, edgeToRow):
-    """SpMM with edge values  Y = A_val @ input,  A_val[row(e), col(e)] = edgeAttention[0, e]."""
+def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, edgeToColumn, edgeToRow, transpose=False):
+    """SpMM with edge values  Y = A_val @ input,  A_val[row(e), col(e)] = edgeAttention[0, e].
+    transpose=True (not in the reference module): Y = A_val^T @ input, edgeAttention still in A's CSR order (row 0): the values are
+    permuted into A^T's order (tcgnn_permute_edge_values, into a buffer held per stream) and A^T's plan aggregates them."""
     _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     _check_input(edgeAttention, "edgeAttention")
     _check_float(edgeAttention, "edgeAttention")
@@ -523,9 +677,16 @@ def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, ed
     if N == 0 or D == 0:
         return [out]
     with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        val = edgeAttention.data_ptr()
+        if transpose:
+            tr = _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+            plan, buf = tr["plan"], _values_buffer(E, dev)
+            _c.check(_c.lib.tcgnn_permute_edge_values(val, tr["perm"].data_ptr(), E, buf.data_ptr(), _stream_handle(dev)), "tcgnn_permute_edge_values")
+            val = buf.data_ptr()
+        else:
+            plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
         ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm_val(plan, input.data_ptr(), edgeAttention.data_ptr(), out.data_ptr(), D, ws, ws_bytes,
+        st = _c.lib.tcgnn_spmm_val(plan, input.data_ptr(), val, out.data_ptr(), D, ws, ws_bytes,
                                    _stream_handle(dev))
     _c.check(st, "tcgnn_spmm_val")
     return [out]

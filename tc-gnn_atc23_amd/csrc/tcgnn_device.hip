@@ -354,6 +354,8 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 
 #include "tcgnn_small_fallback.inc"
 
+#include "tcgnn_transpose.inc"
+
 // ------------------------------------------------------------------------------------------
 // launch tables
 // ------------------------------------------------------------------------------------------

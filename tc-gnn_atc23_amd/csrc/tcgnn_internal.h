@@ -16,5 +16,14 @@ constexpr int kTcCols = 8;     // BLK_W
 constexpr int kWbCols = 32;    // condensed columns per MFMA operand tile (K of 16x16x32)
 constexpr int kMaxChunkDims = 128; // feature columns handled by one workgroup pass
 
+// Launchers of the CSR transpose's hand-written kernels (tcgnn_transpose.inc, compiled into tcgnn_device.hip; the rocPRIM sort and the
+// entry points are in tcgnn_transpose.hip).  Stream-ordered; each returns the hipError_t of its launch as an int.
+int transpose_row_ids(const int32_t* rowptr, int32_t N, int64_t E, int32_t* rowid, void* stream);
+int transpose_row_pointers(const uint32_t* sorted_keys, int64_t E, int32_t N, int32_t* rowptr_t, void* stream);
+int transpose_gather_rows(const int32_t* perm, const int32_t* rowid, int64_t E, int32_t* col_t, void* stream);
+int transpose_check(const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_t, const int32_t* col_t, int32_t N, int64_t E,
+                    uint32_t* res, void* stream);
+int permute_edge_values(const float* val, const int32_t* perm, int64_t E, float* out, void* stream);
+
 } // namespace tcgnn
 #endif

@@ -93,10 +93,38 @@ SHAPES = {  # name: (N, nnz target, in_dim, classes) - SURVEY.md 8(d)
 }
 
 
-def _symmetric_csr(n, nnz_target, draw, g, dev, rounds=6):
+def _directed_csr(n, nnz_target, draw, g, dev, rounds):
+    """The directed counterpart of _symmetric_csr: each drawn pair (a, b) is the CSR entry (a, b) as it is - not symmetrised -, self
+    loops dropped, de-duplicated, topped up towards the target and cut down to it at random; canonical CSR."""
+    want_total = int(nnz_target)
+    keys = torch.empty(0, dtype=torch.int64, device=dev)
+    want, boost = want_total, 1.002
+    for _ in range(rounds):
+        m = int(want * boost) + 16
+        a, b = draw(m)
+        keep = a != b
+        before = keys.numel()
+        keys = torch.unique(torch.cat([keys, a[keep] * n + b[keep]]))
+        if keys.numel() >= want_total:
+            break
+        gained = keys.numel() - before
+        boost = min(64.0, max(boost, 1.05 * m / max(gained, 1)))
+        want = want_total - keys.numel()
+    if keys.numel() > want_total:
+        keys = torch.sort(keys[torch.randperm(keys.numel(), generator=g, device=dev)[:want_total]])[0]
+    rows, cols = keys // n, (keys % n).to(torch.int32)
+    counts = torch.bincount(rows, minlength=n)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(counts, 0)
+    return rowptr.to(torch.int32), cols.contiguous()
+
+
+def _symmetric_csr(n, nnz_target, draw, g, dev, rounds=6, directed=False):
     """Canonical symmetric CSR without self loops from an endpoint sampler: draw(m) -> (a, b) int64 tensors of m candidate
     pairs.  Pairs are symmetrised, de-duplicated and topped up until nnz is within ~0.1 % of the target (or the sampler
-    stops producing new pairs: heavy-tailed samplers saturate their hubs)."""
+    stops producing new pairs: heavy-tailed samplers saturate their hubs).  directed=True: no symmetrisation (_directed_csr)."""
+    if directed:
+        return _directed_csr(n, nnz_target, draw, g, dev, rounds)
     half = int(nnz_target) // 2
     keys = torch.empty(0, dtype=torch.int64, device=dev)
     want, boost = half, 1.002
@@ -123,10 +151,11 @@ def _symmetric_csr(n, nnz_target, draw, g, dev, rounds=6):
     return rowptr.to(torch.int32), cols.contiguous()
 
 
-def synthetic_csr(num_nodes, nnz_target, seed=0, device="cpu", skew=0.0):
+def synthetic_csr(num_nodes, nnz_target, seed=0, device="cpu", skew=0.0, directed=False):
     """Seeded symmetric graph without self loops, canonical CSR, nnz within ~0.1 % of the target.
     skew = 0: uniform endpoints; skew > 0: one endpoint drawn as floor(N * u^(1+skew)) of a random
-    permutation (heavier tail).  Returns int32 (row_pointers, column_index) on `device`."""
+    permutation (heavier tail).  Returns int32 (row_pointers, column_index) on `device`.
+    directed=True (every generator here): the drawn pairs as directed entries, not symmetrised (A != A^T)."""
     dev = torch.device(device)
     g = torch.Generator(device=dev).manual_seed(seed)
     n = int(num_nodes)
@@ -141,10 +170,10 @@ def synthetic_csr(num_nodes, nnz_target, seed=0, device="cpu", skew=0.0):
             perm = torch.randperm(n, generator=g, device=dev)
             a = perm[a]
         return a, b
-    return _symmetric_csr(n, nnz_target, draw, g, dev)
+    return _symmetric_csr(n, nnz_target, draw, g, dev, directed=directed)
 
 
-def rmat_csr(num_nodes, nnz_target, seed=0, device="cpu", abcd=(0.57, 0.19, 0.19, 0.05), shuffle=False):
+def rmat_csr(num_nodes, nnz_target, seed=0, device="cpu", abcd=(0.57, 0.19, 0.19, 0.05), shuffle=False, directed=False):
     """Seeded R-MAT graph (a, b, c, d = 0.57, 0.19, 0.19, 0.05), symmetrised, self loops removed, de-duplicated,
     canonical CSR.  Endpoints are drawn in the 2^s x 2^s square (s = ceil(log2 N)) one bit per level and pairs with an
     endpoint >= N are discarded, which keeps the recursive-quadrant distribution for any N.  Low ids are the hubs and
@@ -172,10 +201,10 @@ def rmat_csr(num_nodes, nnz_target, seed=0, device="cpu", abcd=(0.57, 0.19, 0.19
         if perm is not None:
             src, dst = perm[src], perm[dst]
         return src, dst
-    return _symmetric_csr(n, nnz_target, draw, g, dev, rounds=14)
+    return _symmetric_csr(n, nnz_target, draw, g, dev, rounds=14, directed=directed)
 
 
-def sbm_csr(num_nodes, nnz_target, seed=0, device="cpu", blocks=50, p_in=0.9, shuffle=False, hubs=0, p_hub=0.0):
+def sbm_csr(num_nodes, nnz_target, seed=0, device="cpu", blocks=50, p_in=0.9, shuffle=False, hubs=0, p_hub=0.0, directed=False):
     """Seeded stochastic-block-model graph - the "community" variant SURVEY.md 8d asks for next to the uniform one because
     condensing depends on locality: `blocks` equal communities of consecutive ids; an edge stays inside its first endpoint's
     community with probability p_in, else its second endpoint is uniform.  Same post-processing as synthetic_csr.
@@ -202,17 +231,17 @@ def sbm_csr(num_nodes, nnz_target, seed=0, device="cpu", blocks=50, p_in=0.9, sh
         if perm is not None:
             a, b = perm[a], perm[b]
         return a, b
-    return _symmetric_csr(n, nnz_target, draw, g, dev, rounds=10)
+    return _symmetric_csr(n, nnz_target, draw, g, dev, rounds=10, directed=directed)
 
 
-def sbm_hubs_csr(num_nodes, nnz_target, seed=0, device="cpu"):
+def sbm_hubs_csr(num_nodes, nnz_target, seed=0, device="cpu", directed=False):
     """The 50-community graph with 64 hubs that hold 8 % of the edge endpoints (communities and a power-law tail at once)."""
-    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, hubs=64, p_hub=0.08)
+    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, hubs=64, p_hub=0.08, directed=directed)
 
 
-def sbm_shuffled_csr(num_nodes, nnz_target, seed=0, device="cpu"):
+def sbm_shuffled_csr(num_nodes, nnz_target, seed=0, device="cpu", directed=False):
     """The 50-community graph under random node ids: the structure is there, the numbering hides it (what community_order undoes)."""
-    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, shuffle=True)
+    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, shuffle=True, directed=directed)
 
 
 # In-community edge share at which the 50-community graph of the Reddit shape condenses to as many 16x8 TC blocks as the REAL Reddit
@@ -222,9 +251,9 @@ def sbm_shuffled_csr(num_nodes, nnz_target, seed=0, device="cpu"):
 SBM_REDDIT_P_IN = 0.225
 
 
-def sbm_reddit_csr(num_nodes, nnz_target, seed=0, device="cpu"):
+def sbm_reddit_csr(num_nodes, nnz_target, seed=0, device="cpu", directed=False):
     """The 50-community graph calibrated to real Reddit's condensability (SBM_REDDIT_P_IN)."""
-    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, p_in=SBM_REDDIT_P_IN)
+    return sbm_csr(num_nodes, nnz_target, seed=seed, device=device, p_in=SBM_REDDIT_P_IN, directed=directed)
 
 
 GENERATORS = {"uniform": synthetic_csr, "rmat": rmat_csr, "sbm": sbm_csr, "sbm_reddit": sbm_reddit_csr, "sbm_hubs": sbm_hubs_csr, "sbm_shuffled": sbm_shuffled_csr}
@@ -299,14 +328,15 @@ def permute_csr(row_pointers, column_index, order):
     return rp.to(torch.int32), (key % n).to(torch.int32)
 
 
-def synthetic_shape(name, seed=0, device="cpu", scale=1.0, generator="uniform"):
+def synthetic_shape(name, seed=0, device="cpu", scale=1.0, generator="uniform", directed=False):
     """(row_pointers, column_index, in_dim, classes) for a named shape; `scale` shrinks N and nnz
-    together (tests use small scales); generator: "uniform", "rmat" or "sbm" (GENERATORS)."""
+    together (tests use small scales); generator: "uniform", "rmat" or "sbm" (GENERATORS); directed: not symmetrised."""
     n, nnz, dim, classes = SHAPES[name]
     n2 = max(16, int(n * scale))
     nnz2 = max(2, int(nnz * scale * scale)) if scale < 1.0 else nnz
     nnz2 = min(nnz2, n2 * (n2 - 1) // 2)
-    rp, col = GENERATORS[generator](n2, nnz2, seed=seed, device=device)
+    kw = {"directed": True} if directed else {}
+    rp, col = GENERATORS[generator](n2, nnz2, seed=seed, device=device, **kw)
     return rp, col, dim, classes
 
 

@@ -13,7 +13,9 @@ gnn_conv.py:26-247, so a model written against the reference runs against this f
 
 The reference's backward uses A, not A^T (it assumes a symmetric graph) and does not propagate
 through ef into H; both are reproduced because the golden fixtures captured from gnn_conv.py
-(tests/golden/layers_n200.npz) pin exactly that.
+(tests/golden/layers_n200.npz) pin exactly that.  directed=True (every Function and module here, not in
+the reference) keeps the forward pass and back-propagates through A^T instead - the correct gradients
+on a directed graph (the backend's transpose=True operators; on a symmetric graph the same plan).
 
 The operators come from `backend()`: the TCGNN module of this package (HIP kernels).  Tests on a
 machine without a GPU may install another object with the same three functions via set_backend().
@@ -225,32 +227,41 @@ def dense_update(X, W):
     return _DenseUpdate.apply(X, W)
 
 
+def _bwd_kw(directed):
+    """keyword arguments of a backward aggregation: A^T on a directed graph, nothing otherwise (the reference's calls, unchanged)"""
+    return {"transpose": True} if directed else {}
+
+
 class TCGNNFunction_SAG(torch.autograd.Function):
     """Pure neighbour aggregation."""
 
     @staticmethod
-    def forward(ctx, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+    def forward(ctx, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, directed=False):
         ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.bwd = _bwd_kw(directed)
         return backend().forward(X, *ctx.meta)[0]
 
     @staticmethod
     def backward(ctx, d_output):
-        d_input = backend().forward(d_output.contiguous(), *ctx.meta)[0] if ctx.needs_input_grad[0] else None
-        return (d_input,) + (None,) * 5
+        d_input = backend().forward(d_output.contiguous(), *ctx.meta, **ctx.bwd)[0] if ctx.needs_input_grad[0] else None
+        return (d_input,) + (None,) * 6
 
 
 class TCGNNFunction(torch.autograd.Function):
     """GCN layer: dense update first, aggregation second."""
 
     @staticmethod
-    def forward(ctx, X, weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, fuse_relu=False, aggregate_first=False):
+    def forward(ctx, X, weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, fuse_relu=False, aggregate_first=False,
+                directed=False):
         """fuse_relu (not in the reference): the ReLU that follows the layer (main_tcgnn.py:100-139) runs in the
         SpMM kernel's stores, and its backward mask is applied to dY while dY is staged - relu(layer(x)) without the two
         element-wise passes over N x D.  Same values as F.relu(layer(x)), bit for bit.
         aggregate_first (f3, opt-in): A (X W) evaluated as (A X) W in ONE launch (backend().forward_gemm: the dense update in the
         aggregation kernel's epilogue) - the same matrix, rounded at a different point (X, not X W, meets the 10-bit operand
-        rounding).  The backward pass is unchanged: it only needs X, W and dY."""
+        rounding).  The backward pass is unchanged: it only needs X, W and dY.
+        directed: the backward aggregation G is A^T dY (A^T (dY * [Y > 0]) when fused)."""
         ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.bwd = _bwd_kw(directed)
         ctx.fused = bool(fuse_relu) and hasattr(backend(), "forward_fused")
         if aggregate_first and not fuse_relu and hasattr(backend(), "forward_gemm") and max(weights.shape) <= 128:
             ctx.fused = False
@@ -276,28 +287,31 @@ class TCGNNFunction(torch.autograd.Function):
     def backward(ctx, d_output):
         if ctx.fused:
             X, weights, Y = ctx.saved_tensors
-            g = backend().forward_fused(d_output.contiguous(), *ctx.meta, gate=Y)[0]
+            g = backend().forward_fused(d_output.contiguous(), *ctx.meta, gate=Y, **ctx.bwd)[0]
         elif getattr(ctx, "masked", False):
             X, weights, Y = ctx.saved_tensors
-            g = backend().forward((d_output * (Y > 0)).contiguous(), *ctx.meta)[0]
+            g = backend().forward((d_output * (Y > 0)).contiguous(), *ctx.meta, **ctx.bwd)[0]
         else:
             X, weights = ctx.saved_tensors
-            g = backend().forward(d_output.contiguous(), *ctx.meta)[0]
+            g = backend().forward(d_output.contiguous(), *ctx.meta, **ctx.bwd)[0]
         # the input features of the first layer need no gradient: skip their N x in_dim product
         d_input = tall_nt_mm(g, weights) if ctx.needs_input_grad[0] else None
-        return (d_input, tall_tn_mm(X, g)) + (None,) * 7
+        return (d_input, tall_tn_mm(X, g)) + (None,) * 8
 
 
 class TCGNNFunction_Scaled(torch.autograd.Function):
     """Normalised GCN layer (DGL GraphConv, norm='both' / 'right' / 'left', bias): Y = act(r * (A (c * (X W))) + b) in one
     aggregation (backend().forward_scaled: the column scale applied while X W is staged, row scale, bias and ReLU in the kernel's
     stores).  r, c: fp32 [N] or None; b: fp32 [D_out] or None; act = ReLU when fuse_relu.
-    bwd (A = A^T, as every layer here assumes): dZ = dY * (Y > 0) when fused; G = c * (A (r * dZ)) - the scales swap roles
-    under the transpose - as ONE forward_scaled(dY, row_scale=c, col_scale=r, gate=Y); dX = G W^T; dW = X^T G; db = sum_rows dZ."""
+    bwd (A = A^T, as every layer here assumes unless directed=True): dZ = dY * (Y > 0) when fused; G = c * (A (r * dZ)) - the scales swap roles
+    under the transpose - as ONE forward_scaled(dY, row_scale=c, col_scale=r, gate=Y); dX = G W^T; dW = X^T G; db = sum_rows dZ.
+    directed=True: G = c * (A^T (r * dZ)), forward_scaled(..., transpose=True) - the gradient on a graph with A != A^T."""
 
     @staticmethod
-    def forward(ctx, X, weights, bias, row_scale, col_scale, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, fuse_relu=False):
+    def forward(ctx, X, weights, bias, row_scale, col_scale, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, fuse_relu=False,
+                directed=False):
         ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.bwd = _bwd_kw(directed)
         ctx.relu = bool(fuse_relu)
         ctx.has_bias = bias is not None
         ctx.scales = (row_scale, col_scale)
@@ -315,15 +329,15 @@ class TCGNNFunction_Scaled(torch.autograd.Function):
         d_output = d_output.contiguous()
         if ctx.relu:
             X, weights, Y = ctx.saved_tensors
-            g = backend().forward_scaled(d_output, *ctx.meta, row_scale=col_scale, col_scale=row_scale, gate=Y)[0]
+            g = backend().forward_scaled(d_output, *ctx.meta, row_scale=col_scale, col_scale=row_scale, gate=Y, **ctx.bwd)[0]
         else:
             X, weights = ctx.saved_tensors
-            g = backend().forward_scaled(d_output, *ctx.meta, row_scale=col_scale, col_scale=row_scale)[0]
+            g = backend().forward_scaled(d_output, *ctx.meta, row_scale=col_scale, col_scale=row_scale, **ctx.bwd)[0]
         d_bias = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
             d_bias = (d_output * (Y > 0)).sum(0) if ctx.relu else d_output.sum(0)
         d_input = tall_nt_mm(g, weights) if ctx.needs_input_grad[0] else None
-        return (d_input, tall_tn_mm(X, g), d_bias) + (None,) * 8
+        return (d_input, tall_tn_mm(X, g), d_bias) + (None,) * 9
 
 
 def degree_scales(row_pointers, column_index, norm):
@@ -339,8 +353,9 @@ class TCGNNFunction_GIN(torch.autograd.Function):
     """GIN layer: aggregation first, dense update second."""
 
     @staticmethod
-    def forward(ctx, X, weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+    def forward(ctx, X, weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, directed=False):
         ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.bwd = _bwd_kw(directed)   # (directed: dX = A^T (dY W^T))
         if not any(ctx.needs_input_grad[:2]) and hasattr(backend(), "forward_gemm") and max(weights.shape) <= 128:
             # inference: the dense update runs in the aggregation kernel's epilogue (f3), A X never reaches memory.  Training
             # keeps the two steps: the weight gradient is (A X)^T dY (gnn_conv.py:111) and needs A X
@@ -355,8 +370,8 @@ class TCGNNFunction_GIN(torch.autograd.Function):
         d_weights = tall_tn_mm(agg, d_output.contiguous())
         d_input = None
         if ctx.needs_input_grad[0]:
-            d_input = backend().forward(tall_nt_mm(d_output.contiguous(), weights), *ctx.meta)[0]
-        return (d_input, d_weights) + (None,) * 5
+            d_input = backend().forward(tall_nt_mm(d_output.contiguous(), weights), *ctx.meta, **ctx.bwd)[0]
+        return (d_input, d_weights) + (None,) * 6
 
 
 class TCGNNFunction_AGNN(torch.autograd.Function):
@@ -364,15 +379,18 @@ class TCGNNFunction_AGNN(torch.autograd.Function):
 
     When the backend offers the fused products (TCGNN.agnn_fused_*: one gather of the neighbour rows
     for both, no [E]-sized attention / gradient tensors) they are used; the values are those of the
-    separate calls below, which remain the path for anything the fused kernels do not cover."""
+    separate calls below, which remain the path for anything the fused kernels do not cover.
+    directed=True: G = A_att^T dY (forward_AGNN(..., transpose=True)); the fused pair (whose backward aggregates with A_att) is not
+    used, the separate calls are."""
 
     @staticmethod
-    def forward(ctx, X, weights, attention_w, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+    def forward(ctx, X, weights, attention_w, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, directed=False):
         meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
         H = tall_mm(X, weights)
         b = backend()
         ctx.meta = meta
-        ctx.fused = bool(USE_FUSED_AGNN and attention_w.numel() == 1 and hasattr(b, "agnn_fused_forward")
+        ctx.bwd = _bwd_kw(directed)
+        ctx.fused = bool(not directed and USE_FUSED_AGNN and attention_w.numel() == 1 and hasattr(b, "agnn_fused_forward")
                          and b.agnn_fused_supported(H, *meta))
         if ctx.fused:
             w1 = attention_w.detach().reshape(1).contiguous()
@@ -398,7 +416,7 @@ class TCGNNFunction_AGNN(torch.autograd.Function):
             d_attention_w = d_w.reshape(1, n_heads)
         else:
             X, weights, att = ctx.saved_tensors
-            g = b.forward_AGNN(d_output, row_pointers, column_index, att, blockPartition, edgeToColumn, edgeToRow)[0]
+            g = b.forward_AGNN(d_output, row_pointers, column_index, att, blockPartition, edgeToColumn, edgeToRow, **ctx.bwd)[0]
             d_att = b.forward_ef(d_output, *ctx.meta)[0]
             # reference: mm(d_att[None, :].expand(n_heads, -1), column_index[:, None].float()).T, i.e. the
             # dot product <d_att, column_index> per head.  As an [n_heads, E] x [E] matrix-vector product:
@@ -406,15 +424,16 @@ class TCGNNFunction_AGNN(torch.autograd.Function):
             d_attention_w = torch.mv(d_att[None, :].expand(n_heads, -1), column_index.float()).reshape(1, n_heads)
         d_input = tall_nt_mm(g, weights) if ctx.needs_input_grad[0] else None
         d_weights = tall_tn_mm(X, g)
-        return (d_input, d_weights, d_attention_w) + (None,) * 5
+        return (d_input, d_weights, d_attention_w) + (None,) * 6
 
 
 class SAG(torch.nn.Module):
     """Holds the graph metadata; profile() times `num_rounds` bare aggregations (gnn_conv.py:179-190,
     the single-kernel benchmark of 2_tcgnn_single_kernel.py) and prints the line 1_log2csv.py scrapes."""
 
-    def __init__(self, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+    def __init__(self, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, directed=False):
         super().__init__()
+        self.directed = bool(directed)   # backward through A^T (not in the reference)
         self.row_pointers = row_pointers
         self.column_index = column_index
         self.blockPartition = blockPartition
@@ -426,7 +445,8 @@ class SAG(torch.nn.Module):
             prefetch(row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
 
     def forward(self, X):
-        return TCGNNFunction_SAG.apply(X, self.row_pointers, self.column_index, self.blockPartition, self.edgeToColumn, self.edgeToRow)
+        return TCGNNFunction_SAG.apply(X, self.row_pointers, self.column_index, self.blockPartition, self.edgeToColumn, self.edgeToRow,
+                                       self.directed)
 
     def profile(self, X, num_rounds=200):
         torch.cuda.synchronize()
@@ -444,13 +464,16 @@ class GCNConv(torch.nn.Module):
     """norm (not in the reference): 'none' (the reference's binary A), or DGL GraphConv's degree normalisation 'both'
     (D_in^-1/2 A D_out^-1/2), 'right' (D_in^-1 A, mean aggregation), 'left' (A D_out^-1); bias=True adds a learned [output_dim]
     bias (zeros at first, as DGL).  The defaults keep the reference's layer exactly.  A normalised / biased layer runs
-    TCGNNFunction_Scaled (aggregate_first does not apply to it: the fused dense update is binary)."""
+    TCGNNFunction_Scaled (aggregate_first does not apply to it: the fused dense update is binary).
+    directed=True (not in the reference): the backward pass aggregates with A^T - the layer's true gradient on a graph whose CSR is
+    not symmetric (the forward pass is unchanged; 'right' / 'left' exist mainly for such graphs)."""
 
-    def __init__(self, input_dim, output_dim, norm="none", bias=False):
+    def __init__(self, input_dim, output_dim, norm="none", bias=False, directed=False):
         super().__init__()
         if norm not in ("none", "both", "right", "left"):
             raise ValueError("norm must be 'none', 'both', 'right' or 'left', got %r" % (norm,))
         self.norm = norm
+        self.directed = bool(directed)
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))  # unscaled, as gnn_conv.py:195
         if bias:
             self.bias = torch.nn.Parameter(torch.zeros(output_dim))
@@ -467,12 +490,12 @@ class GCNConv(torch.nn.Module):
         if self.norm != "none" or self.bias is not None:
             r, c = degree_scales(row_pointers, column_index, self.norm)
             return TCGNNFunction_Scaled.apply(X, self.weights, self.bias, r, c, row_pointers, column_index, blockPartition, edgeToColumn,
-                                              edgeToRow, bool(fuse_relu))
+                                              edgeToRow, bool(fuse_relu), self.directed)
         if aggregate_first and not fuse_relu:
-            return TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, False, True)
+            return TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, False, True, self.directed)
         if fuse_relu and hasattr(backend(), "forward_fused"):
-            return TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, True)
-        y = TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+            return TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, True, False, self.directed)
+        y = TCGNNFunction.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, False, False, self.directed)
         return torch.relu(y) if fuse_relu else y
 
 
@@ -481,9 +504,10 @@ GIN_FUSED_INFERENCE = os.environ.get("TCGNN_GIN_FUSED_INFERENCE", "1") != "0"
 
 
 class GINConv(torch.nn.Module):
-    def __init__(self, input_dim, output_dim):
+    def __init__(self, input_dim, output_dim, directed=False):
         super().__init__()
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
+        self.directed = bool(directed)   # backward through A^T (not in the reference)
 
     def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
         # inference (no gradient will be asked for: grad mode off, or neither operand requires one) takes the one-launch form
@@ -498,14 +522,15 @@ class GINConv(torch.nn.Module):
         if (GIN_FUSED_INFERENCE and (not torch.is_grad_enabled() or not (X.requires_grad or self.weights.requires_grad)) and X.is_cuda
                 and hasattr(b, "forward_gemm") and max(self.weights.shape) <= getattr(b, "GEMM_FUSED_MAX_DIM", 128)):
             return b.forward_gemm(X, self.weights.detach(), row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)[0]
-        return TCGNNFunction_GIN.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        return TCGNNFunction_GIN.apply(X, self.weights, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, self.directed)
 
 
 class AGNNConv(torch.nn.Module):
-    def __init__(self, input_dim, output_dim):
+    def __init__(self, input_dim, output_dim, directed=False):
         super().__init__()
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
         self.attention_w = torch.nn.Parameter(torch.randn(1, n_heads))
+        self.directed = bool(directed)   # backward through A_att^T (not in the reference)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -514,4 +539,4 @@ class AGNNConv(torch.nn.Module):
 
     def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
         return TCGNNFunction_AGNN.apply(X, self.weights, self.attention_w, row_pointers, column_index, blockPartition,
-                                        edgeToColumn, edgeToRow)
+                                        edgeToColumn, edgeToRow, self.directed)

@@ -16,7 +16,8 @@ multi-GPU form below is the one SURVEY.md 8(e) derives from the path itself:
   * SDDMM shards the same way; ef stays sharded by edge range, no reduction.
   * graphs that fit one GPU can replicate X and skip the exchange (`exchange=False`).
   * backward of the aggregation uses A, not A^T, exactly like the reference's single-GPU layers
-    (gnn_conv.py:46,80: symmetric graphs), so it is the same gather + SpMM on dY.
+    (gnn_conv.py:46,80: symmetric graphs), so it is the same gather + SpMM on dY.  (The single-GPU layers take directed=True for
+    A^T on a directed graph; sharded plans do not have it: use a symmetric graph here.)
 
 Operators come from a backend: `HipShardOps` (C ABI, tcgnn_plan_create_sharded) on GPUs, or any
 object with the same three methods - the gloo world_size-2 tests on CPU pass an oracle-backed one.
