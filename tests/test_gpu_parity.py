@@ -550,9 +550,10 @@ def test_lds_resident_range_kernel_matches_oracle_and_plain_walk(dev, T, D, shap
         for mode in (1, 3):
             c.check(c.lib.tcgnn_set_spmm_mode(mode), "tcgnn_set_spmm_mode")
             out[mode] = T.forward(tX, trp, tcol, tbp, te2c, te2r)[0].cpu().numpy()
+        assert T.last_kernel(trp, tcol, tbp, te2c, te2r).startswith("spmm_lds_"), T.last_kernel(trp, tcol, tbp, te2c, te2r)   # (mode 3 did not take another walk)
     finally:
         c.lib.tcgnn_set_spmm_mode(0)
-    assert T.plan_info(trp, tcol, tbp, te2c, te2r)["lds_ranges"] in (0, (n + 503) // 504, (n + 631) // 632, (n + 759) // 760, (n + 1527) // 1528)   # finest cell stream built so far
+    assert T.plan_info(trp, tcol, tbp, te2c, te2r)["lds_ranges"] in ((n + 503) // 504, (n + 631) // 632, (n + 759) // 760, (n + 1527) // 1528)   # finest cell stream built so far
     Y64, absY = O.spmm_f64(X, rp, col)
     ref = O.spmm(X, rp, col, bp, e2c, e2r, round_mode=O.ROUND_TF32)
     for mode in (1, 3):
