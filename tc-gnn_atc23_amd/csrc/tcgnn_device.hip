@@ -28,7 +28,7 @@
 //   partial accumulators of the wavefronts are summed through LDS in a fixed order.
 //
 // File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator):
-//   tcgnn_device.hip          plan struct, range-guard helpers, launch tables, run_spmm / run_agnn, the C ABI
+//   tcgnn_device.hip          plan struct, range-guard helpers, launch tables, stage_features, run_agnn, the C ABI
 //   tcgnn_pack_stage.inc      plan-time kernels (pack, locality, longest row) and the staging pass (abs-max, fp16 images)
 //   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel, spmm_blocked_kernel            (+ generated tcgnn_lds_blocks.inc)
 //   tcgnn_lds_spmm.inc        LDS-resident SpMM, ordinary cell stream; cell-stream build kernels
@@ -38,6 +38,7 @@
 //   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
 //   tcgnn_small_fallback.inc  spmm_small_kernel, CSR kernels of non-canonical plans, the range guard's fallbacks, wide_patch_kernel
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
+//   tcgnn_spmm_dispatch.inc   host side of an SpMM call: SpmmCall, route_spmm (which walk runs), one launcher per walk, run_spmm
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -548,7 +549,6 @@ static size_t agnn_partial_bytes(const tcgnn_plan* plan) {
     return (slots * sizeof(double) + 255) / 256 * 256;
 }
 
-// enqueue absmax(X) [+ absmax(val)] + convert; returns the fp16 image pointer
 // The range-blocked walks bind up to 4 windows to one persistent wavefront for the whole launch: a hub window (skewed
 // degrees) then holds its wavefront far beyond the others (measured on a Reddit-sized graph with a 93 k-degree hub:
 // 2.48 ms against 1.60 ms for the per-window walk, which spreads a window over 4 wavefronts).  Automatic mode only takes
@@ -563,6 +563,18 @@ static bool windows_balanced(const tcgnn_plan* plan) {
 // 6250 windows the range-blocked walk left the chip a quarter full (0.33 / 1.03 ms against 0.13 / 0.66 ms per-window).
 static bool ranges_fit_l2(const tcgnn_plan* plan, size_t x16_bytes) {
     return plan->nbuckets > 0 && x16_bytes / (size_t)plan->nbuckets <= ((size_t)8 << 20) && plan->nw_eff >= 32 * plan->num_cus;
+}
+// automatic mode, SpMM and SDDMM alike: a range-major walk pays when the fp16 image overflows L2 and all of the above hold
+static bool range_walk_pays(const tcgnn_plan* plan, size_t x16_bytes) {
+    return x16_bytes > kBlockedMinBytes && windows_balanced(plan) && ranges_fit_l2(plan, x16_bytes) && !has_locality(plan);
+}
+// column ranges of a range-major walk: the image cut in halves until a range holds range_bytes (TCGNN_RANGE_KB, read per call, overrides
+// the operator's size - tests: several ranges on a graph the oracle can handle), at most one range per bucket
+static int range_count(const tcgnn_plan* plan, size_t x16_bytes, size_t range_bytes) {
+    if (const char* e = test_knob("TCGNN_RANGE_KB")) range_bytes = (size_t)atol(e) << 10;
+    int nranges = 1;
+    while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
+    return nranges;
 }
 // The fused AGNN kernel's walks beside the per-window one (agnn_kernel), for graphs whose numbering carries no locality of its own and
 // whose windows are alike, when the fp16 image does not fit an XCD's 4 MB L2 but an eighth of it does:
@@ -634,28 +646,10 @@ static Guard guard_spmm(const tcgnn_plan* p) { return {range_guard_of(p) ? (uint
 //  costs ~25 ms in the CSR fallbacks against 2 ms - so those two answer to the documented bound unless asked to be strict)
 static Guard guard_sddmm(const tcgnn_plan* p, int D) { const int lv = range_guard_of(p); return {lv >= 2 ? (uint32_t)(2 * std::max(D, 1)) : 0u, 2u | (lv >= 3 ? 0x100u : 0u)}; }   // (bit 8: strict, header word 9)
 
-// ldx > 0: X (and the gate) is a column block of a wider row-major matrix with that row stride; the scale words in the
-// header were then computed over the WHOLE matrix by the caller (block_of_wider = true: no memset, no absmax pass here), so
-// every block is rounded exactly as the undivided call would round it.
-static int stage_features(const tcgnn_plan* plan, const float* d_X, const float* d_val, int32_t D,
-                          void* ws, size_t ws_bytes, hipStream_t stream, const uint32_t** hdr_out,
-                          const _Float16** x16_out, int* dpad_out, int* pitch_out, bool planar = false, const float* d_gate = nullptr,
-                          int64_t ldx = 0, bool block_of_wider = false, const uint32_t* hdr_from = nullptr, const Guard* guard = nullptr,
-                          const float* d_cs = nullptr) {
-    // d_cs (tcgnn_spmm_scaled): the operand is d_cs[row] * X'[row, :] - absmax, tiny count and image all of that product
-    const Guard gx = guard ? *guard : guard_spmm(plan);   // (the binary SpMM's bound unless the caller's operator has its own)
-    // hdr_from: the scale words of an image of the same matrix staged a moment ago (the planar one of a plan with a cold remainder):
-    // copied instead of recomputed, so both images are rounded with the same scale without a second pass over X
-    const size_t need = workspace_bytes_for(plan->Nc, D);
-    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(TCGNN_ERR_WORKSPACE, "workspace: need %zu bytes 256-aligned, got %zu at %p", need, ws_bytes, ws);
-    uint32_t* hdr = static_cast<uint32_t*>(ws);
-    _Float16* x16 = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + kHdrBytes);
-    const int dpad = round_up(D, 16);
-    const int pitch = x16_pitch(dpad);
-    if (hdr_from) { HIP_TRY(hipMemcpyAsync(hdr, hdr_from, 32, hipMemcpyDeviceToDevice, stream)); block_of_wider = true; }
-    else if (!block_of_wider) HIP_TRY(hipMemsetAsync(hdr, 0, 64, stream));   // (words 0 .. 7: range words; 8: dirty-row count)
-    const int64_t nx = block_of_wider ? 0 : (int64_t)plan->Nc * D;
+// absmax(X) [+ absmax(val)] into the header's range words: X gated / column-scaled like the image will be (nx elements, 0: the words
+// exist already); the edge values under the SpMM's own cap
+static void launch_absmax(const tcgnn_plan* plan, const float* d_X, const float* d_gate, const float* d_cs, int64_t nx, int32_t D, const float* d_val, uint32_t* hdr, const Guard& gx,
+                          hipStream_t stream) {
     if (nx > 0) {
         const int grid = absmax_grid(nx);
         if (d_cs && d_gate) hipLaunchKernelGGL(absmax_scaled_kernel<true>, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, d_cs, nx, (int64_t)D, hdr, hdr + 2, gx.cap, gx.pow);
@@ -663,10 +657,44 @@ static int stage_features(const tcgnn_plan* plan, const float* d_X, const float*
         else if (d_gate) hipLaunchKernelGGL(absmax_gated_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, nx, hdr, hdr + 2, gx.cap, gx.pow);
         else hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, nx, hdr, hdr + 2, gx.cap, gx.pow);
     }
-    if (d_val && plan->E > 0 && !block_of_wider) {
+    if (d_val && plan->E > 0) {
         const int grid = absmax_grid(plan->E);
         hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_val, plan->E, hdr + 1, hdr + 3, guard_spmm(plan).cap, 0u);
     }
+}
+
+struct StagedImage { const uint32_t* hdr = nullptr; const _Float16* x16 = nullptr; int dpad = 0, pitch = 0; };
+struct StageOpts {
+    bool planar = false;                 // [dpad / 16 planes][Nc + 1][16 halves] for the LDS-resident kernels instead of row-major
+    const float* d_gate = nullptr;
+    // ldx > 0: X (and the gate) is a column block of a wider row-major matrix with that row stride; the scale words in the
+    // header were then computed over the WHOLE matrix by the caller (block_of_wider = true: no memset, no absmax pass here), so
+    // every block is rounded exactly as the undivided call would round it.
+    int64_t ldx = 0; bool block_of_wider = false;
+    // hdr_from: the scale words of an image of the same matrix staged a moment ago (the planar one of a plan with a cold remainder):
+    // copied instead of recomputed, so both images are rounded with the same scale without a second pass over X
+    const uint32_t* hdr_from = nullptr;
+    const Guard* guard = nullptr;        // (null: the binary SpMM's bound; else the caller's operator has its own)
+    const float* d_cs = nullptr;         // (tcgnn_spmm_scaled): the operand is d_cs[row] * X'[row, :] - absmax, tiny count and image all of that product
+};
+// enqueue absmax(X) [+ absmax(val)] + convert; *out: the fp16 image
+static int stage_features(const tcgnn_plan* plan, const float* d_X, const float* d_val, int32_t D, void* ws, size_t ws_bytes, hipStream_t stream, const StageOpts& o, StagedImage* out) {
+    const bool planar = o.planar;
+    const float* const d_gate = o.d_gate; const float* const d_cs = o.d_cs;
+    const int64_t ldx = o.ldx;
+    const uint32_t* const hdr_from = o.hdr_from;
+    const Guard gx = o.guard ? *o.guard : guard_spmm(plan);
+    const size_t need = workspace_bytes_for(plan->Nc, D);
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(TCGNN_ERR_WORKSPACE, "workspace: need %zu bytes 256-aligned, got %zu at %p", need, ws_bytes, ws);
+    uint32_t* hdr = static_cast<uint32_t*>(ws);
+    _Float16* x16 = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + kHdrBytes);
+    const int dpad = round_up(D, 16);
+    const int pitch = x16_pitch(dpad);
+    const bool block_of_wider = o.block_of_wider || hdr_from;
+    if (hdr_from) HIP_TRY(hipMemcpyAsync(hdr, hdr_from, 32, hipMemcpyDeviceToDevice, stream));
+    else if (!block_of_wider) HIP_TRY(hipMemsetAsync(hdr, 0, 64, stream));   // (words 0 .. 7: range words; 8: dirty-row count)
+    if (!block_of_wider) launch_absmax(plan, d_X, d_gate, d_cs, (int64_t)plan->Nc * D, D, d_val, hdr, gx, stream);
     const int64_t chunks = ((int64_t)plan->Nc + 1) * (dpad / 8);
     const unsigned cgrid = (unsigned)((chunks + 255) / 256);
     uint32_t* const tiny = hdr_from ? nullptr : hdr + 6;   // (a second image of the same matrix: its elements are counted already)
@@ -695,7 +723,7 @@ static int stage_features(const tcgnn_plan* plan, const float* d_X, const float*
         else     hipLaunchKernelGGL((convert_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, plan->Nc, D, dpad, pitch, x16, hdr, d_gate, ldx, tiny, dirty);
     }
     HIP_TRY(hipGetLastError());
-    *hdr_out = hdr; *x16_out = x16; *dpad_out = dpad; *pitch_out = pitch;
+    out->hdr = hdr; out->x16 = x16; out->dpad = dpad; out->pitch = pitch;
     return TCGNN_OK;
 }
 
@@ -837,361 +865,7 @@ static SyncArgs sync_args(const tcgnn_plan* plan, int pitch_bytes) {
     return SyncArgs{t.d_T, t.d_nk, t.kmax, std::min(m, t.kmax), t.S, t.R, t.nwx, 0, plan->nw_eff};
 }
 
-// columns one gather-walk launch may cover: the widest row whose pitch the structured descriptor can express, in whole
-// 128-column chunks.  Wider matrices go through the gather walks as independent column blocks (ld = the full row length).
-static constexpr int kMaxGatherBlockDims = 4096;
-
-static bool agnn_supported(const tcgnn_plan* plan, int32_t D);
-// widths the LDS-resident edge-valued walk covers: whole 64-column chunks of a canonical plan whose planar image one descriptor addresses -
-// and, r05, a remainder of THREE planes (Reddit's 41 classes), which goes as one more pair of 32-column chunks with the fourth plane filled
-// with zeros, exactly as the binary walk takes it (lds_passes): 0.85 against the gather walk's 1.48 ms on the calibrated SBM graph
-static bool val_lds_width_ok(const tcgnn_plan* plan, int dp) {
-    return (dp % 64 == 0 || dp % 64 == 48) && dp <= 2 * kMaxChunkDims && plan->canonical && plan->nw_eff > 0 && (int64_t)(dp / 16) * ((int64_t)plan->Nc + 1) * 32 < ((int64_t)1 << 32);
-}
-// tcgnn_spmm_scaled: the column scale enters the staging pass (and the kernels that read fp32 X), the row scale and bias the final store
-struct Scales { const float* col; const float* row; const float* bias; };
-static int run_spmm(const tcgnn_plan* plan, const float* d_X, const float* d_val, float* d_Y, int32_t D,
-                    void* ws, size_t ws_bytes, void* stream_v, int relu = 0, const float* d_gate = nullptr, const void* d_staged = nullptr,
-                    int64_t ld = 0, bool block_of_wider = false, const float* d_W = nullptr, int32_t D_out = 0, bool staged_planar = false,
-                    const Scales* sc = nullptr) {
-    if (!plan || D < 1 || (plan->N > 0 && ((!d_X && !d_staged) || !d_Y))) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm: null argument or D < 1");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (plan->N == 0) return TCGNN_OK;
-    if (ld == 0) ld = D;
-    if (!block_of_wider && (int64_t)plan->nw_eff * kWinRows < plan->N) // windows the caller did not describe stay zero, like zeros_like
-        HIP_TRY(hipMemsetAsync(d_Y, 0, (size_t)plan->N * (d_W ? D_out : D) * sizeof(float), stream));
-    const float* const d_cs = sc ? sc->col : nullptr;
-    const Epi epi{sc ? sc->row : nullptr, sc ? sc->bias : nullptr};
-    if (!block_of_wider && (int64_t)plan->nw_eff * kWinRows < plan->N && (epi.rs || epi.bias)) {   // (those rows: the epilogue of an empty sum)
-        const int64_t n = ((int64_t)plan->N - (int64_t)plan->nw_eff * kWinRows) * D;
-        hipLaunchKernelGGL(epi_fill_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, stream, d_Y, (int64_t)plan->nw_eff * kWinRows, plan->N, D, relu, epi);
-        HIP_TRY(hipGetLastError());
-    }
-    if (d_val && (!plan->canonical || plan->E < 4)) {
-        hipLaunchKernelGGL(spmm_val_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream,
-                           plan->rowptr, plan->col, d_val, d_X, d_Y, plan->N, D);
-        HIP_TRY(hipGetLastError());
-        return TCGNN_OK;
-    }
-    const int mode = spmm_mode_of(plan); // 0 auto, 1 plain, 2 blocked, 3 LDS-resident ranges, 4 single-launch fp32 kernel
-    if (!d_val && !d_staged && !d_W && plan->nw_eff > 0 && (mode == 4 || (mode == 0 && plan->total_wb <= kSmallMaxTiles))) {
-        const SpmmSmallArgs sa{plan->d_wb_ptr, plan->d_cols, plan->d_mask, d_X, d_gate, d_Y, plan->N, plan->Nc, D, relu, plan->nw_eff, nullptr};
-        KernelTimer timer(plan, stream, "spmm_small_kernel");
-        if (sc) hipLaunchKernelGGL(spmm_small_scaled_kernel, dim3((unsigned)plan->nw_eff, (unsigned)((D + 63) / 64)), dim3(64), 0, stream, SpmmSmallScaledArgs{sa, d_cs, epi});
-        else hipLaunchKernelGGL(spmm_small_kernel, dim3((unsigned)plan->nw_eff, (unsigned)((D + 63) / 64)), dim3(64), 0, stream, sa);
-        HIP_TRY(hipGetLastError());
-        return TCGNN_OK;
-    }
-    const uint32_t* hdr; const _Float16* x16; int dpad, pitch;
-    // (the planar image is addressed as planes * rows 32-byte records through one buffer descriptor: 31 bits of record index)
-    // (a caller-staged image is row-major - the gather walks - unless it was staged PLANAR for this kernel: tcgnn_spmm_staged_planar, r06)
-    bool lds = !d_val && (!d_staged || staged_planar) && !block_of_wider && plan->nw_eff > 0 && (mode == 3 || (mode == 0 && lds_chosen(plan, round_up(D, 16)))) &&
-               (int64_t)((D + 15) / 16) * ((int64_t)plan->Nc + 1) * 32 < ((int64_t)1 << 32);   // records * 32 B inside the descriptor's 32-bit offset
-    // f3 on the LDS-resident kernel: one pass stores its product, the two 32-column passes of a 64-column matrix ADD theirs into a
-    // zeroed Y (two addends: the sum does not depend on their order); wider inputs would need an ordered reduction - gather walk
-    if (lds && d_W && !(round_up(D, 16) <= 64 && !g_lds_maxw)) lds = false;
-    if (lds && block_of_wider) lds = false;
-    LdsPass passes[2]; int npass = 0;
-    if (lds) {
-        // every (layout, pass width) has its own cell stream, built the first time it is needed (plan creation builds the
-        // one a 64-column matrix uses; a first call with another width synchronises the stream once) - before the staging
-        // pass, which lays the image out for the kernel that will run, and before the timer starts
-        npass = lds_passes(round_up(D, 16), passes);
-        tcgnn_plan* mp = const_cast<tcgnn_plan*>(plan);
-        for (int i = 0; i < npass && lds; ++i) {
-            const int slot = lds_stream_of(passes[i].nt, passes[i].maxw);
-            if (plan->lds[slot].nranges > 0) continue;
-            // a stream that is being captured into a HIP graph cannot allocate or synchronise: this call takes the gather walks
-            // (nothing is remembered: the next call outside a capture builds the cell stream)
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone) {
-                if (mode == 3) return fail(TCGNN_ERR_INVALID_ARG, "LDS-resident SpMM: the cell stream of this width has to be built before the call is captured into a graph");
-                lds = false;
-                break;
-            }
-            const int b = build_lds_cells(mp, stream, slot);
-            if (b && mode == 3) return b;
-            if (b) {   // automatic mode: the gather walks need no stream (e.g. no memory left for it); remember the answer
-                lds = false;
-                if (round_up(D, 16) / 16 <= 64) plan->lds_choice[round_up(D, 16) / 16] = 0;
-            }
-        }
-    }
-    // ---- a plan with locality: the (workgroup, range) pairs too thin for a range fill were left out of the cell stream and sit
-    //      in a re-condensed remainder that the gather walk ADDS afterwards.  One stream must serve every pass of the call (the
-    //      remainder is per stream), the fused dense update cannot span two kernels, and a stream that kept less than half of the
-    //      columns is not worth its range fills at all.
-    const tcgnn_plan::CellStream* cold = nullptr;
-    if (lds) {
-        const tcgnn_plan::CellStream& c0 = plan->lds[lds_stream_of(passes[0].nt, passes[0].maxw)];
-        bool any_cold = false, thin = false, flat_cold = false;
-        for (int i = 0; i < npass; ++i) {
-            const tcgnn_plan::CellStream& ci = plan->lds[lds_stream_of(passes[i].nt, passes[i].maxw)];
-            // (a flat stream's remainder is added per pass from the planar image by spmm_cold_planar_kernel: no second image, any
-            //  number of passes - but not under the fused dense update, which needs the whole sum before it multiplies)
-            if (ci.flat_tpc) flat_cold = flat_cold || (ci.cold_tiles > 0 && !ci.d_wcold_ptr);   // (a remainder multiplied inside the flat kernel needs nothing from here)
-            else any_cold = any_cold || ci.cold_tiles > 0;
-            thin = thin || ci.hot_cols * 2 < ci.hot_cols + ci.cold_cols;
-        }
-        if ((any_cold && (npass > 1 || d_W)) || (flat_cold && d_W)) {
-            lds = false;
-            // (a width whose passes can never share one remainder: settle the choice, so later calls - and tcgnn_workspace_bytes, which
-            //  reserves a second image for LDS-chosen widths - stop coming back here)
-            if (any_cold && npass > 1 && mode != 3 && round_up(D, 16) / 16 <= 64) plan->lds_choice[round_up(D, 16) / 16] = 0;
-        }
-        else if (thin && mode != 3) { lds = false; if (round_up(D, 16) / 16 <= 64) plan->lds_choice[round_up(D, 16) / 16] = 0; }
-        else if (any_cold) cold = &c0;
-        if (lds && cold && staged_planar) lds = false;   // (the remainder's gather walk wants a row-major image of the same matrix: not in a planar staged call)
-    }
-    if (staged_planar && !lds)
-        return fail(TCGNN_ERR_UNSUPPORTED, "tcgnn_spmm_staged_planar: the LDS-resident kernel does not take this plan at %d columns (tcgnn_spmm_staged_layout tells; stage row-major and call tcgnn_spmm_staged)", D);
-    if (!lds && !pitch_fits_descriptor(D)) {
-        // a row too long for the gather walks' buffer descriptor: independent column blocks, every one rounded
-        // with the scale of the whole matrix (absmax over all of X / the edge values here, once)
-        if (d_staged) return fail(TCGNN_ERR_UNSUPPORTED, "tcgnn_spmm_staged: rows of %d columns exceed the %d-byte descriptor stride", D, kMaxStructStride);
-        if (block_of_wider) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm: nested column blocks");
-        const size_t need = workspace_bytes_for(plan->Nc, D);
-        if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-            return fail(TCGNN_ERR_WORKSPACE, "workspace: need %zu bytes 256-aligned, got %zu at %p", need, ws_bytes, ws);
-        uint32_t* whdr = static_cast<uint32_t*>(ws);
-        HIP_TRY(hipMemsetAsync(whdr, 0, 32, stream));
-        const int64_t nx = (int64_t)plan->Nc * D;
-        const int grid = absmax_grid(nx);
-        if (d_cs) hipLaunchKernelGGL(d_gate ? absmax_scaled_kernel<true> : absmax_scaled_kernel<false>, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, d_cs, nx, (int64_t)D, whdr, whdr + 2,
-                                     guard_spmm(plan).cap, 1u);
-        else if (d_gate) hipLaunchKernelGGL(absmax_gated_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, nx, whdr, whdr + 2, guard_spmm(plan).cap, 1u);
-        else hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, nx, whdr, whdr + 2, guard_spmm(plan).cap, 1u);
-        if (d_val && plan->E > 0) {
-            const int g2 = absmax_grid(plan->E);
-            hipLaunchKernelGGL(absmax_kernel, dim3(g2), dim3(kAbsmaxThreads), 0, stream, d_val, plan->E, whdr + 1, whdr + 3, guard_spmm(plan).cap, 0u);
-        }
-        HIP_TRY(hipGetLastError());
-        for (int c0 = 0; c0 < D; c0 += kMaxGatherBlockDims) {
-            const int db = std::min(kMaxGatherBlockDims, D - c0);
-            const Scales sb{d_cs, epi.rs, epi.bias ? epi.bias + c0 : nullptr};
-            const int rc = run_spmm(plan, d_X + c0, d_val, d_Y + c0, db, ws, ws_bytes, stream_v, relu, d_gate ? d_gate + c0 : nullptr, nullptr, D, true, nullptr, 0, false,
-                                    sc ? &sb : nullptr);
-            if (rc) return rc;
-        }
-        return TCGNN_OK;
-    }
-    // ---- edge values on the LDS-resident flat walk (r04, tcgnn_lds_val.inc): whole 64-column chunks, on graphs the binary SpMM's
-    //      time model sends to the LDS-resident kernel, canonical CSR (the single-edge stream is cut with the packed edge offsets).
-    //      The first such call builds the stream (unless it is being captured into a graph) and still takes a gather walk - its
-    //      workspace was sized before the stream existed; later calls find tcgnn_workspace_bytes grown by the slot values.
-    bool val_lds = false;
-    {
-        const int dp = round_up(D, 16);
-        if (d_val && !d_staged && !block_of_wider && !d_gate && !relu && !d_W && (mode == 0 || mode == 3) && val_lds_width_ok(plan, dp) && (mode == 3 || lds_chosen(plan, dp))) {
-            if (plan->val_choice.load(std::memory_order_acquire) < 0) {
-                hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-                if (!(hipStreamIsCapturing(stream, &capturing) == hipSuccess && capturing != hipStreamCaptureStatusNone)) {
-                    // (the stream is an optional acceleration - in automatic mode a failed build, e.g. no memory for its 0.9 GB
-                    //  of temporaries, settles the plan on the gather walks, as the binary path does; only the forced mode reports it)
-                    const int b = build_val_stream(const_cast<tcgnn_plan*>(plan), stream);
-                    if (b && mode == 3) return b;
-                    if (b) const_cast<tcgnn_plan*>(plan)->val_choice.store(0, std::memory_order_release);
-                }
-            }
-            val_lds = plan->val_choice.load(std::memory_order_acquire) == 1 && ws_bytes >= workspace_bytes_for(plan->Nc, D) + val_stream_bytes(plan);
-        }
-    }
-    if (d_staged) {   // the caller built the (row-major) fp16 image itself: tcgnn_spmm_staged
-        hdr = static_cast<const uint32_t*>(d_staged);
-        x16 = reinterpret_cast<const _Float16*>(static_cast<const char*>(d_staged) + kHdrBytes);
-        dpad = round_up(D, 16);
-        pitch = x16_pitch(dpad);   // (planar: [dpad / 16][Nc + 1][16] halves - the LDS branch below does not use the pitch)
-    } else {
-        const int rc = stage_features(plan, d_X, d_val, D, ws, ws_bytes, stream, &hdr, &x16, &dpad, &pitch, lds || val_lds, d_gate, block_of_wider ? ld : 0, block_of_wider,
-                                      nullptr, nullptr, d_cs);
-        if (rc) return rc;
-    }
-    if (plan->nw_eff == 0) return TCGNN_OK;
-    // the range guard's fallback, launched behind the fp16-path kernels of this call (returns at once unless the staged matrix is
-    // "wide": range_is_wide).  An image the caller staged itself carries no range words: no guard.
-    auto wide_fallback = [&]() -> int {
-        if (d_staged) return TCGNN_OK;
-        const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)plan->N + 3) / 4, 4096);
-        if (d_W) hipLaunchKernelGGL(spmm_gemm_wide_fallback_kernel, dim3(grid), dim3(256), 0, stream, hdr, plan->rowptr, plan->col, d_X, d_W, d_Y, plan->N, D, D_out, relu);
-        else if (!d_val && ld == D) {   // binary A, whole rows: the fp32-MFMA walk small graphs take anyway (10-bit operands, fp32's exponent)
-            const SpmmSmallArgs sa{plan->d_wb_ptr, plan->d_cols, plan->d_mask, d_X, d_gate, d_Y, plan->N, plan->Nc, D, relu, plan->nw_eff, hdr};
-            if (sc) hipLaunchKernelGGL(spmm_small_scaled_kernel, dim3((unsigned)std::min(plan->nw_eff, 2048), (unsigned)((D + 63) / 64)), dim3(64), 0, stream, SpmmSmallScaledArgs{sa, d_cs, epi});
-            else hipLaunchKernelGGL(spmm_small_kernel, dim3((unsigned)std::min(plan->nw_eff, 2048), (unsigned)((D + 63) / 64)), dim3(64), 0, stream, sa);
-        }
-        else if (sc) hipLaunchKernelGGL(spmm_wide_fallback_scaled_kernel, dim3(grid), dim3(256), 0, stream, hdr, plan->rowptr, plan->col, d_X, d_gate, d_cs, epi, d_Y,
-                                        plan->N, D, (int64_t)ld, (int64_t)ld, relu, plan->canonical ? 0 : 1);
-        else hipLaunchKernelGGL(spmm_wide_fallback_kernel, dim3(grid), dim3(256), 0, stream, hdr, d_val ? 1 : 0, plan->rowptr, plan->col, d_val, (const float*)nullptr, d_X, d_gate, d_Y,
-                                plan->N, D, (int64_t)ld, (int64_t)ld, relu, (!d_val && !plan->canonical) ? 1 : 0);
-        HIP_TRY(hipGetLastError());
-        return TCGNN_OK;
-    };
-    // ---- edge values on the LDS-resident flat walk (r04, tcgnn_lds_val.inc; decided above, before the staging pass)
-    if (val_lds) {
-        const tcgnn_plan::CellStream& cs = plan->lds[kLdsValSlot];
-        const size_t image = workspace_bytes_for(plan->Nc, D);
-        _Float16* const vals = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + image);
-        _Float16* const cvals = vals + (size_t)std::max<int64_t>(cs.tiles, 1) * 32;
-        KernelTimer timer(plan, stream, cs.cold_tiles > 0 ? "val_permute_kernel + spmm_lds_val_kernel + spmm_cold_val_kernel (cold remainder)" : "val_permute_kernel + spmm_lds_val_kernel");
-        {
-            static bool attr_set = false;
-            if (!attr_set) { HIP_TRY(hipFuncSetAttribute((const void*)val_permute_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kValSpanHalves * 2)); attr_set = true; }
-            hipLaunchKernelGGL(val_permute_kernel, dim3((unsigned)(cs.nwg * kLdsWaves * (kLdsMaxW2 / kValWpb))), dim3(kValThreads), kValSpanHalves * 2, stream, d_val, plan->rowptr, cs.d_order, cs.d_eidx16, cs.d_rbase, hdr,
-                               vals, plan->N, cs.cold_tiles > 0 ? cs.d_cold_ptr : nullptr, cs.d_cold_eidx16, cvals, cs.d_rl2, cs.dense_entries > 0 ? 1 : 0, std::max(cs.npairs, 1));
-            HIP_TRY(hipGetLastError());
-        }
-        const SpmmValArgs va{cs.d_flat, vals, cs.d_order, x16, hdr, d_Y, plan->N, D, dpad / 16, 0, plan->Nc + 1, plan->nw_eff, cs.nwg, cs.d_rbase, cs.d_rl2, std::max(cs.npairs, 1)};
-        HIP_TRY(launch_lds_val(va, (dpad + 31) / 32, stream));   // (a three-plane remainder: its last chunk's second plane lies beyond the matrix - zeros)
-        if (cs.cold_tiles > 0) {
-            const ColdValArgs ca{cs.d_cold_ptr, cs.d_cold_cols, cs.d_cold_mask, cvals, x16, hdr, d_Y, plan->N, D, plan->Nc + 1, plan->nw_eff, 0, dpad};
-            hipLaunchKernelGGL(spmm_cold_val_kernel, dim3((unsigned)((plan->nw_eff + 3) / 4), (unsigned)((dpad + 63) / 64)), dim3(256), 0, stream, ca);
-            HIP_TRY(hipGetLastError());
-        }
-        timer.stop();
-        return wide_fallback();
-    }
-    // ---- edge values on the fused AGNN kernel's XCD-sliced walk (r03).  Where the fused pair's backward pass takes that walk (graphs
-    //      without locality of their own, windows alike, an fp16 image of 16 - 64 MB: agnn_walk) the edge-valued SpMM is the same
-    //      gather with less to do per tile, so it runs as that kernel with the score half switched off (AgnnArgs::valonly: w = 1,
-    //      ef = the caller's values, their abs-max from this call's header): 76 % L2 hits and 5.8 GB of fabric reads instead of the
-    //      per-window walk's 31 % and 12.2 GB on the Reddit shape at D = 64.  Same operand rounding and scales; the sums run in slice order.
-    if (d_val && !d_staged && !block_of_wider && !d_gate && !relu && mode == 0 && dpad > 32 && dpad <= kMaxChunkDims && agnn_supported(plan, D)) {
-        int ns = 0;
-        const size_t need = workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan) + agnn_slice_bytes(plan, D);
-        if (agnn_walk(plan, D, true, &ns) == kAgnnSliced && ns > 0 && ws_bytes >= need) {
-            double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + workspace_bytes_for(plan->Nc, D));
-            float* const ypart = reinterpret_cast<float*>(static_cast<char*>(ws) + workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan));
-            AgnnArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, nullptr, const_cast<float*>(d_val), const_cast<uint32_t*>(hdr) + 1, ypart, partial,
-                       plan->N, plan->Nc, plan->row_off, dpad, D, pitch, plan->E, plan->rowptr, plan->d_bptr, plan->nbuckets, plan->nbuckets / ns, 0, plan->nw_eff, 0,
-                       image_is_big(plan->Nc, pitch), ns, 1, nullptr, agnn_rot(plan), 0, SyncArgs{}};
-            {
-                KernelTimer timer(plan, stream, "agnn_kernel (XCD-sliced, values only) + agnn_slice_sum_kernel");
-                HIP_TRY((launch_agnn<4, true, 0>(dpad / 16, a, ns * ((plan->nw_eff + 3) / 4), stream)));
-                const int64_t nsum = std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows) * D;   // (rows beyond the windows were zeroed above)
-                const unsigned sg = (unsigned)std::min<int64_t>(2048, (nsum / 4 + 255) / 256 + 1);
-                hipLaunchKernelGGL(agnn_slice_sum_kernel, dim3(sg), dim3(256), 0, stream, ypart, d_Y, nsum, (int64_t)plan->N * D, ns);
-                HIP_TRY(hipGetLastError());
-            }
-            return wide_fallback();
-        }
-    }
-    if (lds) {
-        int total_chunks = 0;
-        for (int i = 0; i < npass; ++i) total_chunks += passes[i].nchunks;
-        const int accumulate = (d_W && total_chunks > 1) ? 1 : 0;
-        if (accumulate) {
-            if (relu) return fail(TCGNN_ERR_UNSUPPORTED, "tcgnn_spmm_gemm: ReLU cannot be fused when the product is accumulated over column passes");
-            HIP_TRY(hipMemsetAsync(d_Y, 0, (size_t)plan->N * D_out * sizeof(float), stream));
-        }
-        const _Float16* x16_rows = nullptr;
-        if (cold) {   // the remainder's gather walk reads the row-major image: staged behind the planar one, with its scale words
-            const size_t image = workspace_bytes_for(plan->Nc, D);
-            if (ws_bytes < 2 * image) return fail(TCGNN_ERR_WORKSPACE, "tcgnn_spmm: a plan with a cold remainder stages two images: %zu bytes, got %zu", 2 * image, ws_bytes);
-            const uint32_t* hdr2; int dpad2, pitch2;
-            const int rc = stage_features(plan, d_X, nullptr, D, static_cast<char*>(ws) + image, ws_bytes - image, stream, &hdr2, &x16_rows, &dpad2, &pitch2, false, d_gate, 0,
-                                          false, hdr, nullptr, d_cs);
-            if (rc) return rc;
-        }
-        const tcgnn_plan::CellStream& cs0 = plan->lds[lds_stream_of(passes[0].nt, passes[0].maxw)];
-        // one launch, binary A, whole rows, nothing added behind it: the kernel is its own range-guard fallback (lds_own_fallback)
-        const bool own_fb = npass == 1 && !cold && !d_W && !d_staged && ld == D && !(cs0.flat_tpc && cs0.cold_tiles > 0 && !cs0.d_wcold_ptr) &&
-                            !sc;   // (a scaled call's fallback is the scaled fp32 kernel behind the launch)
-        const SpmmSmallArgs fb{plan->d_wb_ptr, plan->d_cols, plan->d_mask, d_X, d_gate, d_Y, plan->N, plan->Nc, D, relu, plan->nw_eff, own_fb ? hdr : nullptr};
-        KernelTimer timer(plan, stream, cold ? "spmm_lds_kernel + spmm_kernel (cold remainder)" :
-                                        (cs0.flat_tpc ? (cs0.cold_tiles > 0 && !cs0.d_wcold_ptr ? "spmm_lds_flat_kernel + spmm_cold_planar_kernel (cold remainder)" : "spmm_lds_flat_kernel") : "spmm_lds_kernel"));
-        for (int i = 0; i < npass; ++i) {
-            const tcgnn_plan::CellStream& cs = plan->lds[lds_stream_of(passes[i].nt, passes[i].maxw)];
-            if (cs.flat_tpc) {
-                const bool has_cold = cs.cold_tiles > 0 && !cs.d_wcold_ptr;
-                // (tcgnn_spmm_scaled: with a remainder behind it this kernel stores raw sums and spmm_cold_planar_kernel, the final writer,
-                //  applies row scale, bias and ReLU; otherwise its twin spmm_lds_flat_epi_kernel applies them in its own store)
-                SpmmFlatArgs f{cs.d_flat, cs.d_order, x16, hdr, d_Y, plan->N, D, dpad / 16, passes[i].chunk0, plan->Nc + 1, plan->nw_eff, cs.nwg, g_lds_dbg,
-                               has_cold ? 0 : relu, cs.d_rbase, cs.d_rl2, std::max(cs.npairs, 1), d_W, D_out, accumulate, g_lds_fill_quota, cs.d_wcold_ptr, cs.d_wcold, fb};
-                HIP_TRY(launch_flat_any(passes[i].maxw, passes[i].nt, cs.flat_tpc, f, passes[i].nchunks, stream, cs.dense_entries > 0, has_cold ? Epi{nullptr, nullptr} : epi));
-                if (has_cold && !(g_lds_dbg & 16)) {
-                    const int cd = lds_chunk_dims(passes[i].maxw);
-                    const int col0 = passes[i].chunk0 * cd, ncols = std::min(passes[i].nchunks * cd, dpad - col0);
-                    const ColdPlanarArgs ca{cs.d_cold_ptr, cs.d_cold_cols, cs.d_cold_mask, x16, hdr, d_Y, plan->N, D, plan->Nc + 1, plan->nw_eff, col0, ncols, relu, epi};
-                    hipLaunchKernelGGL(spmm_cold_planar_kernel, dim3((unsigned)((plan->nw_eff + 3) / 4), (unsigned)((ncols + 63) / 64)), dim3(256), 0, stream, ca);
-                    HIP_TRY(hipGetLastError());
-                }
-                continue;
-            }
-            SpmmLdsArgs l{cs.d_cell_ptr, cs.d_cell_tiles, cs.d_order, x16, hdr, d_Y, plan->N, D, dpad / 16, passes[i].chunk0, plan->Nc + 1,
-                          cs.nranges, plan->nw_eff, cs.nwg, g_lds_dbg, cold ? 0 : relu, cs.d_rbase, cs.d_rlist, d_W, D_out, accumulate, cs.d_parts, fb,
-                          cold ? Epi{nullptr, nullptr} : epi};
-            HIP_TRY(launch_lds_any(passes[i].maxw, passes[i].nt, l, passes[i].nchunks, stream));
-        }
-        if (cold) {
-            const int pitch_r = x16_pitch(dpad);
-            // (the per-tile metadata DMA fetches 16 edge-offset words too; binary SpMM never looks at them: the mask array stands in)
-            SpmmArgs a{cold->d_cold_ptr, plan->d_order, cold->d_cold_cols, cold->d_cold_mask, reinterpret_cast<const int32_t*>(cold->d_cold_mask), x16_rows, nullptr, hdr, d_Y, plan->N, D, pitch_r, 0, plan->E,
-                       plan->Nc + 1, relu, (int32_t)D, image_is_big(plan->Nc, pitch_r), nullptr, 0, 1, 0};
-            constexpr int cold_w4 = 48;   // tiles per window from which 4 wavefronts share it (SBM Reddit shape, 25 cold tiles per window: 169 us with one wavefront, 202 with four)
-            // (and a window with hundreds of cold tiles - a hub - is 0.25 us per tile of serial work for one wavefront)
-            const int waves = (cold->cold_tiles >= (int64_t)cold_w4 * plan->nw_eff || cold->cold_max >= 512) ? 4 : 1;
-            const int nfull = dpad / kMaxChunkDims, rem = (dpad % kMaxChunkDims) / 16;
-            if (nfull) { a.chunk0 = 0; HIP_TRY(launch_spmm_any(false, waves, 8, a, plan->nw_eff, nfull, stream, epi)); }
-            if (rem) { a.chunk0 = nfull; HIP_TRY(launch_spmm_any(false, waves, rem, a, plan->nw_eff, 1, stream, epi)); }
-        }
-        timer.stop();
-        return own_fb ? TCGNN_OK : wide_fallback();
-    }
-    SpmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, d_val, hdr, d_Y, plan->N, D, pitch, 0, plan->E, plan->Nc + 1, relu, (int32_t)ld,
-               image_is_big(plan->Nc, pitch), d_W, D_out, 0, d_staged ? 1 : 0};
-    if (d_W) a.ldy = D_out;
-    const int nfull = dpad / kMaxChunkDims, rem = (dpad % kMaxChunkDims) / 16;
-    // range-blocked walk when the fp16 image of X overflows L2 and the windows are long enough to cut
-    const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
-    // (a numbering with locality keeps the per-window walk: in XCD-contiguous order its co-resident workgroups share their gathered
-    //  rows in L2 - 50-community Reddit shape, edge values: 0.92 ms against 1.18 ms range-blocked; the range-blocked walk is for
-    //  graphs without it, where it wins by 1.4x)
-    const bool blocked = !d_W && plan->nbuckets > 0 && mode != 1 && (mode == 2 || (x16_bytes > kBlockedMinBytes && windows_balanced(plan) && ranges_fit_l2(plan, x16_bytes) && !has_locality(plan) &&
-                                                                                     // (edge values: two windows per wavefront instead of four; at Reddit's 30 MB image the per-window walk
-                                                                                     //  in contiguous order is 6 % faster - 1.70 against 1.79 ms per call - so only images beyond the Infinity Cache's reach)
-                                                                                     (!d_val || x16_bytes > ((size_t)64 << 20))));
-    // slice-synchronised range walk (r06, tcgnn_sync_walk.inc): communities larger than an XCD's L2; one launch per slice round
-    if (!d_W && !a.big && sync_chosen(plan, pitch * 2, mode, d_val ? kSyncVal : kSyncSpmm, dpad / 16)) {
-        KernelTimer timer(plan, stream, "spmm_sync_kernel");
-        SpmmSyncArgs sa{a, sync_args(plan, pitch * 2)};
-        auto wgs = [&](int nt) {   // workgroups per launch: what holds a slice (S windows per XCD, 4 wavefronts x MAXW windows per workgroup), at most what is resident
-            const bool val = d_val != nullptr;
-            const int per_xcd = std::min((plan->sync.S + 4 * sync_maxw(nt, val) - 1) / (4 * sync_maxw(nt, val)), plan->num_cus / kSyncXcds * sync_wgs_per_cu(nt, val));
-            return kSyncXcds * std::max(per_xcd, 1);
-        };
-        for (int r = 0; r < plan->sync.R; ++r) {
-            sa.s.round = r;
-            if (nfull) { sa.base.chunk0 = 0; HIP_TRY(launch_sync_any(d_val != nullptr, 8, sa, wgs(8), nfull, stream, epi)); }
-            if (rem) { sa.base.chunk0 = nfull; HIP_TRY(launch_sync_any(d_val != nullptr, rem, sa, wgs(rem), 1, stream, epi)); }
-        }
-        timer.stop();
-        return wide_fallback();
-    }
-    KernelTimer timer(plan, stream, blocked ? "spmm_blocked_kernel" : "spmm_kernel");
-    if (blocked) {
-        size_t range_bytes = kRangeTargetBytes;
-        if (const char* e = test_knob("TCGNN_RANGE_KB")) range_bytes = (size_t)atol(e) << 10;   // (tests: several ranges on a graph the oracle can handle)
-        int nranges = 1;
-        while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
-        SpmmBlockedArgs b{a, plan->d_bptr, plan->nbuckets, plan->nbuckets / nranges, nranges, plan->nw_eff, 0};
-        auto wgs = [&](int nt) {   // persistent grid = what is resident at once: LDS per workgroup (4 wavefronts: tile buffers,
-                                   // pads, + the 4 KB A table) against 160 KB, and the register budget (4 or 2 workgroups per CU)
-            const bool val = d_val != nullptr;
-            const int maxw = blocked_maxw(nt, val);
-            b.ngroups = (plan->nw_eff + maxw - 1) / maxw;
-            const int lds_wg = 4 * (2 * nt * 1024 + kPadBytes + (val ? 1024 : 0)) + 4096;
-            const int per_cu = std::max(1, std::min(nt <= 4 ? 4 : 2, (160 * 1024) / lds_wg));
-            return std::min((b.ngroups + 3) / 4, plan->num_cus * per_cu);
-        };
-        if (nfull) { b.base.chunk0 = 0; const int n = wgs(8); HIP_TRY(launch_blocked_any(d_val != nullptr, 8, b, n, nfull, stream, epi)); }
-        if (rem) { b.base.chunk0 = nfull; const int n = wgs(rem); HIP_TRY(launch_blocked_any(d_val != nullptr, rem, b, n, 1, stream, epi)); }
-        timer.stop();
-        return wide_fallback();
-    }
-    if (nfull) { a.chunk0 = 0; HIP_TRY(launch_spmm_any(d_val != nullptr, plan->waves, 8, a, plan->nw_eff, nfull, stream, epi)); }
-    if (rem) { a.chunk0 = nfull; HIP_TRY(launch_spmm_any(d_val != nullptr, plan->waves, rem, a, plan->nw_eff, 1, stream, epi)); }
-    timer.stop();
-    return wide_fallback();
-}
+#include "tcgnn_spmm_dispatch.inc"
 
 static bool agnn_supported(const tcgnn_plan* plan, int32_t D) {
     return plan && plan->canonical && D >= 1 && D <= kMaxChunkDims && plan->E >= 8;
@@ -1216,10 +890,11 @@ static int run_agnn(const tcgnn_plan* plan, const float* d_X, const float* d_w, 
         if (!bwd) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
     }
     if (!bwd) HIP_TRY(hipMemsetAsync(d_absmax, 0, sizeof(uint32_t), stream));
-    const uint32_t* hdr; const _Float16* x16; int dpad, pitch;
     const Guard gsd = guard_sddmm(plan, D);
-    int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, &hdr, &x16, &dpad, &pitch, false, nullptr, 0, false, nullptr, &gsd);
-    if (rc) return rc;
+    StageOpts so; so.guard = &gsd;
+    StagedImage im;
+    if (const int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, so, &im)) return rc;
+    const uint32_t* const hdr = im.hdr; const _Float16* const x16 = im.x16; const int dpad = im.dpad, pitch = im.pitch;
     double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + workspace_bytes_for(plan->Nc, D));
     if (plan->nw_eff == 0) {
         if (bwd) HIP_TRY(hipMemsetAsync(d_dw, 0, sizeof(float), stream));
@@ -1272,10 +947,7 @@ static int run_agnn(const tcgnn_plan* plan, const float* d_X, const float* d_w, 
                 e = hipGetLastError();
             }
         } else if (blocked) {
-            size_t range_bytes = 4 * kRangeTargetBytes;
-            if (const char* env = test_knob("TCGNN_RANGE_KB")) range_bytes = (size_t)atol(env) << 10;
-            int nranges = 1;
-            while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
+            const int nranges = range_count(plan, x16_bytes, 4 * kRangeTargetBytes);
             a.nranges = nranges;
             a.gsel = plan->nbuckets / nranges;
             a.ngroups = (plan->nw_eff + kAgnnMaxW - 1) / kAgnnMaxW;
@@ -1587,18 +1259,13 @@ int tcgnn_plan_prepare(tcgnn_plan* plan, int32_t D, void* stream_v) {
     if (plan->nw_eff <= 0 || plan->N == 0) return TCGNN_OK;
     const int dpad = round_up(D, 16);
     const int mode = spmm_mode_of(plan);
-    if (!(mode == 3 || (mode == 0 && plan->total_wb > kSmallMaxTiles && lds_chosen(plan, dpad)))) return TCGNN_OK;   // the gather walks need nothing built
-    if ((int64_t)(dpad / 16) * ((int64_t)plan->Nc + 1) * 32 >= ((int64_t)1 << 32)) return TCGNN_OK;
+    // (the gather walks need nothing built, nor does the single-launch kernel: route_spmm's bound for it, applied here on the assumption
+    //  of a plain call - the calls that kernel does not take, staged or with the dense update, build their streams when they come)
+    if (mode == 0 && plan->total_wb <= kSmallMaxTiles) return TCGNN_OK;
+    if (!lds_wanted(plan, mode, dpad) || !planar_records_fit(plan, dpad)) return TCGNN_OK;
     LdsPass passes[2];
-    const int np = lds_passes(dpad, passes);
-    for (int i = 0; i < np; ++i) {
-        const int slot = lds_stream_of(passes[i].nt, passes[i].maxw);
-        if (plan->lds[slot].nranges > 0) continue;
-        const int rc = build_lds_cells(plan, static_cast<hipStream_t>(stream_v), slot);
-        if (rc && mode == 3) return rc;
-        if (rc && dpad / 16 <= 64) plan->lds_choice[dpad / 16] = 0;   // (as the hot path would: no memory for the stream -> the gather walks)
-    }
-    return TCGNN_OK;
+    bool ok;
+    return ensure_lds_streams(plan, static_cast<hipStream_t>(stream_v), mode, dpad, passes, lds_passes(dpad, passes), LdsBuild::kPrepare, &ok);
 }
 
 // Builds, now, what the first tcgnn_spmm_val call of width D would build inside the hot path: the single-edge cell stream of the
@@ -1609,12 +1276,8 @@ int tcgnn_plan_prepare_val(tcgnn_plan* plan, int32_t D, void* stream_v) {
     if (!plan || D < 1) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_prepare_val: null plan or D < 1");
     if (plan->nw_eff <= 0 || plan->N == 0 || plan->E < 4 || !plan->canonical) return TCGNN_OK;
     const int dp = round_up(D, 16), mode = spmm_mode_of(plan);
-    if (!((mode == 0 || mode == 3) && val_lds_width_ok(plan, dp) && (mode == 3 || lds_chosen(plan, dp)))) return TCGNN_OK;
-    if (plan->val_choice.load(std::memory_order_acquire) >= 0) return TCGNN_OK;
-    const int b = build_val_stream(plan, static_cast<hipStream_t>(stream_v));
-    if (b && mode == 3) return b;
-    if (b) plan->val_choice.store(0, std::memory_order_release);
-    return TCGNN_OK;
+    if (!val_lds_wanted(plan, mode, dp)) return TCGNN_OK;
+    return ensure_val_stream(plan, static_cast<hipStream_t>(stream_v), mode, false);
 }
 
 int tcgnn_plan_set_spmm_mode(tcgnn_plan* plan, int32_t mode) {
@@ -1700,40 +1363,48 @@ size_t tcgnn_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
     const size_t image = workspace_bytes_for(plan->Nc, D);
     // (before the width's streams exist the answer is the conservative one; once built, only an ORDINARY stream with a cold
     //  remainder stages the second image - a flat stream's remainder reads the planar one)
-    bool two_images = plan->nw_eff > 0 && (spmm_mode_of(plan) == 3 || (spmm_mode_of(plan) == 0 && lds_chosen(plan, round_up(D, 16))));
+    // (of route_spmm's conditions only the plan-and-width part: it does not know the call.  It does not test planar_records_fit either, so
+    //  a width the record bound keeps off the LDS-resident kernel still reserves the second image - drift rather than intent, kept: the
+    //  size is observable)
+    const int dp = round_up(D, 16);
+    bool two_images = lds_wanted(plan, spmm_mode_of(plan), dp);
     if (two_images) {
         LdsPass passes[2];
-        const int np = lds_passes(round_up(D, 16), passes);
-        bool all_built = np > 0, cold_rows = false;
-        for (int i = 0; i < np; ++i) {
-            const tcgnn_plan::CellStream& ci = plan->lds[lds_stream_of(passes[i].nt, passes[i].maxw)];
-            all_built = all_built && ci.nranges > 0;
-            cold_rows = cold_rows || (ci.nranges > 0 && !ci.flat_tpc && ci.cold_tiles > 0);
-        }
-        if (all_built && !cold_rows) two_images = false;
+        const LdsStreamFacts f = lds_stream_facts(plan, passes, lds_passes(dp, passes));
+        if (f.all_built && !f.rows_cold) two_images = false;
     }
-    // (the edge-valued LDS-resident walk keeps its per-call slot values behind the image, once its stream exists: tcgnn_lds_val.inc)
-    const size_t vals = ((round_up(D, 16) % 64 == 0 || round_up(D, 16) % 64 == 48) && round_up(D, 16) <= 2 * kMaxChunkDims) ? val_stream_bytes(plan) : (size_t)0;   // (val_lds_width_ok's widths)
+    // (the edge-valued LDS-resident walk keeps its per-call slot values behind the image, once its stream exists: tcgnn_lds_val.inc;
+    //  the width alone is asked - a stream only exists where val_lds_width_ok held)
+    const size_t vals = val_lds_width(dp) ? val_stream_bytes(plan) : (size_t)0;
     return image + std::max({agnn_partial_bytes(plan) + agnn_slice_bytes(plan, D), two_images ? image : (size_t)0, vals});
 }
 
+// what every SpMM entry point has: the rest of the request is set by name
+static SpmmCall spmm_call(const tcgnn_plan* plan, const float* d_X, float* d_Y, int32_t D, void* ws, size_t ws_bytes, void* stream) {
+    SpmmCall c;
+    c.plan = plan; c.d_X = d_X; c.d_Y = d_Y; c.D = D; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = static_cast<hipStream_t>(stream);
+    return c;
+}
+
 int tcgnn_spmm(const tcgnn_plan* plan, const float* d_X, float* d_Y, int32_t D, void* ws, size_t ws_bytes, void* stream) {
-    return run_spmm(plan, d_X, nullptr, d_Y, D, ws, ws_bytes, stream);
+    return run_spmm(spmm_call(plan, d_X, d_Y, D, ws, ws_bytes, stream));
 }
 
 int tcgnn_spmm_fused(const tcgnn_plan* plan, const float* d_X, const float* d_gate, float* d_Y, int32_t D, int32_t flags,
                      void* ws, size_t ws_bytes, void* stream) {
     if (flags & ~TCGNN_FUSE_RELU) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_fused: unknown flag bits 0x%x", flags & ~TCGNN_FUSE_RELU);
-    return run_spmm(plan, d_X, nullptr, d_Y, D, ws, ws_bytes, stream, (flags & TCGNN_FUSE_RELU) ? 1 : 0, d_gate);
+    SpmmCall c = spmm_call(plan, d_X, d_Y, D, ws, ws_bytes, stream);
+    c.relu = (flags & TCGNN_FUSE_RELU) ? 1 : 0; c.d_gate = d_gate;
+    return run_spmm(c);
 }
 
 int tcgnn_spmm_scaled(const tcgnn_plan* plan, const float* d_X, const float* d_col_scale, const float* d_gate, const float* d_row_scale,
                       const float* d_bias, float* d_Y, int32_t D, int32_t flags, void* ws, size_t ws_bytes, void* stream) {
     if (flags & ~TCGNN_FUSE_RELU) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_scaled: unknown flag bits 0x%x", flags & ~TCGNN_FUSE_RELU);
-    const Scales sc{d_col_scale, d_row_scale, d_bias};
-    const bool any = d_col_scale || d_row_scale || d_bias;   // (none: exactly tcgnn_spmm_fused)
-    return run_spmm(plan, d_X, nullptr, d_Y, D, ws, ws_bytes, stream, (flags & TCGNN_FUSE_RELU) ? 1 : 0, d_gate, nullptr, 0, false, nullptr, 0, false,
-                    any ? &sc : nullptr);
+    SpmmCall c = spmm_call(plan, d_X, d_Y, D, ws, ws_bytes, stream);
+    c.relu = (flags & TCGNN_FUSE_RELU) ? 1 : 0; c.d_gate = d_gate;
+    c.sc.col = d_col_scale; c.sc.row = d_row_scale; c.sc.bias = d_bias;   // (all null: exactly tcgnn_spmm_fused)
+    return run_spmm(c);
 }
 
 int tcgnn_spmm_gemm(const tcgnn_plan* plan, const float* d_X, const float* d_W, float* d_Y, int32_t D_in, int32_t D_out, int32_t flags,
@@ -1742,7 +1413,9 @@ int tcgnn_spmm_gemm(const tcgnn_plan* plan, const float* d_X, const float* d_W, 
     if (!d_W || D_out < 1) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_gemm: null W or D_out < 1");
     if (D_in > kMaxChunkDims || D_out > kMaxChunkDims)
         return fail(TCGNN_ERR_UNSUPPORTED, "tcgnn_spmm_gemm: the fused dense update covers D_in, D_out <= %d (got %d -> %d)", kMaxChunkDims, D_in, D_out);
-    return run_spmm(plan, d_X, nullptr, d_Y, D_in, ws, ws_bytes, stream, (flags & TCGNN_FUSE_RELU) ? 1 : 0, nullptr, nullptr, 0, false, d_W, D_out);
+    SpmmCall c = spmm_call(plan, d_X, d_Y, D_in, ws, ws_bytes, stream);
+    c.relu = (flags & TCGNN_FUSE_RELU) ? 1 : 0; c.d_W = d_W; c.D_out = D_out;
+    return run_spmm(c);
 }
 
 int tcgnn_x16_pitch(int32_t D) { return D < 1 ? 0 : x16_pitch(round_up(D, 16)); }
@@ -1777,28 +1450,24 @@ int tcgnn_spmm_staged(const tcgnn_plan* plan, const void* d_image, float* d_Y, i
     // (never "wide": there is no fp32 X to fall back to).  The gather walks are told so (SpmmArgs::unguarded) and never look at
     // bytes 4 .. 255 of the header: the image is READ-ONLY to this call, as the signature says - one staged image may be shared by
     // several streams or ranks (r04 cleared those words with a memset on the caller's image, a write racing with other readers).
-    return run_spmm(plan, nullptr, nullptr, d_Y, D, nullptr, 0, stream, 0, nullptr, d_image);
+    SpmmCall c = spmm_call(plan, nullptr, d_Y, D, nullptr, 0, stream);
+    c.d_image = d_image; c.staged = StagedLayout::kRowMajor;
+    return run_spmm(c);
 }
 
 // ---- r06: the staged image in the LDS-resident kernel's own (planar) layout, so that a row-sharded call keeps the fast kernel
 // (VERDICT r05 item 5).  Would tcgnn_spmm run the LDS-resident kernel on this plan at this width?  Builds the width's cell streams if
-// they are missing (synchronises once, like tcgnn_plan_prepare) and applies run_spmm's own conditions.
+// they are missing (synchronises once, like tcgnn_plan_prepare) and asks what route_spmm asks for a planar staged call.
 static bool lds_takes_staged(const tcgnn_plan* plan, int32_t D, hipStream_t stream) {
     const int mode = spmm_mode_of(plan);
     const int dp = round_up(D, 16);
-    if (!(plan->nw_eff > 0 && (mode == 3 || (mode == 0 && lds_chosen(plan, dp))))) return false;
-    if ((int64_t)(dp / 16) * ((int64_t)plan->Nc + 1) * 32 >= ((int64_t)1 << 32)) return false;
+    if (!lds_wanted(plan, mode, dp) || !planar_records_fit(plan, dp)) return false;
     LdsPass passes[2];
     const int npass = lds_passes(dp, passes);
-    bool any_cold = false, thin = false;
-    for (int i = 0; i < npass; ++i) {
-        const int slot = lds_stream_of(passes[i].nt, passes[i].maxw);
-        if (plan->lds[slot].nranges == 0 && build_lds_cells(const_cast<tcgnn_plan*>(plan), stream, slot)) return false;
-        const tcgnn_plan::CellStream& ci = plan->lds[slot];
-        if (!ci.flat_tpc) any_cold = any_cold || ci.cold_tiles > 0;
-        thin = thin || ci.hot_cols * 2 < ci.hot_cols + ci.cold_cols;
-    }
-    return !any_cold && !(thin && mode != 3);
+    bool ok, settle;
+    const tcgnn_plan::CellStream* cold;
+    (void)ensure_lds_streams(plan, stream, mode, dp, passes, npass, LdsBuild::kQuery, &ok);
+    return ok && lds_streams_serve(plan, mode, passes, npass, false, true, &settle, &cold);   // (a query: what would settle the width is left to the call)
 }
 
 int tcgnn_spmm_staged_layout(const tcgnn_plan* plan, int32_t D, void* stream) {
@@ -1821,13 +1490,17 @@ int tcgnn_stage_rows_planar(const float* d_X, int32_t rows, int32_t D, const uin
 
 int tcgnn_spmm_staged_planar(const tcgnn_plan* plan, const void* d_image, float* d_Y, int32_t D, void* stream) {
     if (!d_image || (reinterpret_cast<uintptr_t>(d_image) & 255)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_staged_planar: the image must be 256-byte aligned");
-    return run_spmm(plan, nullptr, nullptr, d_Y, D, nullptr, 0, stream, 0, nullptr, d_image, 0, false, nullptr, 0, true);
+    SpmmCall c = spmm_call(plan, nullptr, d_Y, D, nullptr, 0, stream);
+    c.d_image = d_image; c.staged = StagedLayout::kPlanar;
+    return run_spmm(c);
 }
 
 int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge_val, float* d_Y, int32_t D,
                    void* ws, size_t ws_bytes, void* stream) {
     if (plan && plan->E > 0 && !d_edge_val) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_val: edge values are null");
-    return run_spmm(plan, d_X, plan && plan->E > 0 ? d_edge_val : nullptr, d_Y, D, ws, ws_bytes, stream);
+    SpmmCall c = spmm_call(plan, d_X, d_Y, D, ws, ws_bytes, stream);
+    if (plan && plan->E > 0) c.d_val = d_edge_val;
+    return run_spmm(c);
 }
 
 int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
@@ -1840,10 +1513,11 @@ int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D
         return TCGNN_OK;
     }
     if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
-    const uint32_t* hdr; const _Float16* x16; int dpad, pitch;
     const Guard gsd = guard_sddmm(plan, D);
-    int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, &hdr, &x16, &dpad, &pitch, false, nullptr, 0, false, nullptr, &gsd);
-    if (rc) return rc;
+    StageOpts so; so.guard = &gsd;
+    StagedImage im;
+    if (const int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, so, &im)) return rc;
+    const uint32_t* const hdr = im.hdr; const _Float16* const x16 = im.x16; const int dpad = im.dpad, pitch = im.pitch;
     SddmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, d_ef, plan->N, plan->Nc, plan->row_off, dpad, pitch, plan->rowptr, plan->d_bptr, plan->nbuckets, 0, 0, plan->nw_eff, image_is_big(plan->Nc, pitch), 0, 0, 0, SyncArgs{}};
     const int ks = (dpad + 31) / 32;
     KernelTimer timer(plan, stream, ks <= 4 ? "sddmm_kernel" : "sddmm_wide_kernel");
@@ -1851,7 +1525,7 @@ int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D
     // Range-major walk (bit-identical results).  With the outputs staged per row the loop is bound by the gather again,
     // and keeping it inside ~4 MB column ranges wins on the Reddit shape: D=16 1.14 -> 1.07 ms, D=32 1.38 -> 1.14,
     // D=64 1.74 -> 1.66, D=128 3.37 -> 3.26.  No accumulators live across ranges, so ranges are 4x the SpMM's.
-    const bool blocked = ks <= 4 && plan->nbuckets > 0 && spmm_mode_of(plan) != 1 && (spmm_mode_of(plan) == 2 || (x16_bytes > kBlockedMinBytes && windows_balanced(plan) && ranges_fit_l2(plan, x16_bytes) && !has_locality(plan)));
+    const bool blocked = ks <= 4 && plan->nbuckets > 0 && spmm_mode_of(plan) != 1 && (spmm_mode_of(plan) == 2 || range_walk_pays(plan, x16_bytes));
     hipError_t e = hipSuccess;
     if (ks <= 4 && !a.big && sync_chosen(plan, pitch * 2, spmm_mode_of(plan), kSyncSddmm, dpad / 16)) {
         // slice-synchronised range walk (r06, tcgnn_sync_walk.inc): communities larger than an XCD's L2; one launch per slice round, bit-identical scores
@@ -1868,10 +1542,7 @@ int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D
     } else if (blocked) {
         // (r03, whole-line gathers: D = 64 1.26 / 1.24 ms at 4 / 8 MB ranges, 1.36 at 2 MB; D = 128 - an image of 60 MB - 2.33 at 2 MB,
         //  2.58 at 4 MB, 3.5 per-window; with XCD affinity 2.01 at 2 or 4 MB)
-        size_t range_bytes = x16_bytes > ((size_t)32 << 20) ? 2 * kRangeTargetBytes : 4 * kRangeTargetBytes;
-        if (const char* env = test_knob("TCGNN_RANGE_KB")) range_bytes = (size_t)atol(env) << 10;
-        int nranges = 1;
-        while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
+        const int nranges = range_count(plan, x16_bytes, x16_bytes > ((size_t)32 << 20) ? 2 * kRangeTargetBytes : 4 * kRangeTargetBytes);
         a.nranges = nranges;
         a.gsel = plan->nbuckets / nranges;
         const int lds_wg = 4 * sddmm_wave_lds(ks);

@@ -118,8 +118,9 @@ def transposed_csr(rp, col):
     return a.indptr.astype(np.int32), a.indices.astype(np.int32), (a.data - 1).astype(np.int64)
 
 
-# ---- the range-major walks cut the fp16 image into column ranges of TCGNN_RANGE_KB; mirrors of x16_pitch and of the loop in
-# tcgnn_sddmm / run_spmm / run_agnn that picks the number of ranges, so that a test can force eight of them and say so
+# ---- the range-major walks cut the fp16 image into column ranges of TCGNN_RANGE_KB; mirrors of x16_pitch and of range_count
+# (tcgnn_device.hip: the one loop tcgnn_sddmm, the SpMM dispatcher and run_agnn pick the number of ranges with), so that a test can
+# force eight of them and say so
 def image_bytes(n, D):
     row = (D + 15) // 16 * 16 * 2
     if row > 128:
