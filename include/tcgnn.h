@@ -346,6 +346,42 @@ int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge
 int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D,
                 void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* ef[e] = <X[row(e),:], Z[col(e),:]> for every CSR edge: the SDDMM with two different operands (no counterpart in the reference).
+ * It is what the gradient of an edge-weighted aggregation Y = A_val * H with respect to its edge values is, <dY[row e], H[col e]>.
+ * X (the window operand, read once per row window) and Z (the gathered operand) are fp32 [N, D]; each is staged as its own fp16
+ * image with its own power-of-two scale, so the two may differ in magnitude by any factor.  Same walks as tcgnn_sddmm, chosen by
+ * the same rules and switches (tcgnn_plan_last_kernel names them the same way); tcgnn_sddmm2(X, X) equals tcgnn_sddmm(X) bit for bit
+ * on every walk - unless the range guard takes X for wide (level >= 2): the single-operand call then patches the edges of the dirty
+ * rows behind the MFMA result, this one recomputes every edge in fp32 (another summation order; both hold the contract's bounds).
+ * Range guard (level >= 2): when either operand holds elements that lose bits in its image and the product of the two maxima is
+ * large enough for that to matter (the rule of "Operand range" with max|X| max|Z| in place of max|X|^2), the WHOLE call is computed
+ * in fp32, CSR order, operands rounded like the reference's - decided on the device, no read-back.  That kernel is launched behind
+ * every level >= 2 call and returns at once otherwise; when it does the work it takes one wavefront per row, serial over the row's
+ * edges (a wide operand is a rare input: correct for any magnitudes, far from fast on a hub row).
+ * Workspace: tcgnn_sddmm2_workspace_bytes (two images), 256-byte aligned.  No allocation, no synchronisation. */
+size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D);
+int tcgnn_sddmm2(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t D,
+                 void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* ---- softmax over a node's incoming edges (DGL's edge_softmax; no counterpart in the reference) ------------------------------
+ *
+ * A row is the segment nodePointer[r] .. nodePointer[r + 1] of the edge array (softmax by destination node).  Planless, like
+ * tcgnn_permute_edge_values: device pointers, the caller's stream, no allocation, no synchronisation (capturable in a HIP graph).
+ *   forward   p[e]  = exp(b s[e] - m_r) / sum_{e' in row r} exp(b s[e'] - m_r),  m_r = max over row r of b s;
+ *             b = *d_beta, a DEVICE scalar (NULL: 1).  The maximum is always subtracted: scores of any magnitude are safe.
+ *   backward  g[e]  = p[e] (dp[e] - sum_{row} p dp);  ds[e] = b g[e];  *d_dbeta = sum_e s[e] g[e]
+ *             d_dbeta (a device scalar) may be NULL; when given, d_score must be too, and d_scratch must hold
+ *             tcgnn_edge_softmax_workspace_bytes(num_nodes, num_edges) bytes (one fp64 partial per workgroup, 8-byte aligned).
+ * Results are bit-identical on repetition: every sum is a fixed-order reduction, none uses atomics.  d_p may alias d_score and d_ds
+ * may alias d_dp.  Empty rows touch nothing; num_edges = 0 or num_nodes = 0 returns TCGNN_OK (and zeroes *d_dbeta).  Row pointers
+ * are clamped to [0, num_edges] and a descending pair counts as an empty row: nothing outside [0, num_edges) is ever written. */
+size_t tcgnn_edge_softmax_workspace_bytes(int32_t num_nodes, int64_t num_edges);
+int tcgnn_edge_softmax(const int32_t* d_nodePointer, int32_t num_nodes, int64_t num_edges, const float* d_score,
+                       const float* d_beta, float* d_p, void* stream);
+int tcgnn_edge_softmax_backward(const int32_t* d_nodePointer, int32_t num_nodes, int64_t num_edges, const float* d_p,
+                                const float* d_dp, const float* d_score, const float* d_beta, float* d_ds, float* d_dbeta,
+                                void* d_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

@@ -231,6 +231,91 @@ std::vector<torch::Tensor> sddmm_forward(torch::Tensor input, torch::Tensor node
   return {ef};
 }
 
+// Not in the reference: the SDDMM with two operands, ef[e] = <X[row e], Z[col e]> (tcgnn_sddmm2; TCGNN.forward_ef2 of the ctypes module)
+std::vector<torch::Tensor> sddmm2_forward(torch::Tensor X, torch::Tensor Z, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                          torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow) {
+  CHECK_INPUT(X); CHECK_INPUT(Z); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
+  TORCH_CHECK(X.scalar_type() == torch::kFloat32 && Z.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  check_rows(X, nodePointer);
+  TORCH_CHECK(Z.sizes() == X.sizes() && Z.device() == X.device(), "Z must have the shape and device of X");
+  DeviceGuard guard(X.device());
+  auto ef = torch::empty({edgeList.size(0)}, X.options());
+  if (edgeList.size(0) == 0) return {ef};
+  if (X.size(1) == 0) return {ef.zero_()};
+  auto* plan = plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  const int D = (int)X.size(1);
+  void* ws = nullptr;
+  const size_t need = tcgnn_sddmm2_workspace_bytes(plan, D);
+  torch::Tensor buf = aligned_scratch(need, X, &ws);
+  tcgnn_check(tcgnn_sddmm2(plan, X.data_ptr<float>(), Z.data_ptr<float>(), ef.data_ptr<float>(), D, ws, need, current_stream(X)), "tcgnn_sddmm2");
+  return {ef};
+}
+
+namespace {
+const float* beta_ptr(const c10::optional<torch::Tensor>& beta, const torch::Tensor& like) {
+  if (!beta.has_value()) return nullptr;
+  TORCH_CHECK(beta->is_cuda() && beta->is_contiguous() && beta->scalar_type() == torch::kFloat32 && beta->numel() == 1 && beta->device() == like.device(),
+              "beta must hold one fp32 value on score's device");
+  return beta->data_ptr<float>();
+}
+void check_edge_vector(const torch::Tensor& t, const char* name, const torch::Tensor& nodePointer) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), name, " must be a contiguous CUDA tensor");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.dim() == 1, name, " must be a 1-D fp32 tensor of one value per edge");
+  TORCH_CHECK(nodePointer.numel() >= 1 && nodePointer.scalar_type() == torch::kInt32 && nodePointer.device() == t.device(),
+              "nodePointer must hold num_nodes + 1 int32 entries on ", name, "'s device");
+}
+}  // namespace
+
+// Not in the reference: softmax over every node's incoming edges (tcgnn_edge_softmax; TCGNN.edge_softmax of the ctypes module)
+torch::Tensor edge_softmax(torch::Tensor score, torch::Tensor nodePointer, c10::optional<torch::Tensor> beta, c10::optional<torch::Tensor> out) {
+  CHECK_INPUT(nodePointer);
+  check_edge_vector(score, "score", nodePointer);
+  const float* b = beta_ptr(beta, score);
+  torch::Tensor p = out.has_value() ? *out : torch::empty_like(score);
+  TORCH_CHECK(p.sizes() == score.sizes() && p.scalar_type() == torch::kFloat32 && p.device() == score.device() && p.is_contiguous(),
+              "out must be a contiguous fp32 tensor of score's shape on its device");
+  DeviceGuard guard(score.device());
+  tcgnn_check(tcgnn_edge_softmax(nodePointer.data_ptr<int>(), (int32_t)(nodePointer.numel() - 1), score.numel(), score.data_ptr<float>(), b,
+                                 p.data_ptr<float>(), current_stream(score)), "tcgnn_edge_softmax");
+  return p;
+}
+
+// ... and its backward: (ds, dbeta); dbeta is None unless need_dbeta (which needs the scores)
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> edge_softmax_backward(torch::Tensor p, torch::Tensor dp, torch::Tensor nodePointer,
+                                                                               c10::optional<torch::Tensor> beta, c10::optional<torch::Tensor> score,
+                                                                               bool need_dbeta, c10::optional<torch::Tensor> out) {
+  CHECK_INPUT(nodePointer);
+  check_edge_vector(p, "p", nodePointer);
+  check_edge_vector(dp, "dp", nodePointer);
+  TORCH_CHECK(dp.sizes() == p.sizes() && dp.device() == p.device(), "dp must have the shape and device of p");
+  const float* b = beta_ptr(beta, p);
+  const float* s = nullptr;
+  if (need_dbeta) {
+    TORCH_CHECK(score.has_value(), "dbeta needs the scores the softmax was taken of");
+    check_edge_vector(*score, "score", nodePointer);
+    TORCH_CHECK(score->sizes() == p.sizes() && score->device() == p.device(), "score must have the shape and device of p");
+    s = score->data_ptr<float>();
+  }
+  torch::Tensor ds = out.has_value() ? *out : torch::empty_like(dp);
+  TORCH_CHECK(ds.sizes() == dp.sizes() && ds.scalar_type() == torch::kFloat32 && ds.device() == dp.device() && ds.is_contiguous(),
+              "out must be a contiguous fp32 tensor of dp's shape on its device");
+  DeviceGuard guard(p.device());
+  const int32_t N = (int32_t)(nodePointer.numel() - 1);
+  c10::optional<torch::Tensor> dbeta;
+  void* scratch = nullptr;
+  size_t need = 0;
+  torch::Tensor buf;
+  if (need_dbeta) {
+    dbeta = torch::empty({1}, p.options());
+    need = tcgnn_edge_softmax_workspace_bytes(N, p.numel());
+    buf = aligned_scratch(need, p, &scratch);
+  }
+  tcgnn_check(tcgnn_edge_softmax_backward(nodePointer.data_ptr<int>(), N, p.numel(), p.data_ptr<float>(), dp.data_ptr<float>(), s, b, ds.data_ptr<float>(),
+                                          need_dbeta ? dbeta->data_ptr<float>() : nullptr, scratch, need, current_stream(p)), "tcgnn_edge_softmax_backward");
+  return {ds, dbeta};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -335,4 +420,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"),
         py::arg("row_scale") = py::none(), py::arg("col_scale") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("gate") = py::none(), py::arg("transpose") = false);
+  m.def("forward_ef2", &sddmm2_forward, "SDDMM with two operands, ef[e] = <X[row e], Z[col e]> (not in the reference)");
+  m.def("edge_softmax", &edge_softmax, "softmax over every node's incoming edges (not in the reference)", py::arg("score"), py::arg("nodePointer"),
+        py::arg("beta") = py::none(), py::arg("out") = py::none());
+  m.def("edge_softmax_backward", &edge_softmax_backward, "backward of edge_softmax: (ds, dbeta) (not in the reference)", py::arg("p"), py::arg("dp"),
+        py::arg("nodePointer"), py::arg("beta") = py::none(), py::arg("score") = py::none(), py::arg("need_dbeta") = false, py::arg("out") = py::none());
 }

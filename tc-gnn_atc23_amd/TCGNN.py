@@ -34,7 +34,8 @@ import tcgnn_capi as _c
 
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
-           "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph"]
+           "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
+           "forward_ef2", "edge_softmax", "edge_softmax_backward"]
 
 _plan_cache_size = max(1, int(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8")))
 _plans = collections.OrderedDict()  # key -> (handle, tensors kept alive, device index)
@@ -44,6 +45,7 @@ _scales = {}                        # (nodePointer, edgeList) key -> (tensors ke
 _transposed_csr = {}                # (nodePointer, edgeList) key -> (nodePointer, edgeList, nodePointer_t, edgeList_t, perm, symmetric): transpose_graph
 _transposed = {}                    # A's plan key -> dict(plan=, own=, meta=, perm=, symmetric=): what transpose=True calls run on, evicted with A's plan
 _values_t = {}                      # (device index, stream id) -> fp32 buffer: edge values in A^T's order (forward_AGNN(transpose=True))
+_softmax_scratch = {}               # (device index, stream id) -> uint8 buffer: the fp64 partials of edge_softmax_backward's d_beta
 
 
 def set_plan_cache_size(n):
@@ -166,6 +168,7 @@ def clear_plan_cache():
     _transposed.clear()
     _transposed_csr.clear()
     _values_t.clear()
+    _softmax_scratch.clear()
     _reap(block=True)
     _workspaces.clear()
     _scales.clear()
@@ -298,17 +301,25 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
     return out
 
 
-def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False):
+def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
     forward / backward (/ forward_AGNN) call of those widths synchronises or allocates inside the library, and a call captured into
     a HIP graph takes the walk it would take outside one.  The harness calls it with the model's widths before the dry epochs.
     transpose=True (a model with directed=True layers runs both): also A^T's plan - built now if it is not cached - the same way,
-    and with edge_valued=True the buffer forward_AGNN(transpose=True) permutes the edge values into, on the current stream."""
+    and with edge_valued=True the buffer forward_AGNN(transpose=True) permutes the edge values into, on the current stream.
+    attention=True (a model with softmax-attention layers: forward_ef2, edge_softmax, edge_softmax_backward): the workspace grown to
+    forward_ef2's two images at every width and the scratch of edge_softmax_backward's d_beta, on the current stream - a step that
+    uses them then allocates nothing outside torch's pool and never synchronises."""
     plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     plans = [plan]
     dev = nodePointer.device
+    if attention:
+        with torch.cuda.device(dev):
+            for d in sorted({int(w) for w in widths if int(w) >= 1}):
+                _workspace(plan, d, dev, need=_c.lib.tcgnn_sddmm2_workspace_bytes(plan, d))
+            _softmax_scratch_for(nodePointer.numel() - 1, edgeList.numel(), dev)
     if transpose:
         tr = _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
         if tr["own"] is not None:
@@ -375,8 +386,9 @@ def last_kernel(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, 
     return _c.lib.tcgnn_plan_last_kernel(_plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)).decode()
 
 
-def _workspace(plan, D, device):
-    need = _c.lib.tcgnn_workspace_bytes(plan, D)
+def _workspace(plan, D, device, need=None):
+    if need is None:
+        need = _c.lib.tcgnn_workspace_bytes(plan, D)
     key = (device.index, _stream_handle(device))
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < need + 256:
@@ -709,6 +721,112 @@ def forward_ef(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeT
         st = _c.lib.tcgnn_sddmm(plan, input.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
     _c.check(st, "tcgnn_sddmm")
     return [out]
+
+
+# ---- additions (not in the reference module): what a softmax-attention layer needs -----------------------
+
+def forward_ef2(X, Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
+    """Not in the reference module: the SDDMM with two operands, ef[e] = <X[row(e)], Z[col(e)]>, fp32 [E] (tcgnn_sddmm2) - the
+    gradient of forward_AGNN with respect to its edge values is forward_ef2(dY, input).  Same walks as forward_ef; each operand is
+    rounded with its own scale; forward_ef2(X, X) equals forward_ef(X) bit for bit (unless the range guard takes X for wide: the
+    single-operand call then patches the dirty rows' edges, this one recomputes the whole call in fp32 - include/tcgnn.h)."""
+    _six(X, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    _check_input(Z, "Z")
+    _check_float(Z, "Z")
+    if Z.shape != X.shape or Z.device != X.device:
+        raise RuntimeError("Z must have the shape and device of X")
+    dev = X.device
+    N, D = X.shape
+    E = edgeList.numel()
+    out = torch.empty(E, dtype=torch.float32, device=dev)
+    if E == 0:
+        return [out]
+    if D == 0:
+        return [out.zero_()]
+    with torch.cuda.device(dev):
+        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+        ws, ws_bytes = _workspace(plan, D, dev, need=_c.lib.tcgnn_sddmm2_workspace_bytes(plan, D))
+        st = _c.lib.tcgnn_sddmm2(plan, X.data_ptr(), Z.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
+    _c.check(st, "tcgnn_sddmm2")
+    return [out]
+
+
+def _softmax_args(score, nodePointer, beta):
+    _check_input(score, "score")
+    _check_float(score, "score")
+    _check_input(nodePointer, "nodePointer")
+    _check_int(nodePointer, "nodePointer")
+    if score.dim() != 1:
+        raise RuntimeError("score must be a 1-D tensor of one value per edge")
+    if nodePointer.numel() < 1 or nodePointer.device != score.device:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries on score's device")
+    if beta is not None:
+        _check_input(beta, "beta")
+        _check_float(beta, "beta")
+        if beta.numel() != 1 or beta.device != score.device:
+            raise RuntimeError("beta must hold one value on score's device")
+
+
+def _softmax_scratch_for(N, E, device):
+    need = int(_c.lib.tcgnn_edge_softmax_workspace_bytes(max(N, 0), E))
+    key = (device.index, _stream_handle(device))
+    buf = _softmax_scratch.get(key)
+    if buf is None or buf.numel() < need + 256:
+        buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
+        _softmax_scratch[key] = buf
+    off = (-buf.data_ptr()) % 256
+    return buf.data_ptr() + off, buf.numel() - off
+
+
+def edge_softmax(score, nodePointer, beta=None, out=None):
+    """Not in the reference module: softmax over every node's incoming edges (DGL's edge_softmax; tcgnn_edge_softmax),
+        p[e] = exp(beta s[e] - m_r) / sum_{e' in row r} exp(beta s[e'] - m_r),   row r = nodePointer[r] .. nodePointer[r + 1].
+    score: fp32 [E]; beta: a one-element fp32 tensor on the device (None: 1).  out may be score itself (in place).  Entries of
+    positions no row covers are left as allocated.  Deterministic: a second call returns the same bits."""
+    _softmax_args(score, nodePointer, beta)
+    if out is None:
+        out = torch.empty_like(score)
+    elif out.shape != score.shape or out.dtype != torch.float32 or out.device != score.device or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous fp32 tensor of score's shape on its device")
+    dev = score.device
+    with torch.cuda.device(dev):
+        st = _c.lib.tcgnn_edge_softmax(nodePointer.data_ptr(), nodePointer.numel() - 1, score.numel(), score.data_ptr(),
+                                       beta.data_ptr() if beta is not None else None, out.data_ptr(), _stream_handle(dev))
+    _c.check(st, "tcgnn_edge_softmax")
+    return out
+
+
+def edge_softmax_backward(p, dp, nodePointer, beta=None, score=None, need_dbeta=False, out=None):
+    """Not in the reference module: the backward of edge_softmax (tcgnn_edge_softmax_backward) - (ds, dbeta) with
+        g[e] = p[e] (dp[e] - sum_{row} p dp),  ds[e] = beta g[e],  dbeta = sum_e score[e] g[e]   (a one-element tensor, or None
+    unless need_dbeta; it needs score).  out may be dp itself.  The partial sums of dbeta live in a buffer held per stream."""
+    _softmax_args(p, nodePointer, beta)
+    _check_input(dp, "dp")
+    _check_float(dp, "dp")
+    if dp.shape != p.shape or dp.device != p.device:
+        raise RuntimeError("dp must have the shape and device of p")
+    if need_dbeta:
+        if score is None:
+            raise RuntimeError("dbeta needs the scores the softmax was taken of")
+        _check_input(score, "score")
+        _check_float(score, "score")
+        if score.shape != p.shape or score.device != p.device:
+            raise RuntimeError("score must have the shape and device of p")
+    if out is None:
+        out = torch.empty_like(dp)
+    elif out.shape != dp.shape or out.dtype != torch.float32 or out.device != dp.device or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous fp32 tensor of dp's shape on its device")
+    dev = p.device
+    N, E = nodePointer.numel() - 1, p.numel()
+    dbeta = torch.empty(1, dtype=torch.float32, device=dev) if need_dbeta else None
+    with torch.cuda.device(dev):
+        scratch, scratch_bytes = _softmax_scratch_for(N, E, dev) if need_dbeta else (None, 0)
+        st = _c.lib.tcgnn_edge_softmax_backward(nodePointer.data_ptr(), N, E, p.data_ptr(), dp.data_ptr(),
+                                                score.data_ptr() if need_dbeta else None, beta.data_ptr() if beta is not None else None,
+                                                out.data_ptr(), dbeta.data_ptr() if need_dbeta else None, scratch, scratch_bytes,
+                                                _stream_handle(dev))
+    _c.check(st, "tcgnn_edge_softmax_backward")
+    return out, dbeta
 
 
 # ---- additions (not in the reference module): the two products of an AGNN layer in one pass ------------

@@ -34,7 +34,8 @@
 //   tcgnn_lds_spmm.inc        LDS-resident SpMM, ordinary cell stream; cell-stream build kernels
 //   tcgnn_lds_flat.inc        LDS-resident SpMM, flat cell stream (the headline kernel)
 //   tcgnn_lds_val.inc         LDS-resident edge-valued SpMM (single-edge stream, per-call slot values)
-//   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel
+//   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel (one and two operands), sddmm2_csr_kernel
+//   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
 //   tcgnn_small_fallback.inc  spmm_small_kernel, CSR kernels of non-canonical plans, the range guard's fallbacks, wide_patch_kernel
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
@@ -357,6 +358,8 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 
 #include "tcgnn_transpose.inc"
 
+#include "tcgnn_edge_softmax.inc"
+
 // ------------------------------------------------------------------------------------------
 // launch tables
 // ------------------------------------------------------------------------------------------
@@ -456,18 +459,23 @@ static hipError_t launch_sync_any(bool val, int nt, const SpmmSyncArgs& args, in
 #undef TCGNN_SYNC_CASE
 }
 
-template <int WAVES, bool BLOCKED>
-static hipError_t launch_sddmm_ks(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
+template <int WAVES, bool BLOCKED, bool TWO>
+static hipError_t launch_sddmm_two(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
     const dim3 grid((unsigned)nwg), block(WAVES * 64);
     const size_t lds = (size_t)WAVES * sddmm_wave_lds(ks <= 4 ? ks : 1);
     switch (ks) {
-        case 1: hipLaunchKernelGGL((sddmm_kernel<1, WAVES, BLOCKED>), grid, block, lds, stream, args); break;
-        case 2: hipLaunchKernelGGL((sddmm_kernel<2, WAVES, BLOCKED>), grid, block, lds, stream, args); break;
-        case 3: hipLaunchKernelGGL((sddmm_kernel<3, WAVES, BLOCKED>), grid, block, lds, stream, args); break;
-        case 4: hipLaunchKernelGGL((sddmm_kernel<4, WAVES, BLOCKED>), grid, block, lds, stream, args); break;
-        default: hipLaunchKernelGGL((sddmm_wide_kernel<WAVES>), grid, block, 0, stream, args); break;
+        case 1: hipLaunchKernelGGL((sddmm_kernel<1, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
+        case 2: hipLaunchKernelGGL((sddmm_kernel<2, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
+        case 3: hipLaunchKernelGGL((sddmm_kernel<3, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
+        case 4: hipLaunchKernelGGL((sddmm_kernel<4, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
+        default: hipLaunchKernelGGL((sddmm_wide_kernel<WAVES, TWO>), grid, block, 0, stream, args); break;
     }
     return hipGetLastError();
+}
+// (args.xa16 set: tcgnn_sddmm2's instantiations, the window operand from its own image)
+template <int WAVES, bool BLOCKED>
+static hipError_t launch_sddmm_ks(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
+    return args.xa16 ? launch_sddmm_two<WAVES, BLOCKED, true>(ks, args, nwg, stream) : launch_sddmm_two<WAVES, BLOCKED, false>(ks, args, nwg, stream);
 }
 
 static constexpr int kAgnnMaxW = 2;   // windows owned by a wavefront of the range-major fused kernel
@@ -1503,22 +1511,29 @@ int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge
     return run_spmm(c);
 }
 
-int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
-    if (!plan || D < 1 || (plan->N > 0 && !d_X) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm: null argument or D < 1");
+// tcgnn_sddmm (d_Xw == nullptr: both operands are d_X) and tcgnn_sddmm2 (d_Xw: the window operand, d_X: the gathered one): one
+// walk selection for both
+static int run_sddmm(const tcgnn_plan* plan, const float* d_Xw, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (plan->E == 0 || plan->N == 0) return TCGNN_OK;
     if (!plan->canonical) {
-        hipLaunchKernelGGL(sddmm_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, plan->rowptr, plan->col, d_X, d_ef, plan->N, D, plan->row_off);
+        if (d_Xw) hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, (const uint32_t*)nullptr, (const uint32_t*)nullptr, plan->rowptr, plan->col, d_Xw, d_X, d_ef, plan->N, D, plan->row_off);
+        else hipLaunchKernelGGL(sddmm_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, plan->rowptr, plan->col, d_X, d_ef, plan->N, D, plan->row_off);
         HIP_TRY(hipGetLastError());
         return TCGNN_OK;
     }
     if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
     const Guard gsd = guard_sddmm(plan, D);
     StageOpts so; so.guard = &gsd;
-    StagedImage im;
+    StagedImage im, imw;
     if (const int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, so, &im)) return rc;
+    if (d_Xw) {   // the window operand's image behind the gathered operand's: its own header, its own scale
+        const size_t first = workspace_bytes_for(plan->Nc, D);
+        if (ws_bytes < 2 * first) return fail(TCGNN_ERR_WORKSPACE, "tcgnn_sddmm2: workspace needs %zu bytes (tcgnn_sddmm2_workspace_bytes), got %zu", 2 * first, ws_bytes);
+        if (const int rc = stage_features(plan, d_Xw, nullptr, D, static_cast<char*>(ws) + first, ws_bytes - first, stream, so, &imw)) return rc;
+    }
     const uint32_t* const hdr = im.hdr; const _Float16* const x16 = im.x16; const int dpad = im.dpad, pitch = im.pitch;
-    SddmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, d_ef, plan->N, plan->Nc, plan->row_off, dpad, pitch, plan->rowptr, plan->d_bptr, plan->nbuckets, 0, 0, plan->nw_eff, image_is_big(plan->Nc, pitch), 0, 0, 0, SyncArgs{}};
+    SddmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, d_ef, plan->N, plan->Nc, plan->row_off, dpad, pitch, plan->rowptr, plan->d_bptr, plan->nbuckets, 0, 0, plan->nw_eff, image_is_big(plan->Nc, pitch), 0, 0, 0, SyncArgs{}, imw.x16, imw.hdr};
     const int ks = (dpad + 31) / 32;
     KernelTimer timer(plan, stream, ks <= 4 ? "sddmm_kernel" : "sddmm_wide_kernel");
     const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
@@ -1570,12 +1585,32 @@ int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D
     HIP_TRY(e);
     timer.stop();
     // (the range guard's fallback: returns at once unless X is "wide")
-    if (range_guard_of(plan) >= 2) {   // a few dirty rows: the patch behind the MFMA kernel; many: the CSR fallback (each returns at once otherwise)
+    if (range_guard_of(plan) >= 2 && d_Xw) {   // two operands: the whole call in fp32 when either is wide (sddmm2_wide; returns at once otherwise)
+        // (the rows of the windows the plan was given: what lies behind them stays as the memset above left it, as on the MFMA path)
+        const int32_t rows = (int32_t)std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows);
+        hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048)), dim3(256), 0, stream, imw.hdr, hdr, plan->rowptr, plan->col, d_Xw, d_X, d_ef,
+                           rows, D, plan->row_off);
+    } else if (range_guard_of(plan) >= 2) {   // a few dirty rows: the patch behind the MFMA kernel; many: the CSR fallback (each returns at once otherwise)
         const PatchArgs pa{hdr, dirty_bitmap_of(ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, d_X, x16, pitch, d_ef, nullptr, nullptr, nullptr, nullptr, plan->N, plan->Nc, D, plan->row_off, 0, plan->E, plan->d_sym};
         HIP_TRY(launch_wide_patch(pa, stream));
     }
     HIP_TRY(hipGetLastError());
     return TCGNN_OK;
+}
+
+int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
+    if (!plan || D < 1 || (plan->N > 0 && !d_X) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm: null argument or D < 1");
+    return run_sddmm(plan, nullptr, d_X, d_ef, D, ws, ws_bytes, stream_v);
+}
+
+size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
+    if (!plan || D < 1) return 0;
+    return 2 * workspace_bytes_for(plan->Nc, D);
+}
+
+int tcgnn_sddmm2(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
+    if (!plan || D < 1 || (plan->N > 0 && !(d_X && d_Z)) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm2: null argument or D < 1");
+    return run_sddmm(plan, d_X, d_Z, d_ef, D, ws, ws_bytes, stream_v);
 }
 
 

@@ -23,7 +23,22 @@ struct SddmmArgs {
                                 // a range's communities carry 3x the tiles of the others in that range and the walk falls out of step
     int32_t use_sync;           // the slice-synchronised range walk (tcgnn_sync_walk.inc): this launch covers slice `sync.round` of every XCD's share
     SyncArgs sync;
+    // tcgnn_sddmm2 (the TWO instantiations only; behind every field the single-operand kernels read, whose offsets stay): the WINDOW operand's
+    // own image and header - same pitch and row count as x16, its own power-of-two scale.  x16 / hdr are then the gathered operand's
+    const _Float16* xa16;
+    const uint32_t* hdr_a;
 };
+// tcgnn_sddmm2's range guard (level >= 2: hdr_z[4] = 2 D, else 0): the whole call goes the fp32 way when either operand holds elements
+// that lose bits in its image (range_spread, counted in word 6) and k max|X| max|Z| 2^-39 could leave 2^-10 - range_is_wide's rule for
+// SDDMM with the product of the two maxima in place of the square of one
+__device__ __forceinline__ bool sddmm2_wide(const uint32_t* hx, const uint32_t* hz) {
+    int ex, ez;
+    const bool sx = range_spread(hx, 0, ex) && hx[6] != 0u, sz = range_spread(hz, 0, ez) && hz[6] != 0u;
+    const uint32_t cap = hz[4];
+    if (!(sx || sz) || cap == 0u || hx[0] == 0u || hz[0] == 0u) return false;
+    const uint32_t n = (sx ? hx[6] : 0u) + (sz ? hz[6] : 0u);
+    return (ex - 127) + (ez - 127) >= 29 - ceil_log2_u32(n < cap ? n : cap);
+}
 static constexpr int kXcdCount = 8;   // workgroups are dealt to the XCDs round-robin in launch order
 
 // LDS of one SDDMM wavefront: two operand buffers, the metadata pad, the output staging area
@@ -44,9 +59,11 @@ static constexpr int sddmm_wave_lds(int ks) { return sddmm_nbuf(ks) * (2 * ks * 
 // slot and reads the slot back - LDS is a per-lane landing pad, trivially conflict-free - so the
 // gather of the NEXT tile (both 16-column halves) is in flight while the current one is multiplied
 // and scattered, without any VGPR holding a load in flight (see "memory pipeline discipline").
-template <int KS, int WAVES, bool BLOCKED>
+// TWO (tcgnn_sddmm2): the window rows come from a second image, a.xa16, scaled by its own header word; everything else is the same code
+template <int KS, int WAVES, bool BLOCKED, bool TWO = false>
 __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(const SddmmArgs a) {
-    if (wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
+    if constexpr (TWO) { if (sddmm2_wide(a.hdr_a, a.hdr)) return; }   // (sddmm2_csr_kernel, launched behind this kernel, does the work)
+    else if (wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BUF_BYTES = 2 * KS * 1024;               // both halves of one tile
     constexpr int WAVE_LDS = sddmm_wave_lds(KS);
@@ -57,8 +74,14 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
     const int64_t stride = a.stride;
     const int kx = scale_exp_from_bits(a.hdr[0]);
     // ef = acc * 2^(-2kx); one multiply unless 2kx leaves the fp32 exponent range (then two)
-    const bool two_step = kx > 63 || kx < -63;
-    const float inv_a = two_step ? pow2f(-kx) : pow2f(-2 * kx), inv_b = two_step ? pow2f(-kx) : 1.0f;
+    bool two_step = kx > 63 || kx < -63;
+    float inv_a = two_step ? pow2f(-kx) : pow2f(-2 * kx), inv_b = two_step ? pow2f(-kx) : 1.0f;
+    if constexpr (TWO) {   // ef = acc * 2^-(ka + kx); with ka = kx exactly the factors above
+        const int ka = scale_exp_from_bits(a.hdr_a[0]);
+        two_step = ka + kx > 126 || ka + kx < -126;
+        inv_a = two_step ? pow2f(-ka) : pow2f(-(ka + kx));
+        inv_b = two_step ? pow2f(-kx) : 1.0f;
+    }
     const half8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint32_t below[2] = {(1u << i) - 1u, (1u << (16 + i)) - 1u};   // condensed columns left of mine, per half
 
@@ -122,7 +145,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
   auto load_a = [&](const int w, half8 (&af)[KS]) __attribute__((always_inline)) {
     int64_t arow = (int64_t)w * kWinRows + i;
     arow = arow < a.N ? arow + a.row_off : a.Nc;
-    const _Float16* ap = a.x16 + arow * stride + 8 * g;
+    const _Float16* ap = (TWO ? a.xa16 : a.x16) + arow * stride + 8 * g;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) af[ks] = (ks * 32 + 8 * g < a.Dpad) ? *reinterpret_cast<const half8*>(ap + ks * 32) : hz;
   };
@@ -331,9 +354,10 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
 }
 
 // Run-time-K variant for D > 128: window rows are re-read per tile (L1-resident), ordinary loads.
-template <int WAVES>
+template <int WAVES, bool TWO = false>
 __global__ __launch_bounds__(WAVES * 64) void sddmm_wide_kernel(const SddmmArgs a) {
-    if (wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
+    if constexpr (TWO) { if (sddmm2_wide(a.hdr_a, a.hdr)) return; }
+    else if (wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, i = lane & 15;
@@ -341,11 +365,12 @@ __global__ __launch_bounds__(WAVES * 64) void sddmm_wide_kernel(const SddmmArgs 
     const int64_t tb = a.wb_ptr[w], te = a.wb_ptr[w + 1];
     const int64_t stride = a.stride;
     const float inv = pow2f(-scale_exp_from_bits(a.hdr[0]));
+    const float inv_w = TWO ? pow2f(-scale_exp_from_bits(a.hdr_a[0])) : inv;   // (the window operand's scale)
     const int ksteps = (a.Dpad + 31) >> 5;
     const half8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t arow = (int64_t)w * kWinRows + i;
     arow = arow < a.N ? arow + a.row_off : a.Nc;
-    const _Float16* ap = a.x16 + arow * stride + 8 * g;
+    const _Float16* ap = (TWO ? a.xa16 : a.x16) + arow * stride + 8 * g;
     for (int64_t t = tb + wave; t < te; t += WAVES) {
         const uint4 m4 = *reinterpret_cast<const uint4*>(a.mask + t * kWinRows + 4 * g);
         const int4 eb4 = *reinterpret_cast<const int4*>(a.ebase + t * kWinRows + 4 * g);
@@ -369,9 +394,30 @@ __global__ __launch_bounds__(WAVES * 64) void sddmm_wide_kernel(const SddmmArgs 
             for (int ii = 0; ii < 4; ++ii) {
                 if ((mm[ii] >> bit) & 1u) {
                     const int64_t e = (int64_t)ee[ii] + __popc(mm[ii] & ((1u << bit) - 1u));
-                    a.ef[e] = acc[ii] * inv * inv;
+                    a.ef[e] = acc[ii] * inv * inv_w;
                 }
             }
+        }
+    }
+}
+
+// tcgnn_sddmm2 in plain fp32, CSR order, operands rounded like the reference's - sddmm_csr_kernel with two matrices (the same sums in
+// the same order: X = Z gives its scores bit for bit).  The path of non-canonical plans (hx == nullptr) and the range guard's way
+// through a wide operand: launched behind the MFMA kernel, it returns at once unless sddmm2_wide holds.  A wavefront per row.
+__global__ __launch_bounds__(256) void sddmm2_csr_kernel(const uint32_t* __restrict__ hx, const uint32_t* __restrict__ hz, const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col, const float* __restrict__ X, const float* __restrict__ Z, float* ef,
+                                                         int32_t N, int32_t D, int32_t row_off) {
+    if (hx && !sddmm2_wide(hx, hz)) return;
+    const int lane = threadIdx.x & 63;
+    for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < N; row += (int64_t)gridDim.x * 4) {
+        const float* xr = X + (row + row_off) * D;
+        for (int64_t e = rowptr[row]; e < rowptr[row + 1]; ++e) {
+            const float* xc = Z + (int64_t)col[e] * D;
+            float s = 0.f;
+            for (int d = lane; d < D; d += 64) s += round_rna10(xr[d]) * round_rna10(xc[d]);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) ef[e] = s;
         }
     }
 }

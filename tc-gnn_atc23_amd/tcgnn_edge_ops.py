@@ -1,0 +1,97 @@
+"""Differentiable edge operators over the TCGNN operator API - what an attention layer with a softmax over every node's incoming
+edges is composed of (DGL's AGNNConv / edge_softmax; no counterpart in the reference's gnn_conv.py, whose AGNN layer aggregates with
+unnormalised scores and does not propagate through them).  Every gradient is exact, on directed graphs as well:
+
+    sddmm(X, Z, meta)             ef[e] = <X[row e], Z[col e]>            bwd: dX = A_val(d_ef) Z,  dZ = A_val(d_ef)^T X
+    edge_softmax(s, rowptr, beta) p = softmax over each CSR row of beta s  bwd: g = p (dp - sum_row p dp); ds = beta g; dbeta = <s, g>
+    aggregate(P, H, meta)         Y = A_val(P) H                           bwd: dP = sddmm(dY, H),  dH = A_val(P)^T dY
+
+`meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
+edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
+weights are not symmetric (the backend then permutes the values over A's own plan).
+
+The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward and forward_AGNN(transpose=).  A
+backend without them is an error - there is no composed fallback.
+"""
+import torch
+
+import tcgnn_layers as _L
+
+
+class _SDDMM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X, Z, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        X, Z = X.contiguous(), Z.contiguous()
+        ctx.save_for_backward(X, Z)
+        return _L.backend().forward_ef2(X, Z, *ctx.meta)[0]
+
+    @staticmethod
+    def backward(ctx, d_ef):
+        X, Z = ctx.saved_tensors
+        rp, col, bp, e2c, e2r = ctx.meta
+        b = _L.backend()
+        att = d_ef.contiguous().view(1, -1)
+        d_x = b.forward_AGNN(Z, rp, col, att, bp, e2c, e2r)[0] if ctx.needs_input_grad[0] else None
+        d_z = b.forward_AGNN(X, rp, col, att, bp, e2c, e2r, transpose=True)[0] if ctx.needs_input_grad[1] else None
+        return (d_x, d_z) + (None,) * 5
+
+
+class _EdgeSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, score, row_pointers, beta):
+        score = score.contiguous()
+        b1 = beta.detach().reshape(1).contiguous() if beta is not None else None
+        p = _L.backend().edge_softmax(score, row_pointers, b1)
+        ctx.rowptr = row_pointers
+        ctx.has_beta = beta is not None
+        ctx.beta_shape = beta.shape if beta is not None else None
+        # (the scores - E floats - are kept only where d_beta = sum s g can be asked for)
+        ctx.want_beta = ctx.has_beta and beta.requires_grad
+        ctx.save_for_backward(*([p] + ([b1] if ctx.has_beta else []) + ([score] if ctx.want_beta else [])))
+        return p
+
+    @staticmethod
+    def backward(ctx, d_p):
+        saved = list(ctx.saved_tensors)
+        p = saved.pop(0)
+        b1 = saved.pop(0) if ctx.has_beta else None
+        score = saved.pop(0) if ctx.want_beta else None
+        want_beta = ctx.want_beta and ctx.needs_input_grad[2]
+        d_s, d_beta = _L.backend().edge_softmax_backward(p, d_p.contiguous(), ctx.rowptr, beta=b1, score=score if want_beta else None,
+                                                         need_dbeta=want_beta)
+        return (d_s if ctx.needs_input_grad[0] else None, None, d_beta.reshape(ctx.beta_shape).to(d_s.dtype) if want_beta else None)
+
+
+class _Aggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, H, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        P, H = P.contiguous(), H.contiguous()
+        ctx.save_for_backward(P, H)
+        return _L.backend().forward_AGNN(H, row_pointers, column_index, P.view(1, -1), blockPartition, edgeToColumn, edgeToRow)[0]
+
+    @staticmethod
+    def backward(ctx, d_y):
+        P, H = ctx.saved_tensors
+        rp, col, bp, e2c, e2r = ctx.meta
+        b = _L.backend()
+        d_y = d_y.contiguous()
+        d_p = b.forward_ef2(d_y, H, *ctx.meta)[0] if ctx.needs_input_grad[0] else None
+        d_h = b.forward_AGNN(d_y, rp, col, P.view(1, -1), bp, e2c, e2r, transpose=True)[0] if ctx.needs_input_grad[1] else None
+        return (d_p, d_h) + (None,) * 5
+
+
+def sddmm(X, Z, meta):
+    """ef[e] = <X[row e], Z[col e]> for every CSR edge, differentiable in both operands."""
+    return _SDDMM.apply(X, Z, *meta)
+
+
+def edge_softmax(score, row_pointers, beta=None):
+    """softmax of beta * score over every CSR row (a node's incoming edges); beta: a one-element tensor (a Parameter) or None = 1."""
+    return _EdgeSoftmax.apply(score, row_pointers, beta)
+
+
+def aggregate(P, H, meta):
+    """Y = A_val(P) H with A_val[row e, col e] = P[e], differentiable in the edge values and in H."""
+    return _Aggregate.apply(P, H, *meta)

@@ -49,6 +49,9 @@ def build_parser():
     p.add_argument("--bias", action="store_true", help="GCN only: a learned bias per layer, fused into the aggregation's stores (not in the reference)")
     p.add_argument("--directed", action="store_true", help="a --synthetic shape built without symmetrisation (a dataset is used as stored either way), "
                    "and every layer back-propagates through A^T (directed=True; not in the reference, whose backward uses A)")
+    p.add_argument("--attention", type=str, default="reference", choices=["reference", "softmax"],
+                   help="AGNN only: 'softmax' normalises the cosine scores over every node's incoming edges (DGL's AGNNConv; exact gradients) - "
+                   "not in the reference, whose layer aggregates with the raw scores")
     return p
 
 
@@ -122,14 +125,15 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False):
+                  norm="none", bias=False, directed=False, attention="reference"):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
     Adam, main_tcgnn.py:143) in a HIP graph after the dry epochs and replay it: on Citeseer-sized graphs an epoch is
     ~60 launches of a few microseconds each and the host, not the GPU, sets the time.
     norm / bias (GCN only, not in the reference): GCNConv(norm=..., bias=...), DGL GraphConv's normalised layer.
-    directed (not in the reference): every layer with directed=True (backward through A^T), and A^T's plan prepared with A's."""
+    directed (not in the reference): every layer with directed=True (backward through A^T), and A^T's plan prepared with A's.
+    attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers."""
     import tcgnn_layers as L
     conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv}[model_name]
     torch.manual_seed(seed)
@@ -138,6 +142,10 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     conv_kwargs = {"norm": norm, "bias": True} if bias else ({"norm": norm} if norm != "none" else {})
     if directed:
         conv_kwargs["directed"] = True
+    if attention != "reference":
+        if model_name != "agnn":
+            raise ValueError("attention applies to the AGNN model only")
+        conv_kwargs["attention"] = attention
     model = Net(conv_cls, in_dim, hidden, classes, num_layers, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
@@ -152,7 +160,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     prep = getattr(L.backend(), "prepare", None)
     if prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
         prep(([in_dim] if model_name == "gin" else []) + [hidden] * max(1, num_layers - 1) + [classes], *meta,
-             **({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {}))
+             **({"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
+                ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)
     for _ in range(warmup):
@@ -237,7 +246,8 @@ def run(args, quiet=False):
 
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
-                      norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False))
+                      norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
+                      attention=getattr(args, "attention", "reference"))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

@@ -526,8 +526,18 @@ class GINConv(torch.nn.Module):
 
 
 class AGNNConv(torch.nn.Module):
-    def __init__(self, input_dim, output_dim, directed=False):
+    """attention (not in the reference): 'reference' (the default) is gnn_conv.py's layer exactly - raw scores w * <h_i, h_j>,
+    the fused pair, the reference's backward.  'softmax' is DGL's AGNNConv with the reference's projection in front:
+        H = X W;  Hn = H / |H|_row;  s = sddmm(Hn, Hn);  P = edge_softmax(s, beta = attention_w);  Y = aggregate(P, H)
+    - cosine scores normalised over every node's incoming edges - composed of tcgnn_edge_ops' differentiable operators, whose
+    gradients are exact (through the scores into H and attention_w, through A^T on any graph: `directed` changes nothing there).
+    attention_w starts at 1 in that mode, as DGL's beta does."""
+
+    def __init__(self, input_dim, output_dim, directed=False, attention="reference"):
         super().__init__()
+        if attention not in ("reference", "softmax"):
+            raise ValueError("attention must be 'reference' or 'softmax', got %r" % (attention,))
+        self.attention = attention
         self.weights = torch.nn.Parameter(torch.randn(input_dim, output_dim))
         self.attention_w = torch.nn.Parameter(torch.randn(1, n_heads))
         self.directed = bool(directed)   # backward through A_att^T (not in the reference)
@@ -536,7 +546,16 @@ class AGNNConv(torch.nn.Module):
     def reset_parameters(self):
         bound = 1.0 / math.sqrt(self.weights.size(1))
         self.weights.data.uniform_(-bound, bound)
+        if self.attention == "softmax":
+            self.attention_w.data.fill_(1.0)
 
     def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        if self.attention == "softmax":
+            import tcgnn_edge_ops as E   # (it imports this module)
+            meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+            H = dense_update(X, self.weights)
+            Hn = F.normalize(H, dim=1)
+            P = E.edge_softmax(E.sddmm(Hn, Hn, meta), row_pointers, self.attention_w)
+            return E.aggregate(P, H, meta)
         return TCGNNFunction_AGNN.apply(X, self.weights, self.attention_w, row_pointers, column_index, blockPartition,
                                         edgeToColumn, edgeToRow, self.directed)
