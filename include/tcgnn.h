@@ -382,6 +382,35 @@ int tcgnn_edge_softmax_backward(const int32_t* d_nodePointer, int32_t num_nodes,
                                 const float* d_dp, const float* d_score, const float* d_beta, float* d_ds, float* d_dbeta,
                                 void* d_scratch, size_t scratch_bytes, void* stream);
 
+/* ---- multi-head GAT attention (DGL's GATConv scores; no counterpart in the reference, whose n_heads is the constant 1) ----------
+ *
+ * CSR row = destination node, column = source node.  H = num_heads.  Per-node terms d_el (source side, read at col(e)) and d_er
+ * (destination side, read at row(e)) are fp32 [num_nodes, H] row-major; per-edge arrays are head-major [H, num_edges] - the
+ * reference's edgeAttention layout, so a head's row is what tcgnn_spmm_val takes.  Planless like tcgnn_edge_softmax: device pointers,
+ * the caller's stream, no allocation, no synchronisation (capturable in a HIP graph); bit-identical on repetition (fixed-order
+ * reductions, no atomics).
+ *   tcgnn_gat_softmax           s[h,e] = lrelu(fl32(el[col e, h] + er[row e, h])), lrelu(x) = x > 0 ? x : fl32(x * negative_slope);
+ *                               p[h,.] = softmax of s[h,.] over every CSR row, the maximum always subtracted.  The scores never reach
+ *                               memory; each is rounded to fp32 before the maximum is subtracted (p is the softmax of the score a
+ *                               composition of separate operators would form).
+ *   tcgnn_gat_softmax_backward  g = p (dp - sum_row p dp);  ds[h,e] = g * (raw > 0 ? 1 : negative_slope), raw recomputed from el / er;
+ *                               d_er[r,h] = sum_{e in row r} ds[h,e] in the same kernel: EVERY row is written, an empty one with 0.
+ *                               d_ds may alias d_dp.
+ *   tcgnn_edge_colsum           out[c,h] = sum_{eT in row c of A^T} val[h, perm[eT]]: the per-source-node sum of per-edge values given
+ *                               in A's order; d_nodePointer_t and d_perm are what tcgnn_transpose_ws wrote.  With val = ds: d_el.
+ * Row pointers are clamped to [0, num_edges] and a descending pair is an empty row.  For every read they index, a column id is clamped to
+ * the nearer end of [0, num_nodes) and a perm entry outside [0, num_edges) reads position 0 (as tcgnn_permute_edge_values does): safe
+ * reads either way, values of no meaning for an array that holds such entries.  Nothing outside [0, num_edges) of a head's row of p / ds, or outside
+ * [0, num_nodes * H) of d_er / out, is written.  num_edges = 0 or num_nodes = 0 returns TCGNN_OK (d_er / out zeroed where
+ * num_nodes > 0 and the pointer is given); H < 1, a negative size or a null array otherwise: TCGNN_ERR_INVALID_ARG. */
+int tcgnn_gat_softmax(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                      int32_t num_heads, const float* d_el, const float* d_er, float negative_slope, float* d_p, void* stream);
+int tcgnn_gat_softmax_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                               int32_t num_heads, const float* d_el, const float* d_er, float negative_slope, const float* d_p,
+                               const float* d_dp, float* d_ds, float* d_der, void* stream);
+int tcgnn_edge_colsum(const int32_t* d_nodePointer_t, const int32_t* d_perm, int32_t num_nodes, int64_t num_edges,
+                      int32_t num_heads, const float* d_val, float* d_out, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

@@ -316,6 +316,105 @@ std::tuple<torch::Tensor, c10::optional<torch::Tensor>> edge_softmax_backward(to
   return {ds, dbeta};
 }
 
+// ---- not in the reference: multi-head GAT attention (tcgnn_gat_softmax / _backward / tcgnn_edge_colsum; the ctypes module's
+// gat_softmax, gat_softmax_backward and edge_colsum) ------------------------------------------------------------------------------
+namespace {
+// (N, E, H) of a GAT call, after the checks of the ctypes module
+std::tuple<int32_t, int64_t, int32_t> gat_args(const torch::Tensor& el, const torch::Tensor& er, const torch::Tensor& nodePointer,
+                                               const torch::Tensor& edgeList) {
+  CHECK_INPUT(el); CHECK_INPUT(er); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(el.scalar_type() == torch::kFloat32 && er.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  const int64_t N = nodePointer.numel() - 1;
+  TORCH_CHECK(el.dim() == 2 && el.size(0) == N && el.size(1) >= 1 && er.sizes() == el.sizes(), "el and er must be [num_nodes, heads] (heads >= 1)");
+  TORCH_CHECK(er.device() == el.device() && nodePointer.device() == el.device() && edgeList.device() == el.device(),
+              "el, er, nodePointer and edgeList must be on one device");
+  return {(int32_t)N, edgeList.numel(), (int32_t)el.size(1)};
+}
+void check_head_major(const torch::Tensor& t, const char* name, int64_t H, int64_t E, const torch::Tensor& like) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kFloat32 && t.dim() == 2 && t.size(0) == H && t.size(1) == E &&
+              t.device() == like.device(), name, " must be a contiguous fp32 [heads, num_edges] tensor on the device of el");
+}
+
+// the transposed CSR edge_colsum sums over, one per (nodePointer, edgeList): tcgnn_transpose_ws at first sight, then cached
+struct TransposedCsr {
+  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
+  torch::Tensor nodePointer, edgeList, rp_t, perm;
+};
+std::list<TransposedCsr>& csr_cache() { static std::list<TransposedCsr> c; return c; }
+
+TransposedCsr& transposed_csr(const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
+  for (auto* t : {&nodePointer, &edgeList}) key.emplace_back(t->data_ptr(), t->numel(), (int64_t)t->_version());
+  auto& cache = csr_cache();
+  for (auto it = cache.begin(); it != cache.end(); ++it)
+    if (it->key == key) { cache.splice(cache.begin(), cache, it); return cache.front(); }
+  const int32_t N = (int32_t)(nodePointer.numel() - 1);
+  const int64_t E = edgeList.numel();
+  auto opts = nodePointer.options().dtype(torch::kInt32);
+  TransposedCsr c;
+  c.key = key;
+  c.nodePointer = nodePointer;
+  c.edgeList = edgeList;
+  c.rp_t = torch::empty({(int64_t)N + 1}, opts);
+  c.perm = torch::empty({E}, opts);
+  torch::Tensor col_t = torch::empty({E}, opts);
+  size_t need = 0;
+  void* ws = nullptr;
+  tcgnn_check(tcgnn_transpose_workspace_bytes(N, E, &need), "tcgnn_transpose_workspace_bytes");
+  torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
+  tcgnn_check(tcgnn_transpose_ws(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, c.rp_t.data_ptr<int>(), col_t.data_ptr<int>(),
+                                 c.perm.data_ptr<int>(), ws, need, nullptr, current_stream(nodePointer)), "tcgnn_transpose_ws");
+  cache.push_front(std::move(c));
+  while (cache.size() > kPlanCacheSize) cache.pop_back();   // (tcgnn_transpose_ws synchronised; torch's allocator orders the reuse of the rest)
+  return cache.front();
+}
+}  // namespace
+
+torch::Tensor gat_softmax(torch::Tensor el, torch::Tensor er, torch::Tensor nodePointer, torch::Tensor edgeList, double negative_slope,
+                          c10::optional<torch::Tensor> out) {
+  auto [N, E, H] = gat_args(el, er, nodePointer, edgeList);
+  torch::Tensor p = out.has_value() ? *out : torch::empty({(int64_t)H, E}, el.options());
+  check_head_major(p, "out", H, E, el);
+  DeviceGuard guard(el.device());
+  tcgnn_check(tcgnn_gat_softmax(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, H, el.data_ptr<float>(), er.data_ptr<float>(),
+                                (float)negative_slope, p.data_ptr<float>(), current_stream(el)), "tcgnn_gat_softmax");
+  return p;
+}
+
+std::tuple<torch::Tensor, torch::Tensor> gat_softmax_backward(torch::Tensor p, torch::Tensor dp, torch::Tensor el, torch::Tensor er,
+                                                              torch::Tensor nodePointer, torch::Tensor edgeList, double negative_slope,
+                                                              c10::optional<torch::Tensor> out) {
+  auto [N, E, H] = gat_args(el, er, nodePointer, edgeList);
+  check_head_major(p, "p", H, E, el);
+  check_head_major(dp, "dp", H, E, el);
+  torch::Tensor ds = out.has_value() ? *out : torch::empty_like(dp);
+  check_head_major(ds, "out", H, E, el);
+  DeviceGuard guard(el.device());
+  torch::Tensor d_er = torch::empty({(int64_t)N, (int64_t)H}, el.options());
+  tcgnn_check(tcgnn_gat_softmax_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, H, el.data_ptr<float>(), er.data_ptr<float>(),
+                                         (float)negative_slope, p.data_ptr<float>(), dp.data_ptr<float>(), ds.data_ptr<float>(),
+                                         d_er.data_ptr<float>(), current_stream(el)), "tcgnn_gat_softmax_backward");
+  return {ds, d_er};
+}
+
+torch::Tensor edge_colsum(torch::Tensor val, torch::Tensor nodePointer, torch::Tensor edgeList) {
+  CHECK_INPUT(val); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(val.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  TORCH_CHECK(val.dim() == 2 && val.size(0) >= 1 && val.size(1) == edgeList.numel(), "val must be [heads, num_edges] (heads >= 1)");
+  TORCH_CHECK(val.device() == nodePointer.device() && edgeList.device() == nodePointer.device(), "val, nodePointer and edgeList must be on one device");
+  DeviceGuard guard(val.device());
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  const int64_t N = nodePointer.numel() - 1, H = val.size(0);
+  torch::Tensor out = torch::empty({N, H}, val.options());
+  tcgnn_check(tcgnn_edge_colsum(t.rp_t.data_ptr<int>(), t.perm.data_ptr<int>(), (int32_t)N, edgeList.numel(), (int32_t)H, val.data_ptr<float>(),
+                                out.data_ptr<float>(), current_stream(val)), "tcgnn_edge_colsum");
+  return out;
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -400,6 +499,7 @@ void clear_plan_cache() {
     destroy_entry(e);
   }
   plan_cache().clear();
+  csr_cache().clear();
 }
 
 // TCGNN.cpp:260-272
@@ -425,4 +525,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta") = py::none(), py::arg("out") = py::none());
   m.def("edge_softmax_backward", &edge_softmax_backward, "backward of edge_softmax: (ds, dbeta) (not in the reference)", py::arg("p"), py::arg("dp"),
         py::arg("nodePointer"), py::arg("beta") = py::none(), py::arg("score") = py::none(), py::arg("need_dbeta") = false, py::arg("out") = py::none());
+  m.def("gat_softmax", &gat_softmax, "multi-head GAT attention, p[heads, E] (not in the reference)", py::arg("el"), py::arg("er"), py::arg("nodePointer"),
+        py::arg("edgeList"), py::arg("negative_slope") = 0.2, py::arg("out") = py::none());
+  m.def("gat_softmax_backward", &gat_softmax_backward, "backward of gat_softmax: (ds, d_er) (not in the reference)", py::arg("p"), py::arg("dp"),
+        py::arg("el"), py::arg("er"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2, py::arg("out") = py::none());
+  m.def("edge_colsum", &edge_colsum, "per-source-node sums of per-edge values, [N, heads] (not in the reference)", py::arg("val"), py::arg("nodePointer"),
+        py::arg("edgeList"));
 }

@@ -35,7 +35,7 @@ import tcgnn_capi as _c
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
-           "forward_ef2", "edge_softmax", "edge_softmax_backward"]
+           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum"]
 
 _plan_cache_size = max(1, int(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8")))
 _plans = collections.OrderedDict()  # key -> (handle, tensors kept alive, device index)
@@ -311,7 +311,11 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     and with edge_valued=True the buffer forward_AGNN(transpose=True) permutes the edge values into, on the current stream.
     attention=True (a model with softmax-attention layers: forward_ef2, edge_softmax, edge_softmax_backward): the workspace grown to
     forward_ef2's two images at every width and the scratch of edge_softmax_backward's d_beta, on the current stream - a step that
-    uses them then allocates nothing outside torch's pool and never synchronises."""
+    uses them then allocates nothing outside torch's pool and never synchronises.
+    A GAT model (gat_softmax, gat_softmax_backward, edge_colsum and the per-head forward_AGNN / forward_ef2 calls of
+    tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True and attention=True: the
+    edge-valued streams of A and A^T at that width, the two-image SDDMM workspace, and - with A^T's plan - the transposed CSR
+    edge_colsum sums over."""
     plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     plans = [plan]
     dev = nodePointer.device
@@ -827,6 +831,92 @@ def edge_softmax_backward(p, dp, nodePointer, beta=None, score=None, need_dbeta=
                                                 _stream_handle(dev))
     _c.check(st, "tcgnn_edge_softmax_backward")
     return out, dbeta
+
+
+# ---- additions (not in the reference module): multi-head GAT attention ----------------------------------
+
+def _gat_args(el, er, nodePointer, edgeList):
+    for t, n in ((el, "el"), (er, "er")):
+        _check_input(t, n)
+        _check_float(t, n)
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    N = nodePointer.numel() - 1
+    if N < 0:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    if el.dim() != 2 or el.size(0) != N or el.size(1) < 1 or er.shape != el.shape:
+        raise RuntimeError("el and er must be [num_nodes, heads] (heads >= 1) with num_nodes = %d, got %s and %s" % (N, tuple(el.shape), tuple(er.shape)))
+    if any(t.device != el.device for t in (er, nodePointer, edgeList)):
+        raise RuntimeError("el, er, nodePointer and edgeList must be on one device")
+    return N, edgeList.numel(), el.size(1)
+
+
+def _head_major(t, name, H, E, like):
+    _check_input(t, name)
+    _check_float(t, name)
+    if tuple(t.shape) != (H, E) or t.device != like.device:
+        raise RuntimeError("%s must be a contiguous fp32 [heads, num_edges] = [%d, %d] tensor on the device of el, got %s" % (name, H, E, tuple(t.shape)))
+
+
+def gat_softmax(el, er, nodePointer, edgeList, negative_slope=0.2, out=None):
+    """Not in the reference module: GAT's attention in one kernel (tcgnn_gat_softmax), p fp32 [heads, E] (the reference's edgeAttention
+    layout: p[h] is what forward_AGNN takes),
+        s[h, e] = leaky_relu(el[col(e), h] + er[row(e), h]),   p[h, .] = softmax of s[h, .] over every node's incoming edges.
+    el / er: fp32 [N, heads], the source- and the destination-side term of every node.  The scores never reach memory.  Entries of
+    positions no row covers are left as allocated.  Deterministic: a second call returns the same bits."""
+    N, E, H = _gat_args(el, er, nodePointer, edgeList)
+    if out is None:
+        out = torch.empty(H, E, dtype=torch.float32, device=el.device)
+    else:
+        _head_major(out, "out", H, E, el)
+    dev = el.device
+    with torch.cuda.device(dev):
+        st = _c.lib.tcgnn_gat_softmax(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(), float(negative_slope),
+                                      out.data_ptr(), _stream_handle(dev))
+    _c.check(st, "tcgnn_gat_softmax")
+    return out
+
+
+def gat_softmax_backward(p, dp, el, er, nodePointer, edgeList, negative_slope=0.2, out=None):
+    """Not in the reference module: the backward of gat_softmax (tcgnn_gat_softmax_backward) - (ds [heads, E], d_er [N, heads]) with
+        g = p (dp - sum_row p dp),   ds[h, e] = g (el[col e, h] + er[row e, h] > 0 ? 1 : negative_slope),   d_er[r, h] = sum_{row r} ds[h, .]
+    out may be dp itself.  d_el is edge_colsum(ds, nodePointer, edgeList)."""
+    N, E, H = _gat_args(el, er, nodePointer, edgeList)
+    _head_major(p, "p", H, E, el)
+    _head_major(dp, "dp", H, E, el)
+    if out is None:
+        out = torch.empty_like(dp)
+    else:
+        _head_major(out, "out", H, E, el)
+    dev = el.device
+    d_er = torch.empty(N, H, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = _c.lib.tcgnn_gat_softmax_backward(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(), float(negative_slope),
+                                               p.data_ptr(), dp.data_ptr(), out.data_ptr(), d_er.data_ptr(), _stream_handle(dev))
+    _c.check(st, "tcgnn_gat_softmax_backward")
+    return out, d_er
+
+
+def edge_colsum(val, nodePointer, edgeList):
+    """Not in the reference module: out[c, h] = the sum of val[h, e] over the edges e with col(e) = c, fp32 [N, heads] (tcgnn_edge_colsum) -
+    a segmented sum over the rows of A^T in a fixed order, no atomics.  val: fp32 [heads, E] in A's CSR order.  The transposed CSR
+    is the module's cached one (transpose_graph): built at the first call for a graph, or by prepare(..., transpose=True)."""
+    _check_input(val, "val")
+    _check_float(val, "val")
+    E = edgeList.numel()
+    if val.dim() != 2 or val.size(0) < 1 or val.size(1) != E:
+        raise RuntimeError("val must be [heads, num_edges] (heads >= 1) with num_edges = %d, got %s" % (E, tuple(val.shape)))
+    _, _, rp_t, _, perm, _ = _transpose_csr(nodePointer, edgeList)
+    if val.device != nodePointer.device:
+        raise RuntimeError("val is on %s but nodePointer is on %s" % (val.device, nodePointer.device))
+    dev = val.device
+    N, H = nodePointer.numel() - 1, val.size(0)
+    out = torch.empty(N, H, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        st = _c.lib.tcgnn_edge_colsum(rp_t.data_ptr(), perm.data_ptr(), N, E, H, val.data_ptr(), out.data_ptr(), _stream_handle(dev))
+    _c.check(st, "tcgnn_edge_colsum")
+    return out
 
 
 # ---- additions (not in the reference module): the two products of an AGNN layer in one pass ------------

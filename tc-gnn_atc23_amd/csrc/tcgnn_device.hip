@@ -36,6 +36,7 @@
 //   tcgnn_lds_val.inc         LDS-resident edge-valued SpMM (single-edge stream, per-call slot values)
 //   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel (one and two operands), sddmm2_csr_kernel
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
+//   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
 //   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
 //   tcgnn_small_fallback.inc  spmm_small_kernel, CSR kernels of non-canonical plans, the range guard's fallbacks, wide_patch_kernel
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
@@ -359,6 +360,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_transpose.inc"
 
 #include "tcgnn_edge_softmax.inc"
+#include "tcgnn_gat.inc"
 
 // ------------------------------------------------------------------------------------------
 // launch tables

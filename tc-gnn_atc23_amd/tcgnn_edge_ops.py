@@ -5,6 +5,9 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     sddmm(X, Z, meta)             ef[e] = <X[row e], Z[col e]>            bwd: dX = A_val(d_ef) Z,  dZ = A_val(d_ef)^T X
     edge_softmax(s, rowptr, beta) p = softmax over each CSR row of beta s  bwd: g = p (dp - sum_row p dp); ds = beta g; dbeta = <s, g>
     aggregate(P, H, meta)         Y = A_val(P) H                           bwd: dP = sddmm(dY, H),  dH = A_val(P)^T dY
+    gat_attention(el, er, rowptr, col, slope)  P[h] = softmax by row of leaky_relu(el[col e, h] + er[row e, h])   (multi-head GAT)
+                                  bwd: g as above per head; ds = g lrelu'(raw); d_er = row sums of ds; d_el = column sums of ds
+    aggregate_heads(P, Z, meta)   Y[:, head h] = aggregate(P[h], Z[:, head h])
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
@@ -80,6 +83,74 @@ class _Aggregate(torch.autograd.Function):
         d_p = b.forward_ef2(d_y, H, *ctx.meta)[0] if ctx.needs_input_grad[0] else None
         d_h = b.forward_AGNN(d_y, rp, col, P.view(1, -1), bp, e2c, e2r, transpose=True)[0] if ctx.needs_input_grad[1] else None
         return (d_p, d_h) + (None,) * 5
+
+
+class _GATAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, el, er, row_pointers, column_index, negative_slope):
+        el, er = el.contiguous(), er.contiguous()
+        p = _L.backend().gat_softmax(el, er, row_pointers, column_index, negative_slope)
+        ctx.graph = (row_pointers, column_index)
+        ctx.slope = negative_slope
+        ctx.save_for_backward(p, el, er)
+        return p
+
+    @staticmethod
+    def backward(ctx, d_p):
+        p, el, er = ctx.saved_tensors
+        b = _L.backend()
+        d_p = d_p.contiguous()
+        ds, d_er = b.gat_softmax_backward(p, d_p, el, er, *ctx.graph, ctx.slope)
+        d_el = b.edge_colsum(ds, *ctx.graph) if ctx.needs_input_grad[0] else None
+        return d_el, (d_er if ctx.needs_input_grad[1] else None), None, None, None
+
+
+class _AggregateHeads(torch.autograd.Function):
+    """_Aggregate head by head in one node of the autograd graph: dP is written row by row into one [heads, E] tensor (H separate
+    aggregate() calls on P[h] would each have autograd zero-fill and add a whole [heads, E] gradient)."""
+
+    @staticmethod
+    def _slices(M, H):
+        F = M.shape[1] // H
+        return [M[:, h * F:(h + 1) * F].contiguous() for h in range(H)]
+
+    @staticmethod
+    def forward(ctx, P, Z, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        P = P.contiguous()
+        ctx.save_for_backward(P, Z)
+        b = _L.backend()
+        Zh = _AggregateHeads._slices(Z, P.shape[0])
+        return torch.cat([b.forward_AGNN(z, row_pointers, column_index, P[h].view(1, -1), blockPartition, edgeToColumn, edgeToRow)[0]
+                          for h, z in enumerate(Zh)], dim=1)
+
+    @staticmethod
+    def backward(ctx, d_y):
+        P, Z = ctx.saved_tensors
+        rp, col, bp, e2c, e2r = ctx.meta
+        b = _L.backend()
+        H = P.shape[0]
+        dYh = _AggregateHeads._slices(d_y, H)
+        d_p = d_z = None
+        if ctx.needs_input_grad[0]:
+            d_p = torch.stack([b.forward_ef2(dy, z, *ctx.meta)[0] for dy, z in zip(dYh, _AggregateHeads._slices(Z, H))])
+        if ctx.needs_input_grad[1]:
+            d_z = torch.cat([b.forward_AGNN(dy, rp, col, P[h].view(1, -1), bp, e2c, e2r, transpose=True)[0] for h, dy in enumerate(dYh)], dim=1)
+        return (d_p, d_z) + (None,) * 5
+
+
+def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):
+    """P[h, e] = softmax over every CSR row of leaky_relu(el[col e, h] + er[row e, h]): GAT's attention, [heads, E] (head-major: P[h] is
+    what aggregate takes).  el / er: [N, heads].  bwd: (ds, d_er) from the backend's gat_softmax_backward, d_el = edge_colsum(ds)."""
+    return _GATAttention.apply(el, er, row_pointers, column_index, float(negative_slope))
+
+
+def aggregate_heads(P, Z, meta):
+    """Y[:, hF:(h+1)F] = aggregate(P[h], Z[:, hF:(h+1)F], meta) for P [heads, E] and Z [N, heads * F]: the multi-head aggregation
+    composed of the edge-valued SpMM head by head (dP[h] through forward_ef2, dZ through A^T, both exact)."""
+    if P.dim() != 2 or Z.dim() != 2 or P.shape[0] < 1 or Z.shape[1] % P.shape[0]:
+        raise RuntimeError("P must be [heads, E] and Z [N, heads * F], got %s and %s" % (tuple(P.shape), tuple(Z.shape)))
+    return _AggregateHeads.apply(P, Z, *meta)
 
 
 def sddmm(X, Z, meta):

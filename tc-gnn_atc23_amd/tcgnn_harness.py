@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -52,17 +52,20 @@ def build_parser():
     p.add_argument("--attention", type=str, default="reference", choices=["reference", "softmax"],
                    help="AGNN only: 'softmax' normalises the cosine scores over every node's incoming edges (DGL's AGNNConv; exact gradients) - "
                    "not in the reference, whose layer aggregates with the raw scores")
+    p.add_argument("--heads", type=int, default=1, help="GAT only: attention heads of the hidden layers, which concatenate `heads` heads of "
+                   "hidden / heads features (it must divide); the output layer has one head of `classes` (not in the reference)")
     return p
 
 
 class Net(nn.Module):
     """conv1 -> relu -> dropout -> [hidden convs + relu] -> conv2 -> log_softmax (main_tcgnn.py:75-139)."""
 
-    def __init__(self, conv_cls, in_dim, hidden, classes, num_layers, **conv_kwargs):
+    def __init__(self, conv_cls, in_dim, hidden, classes, num_layers, out_cls=None, **conv_kwargs):
+        """out_cls (a GAT model: one head of `classes` behind hidden layers of several heads): what builds the output layer; None: conv_cls."""
         super().__init__()
         self.conv1 = conv_cls(in_dim, hidden, **conv_kwargs)
         self.hidden_layers = nn.ModuleList(conv_cls(hidden, hidden, **conv_kwargs) for _ in range(num_layers - 2))
-        self.conv2 = conv_cls(hidden, classes, **conv_kwargs)
+        self.conv2 = (out_cls or conv_cls)(hidden, classes, **conv_kwargs)
         self.relu = nn.ReLU()
 
     def _act(self, conv, x, meta):
@@ -125,7 +128,7 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference"):
+                  norm="none", bias=False, directed=False, attention="reference", heads=1):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -133,9 +136,22 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     ~60 launches of a few microseconds each and the host, not the GPU, sets the time.
     norm / bias (GCN only, not in the reference): GCNConv(norm=..., bias=...), DGL GraphConv's normalised layer.
     directed (not in the reference): every layer with directed=True (backward through A^T), and A^T's plan prepared with A's.
-    attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers."""
+    attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers.
+    heads (GAT only, not in the reference): the hidden layers are GATConv(., hidden / heads, heads=heads) - concatenated back to `hidden` -
+    and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths."""
     import tcgnn_layers as L
-    conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv}[model_name]
+    heads = int(heads)
+    if heads != 1 and model_name != "gat":
+        raise ValueError("heads applies to the GAT model only")
+    if model_name == "gat" and (heads < 1 or hidden % heads):
+        raise ValueError("--hidden (%d) must be a multiple of --heads (%d)" % (hidden, heads))
+    out_cls = None
+    if model_name == "gat":
+        def conv_cls(a, b):
+            return L.GATConv(a, b // heads, heads=heads)
+        out_cls = L.GATConv
+    else:
+        conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv}[model_name]
     torch.manual_seed(seed)
     if model_name != "gcn" and (norm != "none" or bias):
         raise ValueError("norm / bias apply to the GCN model only")
@@ -146,7 +162,9 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if model_name != "agnn":
             raise ValueError("attention applies to the AGNN model only")
         conv_kwargs["attention"] = attention
-    model = Net(conv_cls, in_dim, hidden, classes, num_layers, **conv_kwargs).to(x.device)
+    if model_name == "gat":
+        conv_kwargs.pop("directed", None)   # (GATConv back-propagates through A^T on every graph)
+    model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
     def train():
@@ -159,8 +177,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
 
     prep = getattr(L.backend(), "prepare", None)
     if prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
-        prep(([in_dim] if model_name == "gin" else []) + [hidden] * max(1, num_layers - 1) + [classes], *meta,
-             **({"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
+        prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
+             **({"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" or model_name == "gat" else
                 ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)
@@ -247,7 +265,7 @@ def run(args, quiet=False):
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
-                      attention=getattr(args, "attention", "reference"))
+                      attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

@@ -559,3 +559,47 @@ class AGNNConv(torch.nn.Module):
             return E.aggregate(P, H, meta)
         return TCGNNFunction_AGNN.apply(X, self.weights, self.attention_w, row_pointers, column_index, blockPartition,
                                         edgeToColumn, edgeToRow, self.directed)
+
+
+class GATConv(torch.nn.Module):
+    """Not in the reference (whose n_heads is the constant 1): DGL's GATConv - additive attention, several heads, a softmax over
+    every node's incoming edges per head - with the reference's projection in front:
+        Z = X W  [N, heads * output_dim];   el = <Z_h, attn_l_h>,  er = <Z_h, attn_r_h>  per node and head;
+        P[h, e] = softmax by row of leaky_relu(el[col e, h] + er[row e, h]);   Y_h = A_val(P[h]) Z_h
+    (tcgnn_edge_ops.gat_attention - one fused kernel - and aggregate_heads; gradients exact on any graph).  The heads are concatenated
+    ([N, heads * output_dim]) or, with concat=False, averaged ([N, output_dim]); then the bias is added: a node without incoming edges
+    gets the bias only.  Glorot initialisation as in DGL (normal, gain sqrt 2; bias zero).  No attention / feature dropout, no residual."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, bias=True):
+        super().__init__()
+        if heads < 1:
+            raise ValueError("heads must be >= 1, got %r" % (heads,))
+        self.heads, self.output_dim, self.negative_slope, self.concat = int(heads), int(output_dim), float(negative_slope), bool(concat)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, self.heads * self.output_dim))
+        self.attn_l = torch.nn.Parameter(torch.empty(1, self.heads, self.output_dim))
+        self.attn_r = torch.nn.Parameter(torch.empty(1, self.heads, self.output_dim))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(self.heads * self.output_dim if self.concat else self.output_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        torch.nn.init.xavier_normal_(self.weights, gain=gain)
+        torch.nn.init.xavier_normal_(self.attn_l, gain=gain)
+        torch.nn.init.xavier_normal_(self.attn_r, gain=gain)
+        if self.bias is not None:
+            self.bias.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        Z = dense_update(X, self.weights)
+        Zh = Z.view(Z.shape[0], self.heads, self.output_dim)
+        el, er = (Zh * self.attn_l).sum(-1), (Zh * self.attn_r).sum(-1)
+        P = E.gat_attention(el, er, row_pointers, column_index, self.negative_slope)
+        Y = E.aggregate_heads(P, Z, meta)
+        if not self.concat:
+            Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
+        return Y + self.bias if self.bias is not None else Y
