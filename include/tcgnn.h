@@ -42,6 +42,24 @@
  *     (SDDMM, fused AGNN).  A training epoch's activations (one stray 1e-5 among 1e4's) stay on the MFMA path.  Images the
  *     CALLER stages (tcgnn_spmm_staged) carry no range words and always take the MFMA path (the kernels
  *     do not look at the rest of such a header).
+ *   - Alignment.  Every array needs the alignment of its element type (4 bytes) and no more, with these exceptions, all checked
+ *     on the host before anything is enqueued - a refused call has written nothing:
+ *       workspaces (d_workspace of every call that takes one)   256 bytes, else TCGNN_ERR_WORKSPACE;
+ *       caller-staged images (d_image of tcgnn_spmm_staged / _staged_planar)   256 bytes, d_dst of tcgnn_stage_rows 16 bytes and of
+ *         tcgnn_stage_rows_planar 32 bytes, else TCGNN_ERR_INVALID_ARG;
+ *       the [N, D] OUTPUT of the plan-based calls - d_Y of tcgnn_spmm / _fused / _scaled / _gemm / _val / _staged / _staged_planar and
+ *         of tcgnn_agnn_pair_forward, d_G of tcgnn_agnn_pair_backward -   16 bytes, else TCGNN_ERR_INVALID_ARG (kernels behind the
+ *         LDS-resident walks update Y sixteen bytes at a time; any hipMalloc'ed or framework-allocated matrix is aligned far beyond
+ *         that - only a view that starts inside another buffer is not);
+ *       d_scratch of tcgnn_edge_softmax_backward   8 bytes.
+ *     INPUTS of the plan-based calls (X, Z, dY, gate, edge values, row_scale / col_scale / bias, W, the saved ef and ef_absmax, the
+ *     scalars d_w / d_beta) and the per-edge / per-word outputs (d_ef, d_ef_absmax, d_dw, d_out of tcgnn_permute_edge_values) may start
+ *     at any 4-byte boundary, e.g. a contiguous view one float into a larger tensor: the staging pass takes 16-byte loads only where
+ *     the pointer allows them, and the results are bit for bit those of the aligned call.
+ *   - Workspace size.  A call that takes d_workspace returns TCGNN_ERR_WORKSPACE, before anything is enqueued, when workspace_bytes
+ *     is below what the matching query answers NOW (tcgnn_workspace_bytes for the plan and width - ask again after
+ *     tcgnn_plan_prepare[_val] and after a mode switch -, tcgnn_sddmm2_workspace_bytes for tcgnn_sddmm2), whichever walk would run;
+ *     no call writes a byte beyond that size.
  *   - Index arrays are int32 (the reference API's dtype); all address arithmetic inside the
  *     kernels is 64-bit, so N*D may exceed 2^32 (the reference overflows there,
  *     TCGNN_kernel.cu:420).

@@ -673,6 +673,22 @@ static void launch_absmax(const tcgnn_plan* plan, const float* d_X, const float*
     }
 }
 
+// ---- what every hot-path entry point asks of the caller's buffers BEFORE it enqueues anything (include/tcgnn.h "Alignment"): a
+// refused call has touched neither the outputs nor the workspace.
+// [N, D] outputs: spmm_cold_planar_kernel and spmm_cold_val_kernel read-modify-write Y as float4 wherever D % 4 == 0, and
+// agnn_slice_sum_kernel stores it that way - on the host, so that no kernel carries a pointer test
+static int check_output_aligned(const char* call, const char* what, const void* p) {
+    if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCGNN_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned, got %p", call, what, p);
+    return TCGNN_OK;
+}
+// the workspace the header prescribes for the call (tcgnn_workspace_bytes / tcgnn_sddmm2_workspace_bytes), whichever walk will run:
+// a walk that needs less than that does not make a smaller buffer legal
+static int check_workspace(const char* call, const void* ws, size_t ws_bytes, size_t need) {
+    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+        return fail(TCGNN_ERR_WORKSPACE, "%s: workspace needs %zu bytes 256-aligned, got %zu at %p", call, need, ws_bytes, ws);
+    return TCGNN_OK;
+}
+
 struct StagedImage { const uint32_t* hdr = nullptr; const _Float16* x16 = nullptr; int dpad = 0, pitch = 0; };
 struct StageOpts {
     bool planar = false;                 // [dpad / 16 planes][Nc + 1][16 halves] for the LDS-resident kernels instead of row-major
@@ -893,8 +909,9 @@ static int run_agnn(const tcgnn_plan* plan, const float* d_X, const float* d_w, 
     int nslices = 0;
     const int walk = agnn_walk(plan, D, bwd, &nslices);
     const bool sliced = walk == kAgnnSliced;
-    const size_t need = workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan) + agnn_slice_bytes(plan, D);
-    if (!ws || ws_bytes < need) return fail(TCGNN_ERR_WORKSPACE, "%s: workspace needs %zu bytes, got %zu", name, need, ws_bytes);
+    if (const int rc = check_output_aligned(name, bwd ? "G" : "Y", d_Y)) return rc;
+    if (const int rc = check_workspace(name, ws, ws_bytes, tcgnn_workspace_bytes(plan, D))) return rc;
+    // (tcgnn_workspace_bytes holds the image, the reduction slots and the slice addends of this call: image + max(partial + slices, ..))
     if ((int64_t)plan->nw_eff * kWinRows < plan->N) {   // rows the caller's windows do not cover stay zero
         HIP_TRY(hipMemsetAsync(d_Y, 0, (size_t)plan->N * D * sizeof(float), stream));
         if (!bwd) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
@@ -1518,6 +1535,7 @@ int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge
 static int run_sddmm(const tcgnn_plan* plan, const float* d_Xw, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     if (plan->E == 0 || plan->N == 0) return TCGNN_OK;
+    if (const int rc = check_workspace(d_Xw ? "tcgnn_sddmm2" : "tcgnn_sddmm", ws, ws_bytes, d_Xw ? tcgnn_sddmm2_workspace_bytes(plan, D) : tcgnn_workspace_bytes(plan, D))) return rc;
     if (!plan->canonical) {
         if (d_Xw) hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, (const uint32_t*)nullptr, (const uint32_t*)nullptr, plan->rowptr, plan->col, d_Xw, d_X, d_ef, plan->N, D, plan->row_off);
         else hipLaunchKernelGGL(sddmm_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, plan->rowptr, plan->col, d_X, d_ef, plan->N, D, plan->row_off);

@@ -435,6 +435,11 @@ static int run_spmm(const SpmmCall& c) {
     const tcgnn_plan* const plan = c.plan;
     if (!plan || c.D < 1 || (plan->N > 0 && ((!c.d_X && !c.d_image) || !c.d_Y))) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm: null argument or D < 1");
     if (plan->N == 0) return TCGNN_OK;
+    // (the caller's buffers, before anything is enqueued - a column block of a wider call was checked with the whole call)
+    if (!c.block_of_wider) {
+        if (const int rc = check_output_aligned("tcgnn_spmm", "Y", c.d_Y)) return rc;
+        if (!c.d_image) { if (const int rc = check_workspace("tcgnn_spmm", c.ws, c.ws_bytes, tcgnn_workspace_bytes(plan, c.D))) return rc; }
+    }
     if (const int rc = fill_uncovered_rows(c)) return rc;
     SpmmRoute r;
     if (const int rc = route_spmm(c, &r)) return rc;

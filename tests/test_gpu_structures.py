@@ -44,7 +44,6 @@ tcgnn_plan_create builds it from 4 windows per CU, 1 024, on) and EXCEPTIONS say
 entries, and the range-major SDDMM / fused walks, whose kernel carries the per-window walk's name, count as run only where the plan
 holds a bucket table and the range count computed from the image size is a multiple of eight.  The slice-synchronised walk is run on
 the two 40 k entries.  The flat walks also read the plan's verbose line: tiles per cell as forced, dense entries counted."""
-import re
 import sys
 
 import numpy as np
@@ -63,8 +62,7 @@ BUCKETED = graphs.bucketed_boundary_graphs()
 SYNC = graphs.sync_boundary_graphs()
 GRAPHS = {name: (rp, col) for name, rp, col in SMALL + BUCKETED + SYNC}
 SMALL_NAMES, BUCKETED_NAMES, SYNC_NAMES = ([g[0] for g in s] for s in (SMALL, BUCKETED, SYNC))
-KNOBS = ("TCGNN_LDS_FLAT", "TCGNN_LDS_DENSE_COLS", "TCGNN_SDDMM_XCD", "TCGNN_RM_IDENT", "TCGNN_AGNN_SLICED", "TCGNN_AGNN_ROT", "TCGNN_RANGE_KB",
-         "TCGNN_LDS_HOT_COLS", "TCGNN_SYNC")
+KNOBS = W.KNOBS
 NEEDS_BUCKETS = {("forward", "range_blocked"), ("forward_AGNN", "range_blocked"), ("forward_ef", "xcd0"), ("forward_ef", "xcd1"), ("forward_ef", "xcd2"),
                  ("forward_ef", "ident0"), ("forward_ef", "ident1"), ("agnn_fused", "sliced2"), ("agnn_fused", "sliced16"), ("agnn_fused", "sliced2_rot0"),
                  ("agnn_fused", "sliced2_rot1"), ("agnn_fused", "range_major")}
@@ -178,38 +176,10 @@ def _refs(name, D, op):
 
 
 def _zero_rows(name):
-    rp, _ = GRAPHS[name]
-    n = len(rp) - 1
-    z = np.diff(rp) == 0
-    z[W.windows_handed_over(name, n) * 16:] = True
-    return z
+    return W.zero_rows(name, GRAPHS[name][0])
 
 
-def _judge(name, got, ref, r64, s64, what, zero=None, zero_value=0.0):
-    """-> list of failures (empty: fine).  The project's bounds; the non-canonical entry as test_non_canonical_rows_take_the_fallback_kernels
-    judges such a plan (absolute, against the TF32-mode oracle)."""
-    bad = []
-    if not np.isfinite(got).all():
-        bad.append("%s: %d non-finite elements" % (what, int((~np.isfinite(got)).sum())))
-        return bad
-    fig = (float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max()), float((np.abs(got - ref) / (s64 + 1.0)).max()),
-           float((np.abs(got - r64) / (s64 + 1.0)).max())) if got.size else (0.0, 0.0, 0.0)
-    print("FIG %-34s bar %.2e tight %.2e fp64 %.2e" % (what, *fig))
-    if W.is_unsorted(name):
-        lim = 1e-3 if what.startswith("forward ") or what.startswith("epilogues") else 1e-4
-        if got.size and np.abs(got - ref).max() >= lim:
-            bad.append("%s: %.3e from the oracle (non-canonical plan: %.0e)" % (what, np.abs(got - ref).max(), lim))
-    else:
-        try:
-            assert_parity(got, ref, r64, s64, what)
-        except AssertionError as e:
-            bad.append(str(e) or "%s: beyond 2^-9 of the fp64 contract (%.3e)" % (what, fig[2]))
-    if zero is not None and zero.any():
-        z = got[zero]
-        want = np.broadcast_to(np.asarray(zero_value, dtype=np.float32), z.shape)
-        if not np.array_equal(z, want):
-            bad.append("%s: %d elements of rows without edges differ from the empty sum's value" % (what, int((z != want).sum())))
-    return bad
+_judge = W.judge
 
 
 def _kernel_check(op, walk, name, D, kernel, pred, failures, covered=True):
@@ -235,32 +205,8 @@ def _kernel_check(op, walk, name, D, kernel, pred, failures, covered=True):
 
 
 def _forced(T, monkeypatch, mode, env, body):
-    """body() under one walk: an empty plan cache (the stream knobs are read when a stream is built), the knobs, the mode."""
-    import tcgnn_capi as c
-    for k in KNOBS:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v(_CTX["n"], _CTX["D"]) if callable(v) else v)
-    streams = "TCGNN_LDS_FLAT" in env       # (the plan says what it built on stderr: tiles per cell, dense entries)
-    if streams:
-        monkeypatch.setenv("TCGNN_VERBOSE", "1")
-        sys.stdout.write(_CTX["capfd"].readouterr().out)
-    _CTX["stream"] = None
-    T.clear_plan_cache()
-    try:
-        c.check(c.lib.tcgnn_set_spmm_mode(mode), "tcgnn_set_spmm_mode")
-        return body()
-    finally:
-        c.lib.tcgnn_set_spmm_mode(0)
-        T.clear_plan_cache()
-        for k in env:
-            monkeypatch.delenv(k, raising=False)
-        if streams:
-            monkeypatch.delenv("TCGNN_VERBOSE", raising=False)
-            out, err = _CTX["capfd"].readouterr()
-            sys.stdout.write(out)
-            found = re.findall(r"flat: (\d+) tile\(s\) per cell, \d+ entries \((\d+) dense\)", err)
-            _CTX["stream"] = ({int(t) for t, _ in found}, max([int(d) for _, d in found] or [0]))
+    """body() under one walk (walks.forced: an empty plan cache, the knobs, the mode); _CTX["stream"] receives what the plan built."""
+    return W.forced(T, monkeypatch, mode, env, body, _CTX)
 
 
 def _stream_check(op, walk, name, kernel_ran, env, failures):

@@ -144,6 +144,80 @@ def expected_ranges(n, D, column_buckets, range_kb):
     return nranges
 
 
+# ---- forcing a walk, and judging what it returned (tests/test_gpu_structures.py; kept here for the GPU tests that force walks through ctypes)
+KNOBS = ("TCGNN_LDS_FLAT", "TCGNN_LDS_DENSE_COLS", "TCGNN_SDDMM_XCD", "TCGNN_RM_IDENT", "TCGNN_AGNN_SLICED", "TCGNN_AGNN_ROT", "TCGNN_RANGE_KB",
+         "TCGNN_LDS_HOT_COLS", "TCGNN_SYNC")
+
+
+def forced(T, monkeypatch, mode, env, body, ctx):
+    """body() under one walk: an empty plan cache (the stream knobs are read when a stream is built), the knobs, the mode.
+    ctx: {"n", "D"} for knobs whose value is a function of them, "capfd" (may be None: nothing is read back) - and ctx["stream"]
+    receives what the plan said it built, (tiles per cell seen, most dense entries seen), or None."""
+    import re
+    import sys
+    import tcgnn_capi as c
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v(ctx["n"], ctx["D"]) if callable(v) else v)
+    streams = "TCGNN_LDS_FLAT" in env and ctx.get("capfd") is not None       # (the plan says what it built on stderr: tiles per cell, dense entries)
+    if streams:
+        monkeypatch.setenv("TCGNN_VERBOSE", "1")
+        sys.stdout.write(ctx["capfd"].readouterr().out)
+    ctx["stream"] = None
+    T.clear_plan_cache()
+    try:
+        c.check(c.lib.tcgnn_set_spmm_mode(mode), "tcgnn_set_spmm_mode")
+        return body()
+    finally:
+        c.lib.tcgnn_set_spmm_mode(0)
+        T.clear_plan_cache()
+        for k in env:
+            monkeypatch.delenv(k, raising=False)
+        if streams:
+            monkeypatch.delenv("TCGNN_VERBOSE", raising=False)
+            out, err = ctx["capfd"].readouterr()
+            sys.stdout.write(out)
+            found = re.findall(r"flat: (\d+) tile\(s\) per cell, \d+ entries \((\d+) dense\)", err)
+            ctx["stream"] = ({int(t) for t, _ in found}, max([int(d) for _, d in found] or [0]))
+
+
+def judge(name, got, ref, r64, s64, what, zero=None, zero_value=0.0):
+    """-> list of failures (empty: fine).  The project's bounds; the non-canonical entry as test_non_canonical_rows_take_the_fallback_kernels
+    judges such a plan (absolute, against the TF32-mode oracle)."""
+    from test_gpu_parity import assert_parity
+    bad = []
+    if not np.isfinite(got).all():
+        bad.append("%s: %d non-finite elements" % (what, int((~np.isfinite(got)).sum())))
+        return bad
+    fig = (float((np.abs(got - ref) / np.maximum(1.0, np.abs(ref))).max()), float((np.abs(got - ref) / (s64 + 1.0)).max()),
+           float((np.abs(got - r64) / (s64 + 1.0)).max())) if got.size else (0.0, 0.0, 0.0)
+    print("FIG %-34s bar %.2e tight %.2e fp64 %.2e" % (what, *fig))
+    if is_unsorted(name):
+        lim = 1e-3 if what.startswith("forward ") or what.startswith("epilogues") else 1e-4
+        if got.size and np.abs(got - ref).max() >= lim:
+            bad.append("%s: %.3e from the oracle (non-canonical plan: %.0e)" % (what, np.abs(got - ref).max(), lim))
+    else:
+        try:
+            assert_parity(got, ref, r64, s64, what)
+        except AssertionError as e:
+            bad.append(str(e) or "%s: beyond 2^-9 of the fp64 contract (%.3e)" % (what, fig[2]))
+    if zero is not None and zero.any():
+        z = got[zero]
+        want = np.broadcast_to(np.asarray(zero_value, dtype=np.float32), z.shape)
+        if not np.array_equal(z, want):
+            bad.append("%s: %d elements of rows without edges differ from the empty sum's value" % (what, int((z != want).sum())))
+    return bad
+
+
+def zero_rows(name, rp):
+    """rows whose sum is empty: no edges, or beyond the windows handed over (`short_metadata`)"""
+    n = len(rp) - 1
+    z = np.diff(rp) == 0
+    z[windows_handed_over(name, n) * 16:] = True
+    return z
+
+
 # ---- the walks: name -> (spmm mode, test knobs, what last_kernel must report).  A knob's value may be a function of (N, D).  The knobs are read when a stream is built or per
 # call (tcgnn_device.hip "run-time switches"), so a walk starts from an empty plan cache.
 def _is(name):
