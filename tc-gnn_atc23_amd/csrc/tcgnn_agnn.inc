@@ -19,7 +19,6 @@
 //   backward (BWD = true):  att = fl32(w * ef_saved) (edge values DMA'd one tile ahead),
 //            scores of dY are only reduced against the column ids: sum_e s[e] * (float)col(e).
 // ------------------------------------------------------------------------------------------
-static constexpr int kAgnnXcds = 8;   // workgroup b runs on XCD b % 8
 struct AgnnArgs {
     const int64_t* wb_ptr;
     const int32_t* order;
@@ -444,12 +443,12 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
             // slice order: deterministic, and nothing depends on the placement being what is assumed here.
             // (more than eight slices - an image of 16 .. 32 MB - go in ROUNDS of eight: the grid's first 1 / rounds takes slices
             //  0 .. 7, the next one slices 8 .. 15, and workgroups start in grid order, so an XCD is asked for one slice at a time)
-            const unsigned per_round = gridDim.x / (unsigned)(a.nslices / kAgnnXcds), b2 = blockIdx.x % per_round;
-            const int slice = (int)(blockIdx.x / per_round) * kAgnnXcds + (int)(b2 % (unsigned)kAgnnXcds);
-            const int wi = (int)(b2 / (unsigned)kAgnnXcds) * WAVES + wave;
+            const unsigned per_round = gridDim.x / (unsigned)(a.nslices / kXcds), b2 = blockIdx.x % per_round;
+            const int slice = (int)(blockIdx.x / per_round) * kXcds + (int)(b2 % (unsigned)kXcds);
+            const int wi = (int)(b2 / (unsigned)kXcds) * WAVES + wave;
             if (a.rot) {
-                const int span = (int)(per_round / (unsigned)kAgnnXcds) * WAVES;   // window positions of one round (>= nw)
-                int wr = wi + (int)(((int64_t)(slice % kAgnnXcds) * a.nw) / kAgnnXcds);
+                const int span = (int)(per_round / (unsigned)kXcds) * WAVES;   // window positions of one round (>= nw)
+                int wr = wi + (int)(((int64_t)(slice % kXcds) * a.nw) / kXcds);
                 if (wr >= span) wr -= span;
                 w0 = wr < a.nw ? wr : -1;
             } else
@@ -473,7 +472,7 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
         // (a few hot column buckets each, ~3 MB of rows) together - spmm_sync_kernel's schedule with this kernel's run
         int x, w_lo, w_hi, nph;
         sync_slice_of(a.sync, x, w_lo, w_hi, nph);
-        const int nwv = (int)(gridDim.x / (unsigned)kSyncXcds) * WAVES, wid = (int)(blockIdx.x / (unsigned)kSyncXcds) * WAVES + wave;
+        const int nwv = (int)(gridDim.x / (unsigned)kXcds) * WAVES, wid = (int)(blockIdx.x / (unsigned)kXcds) * WAVES + wave;
         const int ts = a.sync.kmax + 1;
         for (int base = w_lo + wid; base < w_hi; base += nwv * MAXW) {
             int wj[MAXW], kaj[MAXW];
@@ -563,8 +562,8 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
     if constexpr (MAXW == 0) {
         if (a.nslices > 0) {   // a wavefront = a window: its sums are one slice's addend
             if (w0 >= 0) {
-                const unsigned per_round = gridDim.x / (unsigned)(a.nslices / kAgnnXcds);
-                const int slice = (int)(blockIdx.x / per_round) * kAgnnXcds + (int)((blockIdx.x % per_round) % (unsigned)kAgnnXcds);
+                const unsigned per_round = gridDim.x / (unsigned)(a.nslices / kXcds);
+                const int slice = (int)(blockIdx.x / per_round) * kXcds + (int)((blockIdx.x % per_round) % (unsigned)kXcds);
                 const int64_t row0 = (int64_t)w0 * kWinRows + 4 * g;
                 float* const yp = a.y + (int64_t)slice * a.N * a.D;
                 float inv2[4];

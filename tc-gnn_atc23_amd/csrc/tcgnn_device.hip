@@ -27,20 +27,26 @@
 //         rows, which are the LDS rows) and issues one v_mfma_f32_16x16x32_f16 per 16 columns;
 //   partial accumulators of the wavefronts are summed through LDS in a fixed order.
 //
-// File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator):
-//   tcgnn_device.hip          plan struct, range-guard helpers, launch tables, stage_features, run_agnn, the C ABI
+// File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator; in include order):
+//   tcgnn_device.hip          struct tcgnn_plan, KernelTimer, device helpers (the range guard's rule, host and device), launch tables, switches
+//                             and walk predicates, stage_features, sync_chosen; behind the includes the C ABI of the operators and tcgnn_range_mode
 //   tcgnn_pack_stage.inc      plan-time kernels (pack, locality, longest row) and the staging pass (abs-max, fp16 images)
-//   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel, spmm_blocked_kernel            (+ generated tcgnn_lds_blocks.inc)
+//   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
+//   tcgnn_sync_walk.inc       slice-synchronised range walk: SyncArgs, spmm_sync_kernel's two forms from tcgnn_sync_kernel.inc, table kernels
+//   tcgnn_small_spmm.inc      spmm_small_kernel (single launch, fp32 MFMA on fp32 X; also the binary SpMM's range-guard fallback)
 //   tcgnn_lds_spmm.inc        LDS-resident SpMM, ordinary cell stream; cell-stream build kernels
-//   tcgnn_lds_flat.inc        LDS-resident SpMM, flat cell stream (the headline kernel)
+//   tcgnn_lds_flat.inc        LDS-resident SpMM, flat cell stream (the headline kernel; its forms from tcgnn_lds_flat_kernel.inc)
 //   tcgnn_lds_val.inc         LDS-resident edge-valued SpMM (single-edge stream, per-call slot values)
 //   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel (one and two operands), sddmm2_csr_kernel
+//   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
+//   tcgnn_small_fallback.inc  CSR kernels of non-canonical plans, the range guard's fallbacks, symmetry_kernel, wide_patch_kernel
+//   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
-//   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
-//   tcgnn_small_fallback.inc  spmm_small_kernel, CSR kernels of non-canonical plans, the range guard's fallbacks, wide_patch_kernel
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
+//   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
 //   tcgnn_spmm_dispatch.inc   host side of an SpMM call: SpmmCall, route_spmm (which walk runs), one launcher per walk, run_spmm
+//   tcgnn_plan.inc            plan lifetime: creation in named steps (order_windows, build_sync_tables, ...), destroy, info, prepare, timing, setters
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -185,6 +191,7 @@ struct KernelTimer {
 // ------------------------------------------------------------------------------------------
 // small device helpers
 // ------------------------------------------------------------------------------------------
+static constexpr int kXcds = 8;   // workgroups are dealt to the XCDs round-robin in launch order: workgroup b runs on XCD b % 8 (observed, used for speed only)
 
 // Power-of-two exponent k such that absmax * 2^k lies in [2^14, 2^15): fp16-safe (max 65504) with
 // 29 binades of normal range below the largest element.  0 for all-zero / non-finite data.
@@ -226,20 +233,27 @@ __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t
 //   edge-valued SpMM   2 k max|A| max|X| 2^-39 <= 2^-10     -> wide iff log2 max|A| + log2 max|X| >= 28 - log2 k
 // Header words (written by the staging pass): 4 = cap for X (0: guard off / an image the caller staged: never wide), 5 = cap for
 // the edge values, 6 = n_tiny of X, 7 = the power of max in the bound (1 or 2).
-__device__ __forceinline__ bool range_spread(const uint32_t* hdr, int k, int& emax) {
+// (host and device: tcgnn_range_mode reports the decision with the same four functions on a copy of the header words)
+__host__ __device__ __forceinline__ bool range_spread(const uint32_t* hdr, int k, int& emax) {
     const uint32_t mx = hdr[k], mi = hdr[k + 2];
     emax = (int)(mx >> 23);
     if (mi == 0u || mx == 0u || mx >= 0x7f800000u) return false;
     return emax - (int)((0x7f800000u - mi) >> 23) > 28;
 }
-__device__ __forceinline__ int ceil_log2_u32(uint32_t k) { return k <= 1u ? 0 : 32 - __clz((int)(k - 1u)); }
-__device__ __forceinline__ bool range_is_wide(const uint32_t* hdr, int) {   // the feature matrix alone (binary SpMM, SDDMM, fused AGNN)
+__host__ __device__ __forceinline__ int ceil_log2_u32(uint32_t k) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return k <= 1u ? 0 : 32 - __clz((int)(k - 1u));
+#else
+    return k <= 1u ? 0 : 32 - __builtin_clz(k - 1u);
+#endif
+}
+__host__ __device__ __forceinline__ bool range_is_wide(const uint32_t* hdr, int) {   // the feature matrix alone (binary SpMM, SDDMM, fused AGNN)
     int emax;
     const uint32_t cap = hdr[4], n = hdr[6];
     if (!range_spread(hdr, 0, emax) || cap == 0u || n == 0u) return false;
     return (int)hdr[7] * (emax - 127) >= 29 - ceil_log2_u32(n < cap ? n : cap);
 }
-__device__ __forceinline__ bool range_is_wide_val(const uint32_t* hdr) {
+__host__ __device__ __forceinline__ bool range_is_wide_val(const uint32_t* hdr) {
     int ex, ea;
     const bool sx = range_spread(hdr, 0, ex), sa = range_spread(hdr, 1, ea);
     const uint32_t cap = hdr[5];
@@ -399,6 +413,8 @@ static hipError_t launch_spmm_any(bool val, int waves, int nt, const SpmmArgs& a
     return val ? launch_spmm_nt<1, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_nt<1, false>(nt, args, nwin, nchunks, stream, epi);
 }
 
+// workgroups of a persistent grid resident on one CU: what its 160 KB of LDS hold, at most what the kernel's registers allow, at least one
+static constexpr int wgs_per_cu(int lds_per_wg, int by_regs) { return std::max(1, std::min(by_regs, (160 * 1024) / lds_per_wg)); }
 // windows owned by one wavefront of the range-blocked kernel (accumulators: MAXW * NT * 4 registers)
 static constexpr int blocked_maxw(int nt, bool val) { return (nt <= 4 && !val) ? 4 : 2; }
 
@@ -434,9 +450,7 @@ static hipError_t launch_blocked_any(bool val, int nt, const SpmmBlockedArgs& ar
 static constexpr int sync_nbuf(int nt, bool val) { return nt <= 2 ? 2 : 1; }
 static constexpr int sync_maxw(int nt, bool val) { return 2; }
 static constexpr int sync_wgs_per_cu(int nt, bool val) {
-    const int lds_wg = 4 * (sync_nbuf(nt, val) * nt * 1024 + kPadBytes + (val ? 2048 : 0) + (sync_nbuf(nt, val) == 1 ? 2048 : 0)) + 4096;
-    const int by_lds = (160 * 1024) / lds_wg, by_regs = nt <= 4 ? 4 : 2;
-    return by_lds < by_regs ? (by_lds < 1 ? 1 : by_lds) : by_regs;
+    return wgs_per_cu(4 * (sync_nbuf(nt, val) * nt * 1024 + kPadBytes + (val ? 2048 : 0) + (sync_nbuf(nt, val) == 1 ? 2048 : 0)) + 4096, nt <= 4 ? 4 : 2);
 }
 template <int NT, bool VAL>
 static hipError_t launch_sync_one(const SpmmSyncArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
@@ -545,6 +559,7 @@ static constexpr int kMaxStructStride = 16383;
 // ... and whose index * stride + offset is formed in 32 bits: an image of 4 GB or more (a papers100M-sized shard: 111 M rows of
 // 128 B) wraps.  The kernels then form 64-bit lane addresses instead (one v_mad_u64_u32 per gathered piece).
 static int32_t image_is_big(int32_t rows, int pitch_halves) { return ((uint64_t)rows + 1) * (uint64_t)pitch_halves * 2u >= (1ull << 32) ? 1 : 0; }
+static size_t image_bytes(const tcgnn_plan* plan, int pitch_halves) { return ((size_t)plan->Nc + 1) * pitch_halves * sizeof(_Float16); }   // (the rows a walk gathers from, + the zero row)
 static bool pitch_fits_descriptor(int D) { return x16_pitch(round_up(D, 16)) * 2 <= kMaxStructStride; }
 
 // (behind the image: the dirty-row bitmap of the range guard, one bit per row of X - wide_patch_kernel)
@@ -586,63 +601,6 @@ static int range_count(const tcgnn_plan* plan, size_t x16_bytes, size_t range_by
     while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
     return nranges;
 }
-// The fused AGNN kernel's walks beside the per-window one (agnn_kernel), for graphs whose numbering carries no locality of its own and
-// whose windows are alike, when the fp16 image does not fit an XCD's 4 MB L2 but an eighth of it does:
-//   XCD-sliced  - nslices addends of Y in the workspace and a pass that sums them;
-//   range-major - persistent wavefronts owning two windows each (no addends; more registers).
-// Measured on the Reddit shape (tools/bench_agnn.py, forward / backward ms; r03 with whole-line gathers at D = 64):
-//   D = 16 (7.4 MB)  per-window 1.13 / 1.43   sliced 1.06 / 1.28   range-major 1.19 / 1.59
-//   D = 32 (14.9 MB) per-window 1.46 / 1.65   sliced 1.20 / 1.38   range-major 1.26 / 1.65
-//   D = 64 (29.8 MB) per-window 1.74 / 1.77   sliced 1.53 / 1.60   range-major 1.45-1.48 / 1.78   (sixteen slices in two rounds 1.81 / 1.85)
-//   D = 128 (59.6 MB) per-window 3.48 / 3.53  sliced 2.61-2.67 / 2.71-2.73   range-major 2.68-2.73 / 2.93-2.95   (slices of 7.4 MB: they do
-//                     not stay in a 4 MB L2, but an XCD that is asked for an eighth of the image still hits more often than one asked for all of it)
-// so: sliced in both directions up to 16 MB; from there to 64 MB range-major forward (within 2 % of sliced, no addends) and sliced backward.
-// What these walks are bound by is the memory system's throughput at their hit rate, not by what a wavefront has in flight nor by
-// its instruction count (r03, measured on the sliced walk at D = 64): a quarter fewer VALU instructions per tile (103 -> 71 in the
-// forward tile block) changed nothing; a second tile buffer with the gather running two tiles ahead (counted vmcnt, no extra
-// registers) moved forward 1.53 -> 1.53 and backward 1.60 -> 1.57 and was taken out again; four wavefronts per SIMD instead of
-// three (forward kernel squeezed from 130 to 128 registers, 12 bytes of scratch) 1.53 -> 1.43-1.45 sliced but 1.73 -> 1.79-1.87 per-window
-// (more wavefronts thrash the L2 harder) - level with range-major's 1.45-1.48, so not kept either.
-// TCGNN_AGNN_SLICED (read per call: tests switch it): 0 per-window only, 1 the rule above, 2 sliced whenever possible, 16 two rounds.
-static constexpr size_t kAgnnSliceBytes = (size_t)4 << 20;
-// (r06) on a graph with locality the sliced walk takes the windows in their own order, rotated per XCD (AgnnArgs::rot: sbm_reddit, forced
-// sliced, 1.96 / 2.50 -> 1.59 / 1.63 ms) - which only a forced walk meets: the automatic rule keeps such graphs per-window.  Without locality
-// the plan's order stays (uniform graph: 1.61 / 1.63 against 1.62 / 1.67 rotated).  TCGNN_AGNN_ROT=0|1 overrides.
-static int agnn_rot(const tcgnn_plan* plan) {
-    const char* const env = test_knob("TCGNN_AGNN_ROT");
-    return (env ? atoi(env) != 0 : plan->near_frac > 0.2) && windows_balanced(plan) ? 1 : 0;
-}
-enum { kAgnnPerWindow = 0, kAgnnSliced = 1, kAgnnRangeMajor = 2 };
-static int agnn_walk(const tcgnn_plan* plan, int32_t D, bool bwd, int* nslices_out) {
-    *nslices_out = 0;
-    const char* const env = test_knob("TCGNN_AGNN_SLICED");
-    const int knob = env ? atoi(env) : 1;
-    if (!knob || plan->waves != 4 || plan->nbuckets < 8 || plan->nw_eff < 1 || plan->nbuckets % kAgnnXcds) return kAgnnPerWindow;
-    const int pitch = x16_pitch(round_up(D, 16));
-    if (image_is_big(plan->Nc, pitch)) return kAgnnPerWindow;
-    const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
-    if (knob >= 2) { *nslices_out = (knob == 16 && plan->nbuckets % 16 == 0) ? 16 : kAgnnXcds; return kAgnnSliced; }   // (forced)
-    if (!(x16_bytes > kBlockedMinBytes && x16_bytes <= 2 * (size_t)kAgnnXcds * kAgnnSliceBytes && plan->nw_eff >= 8 * plan->num_cus &&
-          windows_balanced(plan) && !has_locality(plan))) return kAgnnPerWindow;
-    if (x16_bytes > (size_t)kAgnnXcds * kAgnnSliceBytes && !bwd) return kAgnnRangeMajor;             // 32 - 64 MB: forward
-    if (!bwd && x16_bytes > (size_t)kAgnnXcds * (kAgnnSliceBytes / 2)) return kAgnnRangeMajor;       // 16 - 32 MB: forward
-    // (the sliced walk wants every window's tiles spread evenly over the slices: workgroups are handed to the XCDs round-robin and
-    //  in order, so where a window has most of its tiles in one slice - the calibrated SBM graph: 22.5 % of the edges inside the
-    //  window's own community, near_frac 0.3 - the XCD of that slice holds the others up: backward 1.81 -> 2.40 ms there)
-    if (plan->near_frac > 0.2) return kAgnnPerWindow;
-    *nslices_out = kAgnnXcds;
-    return kAgnnSliced;
-}
-// (the workspace is sized for whichever direction slices)
-static int agnn_slices(const tcgnn_plan* plan, int32_t D) {
-    int nf = 0, nb = 0;
-    (void)agnn_walk(plan, D, false, &nf); (void)agnn_walk(plan, D, true, &nb);
-    return std::max(nf, nb);
-}
-static size_t agnn_slice_bytes(const tcgnn_plan* plan, int32_t D) {
-    return ((size_t)agnn_slices(plan, D) * (size_t)plan->N * D * sizeof(float) + 255) / 256 * 256;
-}
-
 // ---- range guard parameters (range_is_wide): cap = how many lost-precision terms one result can collect at most - the longest row
 // of the graph (SpMM) or 2 D (SDDMM / fused AGNN) - and the power of max|X| in the error bound.  cap 0 = guard off
 // (tcgnn_set_range_guard(0), TCGNN_RANGE_GUARD=0).
@@ -755,95 +713,6 @@ static int stage_features(const tcgnn_plan* plan, const float* d_X, const float*
 
 #include "tcgnn_lds_plan.inc"
 
-// ---- tables of the slice-synchronised range walk (tcgnn_sync_walk.inc), built at plan creation for graphs whose numbering has
-// locality (near_frac > 0.5: the walks that rely on it are the ones this one replaces) and whose windows are alike.  Two small kernels, one
-// histogram copied to the host (slices x fine buckets words), one table of (kmax + 1) words per window.  Any failure leaves sync.ok false:
-// the walk is an optional acceleration, the per-window walk needs nothing from here.
-static int build_sync_tables(tcgnn_plan* p, hipStream_t stream) {
-    tcgnn_plan::SyncTables& t = p->sync;
-    const int nw = p->nw_eff;
-    if (nw < kSyncXcds * 256 || !p->d_cols || p->total_wb < 1) return TCGNN_OK;
-    const char* const verbose = getenv("TCGNN_VERBOSE");
-    t.nwx = (nw + kSyncXcds - 1) / kSyncXcds;
-    t.S = kSyncSlice;
-    t.R = (t.nwx + t.S - 1) / t.S;
-    t.kmax = kSyncKmax;
-    const int nslices = kSyncXcds * t.R;
-    const int nfb0 = (int)((((int64_t)p->Nc + 1) >> kSyncFbShift0) + 1);
-    uint32_t* d_hist = nullptr;
-    std::vector<uint32_t> hist((size_t)nslices * nfb0);
-    hipError_t e = hipMalloc(&d_hist, hist.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist.size() * sizeof(uint32_t), stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sync_hist_kernel, dim3((unsigned)nw), dim3(64), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, kSyncFbShift0, nfb0, d_hist);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), d_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_hist);
-    if (e != hipSuccess) { (void)hipGetLastError(); return TCGNN_OK; }
-    // hot buckets per slice: at least a quarter of a tile per window of the slice; coarser buckets until every slice's list fits
-    std::vector<int32_t> hot((size_t)nslices * t.kmax, 0x7fffffff >> 12), nk((size_t)nslices, 0);
-    int shift = -1;
-    double tiles_all = 0, tiles_hot = 0, k_weighted = 0;
-    for (int sh = 0; sh <= 5 && shift < 0; ++sh) {
-        const int nfb = (nfb0 + (1 << sh) - 1) >> sh;
-        bool fits = true;
-        tiles_all = tiles_hot = k_weighted = 0;
-        t.max_k = 0;
-        for (int s = 0; s < nslices && fits; ++s) {
-            const int x = s / t.R, r = s % t.R;
-            const int64_t lo = (int64_t)x * t.nwx + (int64_t)r * t.S, hi = std::min<int64_t>(std::min<int64_t>(lo + t.S, (int64_t)(x + 1) * t.nwx), nw);
-            const int64_t wins = std::max<int64_t>(hi - lo, 0);
-            const uint32_t thr = (uint32_t)std::max<int64_t>(wins / 4, 16);
-            int k = 0;
-            double all = 0, hsum = 0;
-            for (int b = 0; b < nfb; ++b) {
-                uint64_t c = 0;
-                for (int q = b << sh; q < std::min(nfb0, (b + 1) << sh); ++q) c += hist[(size_t)s * nfb0 + q];
-                all += (double)c;
-                if (c >= thr) {
-                    if (k == t.kmax) { fits = false; break; }
-                    hot[(size_t)s * t.kmax + k++] = b;
-                    hsum += (double)c;
-                }
-            }
-            nk[(size_t)s] = k;
-            t.max_k = std::max(t.max_k, k);
-            tiles_all += all; tiles_hot += hsum; k_weighted += all * k;
-        }
-        if (fits) shift = sh;
-    }
-    if (shift < 0 || tiles_all <= 0) {
-        if (verbose && atoi(verbose) > 0) fprintf(stderr, "[tcgnn] sync walk: hot buckets do not fit %d entries per slice at any bucket size: not built\n", t.kmax);
-        return TCGNN_OK;
-    }
-    t.fb_shift = kSyncFbShift0 + shift;
-    t.hot_frac = tiles_hot / tiles_all;
-    t.avg_k = k_weighted / tiles_all;
-    if (verbose && atoi(verbose) > 0)
-        fprintf(stderr, "[tcgnn] sync walk: %d slices of %d windows, buckets of %d rows, %.1f hot buckets per slice (max %d), %.0f %% of the tiles inside them\n", nslices, t.S,
-                1 << t.fb_shift, t.avg_k, t.max_k, 100.0 * t.hot_frac);
-    if (t.hot_frac < 0.5) return TCGNN_OK;
-    int32_t* d_hot = nullptr;
-    const size_t b_T = (size_t)nw * (t.kmax + 1) * sizeof(uint32_t);
-    e = hipMalloc(&d_hot, hot.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&t.d_nk, nk.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&t.d_T, b_T);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_hot, hot.data(), hot.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t.d_nk, nk.data(), nk.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        const int64_t total = (int64_t)nw * (t.kmax + 1);
-        hipLaunchKernelGGL(sync_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, t.kmax, t.fb_shift, d_hot, t.d_nk, t.d_T);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (host vectors above must outlive the copies)
-    (void)hipFree(d_hot);
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t.d_T); (void)hipFree(t.d_nk); t.d_T = nullptr; t.d_nk = nullptr; return TCGNN_OK; }
-    p->bytes += b_T + nk.size() * sizeof(int32_t);
-    t.ok = true;
-    return TCGNN_OK;
-}
 // When the walk is taken (automatic mode; TCGNN_SYNC=0 never, 2 whenever the tables exist; mode 5 forces it).  Measured on the ogbn-products
 // shape with 25 / 50 / 100 / 200 communities (25 / 12.5 / 6.3 / 3.1 MB of image each at D = 128, half that at 64; tools/exp_r06d.py, kernel ms,
 // per-window -> this walk):
@@ -891,123 +760,12 @@ static SyncArgs sync_args(const tcgnn_plan* plan, int pitch_bytes) {
     return SyncArgs{t.d_T, t.d_nk, t.kmax, std::min(m, t.kmax), t.S, t.R, t.nwx, 0, plan->nw_eff};
 }
 
+#include "tcgnn_edge_dispatch.inc"
 #include "tcgnn_spmm_dispatch.inc"
-
-static bool agnn_supported(const tcgnn_plan* plan, int32_t D) {
-    return plan && plan->canonical && D >= 1 && D <= kMaxChunkDims && plan->E >= 8;
-}
-
-static int run_agnn(const tcgnn_plan* plan, const float* d_X, const float* d_w, float* d_ef, uint32_t* d_absmax, float* d_Y,
-                    float* d_dw, int32_t D, void* ws, size_t ws_bytes, void* stream_v, bool bwd) {
-    const char* name = bwd ? "tcgnn_agnn_pair_backward" : "tcgnn_agnn_pair_forward";
-    if (!plan || D < 1 || !d_w || !d_absmax || (bwd && !d_dw) || (plan->N > 0 && (!d_X || !d_Y)) || (plan->E > 0 && !d_ef))
-        return fail(TCGNN_ERR_INVALID_ARG, "%s: null argument or D < 1", name);
-    if (!agnn_supported(plan, D))
-        return fail(TCGNN_ERR_UNSUPPORTED, "%s: needs a canonical plan, D <= %d and E >= 8 (canonical=%d, D=%d, E=%lld)", name,
-                    kMaxChunkDims, plan->canonical, D, (long long)plan->E);
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    int nslices = 0;
-    const int walk = agnn_walk(plan, D, bwd, &nslices);
-    const bool sliced = walk == kAgnnSliced;
-    if (const int rc = check_output_aligned(name, bwd ? "G" : "Y", d_Y)) return rc;
-    if (const int rc = check_workspace(name, ws, ws_bytes, tcgnn_workspace_bytes(plan, D))) return rc;
-    // (tcgnn_workspace_bytes holds the image, the reduction slots and the slice addends of this call: image + max(partial + slices, ..))
-    if ((int64_t)plan->nw_eff * kWinRows < plan->N) {   // rows the caller's windows do not cover stay zero
-        HIP_TRY(hipMemsetAsync(d_Y, 0, (size_t)plan->N * D * sizeof(float), stream));
-        if (!bwd) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
-    }
-    if (!bwd) HIP_TRY(hipMemsetAsync(d_absmax, 0, sizeof(uint32_t), stream));
-    const Guard gsd = guard_sddmm(plan, D);
-    StageOpts so; so.guard = &gsd;
-    StagedImage im;
-    if (const int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, so, &im)) return rc;
-    const uint32_t* const hdr = im.hdr; const _Float16* const x16 = im.x16; const int dpad = im.dpad, pitch = im.pitch;
-    double* partial = reinterpret_cast<double*>(static_cast<char*>(ws) + workspace_bytes_for(plan->Nc, D));
-    if (plan->nw_eff == 0) {
-        if (bwd) HIP_TRY(hipMemsetAsync(d_dw, 0, sizeof(float), stream));
-        return TCGNN_OK;
-    }
-    AgnnArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, d_w, d_ef, d_absmax, d_Y, partial,
-               plan->N, plan->Nc, plan->row_off, dpad, D, pitch, plan->E, plan->rowptr, plan->d_bptr, plan->nbuckets, 0, 0, plan->nw_eff, 0,
-               image_is_big(plan->Nc, pitch), 0, 0, reinterpret_cast<int32_t*>(d_absmax + 1), 0, 0, SyncArgs{}};   // (the per-row exponents of the edge weights sit behind the max |ef| word)
-    const int nt = dpad / 16;
-    const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
-    float* const ypart = reinterpret_cast<float*>(static_cast<char*>(ws) + workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan));
-    // The range-major variant (bit-compatible scores, sums in another order): slower than the per-window walk while the kernel
-    // asked for every 128-byte line twice (r02: D = 64 1.87 vs 1.80 ms forward); with whole-line gathers (r03) its forward pass
-    // is the fastest form at D = 64 (1.45-1.48 against 1.74 per-window, 1.53 sliced) - agnn_walk picks it there; mode 2 forces it.
-    const bool blocked = plan->nbuckets > 0 && (spmm_mode_of(plan) == 2 || (spmm_mode_of(plan) == 0 && walk == kAgnnRangeMajor)) && x16_bytes > 0 && !a.big;
-    int nwg = plan->nw_eff;
-    // slice-synchronised range walk (r06, tcgnn_sync_walk.inc): communities larger than an XCD's L2; one launch per slice round, each with its own
-    // run of d_w slots
-    // (the backward kernel beyond 96 columns owns its windows at ONE wavefront per SIMD - 256 registers do not hold two windows' accumulators, operands
-    //  and per-row exponents - and loses more than the walk returns there: products shape, D = 128, 4.10 -> 6.24 ms; it stays per-window unless forced)
-    const bool synced = plan->waves == 4 && !a.big && sync_chosen(plan, pitch * 2, spmm_mode_of(plan), bwd ? kSyncFusedBwd : kSyncFusedFwd, nt);
-    const bool sync_one = bwd && nt > 6;   // (r06: ONE window per wavefront there - two wavefronts per SIMD, three trips per slice)
-    {
-        KernelTimer timer(plan, stream, synced ? "agnn_kernel (slice-synchronised)" : ((sliced && !blocked) ? "agnn_kernel (XCD-sliced) + agnn_slice_sum_kernel" : "agnn_kernel"));
-        hipError_t e = hipSuccess;
-        if (synced) {
-            a.use_sync = 1;
-            a.sync = sync_args(plan, pitch * 2);
-            const int lds_wg = 4 * agnn_wave_lds((nt + 1) / 2, bwd);
-            const int per_cu = std::max(1, std::min(nt <= 4 ? 3 : 2, (160 * 1024) / lds_wg));
-            const int mw = sync_one ? 1 : kAgnnMaxW;
-            const int per_launch = kSyncXcds * std::max(1, std::min((plan->sync.S + 4 * mw - 1) / (4 * mw), plan->num_cus / kSyncXcds * per_cu));
-            for (int r = 0; r < plan->sync.R && e == hipSuccess; ++r) {
-                a.sync.round = r;
-                a.partial = partial + (size_t)r * per_launch;
-                e = !bwd ? launch_agnn<4, false, kAgnnMaxW>(nt, a, per_launch, stream) : (sync_one ? launch_agnn_wide_one(nt, a, per_launch, stream) : launch_agnn<4, true, kAgnnMaxW>(nt, a, per_launch, stream));
-            }
-            nwg = plan->sync.R * per_launch;   // (d_w slots: R x 768 workgroups at most, fewer than the windows the workspace counts - build_sync_tables wants 2048 of them)
-        } else if (sliced && !blocked) {
-            a.nslices = nslices;
-            a.gsel = plan->nbuckets / nslices;
-            a.y = ypart;
-            a.rot = agnn_rot(plan);
-            nwg = nslices * ((plan->nw_eff + 3) / 4);
-            e = bwd ? launch_agnn<4, true, 0>(nt, a, nwg, stream) : launch_agnn<4, false, 0>(nt, a, nwg, stream);
-            if (e == hipSuccess) {
-                const int64_t nsum = std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows) * D;   // (rows beyond the windows were zeroed above)
-                const unsigned sg = (unsigned)std::min<int64_t>(2048, (nsum / 4 + 255) / 256 + 1);
-                hipLaunchKernelGGL(agnn_slice_sum_kernel, dim3(sg), dim3(256), 0, stream, ypart, d_Y, nsum, (int64_t)plan->N * D, nslices);
-                e = hipGetLastError();
-            }
-        } else if (blocked) {
-            const int nranges = range_count(plan, x16_bytes, 4 * kRangeTargetBytes);
-            a.nranges = nranges;
-            a.gsel = plan->nbuckets / nranges;
-            a.ngroups = (plan->nw_eff + kAgnnMaxW - 1) / kAgnnMaxW;
-            const int lds_wg = 4 * agnn_wave_lds((nt + 1) / 2, bwd);
-            const int per_cu = std::max(1, std::min(nt <= 4 ? 3 : 2, (160 * 1024) / lds_wg));
-            nwg = std::min((a.ngroups + 3) / 4, plan->num_cus * per_cu);
-            e = bwd ? launch_agnn<4, true, kAgnnMaxW>(nt, a, nwg, stream) : launch_agnn<4, false, kAgnnMaxW>(nt, a, nwg, stream);
-        } else if (plan->waves == 4) {
-            e = bwd ? launch_agnn<4, true, 0>(nt, a, nwg, stream) : launch_agnn<4, false, 0>(nt, a, nwg, stream);
-        } else {
-            e = bwd ? launch_agnn<1, true, 0>(nt, a, nwg, stream) : launch_agnn<1, false, 0>(nt, a, nwg, stream);
-        }
-        HIP_TRY(e);
-    }
-    // (the d_w correction of the patch: a double in header words 10-11, zeroed with the header by the staging pass)
-    double* const dw_extra = reinterpret_cast<double*>(const_cast<uint32_t*>(hdr) + 10);
-    const int guard_level = range_guard_of(plan);
-    if (guard_level >= 2) {
-        // a few dirty rows (what training produces): the MFMA kernel above ran, the edges that touch them are recomputed here
-        const PatchArgs pa{hdr, dirty_bitmap_of(ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, d_X, x16, pitch, d_ef, d_w, d_Y, d_absmax, dw_extra, plan->N, plan->Nc, D, plan->row_off, bwd ? 2 : 1, plan->E, plan->d_sym};
-        // (many: the same launch does all the work in plain fp32 - wide_dense_body; one launch per call either way, returning at once
-        //  unless the staged matrix is "wide")
-        HIP_TRY(launch_wide_patch(pa, stream, partial, nwg));
-    }
-    if (bwd) {
-        hipLaunchKernelGGL(agnn_reduce_kernel, dim3(1), dim3(kReduceThreads), 0, stream, partial, nwg, d_dw, guard_level >= 2 ? dw_extra : (const double*)nullptr);
-        HIP_TRY(hipGetLastError());
-    }
-    return TCGNN_OK;
-}
+#include "tcgnn_plan.inc"
 
 // ------------------------------------------------------------------------------------------
-// C ABI
+// C ABI: the operators (plan lifetime, timing and the mode / guard setters: tcgnn_plan.inc)
 // ------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -1019,367 +777,35 @@ static int agnn_words_ok(const tcgnn_plan* plan, int64_t words, const char* name
     return TCGNN_OK;
 }
 
+static AgnnCall agnn_call(const tcgnn_plan* plan, const float* d_X, const float* d_w, float* d_ef, uint32_t* d_absmax, float* d_Y, float* d_dw, int32_t D, void* ws, size_t ws_bytes, void* stream, bool bwd) {
+    AgnnCall c;
+    c.plan = plan; c.d_X = d_X; c.d_w = d_w; c.d_ef = d_ef; c.d_absmax = d_absmax; c.d_Y = d_Y; c.d_dw = d_dw; c.D = D; c.ws = ws; c.ws_bytes = ws_bytes;
+    c.stream = static_cast<hipStream_t>(stream); c.bwd = bwd; c.name = bwd ? "tcgnn_agnn_pair_backward" : "tcgnn_agnn_pair_forward";
+    return c;
+}
+
 int tcgnn_agnn_pair_forward(const tcgnn_plan* plan, const float* d_X, const float* d_w, float* d_ef, uint32_t* d_ef_absmax, int64_t ef_absmax_words, float* d_Y,
                             int32_t D, void* ws, size_t ws_bytes, void* stream) {
     if (const int rc = agnn_words_ok(plan, ef_absmax_words, "tcgnn_agnn_pair_forward")) return rc;
-    return run_agnn(plan, d_X, d_w, d_ef, d_ef_absmax, d_Y, nullptr, D, ws, ws_bytes, stream, false);
+    return run_agnn(agnn_call(plan, d_X, d_w, d_ef, d_ef_absmax, d_Y, nullptr, D, ws, ws_bytes, stream, false));
 }
 
 int tcgnn_agnn_pair_backward(const tcgnn_plan* plan, const float* d_dY, const float* d_w, const float* d_ef, const uint32_t* d_ef_absmax, int64_t ef_absmax_words,
                              float* d_G, float* d_dw, int32_t D, void* ws, size_t ws_bytes, void* stream) {
     if (const int rc = agnn_words_ok(plan, ef_absmax_words, "tcgnn_agnn_pair_backward")) return rc;
-    return run_agnn(plan, d_dY, d_w, const_cast<float*>(d_ef), const_cast<uint32_t*>(d_ef_absmax), d_G, d_dw, D, ws, ws_bytes, stream, true);
+    return run_agnn(agnn_call(plan, d_dY, d_w, const_cast<float*>(d_ef), const_cast<uint32_t*>(d_ef_absmax), d_G, d_dw, D, ws, ws_bytes, stream, true));
 }
 
-int tcgnn_plan_destroy(tcgnn_plan* plan) {
-    if (!plan) return TCGNN_OK;
-    (void)hipFree(plan->d_wb_ptr); (void)hipFree(plan->d_order); (void)hipFree(plan->d_cols);
-    (void)hipFree(plan->d_mask); (void)hipFree(plan->d_ebase); (void)hipFree(plan->d_bptr);
-    (void)hipFree(plan->sync.d_T); (void)hipFree(plan->sync.d_nk);
-    for (auto& cs : plan->lds) {
-        (void)hipFree(cs.d_cell_ptr); (void)hipFree(cs.d_cell_tiles); (void)hipFree(cs.d_order); (void)hipFree(cs.d_rbase); (void)hipFree(cs.d_rlist); (void)hipFree(cs.d_rl2);
-        (void)hipFree(cs.d_cold_ptr); (void)hipFree(cs.d_cold_cols); (void)hipFree(cs.d_cold_mask); (void)hipFree(cs.d_parts); (void)hipFree(cs.d_flat);
-        (void)hipFree(cs.d_wcold_ptr); (void)hipFree(cs.d_wcold); (void)hipFree(cs.d_eidx); (void)hipFree(cs.d_cold_eidx); (void)hipFree(cs.d_eidx16); (void)hipFree(cs.d_cold_eidx16);
-    }
-    (void)hipFree(plan->d_xwb_ptr); (void)hipFree(plan->d_xcols); (void)hipFree(plan->d_xmask); (void)hipFree(plan->d_xeidx); (void)hipFree(plan->d_sym);
-    for (hipEvent_t e : plan->ev) (void)hipEventDestroy(e);
-    delete plan;
-    return TCGNN_OK;
-}
-
-int tcgnn_plan_create_sharded(const int32_t* d_nodePointer, const int32_t* d_edgeList,
-                              const int32_t* d_blockPartition, const int32_t* d_edgeToColumn,
-                              const int32_t* d_edgeToRow, int32_t num_rows, int32_t num_cols,
-                              int32_t row_offset, int64_t num_edges, int32_t num_windows,
-                              void* stream_v, tcgnn_plan** plan_out) {
-    if (!plan_out) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_create: plan_out is null");
-    *plan_out = nullptr;
-    const int32_t num_nodes = num_rows;
-    if (num_cols < 0 || row_offset < 0 || (int64_t)row_offset + num_rows > (int64_t)num_cols)
-        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_create: rows [%d, %d) do not fit in %d feature rows", row_offset, row_offset + num_rows, num_cols);
-    if (num_nodes < 0 || num_edges < 0 || num_windows < 0 || !d_nodePointer ||
-        (num_windows > 0 && !d_blockPartition) || (num_edges > 0 && (!d_edgeList || !d_edgeToColumn || !d_edgeToRow)))
-        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_create: null array or negative size");
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    tcgnn_plan* p = new (std::nothrow) tcgnn_plan();
-    if (!p) return fail(TCGNN_ERR_OOM, "tcgnn_plan_create: host allocation failed");
-    p->N = num_nodes; p->Nc = num_cols; p->row_off = row_offset; p->E = num_edges; p->nw = num_windows;
-    p->nw_eff = (int32_t)std::min<int64_t>(num_windows, ((int64_t)num_nodes + kWinRows - 1) / kWinRows);
-    p->rowptr = d_nodePointer; p->col = d_edgeList; p->bp = d_blockPartition; p->e2c = d_edgeToColumn; p->e2r = d_edgeToRow;
-    const int nw = p->nw_eff;
-    std::vector<int32_t> bp((size_t)std::max(nw, 1));
-    auto bail = [&](int rc) { tcgnn_plan_destroy(p); return rc; };
-    // TCGNN_VERBOSE=2: where plan creation spends its time (each mark synchronises the stream: a measurement aid, not the product's behaviour)
-    const char* const venv = getenv("TCGNN_VERBOSE");
-    const bool vtime = venv && atoi(venv) >= 2;
-    auto t_last = std::chrono::steady_clock::now();
-    auto mark = [&](const char* what) {
-        if (!vtime) return;
-        (void)hipStreamSynchronize(stream);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[tcgnn] plan_create: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-        t_last = now;
-    };
-    if (nw > 0) {
-        uint32_t* d_maxdeg = nullptr;   // the longest row: what the range guard's bound follows (guard_spmm)
-        uint32_t h_maxdeg = 0;
-        hipError_t e = hipMalloc(&d_maxdeg, sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_maxdeg, 0, sizeof(uint32_t), stream);
-        if (e == hipSuccess && num_nodes > 0) {
-            hipLaunchKernelGGL(max_degree_kernel, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)num_nodes + 255) / 256)), dim3(256), 0, stream, d_nodePointer, num_nodes, d_maxdeg);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&h_maxdeg, d_maxdeg, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(bp.data(), d_blockPartition, (size_t)nw * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_maxdeg);
-        if (e != hipSuccess) return bail(fail(TCGNN_ERR_HIP, "read blockPartition: %s", hipGetErrorString(e)));
-        p->max_degree = (int32_t)std::min<uint32_t>(h_maxdeg, 0x7fffffffu);
-    }
-    mark("blockPartition to the host");
-    std::vector<int64_t> wb_ptr((size_t)nw + 1, 0);
-    for (int w = 0; w < nw; ++w) {
-        if (bp[(size_t)w] < 0) return bail(fail(TCGNN_ERR_BAD_GRAPH, "blockPartition[%d] = %d is negative", w, bp[(size_t)w]));
-        p->tc_blocks += bp[(size_t)w];
-        wb_ptr[(size_t)w + 1] = wb_ptr[(size_t)w] + (bp[(size_t)w] + 3) / 4;
-        p->max_wb = std::max<int64_t>(p->max_wb, (bp[(size_t)w] + 3) / 4);
-    }
-    p->total_wb = wb_ptr[(size_t)nw];
-    p->h_bp.assign(bp.begin(), bp.begin() + nw);
-    std::vector<int32_t> order((size_t)std::max(nw, 1));
-    std::iota(order.begin(), order.begin() + nw, 0);
-    std::stable_sort(order.begin(), order.begin() + nw, [&](int32_t x, int32_t y) { return bp[(size_t)x] > bp[(size_t)y]; });
-    // Block -> window map of the per-window gather walks.  Heaviest first keeps a hub window from starting last; but when no window
-    // is far above the mean the order is free, and then locality decides: workgroup b runs on XCD b % 8 (observed dispatch, used for
-    // speed only), so XCD x takes the x-th contiguous eighth of the windows in their own order - the workgroups resident on one
-    // XCD at one time are neighbours in the graph's numbering and share their gathered rows in that XCD's L2 (communities).
-    {
-        int64_t mx = 0;
-        for (int w = 0; w < nw; ++w) mx = std::max<int64_t>(mx, bp[(size_t)w]);
-        constexpr int order_mode = 0;   // 0 automatic (1 heaviest first / 2 XCD-contiguous were A/B switches of r02)
-        const bool balanced = nw > 0 && mx * nw <= 4 * std::max<int64_t>(p->tc_blocks, 1);
-        // A few hubs over an otherwise even graph (communities + hubs): the K windows more than 4x the mean start first, heaviest first
-        // (the round-robin dispatch spreads them over the XCDs), the rest follows in XCD-contiguous order.  A continuous skew
-        // (R-MAT: the weight falls with the id, the rest is not even either) keeps heaviest-first throughout.
-        int K = 0;
-        if (!balanced && nw >= 64) {
-            const int64_t mean_x4 = 4 * std::max<int64_t>(p->tc_blocks, 1) / nw + 1;
-            while (K < nw && bp[(size_t)order[(size_t)K]] > mean_x4) ++K;
-            int64_t rest = 0, rest_max = 0;
-            for (int q = K; q < nw; ++q) { rest += bp[(size_t)order[(size_t)q]]; rest_max = std::max<int64_t>(rest_max, bp[(size_t)order[(size_t)q]]); }
-            if (K > nw / 16 || rest_max * (int64_t)(nw - K) > 3 * std::max<int64_t>(rest, 1)) K = -1;   // not "a few hubs": keep heaviest-first
-        }
-        if (order_mode == 2 || (order_mode == 0 && nw >= 64 && (balanced || K > 0))) {
-            if (K < 0 || order_mode == 2) K = order_mode == 2 ? 0 : K;
-            std::vector<int32_t> rest;                                   // the windows behind the hubs, in their own order
-            {
-                std::vector<char> is_hub((size_t)nw, 0);
-                for (int q = 0; q < K; ++q) is_hub[(size_t)order[(size_t)q]] = 1;
-                for (int w = 0; w < nw; ++w) if (!is_hub[(size_t)w]) rest.push_back(w);
-            }
-            // every XCD takes one contiguous eighth: the eighths must weigh about the same (a degree that falls with the id -
-            // R-MAT - would hand XCD 0 the heavy end: ogbn-products shape 3.96 -> 4.54 ms), else heaviest-first stays
-            bool even = true;
-            if (order_mode != 2) {
-                int64_t part[8] = {0}, all = 0;
-                for (size_t q = 0; q < rest.size(); ++q) { part[q * 8 / rest.size()] += bp[(size_t)rest[q]]; all += bp[(size_t)rest[q]]; }
-                for (int x = 0; x < 8; ++x) even = even && part[x] * 8 <= all + all / 8;
-            }
-            if (even) {
-            int cnt[8] = {0}, start[9] = {0}, seen[8] = {0};
-            for (int b = K; b < nw; ++b) ++cnt[b % 8];                   // positions XCD x gets behind the hubs
-            for (int x = 0; x < 8; ++x) start[x + 1] = start[x] + cnt[x];
-            for (int b = K; b < nw; ++b) { const int x = b % 8; order[(size_t)b] = rest[(size_t)(start[x] + seen[x]++)]; }
-            }
-        }
-    }
-    p->waves = (nw > 0 && p->total_wb >= (int64_t)6 * nw) ? 4 : 1;
-    mark("window order (host)");
-
-    const size_t n_wb = (size_t)std::max<int64_t>(p->total_wb, 1);
-    const size_t b_ptr = ((size_t)nw + 1) * sizeof(int64_t), b_ord = (size_t)std::max(nw, 1) * sizeof(int32_t);
-    const size_t b_cols = n_wb * kWbCols * sizeof(int32_t), b_mask = n_wb * kWinRows * sizeof(uint32_t), b_eb = n_wb * kWinRows * sizeof(int32_t);
-    int32_t* d_flags = nullptr;
-    hipError_t e = hipMalloc(&p->d_wb_ptr, b_ptr);
-    if (e == hipSuccess) e = hipMalloc(&p->d_order, b_ord);
-    if (e == hipSuccess) e = hipMalloc(&p->d_cols, b_cols);
-    if (e == hipSuccess) e = hipMalloc(&p->d_mask, b_mask);
-    if (e == hipSuccess) e = hipMalloc(&p->d_ebase, b_eb);
-    if (e == hipSuccess) e = hipMalloc(&d_flags, 2 * sizeof(int32_t));
-    if (e != hipSuccess) { (void)hipFree(d_flags); return bail(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "plan allocation (%zu bytes): %s", b_ptr + b_ord + b_cols + b_mask + b_eb, hipGetErrorString(e))); }
-    p->bytes = b_ptr + b_ord + b_cols + b_mask + b_eb;
-    int32_t flags[2] = {0, 0};
-    e = hipMemcpyAsync(p->d_wb_ptr, wb_ptr.data(), b_ptr, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && nw > 0) e = hipMemcpyAsync(p->d_order, order.data(), (size_t)nw * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 2 * sizeof(int32_t), stream);
-    if (e == hipSuccess && nw > 0) {
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nw), dim3(256), 0, stream, d_nodePointer, d_edgeList, d_edgeToColumn,
-                           d_edgeToRow, p->d_wb_ptr, num_rows, num_cols, p->d_cols, p->d_mask, p->d_ebase, d_flags);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream); // host vectors above must outlive the copies
-    (void)hipFree(d_flags);
-    if (e != hipSuccess) return bail(fail(TCGNN_ERR_HIP, "plan build: %s", hipGetErrorString(e)));
-    if (flags[0]) return bail(fail(TCGNN_ERR_BAD_GRAPH, "edgeToColumn / edgeToRow / edgeList hold ids outside the window, blockPartition or node range"));
-    p->canonical = flags[1] ? 0 : 1;
-    mark("allocate + pack_kernel");
-    // Is the graph structurally symmetric?  (The range guard's patch walks a few dirty rows' edges AND their mirrors instead of scanning
-    // every column id, where it is: wide_patch_kernel.)  One thread per edge, a binary search each; the answer stays on the device.
-    if (p->canonical && num_rows == num_cols && row_offset == 0 && num_edges > 0) {
-        e = hipMalloc(&p->d_sym, 2 * sizeof(int32_t));   // [answer, (edges above the diagonal) - (edges below)]
-        static const int32_t sym_init[2] = {1, 0};
-        if (e == hipSuccess) e = hipMemcpyAsync(p->d_sym, sym_init, sizeof sym_init, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(symmetry_kernel, dim3((unsigned)((num_edges + 255) / 256)), dim3(256), 0, stream, d_nodePointer, d_edgeList, d_edgeToRow, num_edges, num_rows, p->d_sym);
-            hipLaunchKernelGGL(symmetry_finish_kernel, dim3(1), dim3(1), 0, stream, p->d_sym);
-            e = hipGetLastError();   // (no synchronisation: nothing on the host waits for the answer - the patch kernels read it on the device)
-        }
-        if (e != hipSuccess) return bail(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "plan build (symmetry): %s", hipGetErrorString(e)));
-    }
-    mark("symmetry_kernel");
-    if (nw > 0) {
-        unsigned long long* d_loc = nullptr;
-        unsigned long long h_loc[2] = {0, 0};
-        e = hipMalloc(&d_loc, sizeof h_loc);
-        if (e == hipSuccess) e = hipMemsetAsync(d_loc, 0, sizeof h_loc, stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(locality_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, num_cols, row_offset, std::max(num_cols / 16, kWinRows), d_loc);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(h_loc, d_loc, sizeof h_loc, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_loc);
-        if (e != hipSuccess) return bail(fail(TCGNN_ERR_HIP, "plan build (locality): %s", hipGetErrorString(e)));
-        p->near_frac = h_loc[1] ? (double)h_loc[0] / (double)h_loc[1] : 0.0;
-        if (const char* v = getenv("TCGNN_VERBOSE")) if (atoi(v) > 0) fprintf(stderr, "[tcgnn] plan: %.0f %% of the condensed columns lie within num_cols / 16 rows of their window\n", 100.0 * p->near_frac);
-    }
-    mark("locality_kernel");
-    {   // column buckets for the range-blocked SpMM: only when windows are long (>= 2 tiles per bucket on
-        // average) and numerous enough to fill the chip with one wavefront per 4 windows (below)
-        hipDeviceProp_t prop;
-        int devid = 0;
-        if (hipGetDevice(&devid) == hipSuccess && hipGetDeviceProperties(&prop, devid) == hipSuccess) p->num_cus = prop.multiProcessorCount;
-        int nb = 8;
-        while (nb < 128 && (int64_t)num_cols / nb > 4096) nb <<= 1;
-        // wide column spaces with short windows (a row shard of a multi-GPU graph: Reddit's 243 tiles per window spread over
-        // N x 232 965 columns): fewer, longer buckets rather than no table - without it the shard falls back to the per-window
-        // walk (measured 1.77 ms against 0.87 ms for the unsharded graph)
-        while (nb > 8 && p->total_wb < (int64_t)g_bucket_min_tiles * nb * nw) nb >>= 1;
-        if (nw >= 4 * p->num_cus && p->total_wb >= (int64_t)g_bucket_min_tiles * nb * nw) {
-            p->nbuckets = nb;
-            p->bucket_rows = (int32_t)(((int64_t)num_cols + nb - 1) / nb);
-            if (p->bucket_rows < 1) p->bucket_rows = 1;
-            const size_t b_bp = (size_t)nw * (nb + 1) * sizeof(uint32_t);
-            e = hipMalloc(&p->d_bptr, b_bp);
-            if (e == hipSuccess) {
-                const int64_t total = (int64_t)nw * (nb + 1);
-                hipLaunchKernelGGL(bucket_ptr_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, nb,
-                                   p->bucket_rows, p->d_bptr);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            }
-            if (e != hipSuccess) return bail(fail(TCGNN_ERR_HIP, "bucket table: %s", hipGetErrorString(e)));
-            p->bytes += b_bp;
-        }
-    }
-    mark("bucket table");
-    if (has_locality(p) && windows_balanced(p)) (void)build_sync_tables(p, stream);
-    mark("sync-walk tables");
-    // Cell stream of the LDS-resident column-range SpMM (tcgnn_lds_spmm.inc) when the time models pick that kernel for a
-    // 64-column matrix: built now rather than inside the first call.  Other widths decide, and build, at their first call.
-    // TCGNN_LDS_AUTO=0 disables the automatic choice.
-    if (lds_chosen(p, 64)) {
-        LdsPass passes[2];
-        const int np = lds_passes(64, passes);
-        for (int i = 0; i < np; ++i) {
-            const int rc = build_lds_cells(p, stream, lds_stream_of(passes[i].nt, passes[i].maxw));
-            if (rc == TCGNN_ERR_OOM) { p->lds_choice[4] = 0; break; }   // (the gather walks need no stream)
-            if (rc) return bail(rc);
-        }
-    }
-    mark("LDS cell streams (64 columns)");
-    *plan_out = p;
-    return TCGNN_OK;
-}
-
-int tcgnn_plan_create(const int32_t* d_nodePointer, const int32_t* d_edgeList,
-                      const int32_t* d_blockPartition, const int32_t* d_edgeToColumn,
-                      const int32_t* d_edgeToRow, int32_t num_nodes, int64_t num_edges,
-                      int32_t num_windows, void* stream, tcgnn_plan** plan_out) {
-    return tcgnn_plan_create_sharded(d_nodePointer, d_edgeList, d_blockPartition, d_edgeToColumn, d_edgeToRow, num_nodes,
-                                     num_nodes, 0, num_edges, num_windows, stream, plan_out);
-}
-
-int tcgnn_plan_get_info(const tcgnn_plan* plan, tcgnn_plan_info* info) {
-    if (!plan || !info) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_get_info: null argument");
-    info->num_nodes = plan->N; info->num_windows = plan->nw; info->num_edges = plan->E;
-    info->tc_blocks = plan->tc_blocks; info->wide_blocks = plan->total_wb; info->plan_bytes = (int64_t)plan->bytes;
-    info->canonical = plan->canonical; info->waves_per_window = plan->waves;
-    info->column_buckets = plan->nbuckets; info->lds_ranges = 0;
-    for (int i = 0; i < kLdsStreams; ++i) if (plan->lds[i].nranges > info->lds_ranges) info->lds_ranges = plan->lds[i].nranges;   // finest stream built so far
-    return TCGNN_OK;
-}
-
-int tcgnn_plan_prepare(tcgnn_plan* plan, int32_t D, void* stream_v) {
-    if (!plan || D < 1) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_prepare: null plan or D < 1");
-    if (plan->nw_eff <= 0 || plan->N == 0) return TCGNN_OK;
-    const int dpad = round_up(D, 16);
-    const int mode = spmm_mode_of(plan);
-    // (the gather walks need nothing built, nor does the single-launch kernel: route_spmm's bound for it, applied here on the assumption
-    //  of a plain call - the calls that kernel does not take, staged or with the dense update, build their streams when they come)
-    if (mode == 0 && plan->total_wb <= kSmallMaxTiles) return TCGNN_OK;
-    if (!lds_wanted(plan, mode, dpad) || !planar_records_fit(plan, dpad)) return TCGNN_OK;
-    LdsPass passes[2];
-    bool ok;
-    return ensure_lds_streams(plan, static_cast<hipStream_t>(stream_v), mode, dpad, passes, lds_passes(dpad, passes), LdsBuild::kPrepare, &ok);
-}
-
-// Builds, now, what the first tcgnn_spmm_val call of width D would build inside the hot path: the single-edge cell stream of the
-// LDS-resident edge-valued walk (tcgnn_lds_val.inc) where the plan's time model takes that walk for D.  After it tcgnn_workspace_bytes
-// already includes the slot values, so the FIRST forward_AGNN (gnn_conv.py:132) runs the LDS-resident kernels and neither allocates nor
-// synchronises (VERDICT r04 item 6 ii).
-int tcgnn_plan_prepare_val(tcgnn_plan* plan, int32_t D, void* stream_v) {
-    if (!plan || D < 1) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_prepare_val: null plan or D < 1");
-    if (plan->nw_eff <= 0 || plan->N == 0 || plan->E < 4 || !plan->canonical) return TCGNN_OK;
-    const int dp = round_up(D, 16), mode = spmm_mode_of(plan);
-    if (!val_lds_wanted(plan, mode, dp)) return TCGNN_OK;
-    return ensure_val_stream(plan, static_cast<hipStream_t>(stream_v), mode, false);
-}
-
-int tcgnn_plan_set_spmm_mode(tcgnn_plan* plan, int32_t mode) {
-    if (!plan || mode < -1 || mode > 5) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_set_spmm_mode: null plan, or mode outside -1 (process-wide value) .. 5");
-    plan->spmm_mode.store((int8_t)mode, std::memory_order_relaxed);
-    return TCGNN_OK;
-}
-
-int tcgnn_plan_set_range_guard(tcgnn_plan* plan, int32_t level) {
-    if (!plan || level < -1 || level > 3) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_set_range_guard: null plan, or level outside -1 (process-wide value) .. 3");
-    plan->range_guard.store((int8_t)level, std::memory_order_relaxed);
-    return TCGNN_OK;
-}
-
-int tcgnn_set_range_guard(int32_t level) {
-    if (level < 0 || level > 3) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_set_range_guard: 0 (off), 1 (SpMM operators), 2 (+ SDDMM / fused AGNN with a few lost elements, default) or 3 (strict)");
-    g_range_guard = level;
-    return TCGNN_OK;
-}
-
+// which way the last staged call on this workspace went: the range guard's own rule (range_is_wide / range_is_wide_val) on the header words
 int tcgnn_range_mode(const void* d_workspace, void* stream_v, int32_t* wide_x, int32_t* wide_val) {
     if (!d_workspace || !wide_x) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_range_mode: null argument");
     uint32_t h[10];
     hipStream_t stream = static_cast<hipStream_t>(stream_v);
     HIP_TRY(hipMemcpyAsync(h, d_workspace, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    auto spread = [&](int k, int& emax) {
-        emax = (int)(h[k] >> 23);
-        if (h[k + 2] == 0u || h[k] == 0u || h[k] >= 0x7f800000u) return false;
-        return emax - (int)((0x7f800000u - h[k + 2]) >> 23) > 28;
-    };
-    auto clog2 = [](uint32_t k) { int c = 0; while (c < 32 && (1ull << c) < k) ++c; return c; };   // (the host mirror of range_is_wide / range_is_wide_val)
-    int ex = 0, ea = 0;
-    const bool sx = spread(0, ex), sa = spread(1, ea);
-    *wide_x = (sx && h[4] != 0u && h[6] != 0u && (int)h[7] * (ex - 127) >= 29 - clog2(std::min(h[4], h[6]))) ? 1 : 0;
+    *wide_x = range_is_wide(h, 0) ? 1 : 0;
     if (*wide_x && h[7] == 2u) *wide_x = h[9] ? 1 : 2;   // (SDDMM / fused AGNN: a few dirty rows - MFMA kernel + wide_patch_kernel; many - fp32 only at the strict level)
-    if (wide_val) {
-        const uint32_t k = (sa || h[6] >= h[5]) ? h[5] : std::max(h[6], 1u);
-        *wide_val = ((sx || sa) && h[5] != 0u && h[0] != 0u && h[1] != 0u && (ex - 127) + (ea - 127) >= 28 - clog2(k)) ? 1 : 0;
-    }
-    return TCGNN_OK;
-}
-
-int tcgnn_set_spmm_mode(int32_t mode) {
-    if (mode < 0 || mode > 5) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_set_spmm_mode: 0 (auto), 1 (plain), 2 (range-blocked), 3 (LDS-resident ranges), 4 (single-launch fp32 kernel) or 5 (slice-synchronised range walk)");
-    g_spmm_mode = mode;
-    return TCGNN_OK;
-}
-
-const char* tcgnn_plan_last_kernel(const tcgnn_plan* plan) { return plan ? plan->last_kernel.load(std::memory_order_relaxed) : ""; }
-
-int tcgnn_plan_set_timing(tcgnn_plan* plan, int32_t max_calls) {
-    if (!plan || max_calls < 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_set_timing: bad argument");
-    for (hipEvent_t e : plan->ev) (void)hipEventDestroy(e);
-    plan->ev.clear();
-    plan->ev_used = 0;
-    for (int i = 0; i < 2 * max_calls; ++i) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        plan->ev.push_back(e);
-    }
-    return TCGNN_OK;
-}
-
-int tcgnn_plan_read_timing(tcgnn_plan* plan, float* ms_out, int32_t capacity, int32_t* count) {
-    if (!plan || !count || (capacity > 0 && !ms_out)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_read_timing: null argument");
-    int n = 0;
-    const int used = std::min(plan->ev_used.load(), (int)plan->ev.size() / 2);
-    for (int i = 0; i < used && n < capacity; ++i) {
-        HIP_TRY(hipEventSynchronize(plan->ev[2 * i + 1]));
-        HIP_TRY(hipEventElapsedTime(&ms_out[n], plan->ev[2 * i], plan->ev[2 * i + 1]));
-        ++n;
-    }
-    *count = n;
-    plan->ev_used = 0;
+    if (wide_val) *wide_val = range_is_wide_val(h) ? 1 : 0;
     return TCGNN_OK;
 }
 
@@ -1530,97 +956,15 @@ int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge
     return run_spmm(c);
 }
 
-// tcgnn_sddmm (d_Xw == nullptr: both operands are d_X) and tcgnn_sddmm2 (d_Xw: the window operand, d_X: the gathered one): one
-// walk selection for both
-static int run_sddmm(const tcgnn_plan* plan, const float* d_Xw, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    if (plan->E == 0 || plan->N == 0) return TCGNN_OK;
-    if (const int rc = check_workspace(d_Xw ? "tcgnn_sddmm2" : "tcgnn_sddmm", ws, ws_bytes, d_Xw ? tcgnn_sddmm2_workspace_bytes(plan, D) : tcgnn_workspace_bytes(plan, D))) return rc;
-    if (!plan->canonical) {
-        if (d_Xw) hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, (const uint32_t*)nullptr, (const uint32_t*)nullptr, plan->rowptr, plan->col, d_Xw, d_X, d_ef, plan->N, D, plan->row_off);
-        else hipLaunchKernelGGL(sddmm_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, stream, plan->rowptr, plan->col, d_X, d_ef, plan->N, D, plan->row_off);
-        HIP_TRY(hipGetLastError());
-        return TCGNN_OK;
-    }
-    if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(d_ef, 0, (size_t)plan->E * sizeof(float), stream));
-    const Guard gsd = guard_sddmm(plan, D);
-    StageOpts so; so.guard = &gsd;
-    StagedImage im, imw;
-    if (const int rc = stage_features(plan, d_X, nullptr, D, ws, ws_bytes, stream, so, &im)) return rc;
-    if (d_Xw) {   // the window operand's image behind the gathered operand's: its own header, its own scale
-        const size_t first = workspace_bytes_for(plan->Nc, D);
-        if (ws_bytes < 2 * first) return fail(TCGNN_ERR_WORKSPACE, "tcgnn_sddmm2: workspace needs %zu bytes (tcgnn_sddmm2_workspace_bytes), got %zu", 2 * first, ws_bytes);
-        if (const int rc = stage_features(plan, d_Xw, nullptr, D, static_cast<char*>(ws) + first, ws_bytes - first, stream, so, &imw)) return rc;
-    }
-    const uint32_t* const hdr = im.hdr; const _Float16* const x16 = im.x16; const int dpad = im.dpad, pitch = im.pitch;
-    SddmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, x16, hdr, d_ef, plan->N, plan->Nc, plan->row_off, dpad, pitch, plan->rowptr, plan->d_bptr, plan->nbuckets, 0, 0, plan->nw_eff, image_is_big(plan->Nc, pitch), 0, 0, 0, SyncArgs{}, imw.x16, imw.hdr};
-    const int ks = (dpad + 31) / 32;
-    KernelTimer timer(plan, stream, ks <= 4 ? "sddmm_kernel" : "sddmm_wide_kernel");
-    const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
-    // Range-major walk (bit-identical results).  With the outputs staged per row the loop is bound by the gather again,
-    // and keeping it inside ~4 MB column ranges wins on the Reddit shape: D=16 1.14 -> 1.07 ms, D=32 1.38 -> 1.14,
-    // D=64 1.74 -> 1.66, D=128 3.37 -> 3.26.  No accumulators live across ranges, so ranges are 4x the SpMM's.
-    const bool blocked = ks <= 4 && plan->nbuckets > 0 && spmm_mode_of(plan) != 1 && (spmm_mode_of(plan) == 2 || range_walk_pays(plan, x16_bytes));
-    hipError_t e = hipSuccess;
-    if (ks <= 4 && !a.big && sync_chosen(plan, pitch * 2, spmm_mode_of(plan), kSyncSddmm, dpad / 16)) {
-        // slice-synchronised range walk (r06, tcgnn_sync_walk.inc): communities larger than an XCD's L2; one launch per slice round, bit-identical scores
-        plan->last_kernel.store("sddmm_kernel (slice-synchronised)", std::memory_order_relaxed);
-        a.use_sync = 1;
-        a.sync = sync_args(plan, pitch * 2);
-        const int lds_wg = 4 * sddmm_wave_lds(ks);
-        const int per_cu = std::max(1, std::min(ks <= 2 ? 4 : 3, (160 * 1024) / lds_wg));
-        const int nwg = kSyncXcds * std::max(1, std::min((plan->sync.S + 3) / 4, plan->num_cus / kSyncXcds * per_cu));
-        for (int r = 0; r < plan->sync.R && e == hipSuccess; ++r) {
-            a.sync.round = r;
-            e = launch_sddmm_ks<4, true>(ks, a, nwg, stream);
-        }
-    } else if (blocked) {
-        // (r03, whole-line gathers: D = 64 1.26 / 1.24 ms at 4 / 8 MB ranges, 1.36 at 2 MB; D = 128 - an image of 60 MB - 2.33 at 2 MB,
-        //  2.58 at 4 MB, 3.5 per-window; with XCD affinity 2.01 at 2 or 4 MB)
-        const int nranges = range_count(plan, x16_bytes, x16_bytes > ((size_t)32 << 20) ? 2 * kRangeTargetBytes : 4 * kRangeTargetBytes);
-        a.nranges = nranges;
-        a.gsel = plan->nbuckets / nranges;
-        const int lds_wg = 4 * sddmm_wave_lds(ks);
-        const int per_cu = std::max(1, std::min(4, (160 * 1024) / lds_wg));
-        const int64_t items = (int64_t)nranges * plan->nw_eff;
-        int nwg = (int)std::min<int64_t>((items + 3) / 4, (int64_t)plan->num_cus * per_cu);
-        // XCD affinity (sddmm_kernel; TCGNN_SDDMM_XCD=0 switches it off, read per call: tests compare the two).  Reddit shape:
-        // D = 128 2.32 -> 2.01 ms, D = 64 1.36 -> 1.33, D = 16 / 32 -1 .. -2.5 %; before the whole-line gathers it returned nothing.
-        const char* const xenv = test_knob("TCGNN_SDDMM_XCD");
-        // (like the fused kernel's sliced walk it wants every window's tiles spread evenly over the ranges: on the calibrated SBM graph -
-        //  22.5 % of a window's edges inside its own community, near_frac 0.3 - the XCD that owns a window's community holds the others
-        //  up, 1.43 -> 2.11 ms at D = 64, where an XCD has ONE range; with four ranges per XCD, spread over the graph, the load evens
-        //  out again: D = 128 2.48 -> 2.25 ms there; TCGNN_SDDMM_XCD=2 forces it)
-        const int xknob = xenv ? atoi(xenv) : 1;
-        // (r06: that was the walk's window order, not the graph - `order` in its XCD-contiguous form hands a persistent wavefront windows of
-        //  ONE eighth of the graph only, SddmmArgs::ident; with the windows taken in their own order every wavefront of an XCD is inside the
-        //  same community at the same time, heavy or light together.  TCGNN_RM_IDENT=0 restores the old order for A/B runs)
-        const char* const ienv = test_knob("TCGNN_RM_IDENT");
-        a.ident = (ienv ? atoi(ienv) : 1) && windows_balanced(plan) ? 1 : 0;
-        if (xknob && (xknob >= 2 || a.ident || plan->near_frac <= 0.2 || nranges >= 4 * kXcdCount) && nranges % kXcdCount == 0 && nwg >= kXcdCount) { a.xcd = 1; nwg -= nwg % kXcdCount; }
-        e = launch_sddmm_ks<4, true>(ks, a, nwg, stream);
-    } else {
-        e = plan->waves == 4 ? launch_sddmm_ks<4, false>(ks, a, plan->nw_eff, stream) : launch_sddmm_ks<1, false>(ks, a, plan->nw_eff, stream);
-    }
-    HIP_TRY(e);
-    timer.stop();
-    // (the range guard's fallback: returns at once unless X is "wide")
-    if (range_guard_of(plan) >= 2 && d_Xw) {   // two operands: the whole call in fp32 when either is wide (sddmm2_wide; returns at once otherwise)
-        // (the rows of the windows the plan was given: what lies behind them stays as the memset above left it, as on the MFMA path)
-        const int32_t rows = (int32_t)std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows);
-        hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048)), dim3(256), 0, stream, imw.hdr, hdr, plan->rowptr, plan->col, d_Xw, d_X, d_ef,
-                           rows, D, plan->row_off);
-    } else if (range_guard_of(plan) >= 2) {   // a few dirty rows: the patch behind the MFMA kernel; many: the CSR fallback (each returns at once otherwise)
-        const PatchArgs pa{hdr, dirty_bitmap_of(ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, d_X, x16, pitch, d_ef, nullptr, nullptr, nullptr, nullptr, plan->N, plan->Nc, D, plan->row_off, 0, plan->E, plan->d_sym};
-        HIP_TRY(launch_wide_patch(pa, stream));
-    }
-    HIP_TRY(hipGetLastError());
-    return TCGNN_OK;
+static SddmmCall sddmm_call(const char* name, const tcgnn_plan* plan, const float* d_Xw, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream) {
+    SddmmCall c;
+    c.plan = plan; c.d_Xw = d_Xw; c.d_X = d_X; c.d_ef = d_ef; c.D = D; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = static_cast<hipStream_t>(stream); c.name = name;
+    return c;
 }
 
 int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
     if (!plan || D < 1 || (plan->N > 0 && !d_X) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm: null argument or D < 1");
-    return run_sddmm(plan, nullptr, d_X, d_ef, D, ws, ws_bytes, stream_v);
+    return run_sddmm(sddmm_call("tcgnn_sddmm", plan, nullptr, d_X, d_ef, D, ws, ws_bytes, stream_v));
 }
 
 size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
@@ -1630,8 +974,7 @@ size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
 
 int tcgnn_sddmm2(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
     if (!plan || D < 1 || (plan->N > 0 && !(d_X && d_Z)) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm2: null argument or D < 1");
-    return run_sddmm(plan, d_X, d_Z, d_ef, D, ws, ws_bytes, stream_v);
+    return run_sddmm(sddmm_call("tcgnn_sddmm2", plan, d_X, d_Z, d_ef, D, ws, ws_bytes, stream_v));
 }
-
 
 } // extern "C"

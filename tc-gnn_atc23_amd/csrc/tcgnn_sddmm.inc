@@ -39,7 +39,6 @@ __device__ __forceinline__ bool sddmm2_wide(const uint32_t* hx, const uint32_t* 
     const uint32_t n = (sx ? hx[6] : 0u) + (sz ? hz[6] : 0u);
     return (ex - 127) + (ez - 127) >= 29 - ceil_log2_u32(n < cap ? n : cap);
 }
-static constexpr int kXcdCount = 8;   // workgroups are dealt to the XCDs round-robin in launch order
 
 // LDS of one SDDMM wavefront: two operand buffers, the metadata pad, the output staging area
 // (16 rows x kSddmmStageCap floats) and 256 bytes of junk slots for lanes that have nothing to stage.
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
             // alike, the launch started every wavefront together, and the phase's rows (~2 MB) are what the XCD's L2 holds meanwhile.
             int x, w_lo, w_hi, nph;
             sync_slice_of(a.sync, x, w_lo, w_hi, nph);
-            const int nwv = (int)(gridDim.x / (unsigned)kSyncXcds) * WAVES, wid = (int)(blockIdx.x / (unsigned)kSyncXcds) * WAVES + wave;
+            const int nwv = (int)(gridDim.x / (unsigned)kXcds) * WAVES, wid = (int)(blockIdx.x / (unsigned)kXcds) * WAVES + wave;
             const int ts = a.sync.kmax + 1;
             // (a wavefront keeps ONE window through all phases, its rows in registers, then takes the next: reloading the A operand per
             //  (window, phase) run cost 4 KB of mostly missing lines and a round trip in front of each of the ~5-tile runs - 4.4 GB per call on
@@ -323,10 +322,10 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
             // the ranges x, x + 8, ... only, one after the other - that XCD's L2 is asked for an eighth of the image, a range or two of
             // it at a time, instead of every range every other XCD is walking as well.  Every edge lies in exactly one range, so
             // nothing is added up afterwards and the scores are bit for bit those of the other walks.
-            const int x = (int)(blockIdx.x % (unsigned)kXcdCount);
-            const int64_t items_x = (int64_t)(a.nranges / kXcdCount) * a.nw, lstride = (int64_t)(gridDim.x / (unsigned)kXcdCount) * WAVES;
-            for (int64_t q = (int64_t)(blockIdx.x / (unsigned)kXcdCount) * WAVES + wave; q < items_x; q += lstride) {
-                const int rr = (int)(q / a.nw), r = x + kXcdCount * rr;
+            const int x = (int)(blockIdx.x % (unsigned)kXcds);
+            const int64_t items_x = (int64_t)(a.nranges / kXcds) * a.nw, lstride = (int64_t)(gridDim.x / (unsigned)kXcds) * WAVES;
+            for (int64_t q = (int64_t)(blockIdx.x / (unsigned)kXcds) * WAVES + wave; q < items_x; q += lstride) {
+                const int rr = (int)(q / a.nw), r = x + kXcds * rr;
                 const int wq = (int)(q - (int64_t)rr * a.nw);
                 const int w = a.ident ? wq : __builtin_amdgcn_readfirstlane(a.order[wq]);
                 const int64_t tb = a.wb_ptr[w];

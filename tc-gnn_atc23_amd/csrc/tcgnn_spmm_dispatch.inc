@@ -5,7 +5,6 @@
 // columns one gather-walk launch may cover: the widest row whose pitch the structured descriptor can express, in whole
 // 128-column chunks.  Wider matrices go through the gather walks as independent column blocks (ld = the full row length).
 static constexpr int kMaxGatherBlockDims = 4096;
-static bool agnn_supported(const tcgnn_plan* plan, int32_t D);
 
 // tcgnn_spmm_scaled: the column scale enters the staging pass (and the kernels that read fp32 X), the row scale and bias the final store
 struct Scales { const float* col = nullptr; const float* row = nullptr; const float* bias = nullptr; };
@@ -193,19 +192,20 @@ static int route_spmm(const SpmmCall& c, SpmmRoute* r) {
         if (plan->val_choice.load(std::memory_order_acquire) == 1 && c.ws_bytes >= workspace_bytes_for(plan->Nc, D) + val_stream_bytes(plan)) { r->walk = Walk::kValLds; return TCGNN_OK; }
     }
     // ---- edge values on the fused AGNN kernel's XCD-sliced walk (r03).  Where the fused pair's backward pass takes that walk (graphs
-    //      without locality of their own, windows alike, an fp16 image of 16 - 64 MB: agnn_walk) the edge-valued SpMM is the same
+    //      without locality of their own, windows alike, an fp16 image of 16 - 64 MB: agnn_plan_walk) the edge-valued SpMM is the same
     //      gather with less to do per tile, so it runs as that kernel with the score half switched off (AgnnArgs::valonly: w = 1,
     //      ef = the caller's values, their abs-max from this call's header): 76 % L2 hits and 5.8 GB of fabric reads instead of the
     //      per-window walk's 31 % and 12.2 GB on the Reddit shape at D = 64.  Same operand rounding and scales; the sums run in slice order.
     if (plain_val && plan->nw_eff > 0 && mode == 0 && dpad > 32 && dpad <= kMaxChunkDims && agnn_supported(plan, D)) {
         const size_t need = workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan) + agnn_slice_bytes(plan, D);
-        if (agnn_walk(plan, D, true, &r->nslices) == kAgnnSliced && r->nslices > 0 && c.ws_bytes >= need) { r->walk = Walk::kValSliced; return TCGNN_OK; }
+        const AgnnRoute bw = agnn_plan_walk(plan, D, true);
+        if (bw.walk == AgnnWalk::kSliced && bw.nslices > 0 && c.ws_bytes >= need) { r->nslices = bw.nslices; r->walk = Walk::kValSliced; return TCGNN_OK; }
     }
     const int pitch = x16_pitch(dpad);
     // slice-synchronised range walk (r06, tcgnn_sync_walk.inc): communities larger than an XCD's L2
     if (plan->nw_eff > 0 && !c.d_W && !image_is_big(plan->Nc, pitch) && sync_chosen(plan, pitch * 2, mode, c.d_val ? kSyncVal : kSyncSpmm, dpad / 16)) { r->walk = Walk::kSync; return TCGNN_OK; }
     // range-blocked walk when the fp16 image of X overflows L2 and the windows are long enough to cut
-    const size_t x16_bytes = ((size_t)plan->Nc + 1) * pitch * sizeof(_Float16);
+    const size_t x16_bytes = image_bytes(plan, pitch);
     // (a numbering with locality keeps the per-window walk: in XCD-contiguous order its co-resident workgroups share their gathered
     //  rows in L2 - 50-community Reddit shape, edge values: 0.92 ms against 1.18 ms range-blocked; the range-blocked walk is for
     //  graphs without it, where it wins by 1.4x)
@@ -283,23 +283,6 @@ static int launch_val_lds(const SpmmCall& c, const StagedImage& im) {
         hipLaunchKernelGGL(spmm_cold_val_kernel, dim3((unsigned)((plan->nw_eff + 3) / 4), (unsigned)((im.dpad + 63) / 64)), dim3(256), 0, stream, ca);
         HIP_TRY(hipGetLastError());
     }
-    return TCGNN_OK;
-}
-static int launch_val_sliced(const SpmmCall& c, const SpmmRoute& r, const StagedImage& im) {
-    const tcgnn_plan* const plan = c.plan;
-    const int32_t D = c.D;
-    const int ns = r.nslices;
-    double* partial = reinterpret_cast<double*>(static_cast<char*>(c.ws) + workspace_bytes_for(plan->Nc, D));
-    float* const ypart = reinterpret_cast<float*>(static_cast<char*>(c.ws) + workspace_bytes_for(plan->Nc, D) + agnn_partial_bytes(plan));
-    AgnnArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, im.x16, im.hdr, nullptr, const_cast<float*>(c.d_val), const_cast<uint32_t*>(im.hdr) + 1, ypart, partial,
-               plan->N, plan->Nc, plan->row_off, im.dpad, D, im.pitch, plan->E, plan->rowptr, plan->d_bptr, plan->nbuckets, plan->nbuckets / ns, 0, plan->nw_eff, 0,
-               image_is_big(plan->Nc, im.pitch), ns, 1, nullptr, agnn_rot(plan), 0, SyncArgs{}};
-    KernelTimer timer(plan, c.stream, "agnn_kernel (XCD-sliced, values only) + agnn_slice_sum_kernel");
-    HIP_TRY((launch_agnn<4, true, 0>(im.dpad / 16, a, ns * ((plan->nw_eff + 3) / 4), c.stream)));
-    const int64_t nsum = std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows) * D;   // (rows beyond the windows were zeroed above)
-    const unsigned sg = (unsigned)std::min<int64_t>(2048, (nsum / 4 + 255) / 256 + 1);
-    hipLaunchKernelGGL(agnn_slice_sum_kernel, dim3(sg), dim3(256), 0, c.stream, ypart, c.d_Y, nsum, (int64_t)plan->N * D, ns);
-    HIP_TRY(hipGetLastError());
     return TCGNN_OK;
 }
 // the remainder of an ordinary stream: spmm_kernel over the re-condensed cold tiles, adding into what the LDS-resident kernel stored
@@ -380,8 +363,8 @@ static int launch_sync(const SpmmCall& c, const StagedImage& im) {
     KernelTimer timer(plan, c.stream, "spmm_sync_kernel");
     SpmmSyncArgs sa{gather_args(c, im), sync_args(plan, im.pitch * 2)};
     auto wgs = [&](int nt) {   // workgroups per launch: what holds a slice (S windows per XCD, 4 wavefronts x MAXW windows per workgroup), at most what is resident
-        const int per_xcd = std::min((plan->sync.S + 4 * sync_maxw(nt, val) - 1) / (4 * sync_maxw(nt, val)), plan->num_cus / kSyncXcds * sync_wgs_per_cu(nt, val));
-        return kSyncXcds * std::max(per_xcd, 1);
+        const int per_xcd = std::min((plan->sync.S + 4 * sync_maxw(nt, val) - 1) / (4 * sync_maxw(nt, val)), plan->num_cus / kXcds * sync_wgs_per_cu(nt, val));
+        return kXcds * std::max(per_xcd, 1);
     };
     for (int r = 0; r < plan->sync.R; ++r) {   // one launch per slice round
         sa.s.round = r;
@@ -395,15 +378,13 @@ static int launch_blocked(const SpmmCall& c, const StagedImage& im) {
     const bool val = c.d_val != nullptr;
     const int nfull = im.dpad / kMaxChunkDims, rem = (im.dpad % kMaxChunkDims) / 16;
     KernelTimer timer(plan, c.stream, "spmm_blocked_kernel");
-    const int nranges = range_count(plan, ((size_t)plan->Nc + 1) * im.pitch * sizeof(_Float16), kRangeTargetBytes);
+    const int nranges = range_count(plan, image_bytes(plan, im.pitch), kRangeTargetBytes);
     SpmmBlockedArgs b{gather_args(c, im), plan->d_bptr, plan->nbuckets, plan->nbuckets / nranges, nranges, plan->nw_eff, 0};
     auto wgs = [&](int nt) {   // persistent grid = what is resident at once: LDS per workgroup (4 wavefronts: tile buffers,
                                // pads, + the 4 KB A table) against 160 KB, and the register budget (4 or 2 workgroups per CU)
         const int maxw = blocked_maxw(nt, val);
         b.ngroups = (plan->nw_eff + maxw - 1) / maxw;
-        const int lds_wg = 4 * (2 * nt * 1024 + kPadBytes + (val ? 1024 : 0)) + 4096;
-        const int per_cu = std::max(1, std::min(nt <= 4 ? 4 : 2, (160 * 1024) / lds_wg));
-        return std::min((b.ngroups + 3) / 4, plan->num_cus * per_cu);
+        return std::min((b.ngroups + 3) / 4, plan->num_cus * wgs_per_cu(4 * (2 * nt * 1024 + kPadBytes + (val ? 1024 : 0)) + 4096, nt <= 4 ? 4 : 2));
     };
     if (nfull) { b.base.chunk0 = 0; const int n = wgs(8); HIP_TRY(launch_blocked_any(val, 8, b, n, nfull, c.stream, c.epi())); }
     if (rem) { b.base.chunk0 = nfull; const int n = wgs(rem); HIP_TRY(launch_blocked_any(val, rem, b, n, 1, c.stream, c.epi())); }
@@ -469,7 +450,7 @@ static int run_spmm(const SpmmCall& c) {
     int rc = TCGNN_OK;
     switch (r.walk) {
         case Walk::kValLds:    rc = launch_val_lds(c, im); break;
-        case Walk::kValSliced: rc = launch_val_sliced(c, r, im); break;
+        case Walk::kValSliced: rc = launch_val_sliced(plan, im, c.d_val, c.d_Y, c.D, c.ws, r.nslices, c.stream); break;
         case Walk::kLds:       rc = launch_lds(c, r, im); break;
         case Walk::kSync:      rc = launch_sync(c, im); break;
         case Walk::kBlocked:   rc = launch_blocked(c, im); break;

@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256, (NT <= 4 ? 4 : 2)) void TCGNN_KERNEL_NAME(TCGN
 
     int x, w_lo, w_hi, nph;
     sync_slice_of(b.s, x, w_lo, w_hi, nph);
-    const int nwv = (int)(gridDim.x / (unsigned)kSyncXcds) * 4, wid = (int)(blockIdx.x / (unsigned)kSyncXcds) * 4 + wave;
+    const int nwv = (int)(gridDim.x / (unsigned)kXcds) * 4, wid = (int)(blockIdx.x / (unsigned)kXcds) * 4 + wave;
     const int tstride = b.s.kmax + 1;
     for (int base = w_lo + wid; base < w_hi; base += nwv * MAXW) {   // (one trip when the grid holds the slice)
         int wj[MAXW];

@@ -25,7 +25,6 @@
 // No partial sums leave the registers, no atomics: as deterministic as the other walks (and bit-identical to the per-window walk
 // with one wavefront per window: same tile order per window).
 // ------------------------------------------------------------------------------------------
-static constexpr int kSyncXcds = 8;
 static constexpr int kSyncKmax = 64;          // hot buckets a slice may list
 static constexpr int kSyncSlice = 768;        // windows of one XCD per launch = what its wavefronts hold at once beyond 64 columns (32 CUs x 12 wavefronts x 2 windows)
 static constexpr int kSyncFbShift0 = 11;      // finest bucket: 2048 rows
@@ -44,7 +43,7 @@ struct SpmmSyncArgs {
 };
 
 __device__ __forceinline__ void sync_slice_of(const SyncArgs& s, int& x, int& w_lo, int& w_hi, int& nph) {
-    x = (int)(blockIdx.x % (unsigned)kSyncXcds);
+    x = (int)(blockIdx.x % (unsigned)kXcds);
     const int64_t share_hi = (int64_t)(x + 1) * s.nwx < (int64_t)s.nw ? (int64_t)(x + 1) * s.nwx : (int64_t)s.nw;
     const int64_t lo = (int64_t)x * s.nwx + (int64_t)s.round * s.S;
     w_lo = (int)(lo < share_hi ? lo : share_hi);
