@@ -106,41 +106,72 @@ torch::Tensor aligned_scratch(size_t bytes, const torch::Tensor& like, void** pt
   return buf;
 }
 
-// A^T of the entry's graph: tcgnn_transpose_ws, then (not symmetric) the device SGT of A^T and its plan - as TCGNN.py does
+// A^T's CSR, one per (nodePointer, edgeList): tcgnn_transpose_ws at first sight, then cached.  edge_colsum sums over it and
+// transposed_for builds A^T's plan from it, so a graph is transposed once and holds one perm.
+struct TransposedCsr {
+  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
+  torch::Tensor nodePointer, edgeList, rp_t, col_t, perm;
+  bool symmetric = false;
+};
+std::list<TransposedCsr>& csr_cache() { static std::list<TransposedCsr> c; return c; }
+
+TransposedCsr& transposed_csr(const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
+  for (auto* t : {&nodePointer, &edgeList}) key.emplace_back(t->data_ptr(), t->numel(), (int64_t)t->_version());
+  auto& cache = csr_cache();
+  for (auto it = cache.begin(); it != cache.end(); ++it)
+    if (it->key == key) { cache.splice(cache.begin(), cache, it); return cache.front(); }
+  const int32_t N = (int32_t)(nodePointer.numel() - 1);
+  const int64_t E = edgeList.numel();
+  auto opts = nodePointer.options().dtype(torch::kInt32);
+  TransposedCsr c;
+  c.key = key;
+  c.nodePointer = nodePointer;
+  c.edgeList = edgeList;
+  c.rp_t = torch::empty({(int64_t)N + 1}, opts);
+  c.perm = torch::empty({E}, opts);
+  c.col_t = torch::empty({E}, opts);
+  int32_t sym = 0;
+  size_t need = 0;
+  void* ws = nullptr;
+  tcgnn_check(tcgnn_transpose_workspace_bytes(N, E, &need), "tcgnn_transpose_workspace_bytes");
+  torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
+  tcgnn_check(tcgnn_transpose_ws(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, c.rp_t.data_ptr<int>(), c.col_t.data_ptr<int>(),
+                                 c.perm.data_ptr<int>(), ws, need, &sym, current_stream(nodePointer)), "tcgnn_transpose_ws");
+  c.symmetric = sym != 0;
+  if (c.symmetric) { c.rp_t = nodePointer; c.col_t = edgeList; }   // A^T = A: its arrays are A's own
+  cache.push_front(std::move(c));
+  while (cache.size() > kPlanCacheSize) cache.pop_back();   // (tcgnn_transpose_ws synchronised; torch's allocator orders the reuse of the rest)
+  return cache.front();
+}
+
+// A^T of the entry's graph: its CSR from csr_cache(), then (not symmetric) the device SGT of A^T and its plan - as TCGNN.py does
 TransposedEntry& transposed_for(PlanEntry& e) {
   TransposedEntry& t = e.t;
   if (t.built) return t;
   const torch::Tensor& nodePointer = e.keep[0];
-  const torch::Tensor& edgeList = e.keep[1];
-  const int32_t N = (int32_t)(nodePointer.numel() - 1);
-  const int64_t E = edgeList.numel(), bp_len = e.keep[2].numel();
-  auto opts = nodePointer.options().dtype(torch::kInt32);
-  torch::Tensor rp_t = torch::empty({(int64_t)N + 1}, opts), col_t = torch::empty({E}, opts), perm = torch::empty({E}, opts);
-  size_t need = 0;
-  void* ws = nullptr;
-  tcgnn_check(tcgnn_transpose_workspace_bytes(N, E, &need), "tcgnn_transpose_workspace_bytes");
-  int32_t sym = 0;
-  {
-    torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
-    tcgnn_check(tcgnn_transpose_ws(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, rp_t.data_ptr<int>(), col_t.data_ptr<int>(),
-                                   perm.data_ptr<int>(), ws, need, &sym, current_stream(nodePointer)), "tcgnn_transpose_ws");
-  }
-  if (!sym) {
+  const TransposedCsr& c = transposed_csr(nodePointer, e.keep[1]);
+  if (!c.symmetric) {
+    const int32_t N = (int32_t)(nodePointer.numel() - 1);
+    const int64_t E = e.keep[1].numel(), bp_len = e.keep[2].numel();
+    auto opts = nodePointer.options().dtype(torch::kInt32);
     torch::Tensor bp_t = torch::zeros({bp_len}, opts), e2c_t = torch::empty({E}, opts), e2r_t = torch::empty({E}, opts);
+    size_t need = 0;
+    void* ws = nullptr;
     tcgnn_check(tcgnn_preprocess_gpu_workspace_bytes(N, E, TCGNN_BLK_H, &need), "tcgnn_preprocess_gpu_workspace_bytes");
     int64_t tc_blocks = 0;
     {
       torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
-      tcgnn_check(tcgnn_preprocess_gpu_ws(col_t.data_ptr<int>(), rp_t.data_ptr<int>(), N, E, TCGNN_BLK_H, TCGNN_BLK_W, bp_t.data_ptr<int>(), bp_len,
+      tcgnn_check(tcgnn_preprocess_gpu_ws(c.col_t.data_ptr<int>(), c.rp_t.data_ptr<int>(), N, E, TCGNN_BLK_H, TCGNN_BLK_W, bp_t.data_ptr<int>(), bp_len,
                                           e2c_t.data_ptr<int>(), e2r_t.data_ptr<int>(), ws, need, &tc_blocks, current_stream(nodePointer)),
                   "tcgnn_preprocess_gpu_ws");
     }
-    tcgnn_check(tcgnn_plan_create(rp_t.data_ptr<int>(), col_t.data_ptr<int>(), bp_t.data_ptr<int>(), e2c_t.data_ptr<int>(), e2r_t.data_ptr<int>(),
+    tcgnn_check(tcgnn_plan_create(c.rp_t.data_ptr<int>(), c.col_t.data_ptr<int>(), bp_t.data_ptr<int>(), e2c_t.data_ptr<int>(), e2r_t.data_ptr<int>(),
                                   N, E, (int32_t)bp_len, current_stream(nodePointer), &t.own), "tcgnn_plan_create");
-    t.keep = {rp_t, col_t, bp_t, e2c_t, e2r_t};
+    t.keep = {c.rp_t, c.col_t, bp_t, e2c_t, e2r_t};
   }
-  t.perm = perm;
-  t.symmetric = sym != 0;
+  t.perm = c.perm;   // (the entry holds the tensors it uses: csr_cache() may drop its own reference first)
+  t.symmetric = c.symmetric;
   t.built = true;
   return t;
 }
@@ -337,39 +368,6 @@ void check_head_major(const torch::Tensor& t, const char* name, int64_t H, int64
               t.device() == like.device(), name, " must be a contiguous fp32 [heads, num_edges] tensor on the device of el");
 }
 
-// the transposed CSR edge_colsum sums over, one per (nodePointer, edgeList): tcgnn_transpose_ws at first sight, then cached
-struct TransposedCsr {
-  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
-  torch::Tensor nodePointer, edgeList, rp_t, perm;
-};
-std::list<TransposedCsr>& csr_cache() { static std::list<TransposedCsr> c; return c; }
-
-TransposedCsr& transposed_csr(const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
-  std::vector<std::tuple<const void*, int64_t, int64_t>> key;
-  for (auto* t : {&nodePointer, &edgeList}) key.emplace_back(t->data_ptr(), t->numel(), (int64_t)t->_version());
-  auto& cache = csr_cache();
-  for (auto it = cache.begin(); it != cache.end(); ++it)
-    if (it->key == key) { cache.splice(cache.begin(), cache, it); return cache.front(); }
-  const int32_t N = (int32_t)(nodePointer.numel() - 1);
-  const int64_t E = edgeList.numel();
-  auto opts = nodePointer.options().dtype(torch::kInt32);
-  TransposedCsr c;
-  c.key = key;
-  c.nodePointer = nodePointer;
-  c.edgeList = edgeList;
-  c.rp_t = torch::empty({(int64_t)N + 1}, opts);
-  c.perm = torch::empty({E}, opts);
-  torch::Tensor col_t = torch::empty({E}, opts);
-  size_t need = 0;
-  void* ws = nullptr;
-  tcgnn_check(tcgnn_transpose_workspace_bytes(N, E, &need), "tcgnn_transpose_workspace_bytes");
-  torch::Tensor buf = aligned_scratch(need, nodePointer, &ws);
-  tcgnn_check(tcgnn_transpose_ws(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, c.rp_t.data_ptr<int>(), col_t.data_ptr<int>(),
-                                 c.perm.data_ptr<int>(), ws, need, nullptr, current_stream(nodePointer)), "tcgnn_transpose_ws");
-  cache.push_front(std::move(c));
-  while (cache.size() > kPlanCacheSize) cache.pop_back();   // (tcgnn_transpose_ws synchronised; torch's allocator orders the reuse of the rest)
-  return cache.front();
-}
 }  // namespace
 
 torch::Tensor gat_softmax(torch::Tensor el, torch::Tensor er, torch::Tensor nodePointer, torch::Tensor edgeList, double negative_slope,

@@ -24,71 +24,79 @@ Differences from the reference that a caller can observe (all supersets, see DES
     forward_AGNN, a leaked stream per call, TCGNN_kernel.cu:245-255),
   * preprocess never writes past the end of blockPartition when num_nodes % blockSize_h == 0.
 """
-import collections
 import os
 import sys
 
 import torch
 
 import tcgnn_capi as _c
+from tcgnn_graph_cache import GraphCache, TransposedCsr, TransposedPlan, graph_key
 
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
-           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum"]
+           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum",
+           "cache_stats", "drop_scales"]
 
-_plan_cache_size = max(1, int(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8")))
-_plans = collections.OrderedDict()  # key -> (handle, tensors kept alive, device index)
-_retired = []                       # evicted plans waiting for the kernels that may still read them: (events, handle, tensors)
-_workspaces = {}                    # (device index, stream id) -> uint8 tensor
-_scales = {}                        # (nodePointer, edgeList) key -> (tensors kept alive, {norm: (row_scale, col_scale)}): degree_scales
-_transposed_csr = {}                # (nodePointer, edgeList) key -> (nodePointer, edgeList, nodePointer_t, edgeList_t, perm, symmetric): transpose_graph
-_transposed = {}                    # A's plan key -> dict(plan=, own=, meta=, perm=, symmetric=): what transpose=True calls run on, evicted with A's plan
-_values_t = {}                      # (device index, stream id) -> fp32 buffer: edge values in A^T's order (forward_AGNN(transpose=True))
-_softmax_scratch = {}               # (device index, stream id) -> uint8 buffer: the fp64 partials of edge_softmax_backward's d_beta
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _record_event(device, stream):
+    with torch.cuda.device(device):
+        e = torch.cuda.Event()
+        e.record(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device))
+    return e
+
+
+# Everything kept per graph (tcgnn_graph_cache.py): plans, their transposed parts, degree scales, transposed CSRs, retired plans and
+# the streams plan-using calls ran on.  Size: plans (packed tile streams, ~3x the CSR's bytes each) kept per process.
+_cache = GraphCache(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8"), _c.lib.tcgnn_plan_destroy, _record_event,
+                    lambda e: e.query(), lambda e: e.synchronize())
+
+# Buffers held per stream: (device index, stream id, kind) -> uint8 tensor.  kind -> (growth when it has to be replaced, alignment,
+# for which the allocation carries as many spare bytes; 0: the buffer is used from its first byte)
+_buffers = {}
+_KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
+          "values": (1, 0),           # fp32 [max(E, 1)]: A's edge values in A^T's order, forward_AGNN(transpose=True)
+          "softmax": (1, 256)}        # the fp64 partials of edge_softmax_backward's d_beta
+
+
+def _buffer(kind, need, device, stream=None):
+    """(aligned address, usable bytes) of the buffer of `kind` of the device's current stream, replaced by a larger one when it
+    holds fewer than `need` bytes.  need=None: only look - None when the stream has none yet."""
+    growth, align = _KINDS[kind]
+    key = (device.index, _stream(device) if stream is None else stream, kind)
+    buf = _buffers.get(key)
+    if need is not None and (buf is None or buf.numel() < need + align):
+        buf = _buffers[key] = torch.empty(int(need * growth) + align, dtype=torch.uint8, device=device)
+    if buf is None:
+        return None
+    off = (-buf.data_ptr()) % align if align else 0
+    return buf.data_ptr() + off, buf.numel() - off
 
 
 def set_plan_cache_size(n):
-    """Plans (packed tile streams, ~3x the CSR's bytes each) kept per process; the least recently used one beyond this is
-    retired.  A mini-batch loop over k graphs wants n >= k.  Also the environment variable TCGNN_PLAN_CACHE_SIZE."""
-    global _plan_cache_size
-    _plan_cache_size = max(1, int(n))
-    _evict()
+    """Plans kept per process; the least recently used one beyond this is retired.  A mini-batch loop over k graphs wants n >= k.
+    Also the environment variable TCGNN_PLAN_CACHE_SIZE."""
+    _cache.size = max(1, int(n))
+    _cache.trim()
 
 
-def _reap(block=False):
-    """Destroy retired plans whose last possible reader has finished (stream-ordered: an event per stream this module has
-    launched on for that device, recorded at eviction time; nothing is synchronised unless block=True)."""
-    keep = []
-    for events, handle, tensors in _retired:
-        if block:
-            for e in events:
-                e.synchronize()
-        if all(e.query() for e in events):
-            _c.lib.tcgnn_plan_destroy(handle)
-        else:
-            keep.append((events, handle, tensors))
-    _retired[:] = keep
+def clear_plan_cache():
+    if torch.cuda.is_available():
+        for d in _cache.devices():
+            torch.cuda.synchronize(d)
+    _cache.clear()
+    _buffers.clear()
 
 
-def _evict():
-    while len(_plans) > _plan_cache_size:
-        key, (old, keep, dev_index) = _plans.popitem(last=False)
-        _drop_scales()
-        tr = _transposed.pop(key, None)
-        _drop_transposed_csr()
-        events = []
-        for (d, stream_id) in list(_workspaces):
-            if d == dev_index:   # the streams this module has launched kernels on, on the EVICTED plan's device
-                with torch.cuda.device(d):
-                    e = torch.cuda.Event()
-                    e.record(torch.cuda.ExternalStream(stream_id, device=d) if stream_id else torch.cuda.default_stream(d))
-                    events.append(e)
-        _retired.append((events, old, keep))
-        if tr is not None and tr["own"] is not None:   # A^T's own plan (a graph that is not symmetric) leaves with A's
-            _retired.append((events, tr["own"], tr["meta"]))
-    if _retired:
-        _reap()
+def cache_stats():
+    """Not part of the reference API: counts of what the module holds - plans (plan entries), csrs (per-(nodePointer, edgeList)
+    entries: scales, transposed CSR), transposed (plan entries whose transpose=True part is built), retired (evicted plan handles
+    waiting for their events), buffers / buffer_bytes (the per-stream workspaces, value and softmax buffers)."""
+    return dict(_cache.stats(), buffers=len(_buffers), buffer_bytes=sum(b.numel() for b in _buffers.values()))
 
 
 # ---------------------------------------------------------------- argument checks (TCGNN.cpp:54-56)
@@ -112,32 +120,14 @@ def _check_float(t, name):
         raise RuntimeError("expected scalar type Float but found %s (%s)" % (str(t.dtype).replace("torch.", "").capitalize(), name))
 
 
-def _stream_handle(device):
-    return torch.cuda.current_stream(device).cuda_stream
+# ---------------------------------------------------------------- plans
 
-
-# ---------------------------------------------------------------- plan cache
-
-def _plan_key(tensors):
-    return tuple((t.data_ptr(), t.numel(), t._version) for t in tensors) + (tensors[0].device.index,)
-
-
-def _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
-    """The packed tile stream is a pure function of the five metadata tensors; it is built on the
-    device the first time they are seen and reused while they are unchanged (storage address,
-    length and in-place version counter).  The cache keeps the tensors alive, so an address can not
-    be recycled under a live entry."""
-    tensors = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    key = _plan_key(tensors)
-    hit = _plans.get(key)
-    if hit is not None:
-        _plans.move_to_end(key)
-        return hit[0]
-    dev = nodePointer.device
-    for t, n in zip(tensors, ("nodePointer", "edgeList", "blockPartition", "edgeToColumn", "edgeToRow")):
+def _create_plan(meta, dev, stream):
+    for t, n in zip(meta, ("nodePointer", "edgeList", "blockPartition", "edgeToColumn", "edgeToRow")):
         _check_int(t, n)
         if t.device != dev:
             raise RuntimeError("%s is on %s but nodePointer is on %s" % (n, t.device, dev))
+    nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow = meta
     N = nodePointer.numel() - 1
     E = edgeList.numel()
     if N < 0:
@@ -148,40 +138,33 @@ def _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
     with torch.cuda.device(dev):
         st = _c.lib.tcgnn_plan_create(nodePointer.data_ptr(), edgeList.data_ptr(), blockPartition.data_ptr(),
                                       edgeToColumn.data_ptr(), edgeToRow.data_ptr(), N, E, blockPartition.numel(),
-                                      _stream_handle(dev), _c.ctypes.byref(handle))
+                                      stream, _c.ctypes.byref(handle))
     _c.check(st, "tcgnn_plan_create")
-    _plans[key] = (handle, tensors, dev.index)
-    _evict()
     return handle
 
 
-def clear_plan_cache():
-    if torch.cuda.is_available():
-        for d in {v[2] for v in _plans.values()}:
-            torch.cuda.synchronize(d)
-    while _plans:
-        _, (old, _keep, _d) = _plans.popitem()
-        _c.lib.tcgnn_plan_destroy(old)
-    for tr in _transposed.values():
-        if tr["own"] is not None:
-            _c.lib.tcgnn_plan_destroy(tr["own"])
-    _transposed.clear()
-    _transposed_csr.clear()
-    _values_t.clear()
-    _softmax_scratch.clear()
-    _reap(block=True)
-    _workspaces.clear()
-    _scales.clear()
+def _plan_entry(meta, stream=None):
+    """The packed tile stream is a pure function of the five metadata tensors; it is built on the
+    device the first time they are seen and reused while they are unchanged (tcgnn_graph_cache.graph_key).
+    Every plan-using entry point comes through here, so this is where the stream it runs on is registered:
+    an evicted plan waits for an event on each of them."""
+    dev = meta[0].device
+    if stream is None:
+        stream = _stream(dev)
+    _cache.register_stream(dev.index, stream)
+    key = graph_key(meta)
+    e = _cache.plan(key)
+    if e is None:
+        e = _cache.add_plan(key, _create_plan(meta, dev, stream), meta, dev.index)
+    return e
+
+
+def _plan_of(meta, transpose=False, stream=None):
+    e = _plan_entry(meta, stream)
+    return _transposed_plan(e).plan if transpose else e.handle
 
 
 # ---------------------------------------------------------------- the transposed graph (A^T)
-
-def _drop_transposed_csr():
-    """Transposed CSRs of graphs no cached plan uses any more leave with their plans (as the scales do)."""
-    live = {k[:2] + (k[-1],) for k in _plans}
-    for k in [k for k in _transposed_csr if k not in live]:
-        del _transposed_csr[k]
-
 
 def _scratch(nbytes, dev):
     """(tensor kept alive, 256-byte aligned address, usable bytes) of torch-allocator scratch for one library call"""
@@ -189,21 +172,9 @@ def _scratch(nbytes, dev):
     return ws, ws.data_ptr() + (-ws.data_ptr()) % 256, int(nbytes)
 
 
-def _transpose_csr(nodePointer, edgeList):
-    """(nodePointer, edgeList, nodePointer_t, edgeList_t, perm, symmetric) - tcgnn_transpose_ws on torch-allocator scratch (one
-    synchronisation), cached per graph like degree_scales."""
-    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
-        _check_input(t, n)
-        _check_int(t, n)
-    if edgeList.device != nodePointer.device:
-        raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, nodePointer.device))
-    key = tuple((t.data_ptr(), t.numel(), t._version) for t in (nodePointer, edgeList)) + (nodePointer.device.index,)
-    hit = _transposed_csr.get(key)
-    if hit is not None:
-        return hit
+def _transpose(nodePointer, edgeList):
+    """TransposedCsr of a graph: tcgnn_transpose_ws on torch-allocator scratch (one synchronisation)"""
     N, E = nodePointer.numel() - 1, edgeList.numel()
-    if N < 0:
-        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
     dev = nodePointer.device
     with torch.cuda.device(dev):
         rp_t = torch.empty(N + 1, dtype=torch.int32, device=dev)
@@ -214,90 +185,78 @@ def _transpose_csr(nodePointer, edgeList):
         ws, ptr, nbytes = _scratch(need.value, dev)
         sym = _c._i32(0)
         st = _c.lib.tcgnn_transpose_ws(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(),
-                                       ptr, nbytes, _c.ctypes.byref(sym), _stream_handle(dev))
+                                       ptr, nbytes, _c.ctypes.byref(sym), _stream(dev))
         del ws   # (the call synchronised the stream: nothing still reads it)
     _c.check(st, "tcgnn_transpose_ws")
-    symmetric = bool(sym.value)
-    if symmetric:   # A^T = A: its arrays are A's own
-        rp_t, col_t = nodePointer, edgeList
-    entry = (nodePointer, edgeList, rp_t, col_t, perm, symmetric)
-    _transposed_csr[key] = entry
-    while len(_transposed_csr) > _plan_cache_size:   # (a graph never handed to the kernels has no plan to leave with)
-        _transposed_csr.pop(next(iter(_transposed_csr)))
-    return entry
+    if sym.value:   # A^T = A: its arrays are A's own
+        return TransposedCsr(nodePointer, edgeList, perm, True)
+    return TransposedCsr(rp_t, col_t, perm, False)
 
 
 def transpose_graph(nodePointer, edgeList):
     """Not in the reference module: the CSR of A^T on the device, (nodePointer_t, edgeList_t, perm, symmetric).  Row c of A^T lists
     the rows r of every entry (r, c) of A in increasing CSR position (sorted; A's duplicates kept); perm[eT] = the CSR position in A
     of A^T's entry eT; symmetric = A^T has exactly A's arrays (then nodePointer_t / edgeList_t ARE nodePointer / edgeList).  Column
-    ids must lie in [0, num_nodes).  Built on the GPU (tcgnn_transpose_ws) and cached beside the graph's plan: the transpose=True
-    calls use the same entry."""
-    return _transpose_csr(nodePointer, edgeList)[2:]
+    ids must lie in [0, num_nodes).  Built on the GPU (tcgnn_transpose_ws) and cached in the graph's CSR entry: the transpose=True
+    calls and edge_colsum use the same one."""
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    if edgeList.device != nodePointer.device:
+        raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, nodePointer.device))
+    if nodePointer.numel() < 1:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    c = _cache.csr((nodePointer, edgeList))
+    if c.transposed is None:
+        c.transposed = _transpose(nodePointer, edgeList)
+    return c.transposed
 
 
-def _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
-    """What transpose=True calls run on, built at first use and kept beside A's plan (and evicted with it): dict(plan = the plan of
-    A^T - A's own when the graph is symmetric -, own = that plan when it is A^T's own else None, meta = A^T's five metadata tensors,
-    perm, symmetric).  A^T's metadata: the transpose, the device SGT on torch-allocator scratch, tcgnn_plan_create."""
-    tensors = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    plan = _plan_for(*tensors)
-    key = _plan_key(tensors)
-    hit = _transposed.get(key)
-    if hit is not None:
-        return hit
-    _, _, rp_t, col_t, perm, symmetric = _transpose_csr(nodePointer, edgeList)
+def _transposed_plan(e):
+    """What transpose=True calls run on, built at first use and owned by A's plan entry (it leaves with it): the plan of A^T - A's
+    own when the graph is symmetric.  A^T's metadata: the transpose (the CSR entry's), the device SGT on torch-allocator scratch,
+    tcgnn_plan_create."""
+    if e.transposed is not None:
+        return e.transposed
+    c = e.csr
+    if c.transposed is None:
+        c.transposed = _transpose(*e.tensors[:2])
+    rp_t, col_t, _, symmetric = c.transposed
     if symmetric:
-        entry = dict(plan=plan, own=None, meta=tensors, perm=perm, symmetric=True)
-    else:
-        dev = nodePointer.device
-        N, E, bp_len = nodePointer.numel() - 1, edgeList.numel(), blockPartition.numel()
-        with torch.cuda.device(dev):
-            bp_t = torch.zeros(bp_len, dtype=torch.int32, device=dev)
-            e2c_t = torch.empty(E, dtype=torch.int32, device=dev)
-            e2r_t = torch.empty(E, dtype=torch.int32, device=dev)
-            need = _c._sz(0)
-            _c.check(_c.lib.tcgnn_preprocess_gpu_workspace_bytes(N, E, 16, _c.ctypes.byref(need)), "tcgnn_preprocess_gpu_workspace_bytes")
-            ws, ptr, nbytes = _scratch(need.value, dev)
-            tc = _c._i64(0)
-            st = _c.lib.tcgnn_preprocess_gpu_ws(col_t.data_ptr(), rp_t.data_ptr(), N, E, 16, 8, bp_t.data_ptr(), bp_len, e2c_t.data_ptr(),
-                                                e2r_t.data_ptr(), ptr, nbytes, _c.ctypes.byref(tc), _stream_handle(dev))
-            del ws
-            _c.check(st, "tcgnn_preprocess_gpu_ws")
-            handle = _c._vp()
-            _c.check(_c.lib.tcgnn_plan_create(rp_t.data_ptr(), col_t.data_ptr(), bp_t.data_ptr(), e2c_t.data_ptr(), e2r_t.data_ptr(), N, E, bp_len,
-                                              _stream_handle(dev), _c.ctypes.byref(handle)), "tcgnn_plan_create")
-        entry = dict(plan=handle, own=handle, meta=(rp_t, col_t, bp_t, e2c_t, e2r_t), perm=perm, symmetric=False)
-    _transposed[key] = entry
-    return entry
-
-
-def _plan_of(meta, transpose):
-    return _transposed_for(*meta)["plan"] if transpose else _plan_for(*meta)
-
-
-def _values_buffer(E, device):
-    """fp32 [max(E, 1)] per (device, stream), like the workspace: A's edge values in A^T's order for forward_AGNN(transpose=True)"""
-    key = (device.index, _stream_handle(device))
-    buf = _values_t.get(key)
-    if buf is None or buf.numel() < max(E, 1):
-        buf = torch.empty(max(E, 1), dtype=torch.float32, device=device)
-        _values_t[key] = buf
-    return buf
+        e.transposed = TransposedPlan(e.handle, None, e.tensors)
+        return e.transposed
+    dev = rp_t.device
+    N, E, bp_len = rp_t.numel() - 1, col_t.numel(), e.tensors[2].numel()
+    with torch.cuda.device(dev):
+        bp_t = torch.zeros(bp_len, dtype=torch.int32, device=dev)
+        e2c_t = torch.empty(E, dtype=torch.int32, device=dev)
+        e2r_t = torch.empty(E, dtype=torch.int32, device=dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_preprocess_gpu_workspace_bytes(N, E, 16, _c.ctypes.byref(need)), "tcgnn_preprocess_gpu_workspace_bytes")
+        ws, ptr, nbytes = _scratch(need.value, dev)
+        tc = _c._i64(0)
+        st = _c.lib.tcgnn_preprocess_gpu_ws(col_t.data_ptr(), rp_t.data_ptr(), N, E, 16, 8, bp_t.data_ptr(), bp_len, e2c_t.data_ptr(),
+                                            e2r_t.data_ptr(), ptr, nbytes, _c.ctypes.byref(tc), _stream(dev))
+        del ws
+    _c.check(st, "tcgnn_preprocess_gpu_ws")
+    meta_t = (rp_t, col_t, bp_t, e2c_t, e2r_t)
+    handle = _create_plan(meta_t, dev, _stream(dev))
+    e.transposed = TransposedPlan(handle, handle, meta_t)
+    return e.transposed
 
 
 def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, transpose=False):
     """Not part of the reference API: statistics of the packed tile stream (dict).  transpose=True: of the plan transpose=True calls
     run on (A's own on a symmetric graph), plus symmetric, shares_plan (no plan of A^T's own) and transpose_bytes (the arrays the
     transposed entry owns: perm, and A^T's five metadata tensors unless the graph is symmetric)."""
-    meta = (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     info = _c.PlanInfo()
-    _c.check(_c.lib.tcgnn_plan_get_info(_plan_of(meta, transpose), _c.ctypes.byref(info)), "tcgnn_plan_get_info")
+    _c.check(_c.lib.tcgnn_plan_get_info(_transposed_plan(e).plan if transpose else e.handle, _c.ctypes.byref(info)), "tcgnn_plan_get_info")
     out = {f: getattr(info, f) for f, _ in info._fields_}
     if transpose:
-        tr = _transposed_for(*meta)
-        owned = [tr["perm"]] + ([] if tr["symmetric"] else list(tr["meta"]))
-        out.update(symmetric=tr["symmetric"], shares_plan=tr["own"] is None, transpose_bytes=sum(t.numel() * t.element_size() for t in owned))
+        csr_t = e.csr.transposed
+        owned = [csr_t.perm] + ([] if csr_t.symmetric else list(e.transposed.meta))
+        out.update(symmetric=csr_t.symmetric, shares_plan=e.transposed.own is None, transpose_bytes=sum(t.numel() * t.element_size() for t in owned))
     return out
 
 
@@ -316,33 +275,33 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True and attention=True: the
     edge-valued streams of A and A^T at that width, the two-image SDDMM workspace, and - with A^T's plan - the transposed CSR
     edge_colsum sums over."""
-    plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    plans = [plan]
+    e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
+    plans = [e.handle]
     dev = nodePointer.device
-    if attention:
-        with torch.cuda.device(dev):
-            for d in sorted({int(w) for w in widths if int(w) >= 1}):
-                _workspace(plan, d, dev, need=_c.lib.tcgnn_sddmm2_workspace_bytes(plan, d))
-            _softmax_scratch_for(nodePointer.numel() - 1, edgeList.numel(), dev)
-    if transpose:
-        tr = _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        if tr["own"] is not None:
-            plans.append(tr["own"])
-        if edge_valued:
-            with torch.cuda.device(dev):
-                _values_buffer(edgeList.numel(), dev)
+    widths = sorted({int(w) for w in widths if int(w) >= 1})
     with torch.cuda.device(dev):
-        for d in sorted({int(w) for w in widths if int(w) >= 1}):
+        stream = _stream(dev)
+        if attention:
+            for d in widths:
+                _buffer("workspace", _c.lib.tcgnn_sddmm2_workspace_bytes(e.handle, d), dev, stream)
+            _buffer("softmax", _c.lib.tcgnn_edge_softmax_workspace_bytes(max(nodePointer.numel() - 1, 0), edgeList.numel()), dev, stream)
+        if transpose:
+            own = _transposed_plan(e).own
+            if own is not None:
+                plans.append(own)
+            if edge_valued:
+                _buffer("values", 4 * max(edgeList.numel(), 1), dev, stream)
+        for d in widths:
             for p in plans:
-                _c.check(_c.lib.tcgnn_plan_prepare(p, d, _stream_handle(dev)), "tcgnn_plan_prepare")
+                _c.check(_c.lib.tcgnn_plan_prepare(p, d, stream), "tcgnn_plan_prepare")
                 if edge_valued:
-                    _c.check(_c.lib.tcgnn_plan_prepare_val(p, d, _stream_handle(dev)), "tcgnn_plan_prepare_val")
+                    _c.check(_c.lib.tcgnn_plan_prepare_val(p, d, stream), "tcgnn_plan_prepare_val")
 
 
 def set_plan_modes(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, spmm_mode=None, range_guard=None):
     """Not part of the reference API: the walk (tcgnn_plan_set_spmm_mode) and the range-guard level (tcgnn_plan_set_range_guard) of
     THIS graph's plan only; -1 hands a setting back to the process-wide value.  Two graphs of one process may differ."""
-    plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     if spmm_mode is not None:
         _c.check(_c.lib.tcgnn_plan_set_spmm_mode(plan, int(spmm_mode)), "tcgnn_plan_set_spmm_mode")
     if range_guard is not None:
@@ -354,12 +313,11 @@ def range_mode(device=None):
     (wide_x, wide_val): 1 = the fp32 fallback ran (a matrix with a wide dynamic range, include/tcgnn.h "Operand range"), 0 = the
     MFMA path.  Reads the workspace header back (synchronises the stream): a test / diagnosis aid."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    ws = _workspaces.get((dev.index, _stream_handle(dev)))
+    ws = _buffer("workspace", None, dev)
     if ws is None:
         return (0, 0)
-    off = (-ws.data_ptr()) % 256
     a, b = _c._i32(0), _c._i32(0)
-    _c.check(_c.lib.tcgnn_range_mode(ws.data_ptr() + off, _stream_handle(dev), _c.ctypes.byref(a), _c.ctypes.byref(b)), "tcgnn_range_mode")
+    _c.check(_c.lib.tcgnn_range_mode(ws[0], _stream(dev), _c.ctypes.byref(a), _c.ctypes.byref(b)), "tcgnn_range_mode")
     return (a.value, b.value)
 
 
@@ -374,7 +332,7 @@ def kernel_timing(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow
     """Not part of the reference API.  kernel_timing(meta..., max_calls=K) arms HIP-event timing of
     the main kernel for the next K calls on this graph; kernel_timing(meta...) (no max_calls) waits
     for them and returns their durations in ms."""
-    plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     if max_calls is not None:
         _c.check(_c.lib.tcgnn_plan_set_timing(plan, int(max_calls)), "tcgnn_plan_set_timing")
         return None
@@ -390,16 +348,25 @@ def last_kernel(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, 
     return _c.lib.tcgnn_plan_last_kernel(_plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)).decode()
 
 
-def _workspace(plan, D, device, need=None):
-    if need is None:
-        need = _c.lib.tcgnn_workspace_bytes(plan, D)
-    key = (device.index, _stream_handle(device))
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need + 256:
-        ws = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=device)
-        _workspaces[key] = ws
-    off = (-ws.data_ptr()) % 256
-    return ws.data_ptr() + off, ws.numel() - off
+def _run(fn, meta, dev, D, operands, transpose=False, need=_c.lib.tcgnn_workspace_bytes, allow=()):
+    """The one path of a plan-based call, on dev and its current stream: fn(plan of the graph - with transpose, the one of A^T -,
+    *operands, the stream's workspace and its bytes, stream).  need(plan, D): the library's size of that workspace.  A status in
+    `allow` is returned, any other but 0 raises."""
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        plan = _plan_of(meta, transpose, stream)
+        ws, ws_bytes = _buffer("workspace", need(plan, D), dev, stream)
+        st = fn(plan, *operands, ws, ws_bytes, stream)
+    if st not in allow:
+        _c.check(st, fn.__name__)
+    return st
+
+
+def _call(fn, dev, *args):
+    """A library call that takes no plan, on dev and its current stream (fn's last argument), status checked"""
+    with torch.cuda.device(dev):
+        st = fn(*args, _stream(dev))
+    _c.check(st, fn.__name__)
 
 
 # ---------------------------------------------------------------- sparse-graph translation
@@ -459,7 +426,7 @@ def preprocess_gpu(edgeList, nodePointer, num_nodes, blockSize_h, blockSize_w, b
         ws = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=dev)
         st = _c.lib.tcgnn_preprocess_gpu_ws(edgeList.data_ptr(), nodePointer.data_ptr(), num_nodes, E, int(blockSize_h),
                                             int(blockSize_w), blockPartition.data_ptr(), blockPartition.numel(),
-                                            edgeToColumn.data_ptr(), edgeToRow.data_ptr(), ws.data_ptr(), ws.numel(), _c.ctypes.byref(n), _stream_handle(dev))
+                                            edgeToColumn.data_ptr(), edgeToRow.data_ptr(), ws.data_ptr(), ws.numel(), _c.ctypes.byref(n), _stream(dev))
         del ws   # (the call synchronised the stream: nothing still reads it)
     _c.check(st, "tcgnn_preprocess_gpu_ws")
     _report(n.value)
@@ -482,23 +449,29 @@ def _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
         raise RuntimeError("input has %d rows but nodePointer describes %d nodes" % (input.size(0), N))
     if input.device != nodePointer.device:
         raise RuntimeError("input and nodePointer are on different devices")
+    return (nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+
+
+def _check_like(t, name, other, other_name):
+    _check_input(t, name)
+    _check_float(t, name)
+    if t.shape != other.shape or t.device != other.device:
+        raise RuntimeError("%s must have the shape and device of %s" % (name, other_name))
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 def forward(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, transpose=False):
     """SpMM  Y = A_bin @ input  (GCN / GIN / SAG aggregation, forward and backward).
     transpose=True (not in the reference module): Y = A_bin^T @ input - the metadata still describe A; A^T's plan is built at
     first use and cached beside A's (A's own plan when the graph is symmetric)."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    dev = input.device
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     N, D = input.shape
     out = torch.empty_like(input)
-    if N == 0 or D == 0:
-        return [out]
-    with torch.cuda.device(dev):
-        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm(plan, input.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_spmm")
+    if N and D:
+        _run(_c.lib.tcgnn_spmm, meta, input.device, D, (input.data_ptr(), out.data_ptr(), D), transpose)
     return [out]
 
 
@@ -507,33 +480,14 @@ def forward_fused(input, nodePointer, edgeList, blockPartition, edgeToColumn, ed
     relu=True: max(A @ input, 0) - the ReLU the reference applies after the layer (main_tcgnn.py:100-139) runs in the
     kernel's stores.  gate (same shape as input): A @ (input * (gate > 0)) - with gate = the forward output, the ReLU
     backward mask is applied to dY while it is staged.  Bit-identical to the unfused compositions.  transpose=True: with A^T."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     if gate is not None:
-        _check_input(gate, "gate")
-        _check_float(gate, "gate")
-        if gate.shape != input.shape or gate.device != input.device:
-            raise RuntimeError("gate must have the shape and device of input")
-    dev = input.device
+        _check_like(gate, "gate", input, "input")
     N, D = input.shape
     out = torch.empty_like(input)
-    if N == 0 or D == 0:
-        return [out]
-    with torch.cuda.device(dev):
-        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm_fused(plan, input.data_ptr(), gate.data_ptr() if gate is not None else None, out.data_ptr(), D,
-                                     1 if relu else 0, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_spmm_fused")
+    if N and D:
+        _run(_c.lib.tcgnn_spmm_fused, meta, input.device, D, (input.data_ptr(), _ptr(gate), out.data_ptr(), D, 1 if relu else 0), transpose)
     return [out]
-
-
-def _check_vector(t, name, n, dev):
-    _check_input(t, name)
-    _check_float(t, name)
-    if t.dim() != 1 or t.numel() != n:
-        raise RuntimeError("%s must be a 1-D tensor of %d elements, got shape %s" % (name, n, tuple(t.shape)))
-    if t.device != dev:
-        raise RuntimeError("%s is on %s but input is on %s" % (name, t.device, dev))
 
 
 def forward_scaled(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, row_scale=None, col_scale=None,
@@ -545,51 +499,34 @@ def forward_scaled(input, nodePointer, edgeList, blockPartition, edgeToColumn, e
     composition forward(col_scale * X') * row_scale + bias, then ReLU, on every walk.  degree_scales gives DGL's scales.
     transpose=True: A^T in place of A, act(row_scale * (A^T @ (col_scale * X')) + bias) - the backward aggregation of the normalised
     layer on a directed graph."""
-    # shapes and dtypes of the optional operands first (they do not depend on the device), then the six of forward
+    vectors = [v for v in ((row_scale, "row_scale", 0), (col_scale, "col_scale", 0), (bias, "bias", 1)) if v[0] is not None]
+    # type, dtype and shape of the optional vectors first (they do not depend on the device), then the six of forward, then where
+    # the vectors live (an input that is no 2-D tensor fails in the six)
     if isinstance(input, torch.Tensor) and input.dim() == 2:
-        for t, name, n in ((row_scale, "row_scale", input.size(0)), (col_scale, "col_scale", input.size(0)), (bias, "bias", input.size(1))):
-            if t is None:
-                continue
+        for t, name, axis in vectors:
+            n = input.size(axis)
             if not isinstance(t, torch.Tensor):
                 raise TypeError("%s must be a torch.Tensor" % name)
             _check_float(t, name)
             if t.dim() != 1 or t.numel() != n:
                 raise RuntimeError("%s must be a 1-D tensor of %d elements, got shape %s" % (name, n, tuple(t.shape)))
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     dev = input.device
-    N, D = input.shape
     if gate is not None:
-        _check_input(gate, "gate")
-        _check_float(gate, "gate")
-        if gate.shape != input.shape or gate.device != dev:
-            raise RuntimeError("gate must have the shape and device of input")
-    if row_scale is not None:
-        _check_vector(row_scale, "row_scale", N, dev)
-    if col_scale is not None:
-        _check_vector(col_scale, "col_scale", N, dev)
-    if bias is not None:
-        _check_vector(bias, "bias", D, dev)
+        _check_like(gate, "gate", input, "input")
+    for t, name, _ in vectors:
+        _check_input(t, name)
+        if t.device != dev:
+            raise RuntimeError("%s is on %s but input is on %s" % (name, t.device, dev))
+    N, D = input.shape
     out = torch.empty_like(input)
-    if N == 0 or D == 0:
-        return [out]
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-    with torch.cuda.device(dev):
-        plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow), transpose)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm_scaled(plan, input.data_ptr(), ptr(col_scale), ptr(gate), ptr(row_scale), ptr(bias), out.data_ptr(), D,
-                                      1 if relu else 0, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_spmm_scaled")
+    if N and D:
+        _run(_c.lib.tcgnn_spmm_scaled, meta, dev, D, (input.data_ptr(), _ptr(col_scale), _ptr(gate), _ptr(row_scale), _ptr(bias), out.data_ptr(), D,
+                                                      1 if relu else 0), transpose)
     return [out]
 
 
 NORMS = ("none", "both", "right", "left")
-
-
-def _drop_scales():
-    """Scales of graphs no cached plan uses any more leave with their plans."""
-    live = {k[:2] + (k[-1],) for k in _plans}
-    for k in [k for k in _scales if k not in live]:
-        del _scales[k]
 
 
 def degree_scales(nodePointer, edgeList, norm):
@@ -597,8 +534,8 @@ def degree_scales(nodePointer, edgeList, norm):
     in_deg = row length, out_deg = column count, both clamped to >= 1:
         'both'  -> (in_deg^-1/2, out_deg^-1/2)    'right' -> (1 / in_deg, None)
         'left'  -> (None, 1 / out_deg)             'none'  -> (None, None)
-    fp32 [N] tensors on the graph's device (CPU tensors work too).  For a graph on the GPU the result is cached beside its plan
-    and leaves with it: repeated layer calls neither recompute nor allocate (which a call captured into a HIP graph needs)."""
+    fp32 [N] tensors on the graph's device (CPU tensors work too).  For a graph on the GPU the result is cached in the graph's CSR
+    entry and leaves with it: repeated layer calls neither recompute nor allocate (which a call captured into a HIP graph needs)."""
     if norm not in NORMS:
         raise ValueError("norm must be one of %s, got %r" % (", ".join(NORMS), norm))
     if norm == "none":
@@ -609,12 +546,9 @@ def degree_scales(nodePointer, edgeList, norm):
         _check_int(t, n)
     if edgeList.device != nodePointer.device:
         raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, nodePointer.device))
-    key = None
-    if nodePointer.is_cuda:
-        key = tuple((t.data_ptr(), t.numel(), t._version) for t in (nodePointer, edgeList)) + (nodePointer.device.index,)
-        hit = _scales.get(key)
-        if hit is not None and norm in hit[1]:
-            return hit[1][norm]
+    scales = _cache.csr((nodePointer, edgeList)).scales if nodePointer.is_cuda else {}
+    if norm in scales:
+        return scales[norm]
     N = nodePointer.numel() - 1
     rp = nodePointer.to(torch.int64)
     in_deg = (rp[1:] - rp[:-1]).clamp(min=1).to(torch.float32)
@@ -630,14 +564,13 @@ def degree_scales(nodePointer, edgeList, norm):
         res = (in_deg.reciprocal(), None)
     else:
         res = (None, out_deg.reciprocal())
-    res = tuple(t.contiguous() if t is not None else None for t in res)
-    if key is not None:
-        if key not in _scales:
-            _scales[key] = ((nodePointer, edgeList), {})
-        _scales[key][1][norm] = res
-        while len(_scales) > _plan_cache_size:   # (a graph never handed to the kernels has no plan to leave with)
-            _scales.pop(next(iter(_scales)))
+    scales[norm] = res = tuple(t.contiguous() if t is not None else None for t in res)
     return res
+
+
+def drop_scales(nodePointer, edgeList):
+    """Not in the reference module: forget the cached degree scales of one graph (the next degree_scales call computes them again)."""
+    _cache.csr((nodePointer, edgeList)).scales.clear()
 
 
 GEMM_FUSED_MAX_DIM = 128
@@ -649,7 +582,7 @@ def forward_gemm(input, weights, nodePointer, edgeList, blockPartition, edgeToCo
     aggregated rows go from the accumulators through LDS into the fp32 matrix pipe against W.  input [N, D_in], weights
     [D_in, D_out], both <= 128 wide.  relu=True fuses max(., 0) where the kernel writes the product in one pass; where it
     accumulates over column passes (the LDS-resident kernel on a 64-column input) the ReLU runs as a separate step here."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     _check_input(weights, "weights")
     _check_float(weights, "weights")
     N, D = input.shape
@@ -660,18 +593,12 @@ def forward_gemm(input, weights, nodePointer, edgeList, blockPartition, edgeToCo
         raise RuntimeError("forward_gemm covers 1 <= D_in, D_out <= %d (got %d -> %d): compose forward() with torch.mm" % (GEMM_FUSED_MAX_DIM, D, Dout))
     dev = input.device
     out = torch.empty(N, Dout, dtype=torch.float32, device=dev)
-    if N == 0:
-        return [out]
-    with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm_gemm(plan, input.data_ptr(), weights.data_ptr(), out.data_ptr(), D, Dout, 1 if relu else 0, ws, ws_bytes,
-                                    _stream_handle(dev))
-        if st == 6 and relu:   # TCGNN_ERR_UNSUPPORTED: the product is accumulated over column passes - ReLU as its own step
-            st = _c.lib.tcgnn_spmm_gemm(plan, input.data_ptr(), weights.data_ptr(), out.data_ptr(), D, Dout, 0, ws, ws_bytes, _stream_handle(dev))
-            _c.check(st, "tcgnn_spmm_gemm")
-            return [torch.relu_(out)]
-    _c.check(st, "tcgnn_spmm_gemm")
+    if N:
+        operands = (input.data_ptr(), weights.data_ptr(), out.data_ptr(), D, Dout)
+        # TCGNN_ERR_UNSUPPORTED (6) with relu: the product is accumulated over column passes - ReLU as its own step
+        if _run(_c.lib.tcgnn_spmm_gemm, meta, dev, D, operands + (1 if relu else 0,), allow=(6,) if relu else ()) == 6:
+            _run(_c.lib.tcgnn_spmm_gemm, meta, dev, D, operands + (0,))
+            torch.relu_(out)
     return [out]
 
 
@@ -679,7 +606,7 @@ def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, ed
     """SpMM with edge values  Y = A_val @ input,  A_val[row(e), col(e)] = edgeAttention[0, e].
     transpose=True (not in the reference module): Y = A_val^T @ input, edgeAttention still in A's CSR order (row 0): the values are
     permuted into A^T's order (tcgnn_permute_edge_values, into a buffer held per stream) and A^T's plan aggregates them."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     _check_input(edgeAttention, "edgeAttention")
     _check_float(edgeAttention, "edgeAttention")
     dev = input.device
@@ -690,40 +617,26 @@ def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, ed
     if edgeAttention.numel() < E:
         raise RuntimeError("edgeAttention holds %d values for %d edges" % (edgeAttention.numel(), E))
     out = torch.empty_like(input)
-    if N == 0 or D == 0:
-        return [out]
-    with torch.cuda.device(dev):
+    if N and D:
         val = edgeAttention.data_ptr()
         if transpose:
-            tr = _transposed_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-            plan, buf = tr["plan"], _values_buffer(E, dev)
-            _c.check(_c.lib.tcgnn_permute_edge_values(val, tr["perm"].data_ptr(), E, buf.data_ptr(), _stream_handle(dev)), "tcgnn_permute_edge_values")
-            val = buf.data_ptr()
-        else:
-            plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_spmm_val(plan, input.data_ptr(), val, out.data_ptr(), D, ws, ws_bytes,
-                                   _stream_handle(dev))
-    _c.check(st, "tcgnn_spmm_val")
+            e = _plan_entry(meta)
+            _transposed_plan(e)
+            val = _buffer("values", 4 * max(E, 1), dev)[0]
+            _call(_c.lib.tcgnn_permute_edge_values, dev, edgeAttention.data_ptr(), e.csr.transposed.perm.data_ptr(), E, val)
+        _run(_c.lib.tcgnn_spmm_val, meta, dev, D, (input.data_ptr(), val, out.data_ptr(), D), transpose)
     return [out]
 
 
 def forward_ef(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
     """SDDMM  ef[e] = <input[row(e)], input[col(e)]>  for every CSR edge, fp32 [E]."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    dev = input.device
-    N, D = input.shape
-    E = edgeList.numel()
-    out = torch.empty(E, dtype=torch.float32, device=dev)
-    if E == 0:
-        return [out]
-    if D == 0:
-        return [out.zero_()]
-    with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_sddmm(plan, input.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_sddmm")
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    D = input.size(1)
+    out = torch.empty(edgeList.numel(), dtype=torch.float32, device=input.device)
+    if out.numel() and D:
+        _run(_c.lib.tcgnn_sddmm, meta, input.device, D, (input.data_ptr(), out.data_ptr(), D))
+    elif out.numel():
+        out.zero_()
     return [out]
 
 
@@ -734,24 +647,14 @@ def forward_ef2(X, Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeT
     gradient of forward_AGNN with respect to its edge values is forward_ef2(dY, input).  Same walks as forward_ef; each operand is
     rounded with its own scale; forward_ef2(X, X) equals forward_ef(X) bit for bit (unless the range guard takes X for wide: the
     single-operand call then patches the dirty rows' edges, this one recomputes the whole call in fp32 - include/tcgnn.h)."""
-    _six(X, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    _check_input(Z, "Z")
-    _check_float(Z, "Z")
-    if Z.shape != X.shape or Z.device != X.device:
-        raise RuntimeError("Z must have the shape and device of X")
-    dev = X.device
-    N, D = X.shape
-    E = edgeList.numel()
-    out = torch.empty(E, dtype=torch.float32, device=dev)
-    if E == 0:
-        return [out]
-    if D == 0:
-        return [out.zero_()]
-    with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev, need=_c.lib.tcgnn_sddmm2_workspace_bytes(plan, D))
-        st = _c.lib.tcgnn_sddmm2(plan, X.data_ptr(), Z.data_ptr(), out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_sddmm2")
+    meta = _six(X, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    _check_like(Z, "Z", X, "X")
+    D = X.size(1)
+    out = torch.empty(edgeList.numel(), dtype=torch.float32, device=X.device)
+    if out.numel() and D:
+        _run(_c.lib.tcgnn_sddmm2, meta, X.device, D, (X.data_ptr(), Z.data_ptr(), out.data_ptr(), D), need=_c.lib.tcgnn_sddmm2_workspace_bytes)
+    elif out.numel():
+        out.zero_()
     return [out]
 
 
@@ -771,15 +674,12 @@ def _softmax_args(score, nodePointer, beta):
             raise RuntimeError("beta must hold one value on score's device")
 
 
-def _softmax_scratch_for(N, E, device):
-    need = int(_c.lib.tcgnn_edge_softmax_workspace_bytes(max(N, 0), E))
-    key = (device.index, _stream_handle(device))
-    buf = _softmax_scratch.get(key)
-    if buf is None or buf.numel() < need + 256:
-        buf = torch.empty(need + 256, dtype=torch.uint8, device=device)
-        _softmax_scratch[key] = buf
-    off = (-buf.data_ptr()) % 256
-    return buf.data_ptr() + off, buf.numel() - off
+def _out_like(out, t, name):
+    if out is None:
+        return torch.empty_like(t)
+    if out.shape != t.shape or out.dtype != torch.float32 or out.device != t.device or not out.is_contiguous():
+        raise RuntimeError("out must be a contiguous fp32 tensor of %s's shape on its device" % name)
+    return out
 
 
 def edge_softmax(score, nodePointer, beta=None, out=None):
@@ -788,15 +688,9 @@ def edge_softmax(score, nodePointer, beta=None, out=None):
     score: fp32 [E]; beta: a one-element fp32 tensor on the device (None: 1).  out may be score itself (in place).  Entries of
     positions no row covers are left as allocated.  Deterministic: a second call returns the same bits."""
     _softmax_args(score, nodePointer, beta)
-    if out is None:
-        out = torch.empty_like(score)
-    elif out.shape != score.shape or out.dtype != torch.float32 or out.device != score.device or not out.is_contiguous():
-        raise RuntimeError("out must be a contiguous fp32 tensor of score's shape on its device")
-    dev = score.device
-    with torch.cuda.device(dev):
-        st = _c.lib.tcgnn_edge_softmax(nodePointer.data_ptr(), nodePointer.numel() - 1, score.numel(), score.data_ptr(),
-                                       beta.data_ptr() if beta is not None else None, out.data_ptr(), _stream_handle(dev))
-    _c.check(st, "tcgnn_edge_softmax")
+    out = _out_like(out, score, "score")
+    _call(_c.lib.tcgnn_edge_softmax, score.device, nodePointer.data_ptr(), nodePointer.numel() - 1, score.numel(), score.data_ptr(), _ptr(beta),
+          out.data_ptr())
     return out
 
 
@@ -816,20 +710,13 @@ def edge_softmax_backward(p, dp, nodePointer, beta=None, score=None, need_dbeta=
         _check_float(score, "score")
         if score.shape != p.shape or score.device != p.device:
             raise RuntimeError("score must have the shape and device of p")
-    if out is None:
-        out = torch.empty_like(dp)
-    elif out.shape != dp.shape or out.dtype != torch.float32 or out.device != dp.device or not out.is_contiguous():
-        raise RuntimeError("out must be a contiguous fp32 tensor of dp's shape on its device")
+    out = _out_like(out, dp, "dp")
     dev = p.device
     N, E = nodePointer.numel() - 1, p.numel()
     dbeta = torch.empty(1, dtype=torch.float32, device=dev) if need_dbeta else None
-    with torch.cuda.device(dev):
-        scratch, scratch_bytes = _softmax_scratch_for(N, E, dev) if need_dbeta else (None, 0)
-        st = _c.lib.tcgnn_edge_softmax_backward(nodePointer.data_ptr(), N, E, p.data_ptr(), dp.data_ptr(),
-                                                score.data_ptr() if need_dbeta else None, beta.data_ptr() if beta is not None else None,
-                                                out.data_ptr(), dbeta.data_ptr() if need_dbeta else None, scratch, scratch_bytes,
-                                                _stream_handle(dev))
-    _c.check(st, "tcgnn_edge_softmax_backward")
+    scratch = _buffer("softmax", _c.lib.tcgnn_edge_softmax_workspace_bytes(max(N, 0), E), dev) if need_dbeta else (None, 0)
+    _call(_c.lib.tcgnn_edge_softmax_backward, dev, nodePointer.data_ptr(), N, E, p.data_ptr(), dp.data_ptr(), _ptr(score if need_dbeta else None),
+          _ptr(beta), out.data_ptr(), _ptr(dbeta), *scratch)
     return out, dbeta
 
 
@@ -870,11 +757,8 @@ def gat_softmax(el, er, nodePointer, edgeList, negative_slope=0.2, out=None):
         out = torch.empty(H, E, dtype=torch.float32, device=el.device)
     else:
         _head_major(out, "out", H, E, el)
-    dev = el.device
-    with torch.cuda.device(dev):
-        st = _c.lib.tcgnn_gat_softmax(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(), float(negative_slope),
-                                      out.data_ptr(), _stream_handle(dev))
-    _c.check(st, "tcgnn_gat_softmax")
+    _call(_c.lib.tcgnn_gat_softmax, el.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(), float(negative_slope),
+          out.data_ptr())
     return out
 
 
@@ -889,12 +773,9 @@ def gat_softmax_backward(p, dp, el, er, nodePointer, edgeList, negative_slope=0.
         out = torch.empty_like(dp)
     else:
         _head_major(out, "out", H, E, el)
-    dev = el.device
-    d_er = torch.empty(N, H, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _c.lib.tcgnn_gat_softmax_backward(nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(), float(negative_slope),
-                                               p.data_ptr(), dp.data_ptr(), out.data_ptr(), d_er.data_ptr(), _stream_handle(dev))
-    _c.check(st, "tcgnn_gat_softmax_backward")
+    d_er = torch.empty(N, H, dtype=torch.float32, device=el.device)
+    _call(_c.lib.tcgnn_gat_softmax_backward, el.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, el.data_ptr(), er.data_ptr(),
+          float(negative_slope), p.data_ptr(), dp.data_ptr(), out.data_ptr(), d_er.data_ptr())
     return out, d_er
 
 
@@ -907,15 +788,12 @@ def edge_colsum(val, nodePointer, edgeList):
     E = edgeList.numel()
     if val.dim() != 2 or val.size(0) < 1 or val.size(1) != E:
         raise RuntimeError("val must be [heads, num_edges] (heads >= 1) with num_edges = %d, got %s" % (E, tuple(val.shape)))
-    _, _, rp_t, _, perm, _ = _transpose_csr(nodePointer, edgeList)
+    rp_t, _, perm, _ = transpose_graph(nodePointer, edgeList)
     if val.device != nodePointer.device:
         raise RuntimeError("val is on %s but nodePointer is on %s" % (val.device, nodePointer.device))
-    dev = val.device
     N, H = nodePointer.numel() - 1, val.size(0)
-    out = torch.empty(N, H, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        st = _c.lib.tcgnn_edge_colsum(rp_t.data_ptr(), perm.data_ptr(), N, E, H, val.data_ptr(), out.data_ptr(), _stream_handle(dev))
-    _c.check(st, "tcgnn_edge_colsum")
+    out = torch.empty(N, H, dtype=torch.float32, device=val.device)
+    _call(_c.lib.tcgnn_edge_colsum, val.device, rp_t.data_ptr(), perm.data_ptr(), N, E, H, val.data_ptr(), out.data_ptr())
     return out
 
 
@@ -925,9 +803,7 @@ def agnn_fused_supported(input, nodePointer, edgeList, blockPartition, edgeToCol
     """True if agnn_fused_forward / agnn_fused_backward cover this graph and width (canonical CSR, D <= 128, E >= 8)."""
     if not (input.is_cuda and input.dim() == 2 and input.dtype == torch.float32) or input.shape[0] == 0 or input.shape[1] == 0:
         return False
-    with torch.cuda.device(input.device):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-    return bool(_c.lib.tcgnn_agnn_supported(plan, input.shape[1]))
+    return bool(_c.lib.tcgnn_agnn_supported(_plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)), input.shape[1]))
 
 
 def _weight_scalar(attention_w, dev):
@@ -941,41 +817,33 @@ def agnn_fused_forward(input, nodePointer, edgeList, attention_w, blockPartition
     """[Y, ef, ef_absmax] with ef = forward_ef(input), Y = forward_AGNN(input, attention_w * ef): what
     gnn_conv.py:125-132 computes with two calls (two gathers of the neighbour rows), here in one pass.
     ef_absmax (1 + N int32 words on the device: max |ef| and the per-row scale exponents) must be handed to agnn_fused_backward."""
-    _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     dev = input.device
     _weight_scalar(attention_w, dev)
     N, D = input.shape
     out = torch.empty_like(input)
     ef = torch.empty(edgeList.numel(), dtype=torch.float32, device=dev)
-    absmax = torch.zeros(1 + input.shape[0], dtype=torch.int32, device=dev)   # word 0: max |ef|; words 1 .. N: per-row exponents of the edge weights (include/tcgnn.h)
-    with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_agnn_pair_forward(plan, input.data_ptr(), attention_w.data_ptr(), ef.data_ptr(), absmax.data_ptr(), absmax.numel(),
-                                            out.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_agnn_pair_forward")
+    absmax = torch.zeros(1 + N, dtype=torch.int32, device=dev)   # word 0: max |ef|; words 1 .. N: per-row exponents of the edge weights (include/tcgnn.h)
+    _run(_c.lib.tcgnn_agnn_pair_forward, meta, dev, D, (input.data_ptr(), attention_w.data_ptr(), ef.data_ptr(), absmax.data_ptr(), absmax.numel(),
+                                                        out.data_ptr(), D))
     return [out, ef, absmax]
 
 
 def agnn_fused_backward(d_output, nodePointer, edgeList, attention_w, ef, ef_absmax, blockPartition, edgeToColumn, edgeToRow):
     """[G, d_w] with G = forward_AGNN(d_output, attention_w * ef) and d_w = <forward_ef(d_output), edgeList.float()>
     (gnn_conv.py:143 and :150-153), one pass."""
-    _six(d_output, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    meta = _six(d_output, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
     dev = d_output.device
     _weight_scalar(attention_w, dev)
     _check_input(ef, "ef")
     _check_float(ef, "ef")
-    if ef.numel() != edgeList.numel() or ef_absmax.numel() != 1 + d_output.shape[0] or ef_absmax.dtype != torch.int32 or not ef_absmax.is_cuda:
-        raise RuntimeError("ef / ef_absmax are not what agnn_fused_forward returned for this graph")
     N, D = d_output.shape
+    if ef.numel() != edgeList.numel() or ef_absmax.numel() != 1 + N or ef_absmax.dtype != torch.int32 or not ef_absmax.is_cuda:
+        raise RuntimeError("ef / ef_absmax are not what agnn_fused_forward returned for this graph")
     out = torch.empty_like(d_output)
     d_w = torch.empty(1, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        plan = _plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
-        ws, ws_bytes = _workspace(plan, D, dev)
-        st = _c.lib.tcgnn_agnn_pair_backward(plan, d_output.data_ptr(), attention_w.data_ptr(), ef.data_ptr(), ef_absmax.data_ptr(), ef_absmax.numel(),
-                                             out.data_ptr(), d_w.data_ptr(), D, ws, ws_bytes, _stream_handle(dev))
-    _c.check(st, "tcgnn_agnn_pair_backward")
+    _run(_c.lib.tcgnn_agnn_pair_backward, meta, dev, D, (d_output.data_ptr(), attention_w.data_ptr(), ef.data_ptr(), ef_absmax.data_ptr(), ef_absmax.numel(),
+                                                         out.data_ptr(), d_w.data_ptr(), D))
     return [out, d_w]
 
 

@@ -1792,7 +1792,7 @@ def test_plan_cache_retires_plans_in_stream_order_without_synchronising(dev, T, 
             for g in gs:
                 outs.append((g, T.forward(g[6], *g[5])[0]))
         assert calls["n"] == 0, "eviction synchronised the device"
-        assert len(T._plans) == 3 and len(T._retired) <= 21
+        assert T.cache_stats()["plans"] == 3 and T.cache_stats()["retired"] <= 21
     finally:
         monkeypatch.undo()
     torch.cuda.synchronize()
@@ -1800,7 +1800,7 @@ def test_plan_cache_retires_plans_in_stream_order_without_synchronising(dev, T, 
         ref = O.spmm(X.cpu().numpy(), rp, col, bp, e2c, e2r, round_mode=O.ROUND_TF32)
         assert np.abs(Y.cpu().numpy() - ref).max() <= 1e-3 * max(1.0, np.abs(ref).max())
     T.forward(gs[0][6], *gs[0][5])                             # a later call reaps what has finished (and retires one more itself)
-    assert len(T._retired) <= 1
+    assert T.cache_stats()["retired"] <= 1
     T.set_plan_cache_size(8)
     T.clear_plan_cache()
 

@@ -297,7 +297,9 @@ def test_the_layer_step_does_not_synchronise(dev, T):
     T.prepare([16, 6], *meta)
     torch.nn.functional.cross_entropy(_gpu_logits(convs, x, meta), y).backward()   # (the plan and workspace exist from here on)
     torch.cuda.synchronize()
-    T._scales.clear()
+    T.drop_scales(meta[0], meta[1])
+    stats = T.cache_stats()
+    assert stats["plans"] >= 1 and stats["buffers"] >= 1   # (the plan and the workspace stay; only the scales are computed again)
     torch.cuda.set_sync_debug_mode("error")
     try:
         torch.nn.functional.cross_entropy(_gpu_logits(convs, x, meta), y).backward()

@@ -211,6 +211,57 @@ def test_symmetric_graph_reuses_its_plan(dev, T):
     T.clear_plan_cache()
 
 
+def test_eviction_takes_everything_a_graph_owns_and_nothing_a_live_one_needs(dev, T):
+    """Five small graphs (four directed, one symmetric) through two cache slots, twice, on a side stream: every call past the
+    second evicts a plan that has a transposed part, degree scales and a transposed CSR.  The second round computes the first's
+    bits, the counts stay within the limit after every call, and clearing gives back every byte."""
+    T.clear_plan_cache()
+    torch.cuda.synchronize()
+    m0 = torch.cuda.memory_allocated()
+    gs = [graphs.uniform_graph(200 + 50 * k, 6, seed=70 + k, symmetric=k == 4) for k in range(5)]
+    data = []
+    for k, (rp, col) in enumerate(gs):
+        gen = torch.Generator().manual_seed(k)
+        data.append((meta_for(dev, rp, col)[1], torch.randn(len(rp) - 1, 16, generator=gen).to(dev), torch.randn(3, len(col), generator=gen).to(dev)))
+    m1 = torch.cuda.memory_allocated()
+    T.set_plan_cache_size(2)
+
+    def within_the_limit():
+        s = T.cache_stats()
+        assert s["plans"] <= 2 and s["transposed"] <= 2 and s["csrs"] <= 2, s   # (every graph here has a plan: no planless CSR entry)
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    rounds = []
+    try:
+        with torch.cuda.stream(side):
+            for rnd in range(2):
+                outs = []
+                for meta, X, val in data:
+                    outs.append(T.forward(X, *meta, transpose=True)[0])
+                    within_the_limit()
+                    outs.append(T.forward_AGNN(X, meta[0], meta[1], val[:1], *meta[2:], transpose=True)[0])
+                    within_the_limit()
+                    outs.extend(T.degree_scales(meta[0], meta[1], "both"))
+                    within_the_limit()
+                    outs.append(T.edge_colsum(val, meta[0], meta[1]))
+                    within_the_limit()
+                rounds.append(outs)
+        side.synchronize()
+        assert T.cache_stats()["plans"] == 2 and T.cache_stats()["buffers"] >= 2    # (the side stream's workspace and value buffer)
+        assert len(rounds[0]) == len(rounds[1]) == 25
+        for a, b in zip(*rounds):
+            assert a is not b and torch.equal(a, b)
+    finally:
+        T.set_plan_cache_size(8)
+        T.clear_plan_cache()
+    assert T.cache_stats() == dict(plans=0, csrs=0, transposed=0, retired=0, buffers=0, buffer_bytes=0)
+    del rounds, outs, a, b
+    assert torch.cuda.memory_allocated() == m1
+    del data, meta, X, val
+    assert torch.cuda.memory_allocated() == m0
+
+
 def _directed_community_graph(n=3000, blocks=6, avg_deg=12, seed=6):
     import tcgnn_graph as G
     rp, col = G.sbm_csr(n, n * avg_deg, seed=seed, blocks=blocks, p_in=0.8, directed=True)
