@@ -359,6 +359,29 @@ int tcgnn_spmm_staged(const tcgnn_plan* plan, const void* d_image, float* d_Y, i
 int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge_val, float* d_Y,
                    int32_t D, void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* The edge-valued SpMM for H heads at once (multi-head GAT; no counterpart in the reference, whose n_heads is the constant 1):
+ *   Y[:, hF:(h+1)F] = A_val(d_edge_val[h, :]) * X[:, hF:(h+1)F]   for h < H.
+ * X and Y are fp32 [N, H F] row-major; d_edge_val is fp32 [H, E] head-major - what tcgnn_gat_softmax writes, the reference's
+ * edgeAttention layout.  Works on any plan: on A^T's plan with the values in A^T's order (tcgnn_permute_edge_values per head) it is
+ * the gradient with respect to X.  The contract is tcgnn_spmm_val's: Y is fully overwritten (rows without edges: 0); the caller
+ * owns the workspace - tcgnn_spmm_heads_workspace_bytes(plan, H, F) bytes, 256-byte aligned - and the call neither allocates nor
+ * synchronises (capturable in a HIP graph); a repeated call returns the same bits (fixed-order reductions, no atomics); d_Y is
+ * 16-byte aligned.  X is rounded with ONE power-of-two scale and the edge values with ONE scale over all H E of them; the range
+ * guard ("Operand range", the edge-valued rule) decides once for the whole call.
+ * The library picks its way from the plan and (H, F) alone - tcgnn_plan_last_kernel tells which:
+ *   H == 1                                 exactly tcgnn_spmm_val (bit-identical, every walk it has);
+ *   F in {8, 16, 24, 32}, canonical CSR, E >= 4, an image below 4 GB
+ *                                          "spmm_heads_kernel": one fp16 image of X, one walk of the tile stream per pass of whole
+ *                                          heads (at most 4 heads and 64 columns a pass) - one gather feeds every head of the pass;
+ *   otherwise                              head by head inside the library, each head a column block of X and Y on the gather
+ *                                          walks of tcgnn_spmm_val (one abs-max pass for the whole call); a non-canonical CSR or
+ *                                          E < 4: one plain-fp32 CSR launch for all heads.
+ * H < 1, F < 1, H F beyond int32 or a null array with N > 0: TCGNN_ERR_INVALID_ARG.  N = 0 or E = 0: TCGNN_OK (Y zeroed where N > 0;
+ * d_edge_val may then be NULL).  A workspace too small or misaligned: TCGNN_ERR_WORKSPACE before anything is enqueued. */
+size_t tcgnn_spmm_heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F);
+int tcgnn_spmm_heads(const tcgnn_plan* plan, const float* d_X, const float* d_edge_val, float* d_Y, int32_t H, int32_t F,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ef[e] = <X[row(e),:], X[col(e),:]> for every CSR edge.  Replaces TCGNN.forward_ef /
  * TCGNN.backward_ef (TCGNN.cpp:126-150).  d_ef: fp32 [E], fully overwritten. */
 int tcgnn_sddmm(const tcgnn_plan* plan, const float* d_X, float* d_ef, int32_t D,

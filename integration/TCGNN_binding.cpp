@@ -244,6 +244,41 @@ std::vector<torch::Tensor> spmm_forward_AGNN(torch::Tensor input, torch::Tensor 
   return {output};
 }
 
+// Not in the reference: the edge-valued SpMM for every head at once, Y[:, hF:(h+1)F] = A_val(edgeAttention[h]) input[:, hF:(h+1)F]
+// (tcgnn_spmm_heads; TCGNN.forward_heads of the ctypes module).  transpose: every head's row permuted into A^T's order, A^T's plan
+std::vector<torch::Tensor> spmm_forward_heads(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                              torch::Tensor edgeAttention, torch::Tensor blockPartition, torch::Tensor edgeToColumn,
+                                              torch::Tensor edgeToRow, int64_t heads, bool transpose) {
+  CHECK_INPUT(input); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList); CHECK_INPUT(edgeAttention);
+  CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
+  TORCH_CHECK(input.scalar_type() == torch::kFloat32 && edgeAttention.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  check_rows(input, nodePointer);
+  const int64_t E = edgeList.numel(), D = input.size(1);
+  TORCH_CHECK(heads >= 1 && D % heads == 0, "input has ", D, " columns, which ", heads, " heads do not divide");
+  TORCH_CHECK(edgeAttention.dim() == 2 && edgeAttention.size(0) == heads && edgeAttention.size(1) == E && edgeAttention.device() == input.device(),
+              "edgeAttention must be [heads, num_edges] on the input's device");
+  DeviceGuard guard(input.device());
+  auto output = torch::empty_like(input);
+  if (input.numel() == 0) return {output};
+  PlanEntry& entry = entry_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  auto* plan = plan_of(entry, transpose);
+  const int H = (int)heads, F = (int)(D / heads);
+  void* ws = nullptr;
+  const size_t need = tcgnn_spmm_heads_workspace_bytes(plan, H, F);
+  torch::Tensor buf = aligned_scratch(need, input, &ws);
+  const float* val = edgeAttention.data_ptr<float>();
+  torch::Tensor val_t;
+  if (transpose) {
+    val_t = torch::empty({std::max<int64_t>(heads * E, 1)}, input.options());
+    for (int64_t h = 0; h < heads; ++h)
+      tcgnn_check(tcgnn_permute_edge_values(val + h * E, entry.t.perm.data_ptr<int>(), E, val_t.data_ptr<float>() + h * E, current_stream(input)),
+                  "tcgnn_permute_edge_values");
+    val = val_t.data_ptr<float>();
+  }
+  tcgnn_check(tcgnn_spmm_heads(plan, input.data_ptr<float>(), val, output.data_ptr<float>(), H, F, ws, need, current_stream(input)), "tcgnn_spmm_heads");
+  return {output};
+}
+
 // TCGNN.cpp:126-150
 std::vector<torch::Tensor> sddmm_forward(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
                                          torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow) {
@@ -510,6 +545,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward_ef", &sddmm_forward, "TC-GNN SDDMM forward (CUDA)");
   m.def("forward_AGNN", &spmm_forward_AGNN, "TC-GNN SPMM (AGNN) forward (CUDA)", py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"),
         py::arg("edgeAttention"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("transpose") = false);
+  m.def("forward_heads", &spmm_forward_heads, "edge-valued SpMM for every head at once (not in the reference)", py::arg("input"), py::arg("nodePointer"),
+        py::arg("edgeList"), py::arg("edgeAttention"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("heads"),
+        py::arg("transpose") = false);
   m.def("backward", &spmm_forward, "TC-GNN SPMM backward (CUDA)", py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"),
         py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("transpose") = false);
   m.def("backward_ef", &sddmm_forward, "TC-GNN SDDMM backward (CUDA)");

@@ -35,7 +35,7 @@ from tcgnn_graph_cache import GraphCache, TransposedCsr, TransposedPlan, graph_k
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
-           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum",
+           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads",
            "cache_stats", "drop_scales"]
 
 
@@ -59,7 +59,7 @@ _cache = GraphCache(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8"), _c.lib.tcgnn_p
 # for which the allocation carries as many spare bytes; 0: the buffer is used from its first byte)
 _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
-          "values": (1, 0),           # fp32 [max(E, 1)]: A's edge values in A^T's order, forward_AGNN(transpose=True)
+          "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
           "softmax": (1, 256)}        # the fp64 partials of edge_softmax_backward's d_beta
 
 
@@ -260,7 +260,7 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
     return out
 
 
-def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False):
+def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
@@ -271,10 +271,11 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     attention=True (a model with softmax-attention layers: forward_ef2, edge_softmax, edge_softmax_backward): the workspace grown to
     forward_ef2's two images at every width and the scratch of edge_softmax_backward's d_beta, on the current stream - a step that
     uses them then allocates nothing outside torch's pool and never synchronises.
-    A GAT model (gat_softmax, gat_softmax_backward, edge_colsum and the per-head forward_AGNN / forward_ef2 calls of
-    tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True and attention=True: the
-    edge-valued streams of A and A^T at that width, the two-image SDDMM workspace, and - with A^T's plan - the transposed CSR
-    edge_colsum sums over."""
+    A GAT model (gat_softmax, gat_softmax_backward, edge_colsum, and forward_heads / the per-head forward_ef2 calls of
+    tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True, attention=True and heads=H: the
+    edge-valued streams of A and A^T at that width (what a layer of ONE head runs on), the two-image SDDMM workspace, with A^T's
+    plan the transposed CSR edge_colsum sums over, and - heads > 1 - the workspace of forward_heads at H heads of every width in
+    `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream."""
     e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     plans = [e.handle]
     dev = nodePointer.device
@@ -290,9 +291,11 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
             if own is not None:
                 plans.append(own)
             if edge_valued:
-                _buffer("values", 4 * max(edgeList.numel(), 1), dev, stream)
+                _buffer("values", 4 * max(int(heads) * edgeList.numel(), 1), dev, stream)
         for d in widths:
             for p in plans:
+                if int(heads) > 1:
+                    _buffer("workspace", _c.lib.tcgnn_spmm_heads_workspace_bytes(p, int(heads), d), dev, stream)
                 _c.check(_c.lib.tcgnn_plan_prepare(p, d, stream), "tcgnn_plan_prepare")
                 if edge_valued:
                     _c.check(_c.lib.tcgnn_plan_prepare_val(p, d, stream), "tcgnn_plan_prepare_val")
@@ -625,6 +628,40 @@ def forward_AGNN(input, nodePointer, edgeList, edgeAttention, blockPartition, ed
             val = _buffer("values", 4 * max(E, 1), dev)[0]
             _call(_c.lib.tcgnn_permute_edge_values, dev, edgeAttention.data_ptr(), e.csr.transposed.perm.data_ptr(), E, val)
         _run(_c.lib.tcgnn_spmm_val, meta, dev, D, (input.data_ptr(), val, out.data_ptr(), D), transpose)
+    return [out]
+
+
+def forward_heads(input, nodePointer, edgeList, edgeAttention, blockPartition, edgeToColumn, edgeToRow, heads, transpose=False):
+    """Not in the reference module (whose n_heads is the constant 1): the edge-valued SpMM for every head at once (tcgnn_spmm_heads),
+        Y[:, hF:(h+1)F] = A_val(edgeAttention[h]) @ input[:, hF:(h+1)F],   F = input.size(1) / heads.
+    edgeAttention: fp32 [heads, E], head-major (what gat_softmax returns).  One call whatever the shape: the library takes the fused
+    walk - one gather of the neighbour rows feeds every head - where it covers (heads, F) and goes head by head itself elsewhere
+    (include/tcgnn.h; last_kernel tells).  heads = 1 is forward_AGNN bit for bit.  transpose=True: with A_val^T - every head's row is
+    permuted into A^T's order (tcgnn_permute_edge_values, into the [heads, E] buffer held per stream) and A^T's plan aggregates."""
+    meta = _six(input, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    _check_input(edgeAttention, "edgeAttention")
+    _check_float(edgeAttention, "edgeAttention")
+    dev = input.device
+    N, D = input.shape
+    E = edgeList.numel()
+    H = int(heads)
+    if H < 1 or D % H:
+        raise RuntimeError("input has %d columns, which %d heads do not divide" % (D, H))
+    if tuple(edgeAttention.shape) != (H, E) or edgeAttention.device != dev:
+        raise RuntimeError("edgeAttention must be [heads, num_edges] = [%d, %d] on the input's device, got %s" % (H, E, tuple(edgeAttention.shape)))
+    out = torch.empty_like(input)
+    if N and D:
+        F = D // H
+        val = edgeAttention.data_ptr()
+        if transpose:
+            e = _plan_entry(meta)
+            _transposed_plan(e)
+            val = _buffer("values", 4 * max(H * E, 1), dev)[0]
+            perm = e.csr.transposed.perm.data_ptr()
+            for h in range(H):
+                _call(_c.lib.tcgnn_permute_edge_values, dev, edgeAttention.data_ptr() + 4 * h * E, perm, E, val + 4 * h * E)
+        _run(_c.lib.tcgnn_spmm_heads, meta, dev, D, (input.data_ptr(), val, out.data_ptr(), H, F), transpose,
+             need=lambda plan, _: _c.lib.tcgnn_spmm_heads_workspace_bytes(plan, H, F))
     return [out]
 
 

@@ -32,6 +32,7 @@
 //                             and walk predicates, stage_features, sync_chosen; behind the includes the C ABI of the operators and tcgnn_range_mode
 //   tcgnn_pack_stage.inc      plan-time kernels (pack, locality, longest row) and the staging pass (abs-max, fp16 images)
 //   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
+//   tcgnn_heads.inc           multi-head edge-valued SpMM: HeadsWalker (TileWalker with one A fragment per head), spmm_heads_kernel, spmm_heads_csr_kernel
 //   tcgnn_sync_walk.inc       slice-synchronised range walk: SyncArgs, spmm_sync_kernel's two forms from tcgnn_sync_kernel.inc, table kernels
 //   tcgnn_small_spmm.inc      spmm_small_kernel (single launch, fp32 MFMA on fp32 X; also the binary SpMM's range-guard fallback)
 //   tcgnn_lds_spmm.inc        LDS-resident SpMM, ordinary cell stream; cell-stream build kernels
@@ -45,7 +46,8 @@
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
-//   tcgnn_spmm_dispatch.inc   host side of an SpMM call: SpmmCall, route_spmm (which walk runs), one launcher per walk, run_spmm
+//   tcgnn_spmm_dispatch.inc   host side of an SpMM call: SpmmCall, route_spmm (which walk runs), one launcher per walk, run_spmm; of a
+//                             multi-head call: route_heads, run_spmm_heads
 //   tcgnn_plan.inc            plan lifetime: creation in named steps (order_windows, build_sync_tables, ...), destroy, info, prepare, timing, setters
 #include <hip/hip_runtime.h>
 
@@ -370,6 +372,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_agnn.inc"
 
 #include "tcgnn_small_fallback.inc"
+#include "tcgnn_heads.inc"   // (behind the fallbacks: its range-guard kernel is spmm_wide_fallback_body per head)
 
 #include "tcgnn_transpose.inc"
 
@@ -411,6 +414,31 @@ static hipError_t launch_spmm_any(bool val, int waves, int nt, const SpmmArgs& a
                                   const Epi& epi = Epi{nullptr, nullptr}) {
     if (waves == 4) return val ? launch_spmm_nt<4, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_nt<4, false>(nt, args, nwin, nchunks, stream, epi);
     return val ? launch_spmm_nt<1, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_nt<1, false>(nt, args, nwin, nchunks, stream, epi);
+}
+
+// spmm_heads_kernel: G whole heads of 8 FB columns per pass - the shapes heads_per_pass (tcgnn_spmm_dispatch.inc) forms, full passes and remainders
+template <int G, int FB>
+static hipError_t launch_heads_one(const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
+    const size_t lds = (size_t)waves * HeadsWalker<G, FB>::WAVE_LDS;
+    static bool attr_set = false;   // (four wavefronts of a 4 x 16 pass hold 65 KB)
+    if (!attr_set) {
+        const hipError_t e = hipFuncSetAttribute((const void*)spmm_heads_kernel<G, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * HeadsWalker<G, FB>::WAVE_LDS);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((spmm_heads_kernel<G, FB>), dim3((unsigned)nwin, (unsigned)npass), dim3((unsigned)waves * 64), lds, stream, args);
+    return hipGetLastError();
+}
+static hipError_t launch_heads_any(int g, int fb, const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
+#define TCGNN_HEADS_CASE(G, FB) case (G) * 100 + (FB): return launch_heads_one<G, FB>(args, waves, nwin, npass, stream)
+    switch (g * 100 + fb) {
+        TCGNN_HEADS_CASE(1, 1); TCGNN_HEADS_CASE(2, 1); TCGNN_HEADS_CASE(3, 1); TCGNN_HEADS_CASE(4, 1);   // F = 8
+        TCGNN_HEADS_CASE(1, 2); TCGNN_HEADS_CASE(2, 2); TCGNN_HEADS_CASE(3, 2); TCGNN_HEADS_CASE(4, 2);   // F = 16
+        TCGNN_HEADS_CASE(1, 3); TCGNN_HEADS_CASE(2, 3);                                                   // F = 24
+        TCGNN_HEADS_CASE(1, 4); TCGNN_HEADS_CASE(2, 4);                                                   // F = 32
+        default: return hipErrorInvalidValue;
+    }
+#undef TCGNN_HEADS_CASE
 }
 
 // workgroups of a persistent grid resident on one CU: what its 160 KB of LDS hold, at most what the kernel's registers allow, at least one
@@ -954,6 +982,18 @@ int tcgnn_spmm_val(const tcgnn_plan* plan, const float* d_X, const float* d_edge
     SpmmCall c = spmm_call(plan, d_X, d_Y, D, ws, ws_bytes, stream);
     if (plan && plan->E > 0) c.d_val = d_edge_val;
     return run_spmm(c);
+}
+
+size_t tcgnn_spmm_heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    if (!plan || H < 1 || F < 1 || (int64_t)H * F > INT32_MAX) return 0;
+    return heads_workspace_bytes(plan, H, F);
+}
+
+int tcgnn_spmm_heads(const tcgnn_plan* plan, const float* d_X, const float* d_edge_val, float* d_Y, int32_t H, int32_t F,
+                     void* ws, size_t ws_bytes, void* stream) {
+    HeadsCall c;
+    c.plan = plan; c.d_X = d_X; c.d_val = d_edge_val; c.d_Y = d_Y; c.H = H; c.F = F; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = static_cast<hipStream_t>(stream);
+    return run_spmm_heads(c);
 }
 
 static SddmmCall sddmm_call(const char* name, const tcgnn_plan* plan, const float* d_Xw, const float* d_X, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream) {

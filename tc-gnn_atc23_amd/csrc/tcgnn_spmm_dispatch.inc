@@ -458,3 +458,118 @@ static int run_spmm(const SpmmCall& c) {
     }
     return (rc || r.own_fb) ? rc : launch_wide_fallback(c, im);
 }
+
+// ------------------------------------------------------------------------------------------
+// tcgnn_spmm_heads: Y[:, hF:(h+1)F] = A_val(edge_val[h, :]) X[:, hF:(h+1)F] for H heads.  One decision (route_heads), from the plan
+// and (H, F) alone, before anything is staged; tcgnn_spmm_heads_workspace_bytes asks the same function.
+// ------------------------------------------------------------------------------------------
+struct HeadsCall {
+    const tcgnn_plan* plan = nullptr;
+    const float *d_X = nullptr, *d_val = nullptr;   // X [N, H F]; edge values [H, E] head-major
+    float* d_Y = nullptr;
+    int32_t H = 0, F = 0;
+    void* ws = nullptr; size_t ws_bytes = 0;
+    hipStream_t stream = nullptr;
+};
+// kSingle: H == 1 is tcgnn_spmm_val itself (run_spmm, every walk it has); kFused: spmm_heads_kernel - one staged image, one walk of the
+// tile stream per pass of whole heads; kCsr: a plan the tile stream cannot serve with edge values (route_spmm's kValCsr), all heads in
+// one CSR launch; kPerHead: head by head inside the library - each head a column block of X and Y (run_spmm with ld, block_of_wider,
+// as run_column_blocks does it) with its own row of edge values, every block rounded with the scales of the whole call
+enum class HeadsWay { kSingle, kFused, kCsr, kPerHead };
+// heads one pass of the fused walk takes at F columns each; 0: a width it does not cover.  At most kMaxHeadsPerPass heads and
+// kMaxHeadsPassDims columns (what a workgroup's LDS then holds: tcgnn_heads.inc) and at least TWO heads: a pass of one head shares
+// no gather with another, it would be the per-window walk once per head - the head-by-head way keeps run_spmm's choice among the
+// gather walks for such widths (F > 32).  A pass starts at a multiple of 16 columns (the gather's slices), so where F is not one
+// the FULL passes take an even number of heads: F = 8 -> 4, F = 24 -> 2 (F = 16 -> 4, F = 32 -> 2).
+static int heads_per_pass(int F) {
+    if (F < 8 || F % 8 || F > kMaxHeadsPassDims / 2) return 0;
+    const int g = std::min(kMaxHeadsPerPass, kMaxHeadsPassDims / F);
+    return F % 16 == 0 ? g : (g & ~1);
+}
+static HeadsWay route_heads(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    if (H == 1) return HeadsWay::kSingle;
+    if (!plan->canonical || plan->E < 4) return HeadsWay::kCsr;
+    const int D = H * F;
+    if (heads_per_pass(F) > 0 && plan->nw_eff > 0 && pitch_fits_descriptor(D) && !image_is_big(plan->Nc, x16_pitch(round_up(D, 16)))) return HeadsWay::kFused;
+    return HeadsWay::kPerHead;
+}
+static size_t heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    switch (route_heads(plan, H, F)) {
+        case HeadsWay::kSingle: return tcgnn_workspace_bytes(plan, F);
+        case HeadsWay::kFused:  return workspace_bytes_for(plan->Nc, H * F);                          // one image of all of X
+        // one head's block at a time.  (kCsr stages nothing, but is handed the same buffer: pointer, alignment and size are checked
+        //  alike on every route, so what a caller must provide does not depend on the route)
+        default:                return workspace_bytes_for(plan->Nc, std::min(F, kMaxGatherBlockDims));
+    }
+}
+// max |edge_val| over all H E values into header words 1 / 3 / 5: ONE scale and one range-guard decision for the whole call
+static void launch_absmax_heads_val(const HeadsCall& c, uint32_t* hdr) {
+    const int64_t n = (int64_t)c.H * c.plan->E;
+    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n)), dim3(kAbsmaxThreads), 0, c.stream, c.d_val, n, hdr + 1, hdr + 3, guard_spmm(c.plan).cap, 0u);
+}
+static int launch_heads_fused(const HeadsCall& c) {
+    const tcgnn_plan* const plan = c.plan;
+    const int32_t D = c.H * c.F;
+    StagedImage im;
+    if (const int rc = stage_features(plan, c.d_X, nullptr, D, c.ws, c.ws_bytes, c.stream, StageOpts{}, &im)) return rc;
+    launch_absmax_heads_val(c, static_cast<uint32_t*>(c.ws));
+    HIP_TRY(hipGetLastError());
+    {
+        KernelTimer timer(plan, c.stream, "spmm_heads_kernel");
+        SpmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, im.x16, c.d_val, im.hdr, c.d_Y, plan->N, D, im.pitch, 0, plan->E, plan->Nc + 1, 0, D,
+                   0, nullptr, 0, 0, 0};
+        const int g = heads_per_pass(c.F), nfull = c.H / g, rem = c.H % g;
+        if (nfull) HIP_TRY(launch_heads_any(g, c.F / 8, SpmmHeadsArgs{a, 0}, plan->waves, plan->nw_eff, nfull, c.stream));
+        if (rem) HIP_TRY(launch_heads_any(rem, c.F / 8, SpmmHeadsArgs{a, nfull * g}, plan->waves, plan->nw_eff, 1, c.stream));
+    }
+    // the range guard's fp32 way behind the kernel, one launch for all heads (returns at once unless the call is "wide": range_is_wide_val)
+    const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)plan->N + 3) / 4, 4096);
+    hipLaunchKernelGGL(spmm_heads_wide_fallback_kernel, dim3(grid, (unsigned)c.H), dim3(256), 0, c.stream, im.hdr, plan->rowptr, plan->col, c.d_val, c.d_X, c.d_Y, plan->N, c.F,
+                       plan->E, (int64_t)D);
+    HIP_TRY(hipGetLastError());
+    return TCGNN_OK;
+}
+static int run_heads_one_by_one(const HeadsCall& c) {
+    const tcgnn_plan* const plan = c.plan;
+    const int32_t D = c.H * c.F;
+    uint32_t* whdr = static_cast<uint32_t*>(c.ws);
+    HIP_TRY(hipMemsetAsync(whdr, 0, 64, c.stream));
+    launch_absmax(plan, c.d_X, nullptr, nullptr, (int64_t)plan->Nc * D, D, nullptr, whdr, guard_spmm(plan), c.stream);
+    launch_absmax_heads_val(c, whdr);
+    HIP_TRY(hipGetLastError());
+    for (int h = 0; h < c.H; ++h)
+        for (int c0 = 0; c0 < c.F; c0 += kMaxGatherBlockDims) {   // (a head wider than one gather launch covers: its own column blocks)
+            SpmmCall b;
+            b.plan = plan; b.d_X = c.d_X + (int64_t)h * c.F + c0; b.d_Y = c.d_Y + (int64_t)h * c.F + c0; b.d_val = c.d_val + (int64_t)h * plan->E;
+            b.D = std::min(kMaxGatherBlockDims, c.F - c0); b.ws = c.ws; b.ws_bytes = c.ws_bytes; b.stream = c.stream;
+            b.ld = D; b.block_of_wider = true;
+            if (const int rc = run_spmm(b)) return rc;
+        }
+    return TCGNN_OK;
+}
+// check, zero fill, route, run
+static int run_spmm_heads(const HeadsCall& c) {
+    const tcgnn_plan* const plan = c.plan;
+    if (!plan || c.H < 1 || c.F < 1 || (int64_t)c.H * c.F > INT32_MAX) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_heads: null plan, H < 1, F < 1 or H * F beyond int32");
+    if (plan->N > 0 && (!c.d_X || !c.d_Y || (plan->E > 0 && !c.d_val))) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_heads: null array");
+    if (plan->N == 0) return TCGNN_OK;
+    if (c.H == 1) {   // exactly tcgnn_spmm_val
+        SpmmCall s;
+        s.plan = plan; s.d_X = c.d_X; s.d_Y = c.d_Y; s.D = c.F; s.ws = c.ws; s.ws_bytes = c.ws_bytes; s.stream = c.stream;
+        if (plan->E > 0) s.d_val = c.d_val;
+        return run_spmm(s);
+    }
+    if (const int rc = check_output_aligned("tcgnn_spmm_heads", "Y", c.d_Y)) return rc;
+    if (const int rc = check_workspace("tcgnn_spmm_heads", c.ws, c.ws_bytes, heads_workspace_bytes(plan, c.H, c.F))) return rc;
+    const size_t y_bytes = (size_t)plan->N * c.H * c.F * sizeof(float);
+    if (plan->E == 0) { HIP_TRY(hipMemsetAsync(c.d_Y, 0, y_bytes, c.stream)); return TCGNN_OK; }
+    const HeadsWay way = route_heads(plan, c.H, c.F);
+    if (way == HeadsWay::kCsr) {
+        hipLaunchKernelGGL(spmm_heads_csr_kernel, dim3((unsigned)((plan->N + 3) / 4)), dim3(256), 0, c.stream, plan->rowptr, plan->col, c.d_val, c.d_X, c.d_Y, plan->N, c.H, c.F, plan->E);
+        HIP_TRY(hipGetLastError());
+        return TCGNN_OK;
+    }
+    // rows beyond the windows the caller described stay zero, like zeros_like (fill_uncovered_rows, for all heads at once)
+    if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(c.d_Y, 0, y_bytes, c.stream));
+    return way == HeadsWay::kFused ? launch_heads_fused(c) : run_heads_one_by_one(c);
+}

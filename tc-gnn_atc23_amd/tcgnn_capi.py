@@ -64,6 +64,8 @@ SIGNATURES = {
     "tcgnn_workspace_bytes": (_sz, [_vp, _i32]),
     "tcgnn_spmm": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "tcgnn_spmm_val": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "tcgnn_spmm_heads_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "tcgnn_spmm_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "tcgnn_spmm_fused": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "tcgnn_spmm_scaled": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "tcgnn_spmm_gemm": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),

@@ -7,14 +7,15 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate(P, H, meta)         Y = A_val(P) H                           bwd: dP = sddmm(dY, H),  dH = A_val(P)^T dY
     gat_attention(el, er, rowptr, col, slope)  P[h] = softmax by row of leaky_relu(el[col e, h] + er[row e, h])   (multi-head GAT)
                                   bwd: g as above per head; ds = g lrelu'(raw); d_er = row sums of ds; d_el = column sums of ds
-    aggregate_heads(P, Z, meta)   Y[:, head h] = aggregate(P[h], Z[:, head h])
+    aggregate_heads(P, Z, meta)   Y[:, head h] = A_val(P[h]) Z[:, head h], all heads in one call   bwd: dP[h] = sddmm(dY_h, Z_h),  dZ through A^T, one call
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
-The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward and forward_AGNN(transpose=).  A
-backend without them is an error - there is no composed fallback.
+The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=) and
+forward_heads(transpose=).  A backend without them is an error - there is no composed fallback in this module (a stand-in backend
+installed with tcgnn_layers.set_backend is given forward_heads there, if it has none).
 """
 import torch
 
@@ -106,36 +107,29 @@ class _GATAttention(torch.autograd.Function):
 
 
 class _AggregateHeads(torch.autograd.Function):
-    """_Aggregate head by head in one node of the autograd graph: dP is written row by row into one [heads, E] tensor (H separate
-    aggregate() calls on P[h] would each have autograd zero-fill and add a whole [heads, E] gradient)."""
-
-    @staticmethod
-    def _slices(M, H):
-        F = M.shape[1] // H
-        return [M[:, h * F:(h + 1) * F].contiguous() for h in range(H)]
+    """Y = forward_heads(Z, P): one call for all heads, and one over A^T for dZ.  dP is written row by row into one [heads, E] tensor,
+    a forward_ef2 per head (a multi-head SDDMM does not exist yet)."""
 
     @staticmethod
     def forward(ctx, P, Z, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
         ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
-        P = P.contiguous()
+        P, Z = P.contiguous(), Z.contiguous()
         ctx.save_for_backward(P, Z)
-        b = _L.backend()
-        Zh = _AggregateHeads._slices(Z, P.shape[0])
-        return torch.cat([b.forward_AGNN(z, row_pointers, column_index, P[h].view(1, -1), blockPartition, edgeToColumn, edgeToRow)[0]
-                          for h, z in enumerate(Zh)], dim=1)
+        rp, col, bp, e2c, e2r = ctx.meta
+        return _L.backend().forward_heads(Z, rp, col, P, bp, e2c, e2r, P.shape[0])[0]
 
     @staticmethod
     def backward(ctx, d_y):
         P, Z = ctx.saved_tensors
-        rp, col, bp, e2c, e2r = ctx.meta
         b = _L.backend()
-        H = P.shape[0]
-        dYh = _AggregateHeads._slices(d_y, H)
+        H, F = P.shape[0], Z.shape[1] // P.shape[0]
+        d_y = d_y.contiguous()
         d_p = d_z = None
         if ctx.needs_input_grad[0]:
-            d_p = torch.stack([b.forward_ef2(dy, z, *ctx.meta)[0] for dy, z in zip(dYh, _AggregateHeads._slices(Z, H))])
+            d_p = torch.stack([b.forward_ef2(d_y[:, h * F:(h + 1) * F].contiguous(), Z[:, h * F:(h + 1) * F].contiguous(), *ctx.meta)[0] for h in range(H)])
         if ctx.needs_input_grad[1]:
-            d_z = torch.cat([b.forward_AGNN(dy, rp, col, P[h].view(1, -1), bp, e2c, e2r, transpose=True)[0] for h, dy in enumerate(dYh)], dim=1)
+            rp, col, bp, e2c, e2r = ctx.meta
+            d_z = b.forward_heads(d_y, rp, col, P, bp, e2c, e2r, H, transpose=True)[0]
         return (d_p, d_z) + (None,) * 5
 
 
@@ -146,8 +140,9 @@ def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):
 
 
 def aggregate_heads(P, Z, meta):
-    """Y[:, hF:(h+1)F] = aggregate(P[h], Z[:, hF:(h+1)F], meta) for P [heads, E] and Z [N, heads * F]: the multi-head aggregation
-    composed of the edge-valued SpMM head by head (dP[h] through forward_ef2, dZ through A^T, both exact)."""
+    """Y[:, hF:(h+1)F] = A_val(P[h]) Z[:, hF:(h+1)F] for P [heads, E] and Z [N, heads * F]: the multi-head aggregation, one
+    forward_heads call of the backend (the library's multi-head edge-valued SpMM: one gather feeds every head where its fused walk
+    covers the shape).  dZ is one forward_heads call over A^T, dP[h] a forward_ef2 per head; both exact."""
     if P.dim() != 2 or Z.dim() != 2 or P.shape[0] < 1 or Z.shape[1] % P.shape[0]:
         raise RuntimeError("P must be [heads, E] and Z [N, heads * F], got %s and %s" % (tuple(P.shape), tuple(Z.shape)))
     return _AggregateHeads.apply(P, Z, *meta)

@@ -178,7 +178,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     prep = getattr(L.backend(), "prepare", None)
     if prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
         prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
-             **({"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" or model_name == "gat" else
+             **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if model_name == "gat" else
+                {"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
                 ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)

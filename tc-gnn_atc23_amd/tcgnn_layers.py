@@ -35,8 +35,21 @@ USE_FUSED_AGNN = True  # tests switch it off to compare with the separate calls
 _backend = None
 
 
+def _heads_of_single(module):
+    """forward_heads by its definition, forward_AGNN on each head's columns: what set_backend gives a stand-in that has no such call"""
+    def forward_heads(input, nodePointer, edgeList, edgeAttention, blockPartition, edgeToColumn, edgeToRow, heads, transpose=False):
+        F = input.shape[1] // heads
+        return [torch.cat([module.forward_AGNN(input[:, h * F:(h + 1) * F].contiguous(), nodePointer, edgeList, edgeAttention[h].view(1, -1),
+                                               blockPartition, edgeToColumn, edgeToRow, transpose=transpose)[0] for h in range(heads)], dim=1)]
+    return forward_heads
+
+
 def set_backend(module):
+    """Install a stand-in for the TCGNN module (host tests: pure-torch or scipy objects).  One that has forward_AGNN but no
+    forward_heads is given the latter by its definition; the product's own backends (TCGNN, the binding) have the call."""
     global _backend
+    if module is not None and hasattr(module, "forward_AGNN") and not hasattr(module, "forward_heads"):
+        module.forward_heads = _heads_of_single(module)
     _backend = module
 
 

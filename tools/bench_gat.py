@@ -7,10 +7,10 @@ Graphs: sbm_reddit, R-MAT at the Reddit shape, and an SBM graph at the ogbn-prod
                   where torch's row gather does not agree with them: checked per call) and leaky_relu into an [H, E] score array, H calls of TCGNN.edge_softmax; backward: H calls of TCGNN.edge_softmax_backward, the leaky_relu mask, index_add_
                   over the rows for d_er; index_add_ over the SOURCE nodes for d_el - and the forward against the HBM roofline B / 8 TB/s,
                   B = 4 (N + 1) + 4 E + 8 N H + 4 H E
-  aggregate       aggregate_heads (H edge-valued SpMMs of width F, forward; forward + backward) against ONE binary forward at width H F:
-                  the ratio is the price of the per-head composition
+  aggregate       aggregate_heads (ONE multi-head edge-valued SpMM, forward; forward + backward) against ONE binary forward at width H F;
+                  heads_walk names the kernel the multi-head call ran
   epoch           a GAT epoch, 2 layers, hidden = H F
-    python tools/bench_gat.py [--epochs K] [--skip-epochs] [--graphs a,b]"""
+    python tools/bench_gat.py [--epochs K] [--skip-epochs] [--graphs a,b] [--configs 8x8,4x32,2x64]"""
 import argparse
 import json
 import os
@@ -125,6 +125,7 @@ def aggregate_times(graph, n, meta, heads, feat, dev):
     dY = torch.randn(n, heads * feat, device=dev, generator=g)
     with torch.no_grad():
         t_h = median_ms(lambda: E_ops.aggregate_heads(P, Z, meta))
+        walk_h = TCGNN.last_kernel(*meta)
         t_1 = median_ms(lambda: TCGNN.forward(Z, *meta))
         walk_1 = TCGNN.last_kernel(*meta)
 
@@ -133,7 +134,7 @@ def aggregate_times(graph, n, meta, heads, feat, dev):
         torch.autograd.grad(E_ops.aggregate_heads(p, z, meta), (p, z), dY)
     t_hb = median_ms(both, reps=10, warmup=3)
     emit(graph=graph, what="aggregate", heads=heads, features=feat, aggregate_heads_ms=t_h, binary_forward_ms=t_1, ratio=t_h / t_1,
-         aggregate_heads_forward_backward_ms=t_hb, binary_walk=walk_1, per_head_walk=TCGNN.last_kernel(*meta))
+         aggregate_heads_forward_backward_ms=t_hb, binary_walk=walk_1, heads_walk=walk_h)
 
 
 def main():
@@ -141,6 +142,7 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--skip-epochs", action="store_true")
     ap.add_argument("--graphs", type=str, default="sbm_reddit,rmat_reddit,sbm_products")
+    ap.add_argument("--configs", type=str, default=",".join("%dx%d" % c for c in CONFIGS), help="heads x features per head, e.g. 8x8,4x32,2x64")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     table = {"sbm_reddit": ("reddit", "sbm_reddit"), "rmat_reddit": ("reddit", "rmat"), "sbm_products": ("ogbn-products", "sbm")}
@@ -150,8 +152,9 @@ def main():
         rp, col = G.GENERATORS[gen](n, nnz, seed=0, device=dev)
         emit(graph=graph, what="graph", num_nodes=n, num_edges=col.numel())
         meta = translate(rp, col, n, dev)
-        for heads, feat in CONFIGS:
+        for heads, feat in [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]:
             TCGNN.prepare([feat, heads * feat], *meta, transpose=True, edge_valued=True, attention=True)
+            TCGNN.prepare([feat], *meta, transpose=True, edge_valued=True, heads=heads)
             with torch.no_grad():
                 attention_times(graph, n, rp, col, heads, dev)
             torch.cuda.empty_cache()
