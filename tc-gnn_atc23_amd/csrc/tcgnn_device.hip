@@ -28,7 +28,7 @@
 //   partial accumulators of the wavefronts are summed through LDS in a fixed order.
 //
 // File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator; in include order):
-//   tcgnn_device.hip          struct tcgnn_plan, KernelTimer, device helpers (the range guard's rule, host and device), launch tables, switches
+//   tcgnn_device.hip          HIP_TRY, DevBuf (owner of one device allocation), struct tcgnn_plan, KernelTimer, device helpers (the range guard's rule, host and device), launch tables, switches
 //                             and walk predicates, stage_features, sync_chosen; behind the includes the C ABI of the operators and tcgnn_range_mode
 //   tcgnn_pack_stage.inc      plan-time kernels (pack, locality, longest row) and the staging pass (abs-max, fp16 images)
 //   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
@@ -44,7 +44,8 @@
 //   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
-//   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells, build_val_stream
+//   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells (a cell stream in named steps over a
+//                             CellBuild; flat_entries, the entry records, is a pure host function; cells_publish cannot fail), build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
 //   tcgnn_spmm_dispatch.inc   host side of an SpMM call: SpmmCall, route_spmm (which walk runs), one launcher per walk, run_spmm; of a
 //                             multi-head call: route_heads, run_spmm_heads
@@ -82,6 +83,28 @@ typedef __attribute__((__vector_size__(4 * sizeof(__fp16)))) __fp16 fp16x4_raw;
         hipError_t e_ = (expr);                                                             \
         if (e_ != hipSuccess) return fail(TCGNN_ERR_HIP, "%s -> %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+static inline int hip_rc(hipError_t e) { return e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP; }
+// Owner of one device allocation: frees it on every way out of a scope; release() hands the pointer over (to the plan, which keeps
+// raw pointers) and returns the bytes handed over, so what the plan owns is summed from what it was given.
+template <class T> struct DevBuf {
+    T* ptr = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t e = hipMalloc(&ptr, count * sizeof(T));
+        if (e == hipSuccess) bytes = count * sizeof(T); else ptr = nullptr;
+        return e;
+    }
+    void reset() { if (ptr) (void)hipFree(ptr); ptr = nullptr; bytes = 0; }
+    size_t release(T*& to) { const size_t b = bytes; to = ptr; ptr = nullptr; bytes = 0; return b; }
+    operator T*() const { return ptr; }
+};
 
 struct tcgnn_plan {
     int32_t N = 0, nw = 0, nw_eff = 0;   // N: rows of A (= rows of Y)
@@ -555,6 +578,7 @@ static hipError_t launch_agnn_wide_one(int nt, const AgnnArgs& args, int nwg, hi
 // TCGNN_SDDMM_XCD=0|1|2, TCGNN_RANGE_KB (column-range size of the range-major walks).  The A/B switches of closed experiments (r01-r03: DESIGN.md lists what each measured) are gone; the
 // phase timers of the LDS-resident kernels (TCGNN_LDS_DBG) exist only in a -DTCGNN_DEBUG_TIMERS build (make DEBUG_TIMERS=1).
 static const char* test_knob(const char* name) { return getenv(name); }
+static int verbose_level() { const char* e = getenv("TCGNN_VERBOSE"); return e ? atoi(e) : 0; }   // (read per build, not once: builds are rare, and tests switch it on)
 static constexpr int g_bucket_min_tiles = 2;   // tiles per (window, bucket) a bucket table needs
 static int g_lds_auto = [] { const char* e = test_knob("TCGNN_LDS_AUTO"); return e ? atoi(e) : 1; }();
 #ifdef TCGNN_DEBUG_TIMERS

@@ -1,5 +1,7 @@
-// tcgnn_lds_plan.inc - host side of the LDS-resident walks: passes per width, time models, window placement, build_lds_cells (the cell
-// streams), build_val_stream (the single-edge stream of the edge-valued walk).  Included by tcgnn_device.hip.
+// tcgnn_lds_plan.inc - host side of the LDS-resident walks: passes per width, time models, window placement (lds_place_windows),
+// build_lds_cells (a cell stream in named steps - cells_* - over one CellBuild, whose DevBufs own every allocation until cells_publish
+// hands the stream to the plan), release_cell_stream, build_val_stream (the single-edge stream of the edge-valued walk: val_source_stream,
+// build_lds_cells, val_index16).  Included by tcgnn_device.hip.
 // Cell stream of the LDS-resident column-range SpMM: per (workgroup, range, wavefront, window slot) the window's
 // condensed columns inside the range, re-tiled 32 to a tile.  Built from the packed tile stream (cols / mask).
 static int g_lds_maxw = [] { const char* e = test_knob("TCGNN_LDS_MAXW"); const int v = e ? atoi(e) : 0; return (v == 4 || v == 8) ? v : 0; }();   // 0: by width
@@ -59,14 +61,13 @@ static int lds_workgroups_unsplit(const tcgnn_plan* p, int maxw, int extra_slots
 // Hub windows: a wavefront owns whole windows, so a window whose tiles exceed a wavefront's fair share of the workgroup's work
 // is the critical path of every range (R-MAT, Reddit shape: the window of the sixteen top hubs holds 3.6 wavefront shares).
 // Such a window is SPLIT: k wavefronts of one workgroup each take every k-th run of its tiles in every range and their partial
-// sums are added through LDS, in a fixed order, at the end of the kernel.  parts[w] = k (1: whole).  Only on graphs that take the
-// graphs with hubs (lds_has_hubs); TCGNN_LDS_SPLIT=0 switches it off.
+// sums are added through LDS, in a fixed order, at the end of the kernel.  parts[w] = k (1: whole).  Only on graphs with hubs
+// (lds_has_hubs); TCGNN_LDS_PLACE=local keeps every window whole.
 static constexpr int kLdsMaxParts = 8, kLdsMaxFollowers = 32;   // (followers of a workgroup: 32 x NT KB of LDS scratch)
 static int lds_split_parts(const tcgnn_plan* p, int maxw, std::vector<uint8_t>* parts, const std::vector<double>* exact = nullptr) {
-    constexpr int enabled = 1;
     const int nw = p->nw_eff;
     if (parts) parts->assign((size_t)nw, 1);
-    if (!enabled || nw <= 0 || !lds_has_hubs(p)) return 0;
+    if (nw <= 0 || !lds_has_hubs(p)) return 0;
     const double nranges_d = std::max(1.0, std::ceil((double)p->Nc / (lds_buf_rows_for_maxw(maxw) - 8)));
     auto weight = [&](int w) { return exact ? (*exact)[(size_t)w] : lds_window_weight(p, w, nranges_d); };
     double total = 0;
@@ -222,9 +223,7 @@ static bool lds_place_windows(const tcgnn_plan* p, int nwg, int maxw, std::vecto
         if (nsplit == 0) parts_out.clear();
         return true;
     }
-    // weight of a window = the tiles it is likely to cost the LDS-resident walk: its condensed columns spread over the column
-    // ranges (a cell with a handful of columns still costs a whole tile step), not the column count alone
-    const std::vector<double>& wt = exact;
+    const std::vector<double>& wt = exact;   // (the tiles a window costs THIS stream: window_tiles_kernel)
     double total = 0;
     for (int w = 0; w < nw; ++w) total += wt[(size_t)w];
     std::vector<uint8_t> k;
@@ -245,15 +244,13 @@ static bool lds_place_windows(const tcgnn_plan* p, int nwg, int maxw, std::vecto
     double acc = 0;
     int wg = 0, blk_slots = 0, blk_fol = 0;
     bool ok = true;
-    constexpr int natural = 1;
     auto deal = [&]() {
         // Even windows are dealt in their own order (least loaded wavefront first = round-robin): a block that spans two communities
         // then gives every wavefront its share of both, and in a range of either community all sixteen are busy.  Sorting by
         // weight first is for blocks with windows far above the others.
         double mx = 0, sum = 0;
         for (const int32_t w : blk) { mx = std::max(mx, wt[(size_t)w]); sum += wt[(size_t)w]; }
-        if (!natural) std::stable_sort(blk.begin(), blk.end(), [&](int32_t x, int32_t y) { return wt[(size_t)x] > wt[(size_t)y]; });
-        else if (mx * (double)blk.size() > 1.5 * sum) {   // the windows far above the mean first, heaviest first; the others keep their order
+        if (mx * (double)blk.size() > 1.5 * sum) {   // the windows far above the mean first, heaviest first; the others keep their order
             const double heavy = 2.0 * sum / (double)blk.size();
             auto mid = std::stable_partition(blk.begin(), blk.end(), [&](int32_t x) { return wt[(size_t)x] > heavy; });
             std::stable_sort(blk.begin(), mid, [&](int32_t x, int32_t y) { return wt[(size_t)x] > wt[(size_t)y]; });
@@ -285,626 +282,721 @@ static bool lds_place_windows(const tcgnn_plan* p, int nwg, int maxw, std::vecto
     return ok;
 }
 
-static int build_lds_cells(tcgnn_plan* p, hipStream_t stream, int slot) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    if (p->lds[slot].nranges > 0) return TCGNN_OK;
-    if (p->nw_eff <= 0 || p->Nc <= 0) return fail(TCGNN_ERR_INVALID_ARG, "LDS-range SpMM: empty graph");
-    // the stream is cut from the packed tile stream (cols / mask) or, slot kLdsValSlot, from the single-edge one, whose K slots also
-    // carry the CSR position of their edge: that index follows every slot into the tiles (s_eidx / d_eidx)
-    const bool val = slot == kLdsValSlot;
-    if (val && !p->d_xwb_ptr) return fail(TCGNN_ERR_INVALID_ARG, "edge-valued LDS-resident SpMM: the single-edge stream has not been built");
-    const int64_t* const s_wb = val ? p->d_xwb_ptr : p->d_wb_ptr;
-    const int32_t* const s_cols = val ? p->d_xcols : p->d_cols;
-    const uint32_t* const s_mask = val ? p->d_xmask : p->d_mask;
-    const int32_t* const s_eidx = val ? p->d_xeidx : nullptr;
-    int32_t *d_eidx = nullptr, *d_cold_eidx = nullptr;
-    const int maxw = lds_stream_maxw(slot);
-    const int rows = lds_stream_buf_rows(slot) - 8;          // data rows of a range
-    const int nranges = (p->Nc + rows - 1) / rows;
-    const int per_wg = kLdsWaves * maxw;
-    const int nwg = lds_workgroups(p, maxw);
-    const int nw = nwg * per_wg;                              // window SLOTS of this stream
-    const int64_t ncell = (int64_t)nwg * nranges * per_wg;
-    uint32_t *d_cnt = nullptr, *d_firstq = nullptr, *d_tiles = nullptr;
-    int32_t* d_sorder = nullptr;
-    uint32_t* d_parts_guard = nullptr;   // (set below; freed by bail)
-    auto bail = [&](int rc) { (void)hipFree(d_cnt); (void)hipFree(d_firstq); (void)hipFree(d_tiles); (void)hipFree(d_sorder); (void)hipFree(d_parts_guard); return rc; };
-    // exact weight of every window in THIS stream: the tiles it will cost (at least one, so empty windows still take a slot's worth)
-    std::vector<double> exact((size_t)p->nw_eff, 1.0);
-    {
-        uint32_t* d_wt = nullptr;
-        std::vector<uint32_t> h_wt((size_t)p->nw_eff, 0u);
-        hipError_t e0 = hipMalloc(&d_wt, h_wt.size() * sizeof(uint32_t));
-        if (e0 == hipSuccess) e0 = hipMemsetAsync(d_wt, 0, h_wt.size() * sizeof(uint32_t), stream);
-        if (e0 == hipSuccess) {
-            const int64_t nth = (int64_t)p->nw_eff * nranges;
-            hipLaunchKernelGGL(window_tiles_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, stream, s_wb, s_cols, p->nw_eff, nranges, p->Nc, rows, d_wt);
-            e0 = hipGetLastError();
-        }
-        if (e0 == hipSuccess) e0 = hipMemcpyAsync(h_wt.data(), d_wt, h_wt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e0 == hipSuccess) e0 = hipStreamSynchronize(stream);
-        (void)hipFree(d_wt);
-        if (e0 != hipSuccess) return fail(e0 == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "window weights: %s", hipGetErrorString(e0));
-        for (size_t w = 0; w < h_wt.size(); ++w) exact[w] = std::max<double>(1.0, h_wt[w]);
-    }
-    // ---- candidate placements: window slots, columns per cell, columns and busiest-wavefront tiles per (workgroup, range) pair,
-    //      and from those an estimate of the kernel time (+ the cold remainder's); the cheapest is built
-    const int64_t npairs_all = (int64_t)nwg * nranges;
-    struct Cand {
-        int mode = kPlaceLocal, nsplit = 0;
-        uint32_t hot_min = 1u;
-        double est_us = 0;
-        std::vector<int32_t> sorder;
-        std::vector<uint32_t> sparts, paircols, pairmax, pairover, pairtiles;   // pairover: [2][pairs] columns beyond 32 / 64 per cell
-        uint32_t *d_cellcols = nullptr, *d_firstq = nullptr, *d_parts = nullptr;
-        int32_t* d_sorder = nullptr;
-        void release() { (void)hipFree(d_cellcols); (void)hipFree(d_firstq); (void)hipFree(d_parts); (void)hipFree(d_sorder); d_cellcols = d_firstq = d_parts = nullptr; d_sorder = nullptr; }
-    };
-    const char* const verbose_env0 = getenv("TCGNN_VERBOSE");
-    const bool verbose0 = verbose_env0 && atoi(verbose_env0) > 0;
-    auto prepare = [&](int mode, Cand& c) -> hipError_t {
-        c.mode = mode;
-        if (!lds_place_windows(p, nwg, maxw, c.sorder, c.sparts, c.nsplit, exact, mode)) {   // (a placement with parts that ran out of slots)
-            c.mode = kPlaceLocal;
-            if (!lds_place_windows(p, nwg, maxw, c.sorder, c.sparts, c.nsplit, exact, kPlaceLocal)) return hipErrorInvalidValue;
-        }
-        // threshold: a range step costs a workgroup ~1.7 us (8-window layout, two passes over 256 CUs: ~13 ns of chip time) or
-        // ~1 us (4-window layout, one pass: ~4 ns), a column in the gather walk ~10 ps of chip time.  Forcing the LDS-resident walk
-        // (mode 3: tests, timing) keeps every pair that holds a column, and so does the graph-wide placement (no locality to split
-        // on: every pair holds about the same share); TCGNN_LDS_HOT_COLS overrides.
-        c.hot_min = maxw == kLdsMaxW2 ? 1000u : 400u;
-        if (spmm_mode_of(p) == 3 || c.mode == kPlaceGlobal) c.hot_min = 1u;
-        if (const char* env = test_knob("TCGNN_LDS_HOT_COLS")) c.hot_min = (uint32_t)std::max(1, atoi(env));
-        uint32_t *d_pc = nullptr, *d_pm = nullptr, *d_po = nullptr, *d_pt = nullptr;
-        hipError_t e = hipMalloc(&c.d_cellcols, (size_t)(ncell + 1) * sizeof(uint32_t));
-        if (e == hipSuccess && c.nsplit > 0) {
-            e = hipMalloc(&c.d_parts, c.sparts.size() * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemcpyAsync(c.d_parts, c.sparts.data(), c.sparts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-        }
-        if (e == hipSuccess) e = hipMalloc(&c.d_firstq, (size_t)nw * nranges * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&c.d_sorder, c.sorder.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_pc, (size_t)npairs_all * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_pm, (size_t)npairs_all * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_po, (size_t)npairs_all * 2 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_pt, (size_t)npairs_all * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(c.d_sorder, c.sorder.data(), c.sorder.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(c.d_cellcols, 0, (size_t)(ncell + 1) * sizeof(uint32_t), stream);
-        std::vector<uint32_t>& pairmax = c.pairmax;
-        pairmax.resize((size_t)npairs_all);
-        c.paircols.resize((size_t)npairs_all);
-        c.pairover.resize((size_t)npairs_all * 2);
-        c.pairtiles.resize((size_t)npairs_all);
-        if (e == hipSuccess) {
-            const int64_t nthreads = (int64_t)nw * nranges;
-            hipLaunchKernelGGL(cell_count_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, stream, s_wb, c.d_sorder, s_cols, nw, nwg,
-                               nranges, p->Nc, maxw, rows, c.d_cellcols, c.d_firstq, c.d_parts);
-            hipLaunchKernelGGL(cell_pair_cols_kernel, dim3((unsigned)((npairs_all + 255) / 256)), dim3(256), 0, stream, c.d_cellcols, npairs_all, per_wg, maxw, d_pc, d_pm, d_po, d_pt);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(c.paircols.data(), d_pc, c.paircols.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c.pairover.data(), d_po, c.pairover.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c.pairtiles.data(), d_pt, c.pairtiles.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(pairmax.data(), d_pm, pairmax.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_pc); (void)hipFree(d_pm); (void)hipFree(d_po); (void)hipFree(d_pt);
-        if (e != hipSuccess) return e;
-        // every range ends at a barrier: a workgroup's time is the sum over its hot ranges of a fixed part and its busiest
-        // wavefront's tiles (constants of lds_estimate_us); the kernel lasts as long as its slowest workgroup, times the rounds
-        // beyond one workgroup per CU; the cold remainder's columns go through a gather walk at ~20 ps each.
-        const double rounds = std::max(1.0, std::ceil((double)nwg * (maxw == kLdsMaxW2 ? 2 : 1) / std::max(p->num_cus, 1)));
-        auto estimate = [&](uint32_t hot_min) {
-            double worst = 0, cold = 0;
-            for (int wg = 0; wg < nwg; ++wg) {
-                double t = 0;
-                for (int r = 0; r < nranges; ++r) {
-                    const size_t k = (size_t)wg * nranges + r;
-                    if (c.paircols[k] >= hot_min) t += 0.80 + 0.135 * pairmax[k]; else cold += c.paircols[k];
-                }
-                worst = std::max(worst, t);
-            }
-            return worst * rounds + cold * 20e-6;
-        };
-        c.est_us = estimate(c.hot_min);
-        if (verbose0 && c.mode != kPlaceGlobal)
-            for (uint32_t h : {1u, 125u, 250u, 500u, 1000u, 2000u}) fprintf(stderr, "[tcgnn]   placement %d, hot threshold %u: estimated %.0f us\n", c.mode, h, estimate(h));
-        return hipSuccess;
-    };
-    Cand best;
-    {
-        const int forced = lds_place_forced();
-        const bool hubs = lds_has_hubs(p);
-        hipError_t e0 = prepare(forced >= 0 ? forced : (hubs ? kPlaceGlobal : kPlaceLocal), best);
-        if (e0 == hipSuccess && forced < 0 && hubs) {
-            Cand other;
-            e0 = prepare(kPlaceLocalSplit, other);
-            if (verbose0) fprintf(stderr, "[tcgnn] cell stream %d: estimated %.0f us longest-first over the graph, %.0f us contiguous blocks (+ cold remainder)\n", slot, best.est_us, other.est_us);
-            if (e0 == hipSuccess && other.est_us < best.est_us) std::swap(best, other);
-            other.release();
-        }
-        if (e0 != hipSuccess) { best.release(); return fail(e0 == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell table: %s", hipGetErrorString(e0)); }
-    }
-    std::vector<int32_t>& sorder = best.sorder;
-    std::vector<uint32_t>& sparts = best.sparts;
-    const int nsplit = best.nsplit;
-    const uint32_t hot_min = best.hot_min;
-    const std::vector<uint32_t>& paircols = best.paircols;
-    uint32_t* d_parts = best.d_parts;
-    d_parts_guard = d_parts;
-    d_firstq = best.d_firstq;
-    d_sorder = best.d_sorder;
-    uint32_t* d_cellcols = best.d_cellcols;   // (the dense table of step one holds columns per cell)
-    hipError_t e = hipSuccess;
-    // ---- hot / cold: a (workgroup, range) pair is worth a range fill only if enough of the workgroup's columns fall into it
-    uint32_t* d_paircols = nullptr;
-    int32_t *d_kmap = nullptr, *d_rbase = nullptr, *d_rlist = nullptr;
-    uint32_t* d_coldcols = nullptr;
-    int64_t* d_cold_ptr = nullptr;
-    int32_t* d_ccols = nullptr;
-    uint32_t* d_cmask = nullptr;
-    uint32_t* d_flat = nullptr;
-    auto bail2 = [&](int rc) {
-        (void)hipFree(d_flat); (void)hipFree(d_paircols); (void)hipFree(d_kmap); (void)hipFree(d_rbase); (void)hipFree(d_rlist); (void)hipFree(d_cellcols); (void)hipFree(d_coldcols);
-        (void)hipFree(d_cold_ptr); (void)hipFree(d_ccols); (void)hipFree(d_cmask); (void)hipFree(d_eidx); (void)hipFree(d_cold_eidx);
-        return bail(rc);
-    };
-    e = hipMalloc(&d_kmap, (size_t)npairs_all * sizeof(int32_t));
-    if (e != hipSuccess) return bail2(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell table: %s", hipGetErrorString(e)));
-    std::vector<int32_t> kmap((size_t)npairs_all, -1), rbase((size_t)nwg + 1, 0), rlist;
-    int64_t hot_cols = 0, cold_cols = 0;
+// ---- build_lds_cells: a cell stream built in named steps over one CellBuild.  Every step is fallible and owns what it allocates
+// through the context's DevBufs; cells_publish, last, cannot fail: a failed build leaves the plan's slot exactly as it found it.
+
+// A candidate placement: window slots, columns per cell, columns and busiest-wavefront tiles per (workgroup, range) pair, and from
+// those an estimate of the kernel time (+ the cold remainder's); the cheapest is built.
+struct CellPlacement {
+    int mode = kPlaceLocal, nsplit = 0;
+    uint32_t hot_min = 1u;
+    double est_us = 0;
+    std::vector<int32_t> sorder;
+    std::vector<uint32_t> sparts, paircols, pairmax, pairover, pairtiles;   // pairover: [2][pairs] columns beyond 32 / 64 per cell
+    DevBuf<uint32_t> d_cellcols, d_firstq, d_parts;
+    DevBuf<int32_t> d_sorder;
+};
+// Entries of a flat stream (tcgnn_lds_flat.inc): per workgroup its normal entries first - one per hot pair, in range order - then
+// the dense entries of its dense pairs, grouped by pair.  ent2[2 k] = normal entry of pair k, ent2[2 k + 1] = its first dense entry
+// (-1: not a dense pair); entry numbers are global (a workgroup's entries are contiguous: wg_first).
+struct FlatEntries {
+    std::vector<int32_t> ent2, nd, wg_first;
+    std::vector<uint32_t> xbase, rl2;   // (records only) first extra tile of every cell among its wavefront's; the entry records
+    int64_t nentries = 0;
+};
+// Pure host function, no HIP call: the entry layout and - records - the entry records of a flat stream from the hot pairs (rbase,
+// rlist), the tiles of every hot cell (cnt) and the extra tiles of every pair's busiest wavefront (dense_mx; dense_on: dense pairs
+// get dense entries).
+static FlatEntries flat_entries(int nwg, int maxw, const std::vector<int32_t>& rbase, const std::vector<int32_t>& rlist, const std::vector<uint32_t>& cnt,
+                                const std::vector<uint32_t>& dense_mx, bool dense_on, bool records) {
+    FlatEntries f;
+    const int64_t npairs = rbase[(size_t)nwg];
+    f.ent2.assign((size_t)npairs * 2 + 2, -1); f.nd.assign((size_t)npairs, 0); f.wg_first.assign((size_t)nwg + 1, 0);
+    int32_t eidx = 0;
     for (int wg = 0; wg < nwg; ++wg) {
-        rbase[(size_t)wg] = (int32_t)rlist.size();
-        for (int r = 0; r < nranges; ++r) {
-            const uint32_t c = paircols[(size_t)wg * nranges + r];
-            if (c >= hot_min) { kmap[(size_t)wg * nranges + r] = (int32_t)rlist.size(); rlist.push_back(r); hot_cols += c; }
-            else cold_cols += c;
+        f.wg_first[(size_t)wg] = eidx;
+        for (int64_t k = rbase[(size_t)wg]; k < rbase[(size_t)wg + 1]; ++k) f.ent2[(size_t)k * 2] = eidx++;
+        for (int64_t k = rbase[(size_t)wg]; k < rbase[(size_t)wg + 1]; ++k) {
+            f.nd[(size_t)k] = dense_on ? (int32_t)((dense_mx[(size_t)k] + maxw - 1) / maxw) : 0;
+            f.ent2[(size_t)k * 2 + 1] = f.nd[(size_t)k] ? eidx : -1;
+            eidx += f.nd[(size_t)k];
         }
     }
-    rbase[(size_t)nwg] = (int32_t)rlist.size();
-    const int64_t npairs = (int64_t)rlist.size();
+    f.wg_first[(size_t)nwg] = eidx;
+    f.nentries = eidx;
+    if (!records) return f;
+    const std::vector<int32_t>& nd = f.nd;
+    std::vector<uint32_t>& xbase = f.xbase;
+    if (dense_on) {
+        xbase.assign((size_t)(npairs * kLdsWaves * maxw), 0u);
+        for (int64_t k = 0; k < npairs; ++k) {
+            if (!nd[(size_t)k]) continue;
+            for (int v = 0; v < kLdsWaves; ++v) {
+                uint32_t run = 0;
+                for (int j = 0; j < maxw; ++j) { const size_t c = (size_t)((k * kLdsWaves + v) * maxw + j); xbase[c] = run; run += cnt[c] > 1u ? cnt[c] - 1u : 0u; }
+            }
+        }
+    }
+    // entry words: w0 = range | bit 31 dense | bit 30 another range than the entry before; w1 = dense: tiles per window slot;
+    // w2 = range to fetch at the top of the entry (~0: none); w3 = 0
+    // (layout: [entries][4] records - w0, w2, normal entries of the workgroup, 0: the same for every wavefront, 16 bytes per entry,
+    //  L2-resident - followed by [entries][16 wavefronts] descriptor words w1, read in the dense phase only.  The kernels load the
+    //  FIRST TWO words of a record and use both: a loaded word nobody reads is a register the allocator hands to another value
+    //  while the load is in flight, and hipcc then waits vmcnt(0) before writing it - at the top of every entry, right behind the
+    //  range fill (r05: the edge-valued walk ran 26 % slower for one such word, the remainder layouts of the binary walk too).
+    //  A per-(entry, wavefront) record of all three words was 10 MB per stream and a DRAM miss per wavefront and entry: the uniform
+    //  Reddit shape ran 5 % slower for it)
+    const int64_t nrec = std::max<int64_t>(f.nentries, 1);
+    f.rl2.assign((size_t)nrec * (4 + kLdsWaves), 0u);
+    auto put = [&](int64_t en, int v, uint32_t w0, uint32_t w1, uint32_t w2) {
+        uint32_t* q = &f.rl2[(size_t)(en * 4)];
+        q[0] = w0; q[1] = w2; q[3] = 0u;   // (q[2]: normal entries of the entry's workgroup, written below)
+        f.rl2[(size_t)(nrec * 4 + en * kLdsWaves + v)] = w1;
+    };
+    for (int wg = 0; wg < nwg; ++wg)   // record word 2: how many NORMAL entries the entry's workgroup has (its dense entries follow them: val_permute_kernel)
+        for (int64_t en = f.wg_first[(size_t)wg]; en < f.wg_first[(size_t)wg + 1]; ++en) f.rl2[(size_t)(en * 4 + 2)] = (uint32_t)(rbase[(size_t)wg + 1] - rbase[(size_t)wg]);
+    for (int wg = 0; wg < nwg; ++wg) {
+        const int64_t k0 = rbase[(size_t)wg], k1 = rbase[(size_t)wg + 1];
+        std::vector<int64_t> dk;   // the workgroup's dense pairs, in order
+        for (int64_t k = k0; k < k1; ++k) if (nd[(size_t)k]) dk.push_back(k);
+        for (int64_t k = k0; k < k1; ++k) {
+            const uint32_t r = (uint32_t)rlist[(size_t)k];
+            const uint32_t nextr = k + 1 < k1 ? (uint32_t)rlist[(size_t)k + 1] : (dk.empty() ? 0xffffffffu : (uint32_t)rlist[(size_t)dk[0]]);
+            for (int v = 0; v < kLdsWaves; ++v) put(f.ent2[(size_t)k * 2], v, r | (k > k0 ? 0x40000000u : 0u), 0u, nextr);
+        }
+        for (size_t gi = 0; gi < dk.size(); ++gi) {
+            const int64_t k = dk[gi];
+            const uint32_t r = (uint32_t)rlist[(size_t)k];
+            const uint32_t nextr = gi + 1 < dk.size() ? (uint32_t)rlist[(size_t)dk[gi + 1]] : 0xffffffffu;
+            for (int64_t d = 0; d < nd[(size_t)k]; ++d)
+                for (int v = 0; v < kLdsWaves; ++v) {
+                    uint32_t desc = 0u;   // tiles of every window slot among this wavefront's extras [maxw d, maxw (d + 1))
+                    for (int j = 0; j < maxw; ++j) {
+                        const size_t c = (size_t)((k * kLdsWaves + v) * maxw + j);
+                        const int64_t lo = xbase[c], hi = lo + (cnt[c] > 1u ? cnt[c] - 1u : 0u);
+                        const int64_t a0 = std::max<int64_t>(lo, d * maxw), a1 = std::min<int64_t>(hi, (d + 1) * maxw);
+                        if (a1 > a0) desc |= (uint32_t)(a1 - a0) << (4 * j);
+                    }
+                    put(f.ent2[(size_t)k * 2 + 1] + d, v, r | 0x80000000u | (d == 0 ? 0x40000000u : 0u), desc, d == 0 ? nextr : 0xffffffffu);
+                }
+        }
+    }
+    return f;
+}
+
+// The build context: what the stream is cut from, its geometry, the host tables the steps hand each other (they also outlive the
+// copies enqueued from them) and the device buffers still alive.  What is left in it when the build returns is freed.
+struct CellBuild {
+    tcgnn_plan* p; hipStream_t stream; int slot;
+    // the source: the packed tile stream (cols / mask) or, slot kLdsValSlot, the single-edge one, whose K slots also carry the CSR
+    // position of their edge: that index follows every slot into the tiles (s_eidx / d_eidx)
+    bool val;
+    const int64_t* s_wb; const int32_t* s_cols; const uint32_t* s_mask; const int32_t* s_eidx;
+    int maxw, rows, nranges, per_wg, nwg, nw;   // rows: data rows of a range; nw: window SLOTS of this stream
+    int64_t ncell, npairs_all;
+    bool verbose;
+    // host tables, in the order the steps fill them
+    std::vector<double> exact;                      // exact weight of every window in THIS stream: the tiles it will cost
+    CellPlacement best;
+    std::vector<int32_t> kmap, rbase, rlist;        // hot pairs: compact number of pair (wg, range) or -1; per workgroup; their ranges
+    int64_t npairs = 0, ncell_hot = 0, hot_cols = 0, cold_cols = 0;
+    std::vector<uint32_t> cnt;                      // tiles of every hot cell (ordinary count); an ordinary stream's cell table once summed
+    std::vector<uint32_t> dense_mx;                 // extra tiles of the pair's busiest wavefront (0: not a dense pair)
+    int64_t over_dense = 0, dense_steps = 0, ndense_pairs = 0, ndense_entries = 0;
+    int flat_tpc = 0;
+    int64_t over_cols = 0;
+    FlatEntries ent;
+    int64_t ntiles = 0, nwords = 0, cold_tiles = 0, cold_max = 0;
+    std::vector<int64_t> cptr;                      // first cold tile of every window
+    std::vector<int32_t> wptr;
+    std::vector<uint32_t> wlist;
+    // device buffers (the placement's are in best)
+    DevBuf<int32_t> d_kmap, d_rbase, d_rlist, d_ent, d_ccols, d_eidx, d_cold_eidx, d_wcold_ptr;
+    DevBuf<uint32_t> d_cnt, d_tiles, d_flat, d_rl2, d_xbase, d_cmask, d_wcold;
+    DevBuf<int64_t> d_cold_ptr;
+    bool with_dense() const { return flat_tpc == 1 && ndense_pairs > 0; }
+};
+
+// step 1: exact weight of every window (window_tiles_kernel; at least one, so empty windows still take a slot's worth)
+static int cells_window_weights(CellBuild& b) {
+    const tcgnn_plan* p = b.p;
+    b.exact.assign((size_t)p->nw_eff, 1.0);
+    DevBuf<uint32_t> d_wt;
+    std::vector<uint32_t> h_wt((size_t)p->nw_eff, 0u);
+    hipError_t e = d_wt.alloc(h_wt.size());
+    if (e == hipSuccess) e = hipMemsetAsync(d_wt, 0, h_wt.size() * sizeof(uint32_t), b.stream);
+    if (e == hipSuccess) {
+        const int64_t nth = (int64_t)p->nw_eff * b.nranges;
+        hipLaunchKernelGGL(window_tiles_kernel, dim3((unsigned)((nth + 255) / 256)), dim3(256), 0, b.stream, b.s_wb, b.s_cols, p->nw_eff, b.nranges, p->Nc, b.rows, d_wt.ptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(h_wt.data(), d_wt, h_wt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    if (e != hipSuccess) return fail(hip_rc(e), "window weights: %s", hipGetErrorString(e));
+    for (size_t w = 0; w < h_wt.size(); ++w) b.exact[w] = std::max<double>(1.0, h_wt[w]);
+    return TCGNN_OK;
+}
+// step 2a: one candidate: the placement (host), its count tables (cell_count_kernel, cell_pair_cols_kernel) and its estimate
+static hipError_t cells_prepare_placement(const CellBuild& b, int mode, CellPlacement& c) {
+    const tcgnn_plan* p = b.p;
+    const int nwg = b.nwg, nranges = b.nranges, maxw = b.maxw;
+    const int64_t npairs_all = b.npairs_all;
+    c.mode = mode;
+    if (!lds_place_windows(p, nwg, maxw, c.sorder, c.sparts, c.nsplit, b.exact, mode)) {   // (a placement with parts that ran out of slots)
+        c.mode = kPlaceLocal;
+        if (!lds_place_windows(p, nwg, maxw, c.sorder, c.sparts, c.nsplit, b.exact, kPlaceLocal)) return hipErrorInvalidValue;
+    }
+    // threshold: a range step costs a workgroup ~1.7 us (8-window layout, two passes over 256 CUs: ~13 ns of chip time) or
+    // ~1 us (4-window layout, one pass: ~4 ns), a column in the gather walk ~10 ps of chip time.  Forcing the LDS-resident walk
+    // (mode 3: tests, timing) keeps every pair that holds a column, and so does the graph-wide placement (no locality to split
+    // on: every pair holds about the same share); TCGNN_LDS_HOT_COLS overrides.
+    c.hot_min = maxw == kLdsMaxW2 ? 1000u : 400u;
+    if (spmm_mode_of(p) == 3 || c.mode == kPlaceGlobal) c.hot_min = 1u;
+    if (const char* env = test_knob("TCGNN_LDS_HOT_COLS")) c.hot_min = (uint32_t)std::max(1, atoi(env));
+    DevBuf<uint32_t> d_pc, d_pm, d_po, d_pt;
+    hipError_t e = c.d_cellcols.alloc((size_t)(b.ncell + 1));
+    if (e == hipSuccess && c.nsplit > 0) {
+        e = c.d_parts.alloc(c.sparts.size());
+        if (e == hipSuccess) e = hipMemcpyAsync(c.d_parts, c.sparts.data(), c.sparts.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b.stream);
+    }
+    if (e == hipSuccess) e = c.d_firstq.alloc((size_t)b.nw * nranges);
+    if (e == hipSuccess) e = c.d_sorder.alloc(c.sorder.size());
+    if (e == hipSuccess) e = d_pc.alloc((size_t)npairs_all);
+    if (e == hipSuccess) e = d_pm.alloc((size_t)npairs_all);
+    if (e == hipSuccess) e = d_po.alloc((size_t)npairs_all * 2);
+    if (e == hipSuccess) e = d_pt.alloc((size_t)npairs_all);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.d_sorder, c.sorder.data(), c.sorder.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c.d_cellcols, 0, (size_t)(b.ncell + 1) * sizeof(uint32_t), b.stream);
+    c.pairmax.resize((size_t)npairs_all);
+    c.paircols.resize((size_t)npairs_all);
+    c.pairover.resize((size_t)npairs_all * 2);
+    c.pairtiles.resize((size_t)npairs_all);
+    if (e == hipSuccess) {
+        const int64_t nthreads = (int64_t)b.nw * nranges;
+        hipLaunchKernelGGL(cell_count_kernel, dim3((unsigned)((nthreads + 255) / 256)), dim3(256), 0, b.stream, b.s_wb, c.d_sorder.ptr, b.s_cols, b.nw, nwg,
+                           nranges, p->Nc, maxw, b.rows, c.d_cellcols.ptr, c.d_firstq.ptr, c.d_parts.ptr);
+        hipLaunchKernelGGL(cell_pair_cols_kernel, dim3((unsigned)((npairs_all + 255) / 256)), dim3(256), 0, b.stream, c.d_cellcols.ptr, npairs_all, b.per_wg, maxw, d_pc.ptr, d_pm.ptr,
+                           d_po.ptr, d_pt.ptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(c.paircols.data(), d_pc, c.paircols.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.pairover.data(), d_po, c.pairover.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.pairtiles.data(), d_pt, c.pairtiles.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(c.pairmax.data(), d_pm, c.pairmax.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    if (e != hipSuccess) return e;
+    // every range ends at a barrier: a workgroup's time is the sum over its hot ranges of a fixed part and its busiest
+    // wavefront's tiles (constants of lds_estimate_us); the kernel lasts as long as its slowest workgroup, times the rounds
+    // beyond one workgroup per CU; the cold remainder's columns go through a gather walk at ~20 ps each.
+    const double rounds = std::max(1.0, std::ceil((double)nwg * (maxw == kLdsMaxW2 ? 2 : 1) / std::max(p->num_cus, 1)));
+    auto estimate = [&](uint32_t hot_min) {
+        double worst = 0, cold = 0;
+        for (int wg = 0; wg < nwg; ++wg) {
+            double t = 0;
+            for (int r = 0; r < nranges; ++r) {
+                const size_t k = (size_t)wg * nranges + r;
+                if (c.paircols[k] >= hot_min) t += 0.80 + 0.135 * c.pairmax[k]; else cold += c.paircols[k];
+            }
+            worst = std::max(worst, t);
+        }
+        return worst * rounds + cold * 20e-6;
+    };
+    c.est_us = estimate(c.hot_min);
+    if (b.verbose && c.mode != kPlaceGlobal)
+        for (uint32_t h : {1u, 125u, 250u, 500u, 1000u, 2000u}) fprintf(stderr, "[tcgnn]   placement %d, hot threshold %u: estimated %.0f us\n", c.mode, h, estimate(h));
+    return hipSuccess;
+}
+// step 2: the placement that is built: the forced one, contiguous blocks for graphs without hubs, else the cheaper of longest-first
+// over the graph and contiguous blocks with split hub windows
+static int cells_choose_placement(CellBuild& b) {
+    const int forced = lds_place_forced();
+    const bool hubs = lds_has_hubs(b.p);
+    hipError_t e = cells_prepare_placement(b, forced >= 0 ? forced : (hubs ? kPlaceGlobal : kPlaceLocal), b.best);
+    if (e == hipSuccess && forced < 0 && hubs) {
+        CellPlacement other;
+        e = cells_prepare_placement(b, kPlaceLocalSplit, other);
+        if (b.verbose) fprintf(stderr, "[tcgnn] cell stream %d: estimated %.0f us longest-first over the graph, %.0f us contiguous blocks (+ cold remainder)\n", b.slot, b.best.est_us, other.est_us);
+        if (e == hipSuccess && other.est_us < b.best.est_us) std::swap(b.best, other);
+    }
+    if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 3: hot / cold: a (workgroup, range) pair is worth a range fill only if enough of the workgroup's columns fall into it.  Then
+// the tiles of every hot cell (ordinary count: ceil(columns / 32); cell_compact_kernel) on the host: the ordinary stream's cell
+// table is their prefix sum, and a flat stream's DENSE entries (tcgnn_lds_flat.inc) are laid out from them
+static int cells_hot_pairs(CellBuild& b) {
+    const std::vector<uint32_t>& paircols = b.best.paircols;
+    hipError_t e = b.d_kmap.alloc((size_t)b.npairs_all);
+    if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
+    b.kmap.assign((size_t)b.npairs_all, -1); b.rbase.assign((size_t)b.nwg + 1, 0);
+    std::vector<int32_t>& rlist = b.rlist;
+    for (int wg = 0; wg < b.nwg; ++wg) {
+        b.rbase[(size_t)wg] = (int32_t)rlist.size();
+        for (int r = 0; r < b.nranges; ++r) {
+            const uint32_t c = paircols[(size_t)wg * b.nranges + r];
+            if (c >= b.best.hot_min) { b.kmap[(size_t)wg * b.nranges + r] = (int32_t)rlist.size(); rlist.push_back(r); b.hot_cols += c; }
+            else b.cold_cols += c;
+        }
+    }
+    b.rbase[(size_t)b.nwg] = (int32_t)rlist.size();
+    b.npairs = (int64_t)rlist.size();
     rlist.resize(rlist.size() + 4, 0);
-    const int64_t ncell_hot = npairs * per_wg;
-    e = hipMalloc(&d_cnt, (size_t)(ncell_hot + 1) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_rbase, rbase.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&d_rlist, rlist.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, (size_t)(ncell_hot + 1) * sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_kmap, kmap.data(), kmap.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rbase, rbase.data(), rbase.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rlist, rlist.data(), rlist.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return bail2(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell table: %s", hipGetErrorString(e)));
-    // ---- tiles of every hot cell (ordinary count: ceil(columns / 32)) on the host: the ordinary stream's cell table is their prefix
-    //      sum, and a flat stream's DENSE entries (tcgnn_lds_flat.inc) are laid out from them
-    if (ncell > 0) hipLaunchKernelGGL(cell_compact_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, stream, d_cellcols, d_kmap, npairs_all, per_wg, d_cnt);
-    std::vector<uint32_t> cnt((size_t)ncell_hot + 1);
+    b.ncell_hot = b.npairs * b.per_wg;
+    e = b.d_cnt.alloc((size_t)(b.ncell_hot + 1));
+    if (e == hipSuccess) e = b.d_rbase.alloc(b.rbase.size());
+    if (e == hipSuccess) e = b.d_rlist.alloc(rlist.size());
+    if (e == hipSuccess) e = hipMemsetAsync(b.d_cnt, 0, (size_t)(b.ncell_hot + 1) * sizeof(uint32_t), b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d_kmap, b.kmap.data(), b.kmap.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d_rbase, b.rbase.data(), b.rbase.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d_rlist, rlist.data(), rlist.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+    if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
+    if (b.ncell > 0) hipLaunchKernelGGL(cell_compact_kernel, dim3((unsigned)((b.ncell + 255) / 256)), dim3(256), 0, b.stream, b.best.d_cellcols.ptr, b.d_kmap.ptr, b.npairs_all, b.per_wg, b.d_cnt.ptr);
+    b.cnt.resize((size_t)b.ncell_hot + 1);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return bail2(fail(TCGNN_ERR_HIP, "cell count: %s", hipGetErrorString(e)));
-    // ---- dense pairs (flat streams with one tile per cell): a hot pair whose cells overflow their one tile by `dense_min` columns
-    //      or more keeps ALL its columns in the LDS-resident walk - the tiles beyond each cell's first go into dense entries behind
-    //      the pair's normal entry, T = maxw of them per wavefront and entry - instead of leaving them to the cold remainder.
-    //      (a community's own ranges on the SBM calibrated to real Reddit: ~27 000 overflow columns per pair against ~2 elsewhere;
-    //       a thin overflow is better off re-condensed per window across all ranges: 32 columns to a cold tile, whatever their range)
-    // ... and so does a pair in which SOME cell holds three tiles or more (a workgroup at a community's border has one or two windows
-    // in it: their six dense cells are 40 cold tiles for one window - the trial below sent the whole stream back to the ordinary
-    // format for them; on the uniform graph a 65-column cell does not occur)
+    if (e == hipSuccess) e = hipMemcpyAsync(b.cnt.data(), b.d_cnt, b.cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "cell count: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 4 (host): dense pairs (flat streams with one tile per cell): a hot pair whose cells overflow their one tile by `dense_min`
+// columns or more keeps ALL its columns in the LDS-resident walk - the tiles beyond each cell's first go into dense entries behind
+// the pair's normal entry, T = maxw of them per wavefront and entry - instead of leaving them to the cold remainder.
+// (a community's own ranges on the SBM calibrated to real Reddit: ~27 000 overflow columns per pair against ~2 elsewhere;
+//  a thin overflow is better off re-condensed per window across all ranges: 32 columns to a cold tile, whatever their range)
+// ... and so does a pair in which SOME cell holds three tiles or more (a workgroup at a community's border has one or two windows
+// in it: their six dense cells are 40 cold tiles for one window - the hub-row trial sent the whole stream back to the ordinary
+// format for them; on the uniform graph a 65-column cell does not occur)
+static void cells_dense_pairs(CellBuild& b) {
+    const int maxw = b.maxw;
     uint32_t dense_min = 1024u, dense_cell_tiles = 3u;
     if (const char* env = test_knob("TCGNN_LDS_DENSE_COLS")) { dense_min = (uint32_t)std::max(1, atoi(env)); dense_cell_tiles = 0xffffffffu; }   // (tests: dense entries on graphs the oracle can handle)
-    if (!flat_dense_ok(lds_stream_nt(slot), maxw, 1)) dense_min = dense_cell_tiles = 0xffffffffu;   // (layouts whose kernel has no dense walk)
-    std::vector<int64_t> kall_of((size_t)npairs, 0);
-    for (int64_t ka = 0; ka < npairs_all; ++ka) if (kmap[(size_t)ka] >= 0) kall_of[(size_t)kmap[(size_t)ka]] = ka;
-    std::vector<uint32_t> dense_mx((size_t)npairs, 0u);   // extra tiles of the pair's busiest wavefront (0: not a dense pair)
-    int64_t over_dense = 0, dense_steps = 0, ndense_pairs = 0, ndense_entries = 0;
-    for (int64_t k = 0; k < npairs; ++k) {
+    if (!flat_dense_ok(lds_stream_nt(b.slot), maxw, 1)) dense_min = dense_cell_tiles = 0xffffffffu;   // (layouts whose kernel has no dense walk)
+    std::vector<int64_t> kall_of((size_t)b.npairs, 0);
+    for (int64_t ka = 0; ka < b.npairs_all; ++ka) if (b.kmap[(size_t)ka] >= 0) kall_of[(size_t)b.kmap[(size_t)ka]] = ka;
+    b.dense_mx.assign((size_t)b.npairs, 0u);
+    for (int64_t k = 0; k < b.npairs; ++k) {
         if (dense_min == 0xffffffffu && dense_cell_tiles == 0xffffffffu) break;
         uint32_t mx = 0, cell_mx = 0;
         for (int v = 0; v < kLdsWaves; ++v) {
             uint32_t ex = 0;
-            for (int j = 0; j < maxw; ++j) { const uint32_t c = cnt[(size_t)((k * kLdsWaves + v) * maxw + j)]; ex += c > 1u ? c - 1u : 0u; cell_mx = std::max(cell_mx, c); }
+            for (int j = 0; j < maxw; ++j) { const uint32_t c = b.cnt[(size_t)((k * kLdsWaves + v) * maxw + j)]; ex += c > 1u ? c - 1u : 0u; cell_mx = std::max(cell_mx, c); }
             mx = std::max(mx, ex);
         }
-        if (!mx || (best.pairover[(size_t)kall_of[(size_t)k]] < dense_min && cell_mx < dense_cell_tiles)) continue;
-        dense_mx[(size_t)k] = mx;
-        over_dense += best.pairover[(size_t)kall_of[(size_t)k]];
-        dense_steps += mx; ++ndense_pairs; ndense_entries += (mx + maxw - 1) / maxw;
+        if (!mx || (b.best.pairover[(size_t)kall_of[(size_t)k]] < dense_min && cell_mx < dense_cell_tiles)) continue;
+        b.dense_mx[(size_t)k] = mx;
+        b.over_dense += b.best.pairover[(size_t)kall_of[(size_t)k]];
+        b.dense_steps += mx; ++b.ndense_pairs; b.ndense_entries += (mx + maxw - 1) / maxw;
     }
-    // ---- flat or ordinary (tcgnn_lds_flat.inc): a flat stream gives every cell of a hot pair exactly tpc tiles and sends what
-    //      a cell holds beyond 32 tpc columns to the cold remainder (one tile per cell: or, for dense pairs, to dense entries).
-    //      Taken when that costs few columns (the cold remainder of a
-    //      flat stream is added by a latency-bound kernel) and no more tile steps than the ordinary stream's; never with split
-    //      hub windows (their cells are nowhere near uniform).  TCGNN_LDS_FLAT=0 / 1 / 2 forces ordinary / one / two tiles per cell.
-    int flat_tpc = 0;
-    int64_t over_cols = 0;
-    {
-        // (what a range lasts is its busiest wavefront's tile steps - every range ends at a barrier: pairmax for the ordinary
-        //  stream, maxw x tpc for a flat one, whose empty window slots are skipped but whose wavefronts all wait for a full one)
-        int64_t classic_tiles = 0, classic_steps = 0, over[2] = {0, 0};
-        for (int64_t k = 0; k < npairs_all; ++k)
-            if (kmap[(size_t)k] >= 0) { classic_tiles += best.pairtiles[(size_t)k]; classic_steps += best.pairmax[(size_t)k];
-                                        over[0] += best.pairover[(size_t)k]; over[1] += best.pairover[(size_t)(npairs_all + k)]; }
-        const char* fenv = test_knob("TCGNN_LDS_FLAT");
-        const int forced_flat = fenv ? atoi(fenv) : -1;
-        if (nsplit == 0 && npairs > 0 && forced_flat != 0) {
-            double best_cost = 0.0;
-            for (int tpc = 1; tpc <= 2; ++tpc) {
-                if (maxw * tpc > 16 || (val && tpc != 1)) break;   // (spmm_lds_val_kernel walks one tile per cell only)
-                // (one tile per cell: the overflow of the dense pairs stays in the walk, as dense entries; their steps count)
-                const int64_t kept = tpc == 1 ? over_dense : 0, extra_steps = tpc == 1 ? dense_steps : 0;
-                const bool few_cold = (double)(cold_cols + over[tpc - 1] - kept) <= 0.04 * (double)std::max<int64_t>(hot_cols + cold_cols, 1);
-                // (a flat step costs ~0.75 of an ordinary one - 1.46 against 1.84 us per range of ~8 steps on the Reddit shape - and a
-                //  stream of nearly-empty cells, a wide row shard, ties on the count: 627 712 flat steps against 627 699)
-                const bool no_more_steps = (double)(npairs * maxw * tpc + extra_steps) <= 1.2 * (double)std::max<int64_t>(classic_steps, 1);
-                if (forced_flat == tpc) { flat_tpc = tpc; over_cols = over[tpc - 1] - kept; break; }
-                if (forced_flat >= 0 || !few_cold || !no_more_steps) continue;
-                // Both forms may qualify - the one-plane layout on the Reddit shape: 51 columns per 1 528-row cell, which one tile per cell
-                // only holds with 93 % of the pairs dense (0.40 ms) and two tiles per cell hold as they are (0.21 ms) - so they are
-                // priced: a flat step = 1, a dense entry's run-time step ~1.6 (31 instructions against 19), + ~4 steps per dense entry
-                // (its barrier, metadata block and descriptor words).  Dense entries are for the EXCEPTIONS of a stream.
-                const double cost = (double)(npairs * maxw * tpc) + (tpc == 1 ? 1.6 * (double)dense_steps + 4.0 * (double)ndense_entries : 0.0);
-                if (!flat_tpc || cost < best_cost) { flat_tpc = tpc; over_cols = over[tpc - 1] - kept; best_cost = cost; }
-            }
-        }
-        if (verbose0) fprintf(stderr, "[tcgnn] cell stream %d: %lld tiles ordinary, %lld steps of the busiest wavefronts; flat would take %lld steps (+%lld columns cold; %lld dense pairs keep %lld columns "
-                                      "in %lld dense entries, %lld steps) / %lld (+%lld): %s\n", slot,
-                              (long long)classic_tiles, (long long)classic_steps, (long long)(npairs * maxw), (long long)(over[0] - over_dense), (long long)ndense_pairs, (long long)over_dense,
-                              (long long)ndense_entries, (long long)dense_steps, (long long)(2 * npairs * maxw), (long long)over[1],
-                              flat_tpc ? (flat_tpc == 1 ? "flat, 1 tile per cell" : "flat, 2 tiles per cell") : "ordinary");
-    }
-    // ---- entries of a flat stream (tcgnn_lds_flat.inc): per workgroup its normal entries first - one per hot pair, in range order -
-    //      then the dense entries of its dense pairs, grouped by pair.  ent2[2 k] = normal entry of pair k, ent2[2 k + 1] = its
-    //      first dense entry (-1: not a dense pair); entry numbers are global (a workgroup's entries are contiguous).
-    std::vector<int32_t> ent2((size_t)npairs * 2 + 2, -1), nd((size_t)npairs, 0), wg_first((size_t)nwg + 1, 0);
-    auto layout_entries = [&](bool dense_on) {
-        int32_t eidx = 0;
-        for (int wg = 0; wg < nwg; ++wg) {
-            wg_first[(size_t)wg] = eidx;
-            for (int64_t k = rbase[(size_t)wg]; k < rbase[(size_t)wg + 1]; ++k) ent2[(size_t)k * 2] = eidx++;
-            for (int64_t k = rbase[(size_t)wg]; k < rbase[(size_t)wg + 1]; ++k) {
-                nd[(size_t)k] = dense_on ? (int32_t)((dense_mx[(size_t)k] + maxw - 1) / maxw) : 0;
-                ent2[(size_t)k * 2 + 1] = nd[(size_t)k] ? eidx : -1;
-                eidx += nd[(size_t)k];
-            }
-        }
-        wg_first[(size_t)nwg] = eidx;
-        return eidx;
-    };
-    (void)layout_entries(flat_tpc == 1 && ndense_pairs > 0);
-    int32_t* d_ent = nullptr;
-    uint32_t *d_xbase = nullptr, *d_rl2 = nullptr;
-    auto bail3 = [&](int rc) { (void)hipFree(d_ent); (void)hipFree(d_xbase); (void)hipFree(d_rl2); return bail2(rc); };
-    if (flat_tpc == 1 && ndense_pairs > 0) {   // (the cold-remainder counts below leave the dense pairs' overflow out: they read the table)
-        e = hipMalloc(&d_ent, ent2.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_ent, ent2.data(), ent2.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "flat stream entries: %s", hipGetErrorString(e)));
-    }
-    if (flat_tpc && !test_knob("TCGNN_LDS_FLAT")) {
-        // ... nor where ONE window would leave a long remainder behind (a hub row: its cells overflow in every range, and the
-        // remainder of a window is one wavefront's serial work - a 24 k-degree hub cost the flat walk 0.72 ms against 0.61):
-        // the remainder is counted with the flat cap before anything is built
-        uint32_t* d_trial = nullptr;
-        std::vector<uint32_t> trial((size_t)p->nw_eff, 0u);
-        e = hipMalloc(&d_trial, trial.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_trial, 0, trial.size() * sizeof(uint32_t), stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(cell_cold_count_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, d_cellcols, d_kmap, d_sorder, nw, nranges, maxw, d_trial, (uint32_t)(32 * flat_tpc), d_ent);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(trial.data(), d_trial, trial.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_trial);
-        if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell table: %s", hipGetErrorString(e)));
-        uint32_t worst = 0;
-        for (uint32_t c : trial) worst = std::max(worst, (c + 31u) / 32u);
-        if (worst > 16u) {
-            if (verbose0) fprintf(stderr, "[tcgnn] cell stream %d: ordinary after all - one window would leave %u cold tiles behind\n", slot, worst);
-            flat_tpc = 0; over_cols = 0;
+}
+// step 5 (host): flat or ordinary (tcgnn_lds_flat.inc): a flat stream gives every cell of a hot pair exactly tpc tiles and sends
+// what a cell holds beyond 32 tpc columns to the cold remainder (one tile per cell: or, for dense pairs, to dense entries).  Taken
+// when that costs few columns (the cold remainder of a flat stream is added by a latency-bound kernel) and no more tile steps than
+// the ordinary stream's; never with split hub windows (their cells are nowhere near uniform).  TCGNN_LDS_FLAT=0 / 1 / 2 forces
+// ordinary / one / two tiles per cell.
+static void cells_flat_or_ordinary(CellBuild& b) {
+    const CellPlacement& best = b.best;
+    const int maxw = b.maxw;
+    const int64_t npairs = b.npairs, npairs_all = b.npairs_all;
+    // (what a range lasts is its busiest wavefront's tile steps - every range ends at a barrier: pairmax for the ordinary
+    //  stream, maxw x tpc for a flat one, whose empty window slots are skipped but whose wavefronts all wait for a full one)
+    int64_t classic_tiles = 0, classic_steps = 0, over[2] = {0, 0};
+    for (int64_t k = 0; k < npairs_all; ++k)
+        if (b.kmap[(size_t)k] >= 0) { classic_tiles += best.pairtiles[(size_t)k]; classic_steps += best.pairmax[(size_t)k];
+                                      over[0] += best.pairover[(size_t)k]; over[1] += best.pairover[(size_t)(npairs_all + k)]; }
+    const char* fenv = test_knob("TCGNN_LDS_FLAT");
+    const int forced_flat = fenv ? atoi(fenv) : -1;
+    if (best.nsplit == 0 && npairs > 0 && forced_flat != 0) {
+        double best_cost = 0.0;
+        for (int tpc = 1; tpc <= 2; ++tpc) {
+            if (maxw * tpc > 16 || (b.val && tpc != 1)) break;   // (spmm_lds_val_kernel walks one tile per cell only)
+            // (one tile per cell: the overflow of the dense pairs stays in the walk, as dense entries; their steps count)
+            const int64_t kept = tpc == 1 ? b.over_dense : 0, extra_steps = tpc == 1 ? b.dense_steps : 0;
+            const bool few_cold = (double)(b.cold_cols + over[tpc - 1] - kept) <= 0.04 * (double)std::max<int64_t>(b.hot_cols + b.cold_cols, 1);
+            // (a flat step costs ~0.75 of an ordinary one - 1.46 against 1.84 us per range of ~8 steps on the Reddit shape - and a
+            //  stream of nearly-empty cells, a wide row shard, ties on the count: 627 712 flat steps against 627 699)
+            const bool no_more_steps = (double)(npairs * maxw * tpc + extra_steps) <= 1.2 * (double)std::max<int64_t>(classic_steps, 1);
+            if (forced_flat == tpc) { b.flat_tpc = tpc; b.over_cols = over[tpc - 1] - kept; break; }
+            if (forced_flat >= 0 || !few_cold || !no_more_steps) continue;
+            // Both forms may qualify - the one-plane layout on the Reddit shape: 51 columns per 1 528-row cell, which one tile per cell
+            // only holds with 93 % of the pairs dense (0.40 ms) and two tiles per cell hold as they are (0.21 ms) - so they are
+            // priced: a flat step = 1, a dense entry's run-time step ~1.6 (31 instructions against 19), + ~4 steps per dense entry
+            // (its barrier, metadata block and descriptor words).  Dense entries are for the EXCEPTIONS of a stream.
+            const double cost = (double)(npairs * maxw * tpc) + (tpc == 1 ? 1.6 * (double)b.dense_steps + 4.0 * (double)b.ndense_entries : 0.0);
+            if (!b.flat_tpc || cost < best_cost) { b.flat_tpc = tpc; b.over_cols = over[tpc - 1] - kept; best_cost = cost; }
         }
     }
-    const bool with_dense = flat_tpc == 1 && ndense_pairs > 0;
-    if (!with_dense) { (void)hipStreamSynchronize(stream); (void)hipFree(d_ent); d_ent = nullptr; }
-    const int64_t nentries = layout_entries(with_dense);
-    std::vector<uint32_t> rl2;
-    if (flat_tpc) {
-        std::vector<uint32_t> xbase;
-        if (with_dense) {
-            xbase.assign((size_t)ncell_hot, 0u);
-            for (int64_t k = 0; k < npairs; ++k) {
-                if (!nd[(size_t)k]) continue;
-                for (int v = 0; v < kLdsWaves; ++v) {
-                    uint32_t run = 0;
-                    for (int j = 0; j < maxw; ++j) { const size_t c = (size_t)((k * kLdsWaves + v) * maxw + j); xbase[c] = run; run += cnt[c] > 1u ? cnt[c] - 1u : 0u; }
-                }
-            }
-        }
-        // entry words: w0 = range | bit 31 dense | bit 30 another range than the entry before; w1 = dense: tiles per window slot;
-        // w2 = range to fetch at the top of the entry (~0: none); w3 = 0
-        // (layout: [entries][4] records - w0, w2, normal entries of the workgroup, 0: the same for every wavefront, 16 bytes per entry,
-        //  L2-resident - followed by [entries][16 wavefronts] descriptor words w1, read in the dense phase only.  The kernels load the
-        //  FIRST TWO words of a record and use both: a loaded word nobody reads is a register the allocator hands to another value
-        //  while the load is in flight, and hipcc then waits vmcnt(0) before writing it - at the top of every entry, right behind the
-        //  range fill (r05: the edge-valued walk ran 26 % slower for one such word, the remainder layouts of the binary walk too).
-        //  A per-(entry, wavefront) record of all three words was 10 MB per stream and a DRAM miss per wavefront and entry: the uniform
-        //  Reddit shape ran 5 % slower for it)
-        rl2.assign((size_t)std::max<int64_t>(nentries, 1) * (4 + kLdsWaves), 0u);
-        auto put = [&](int64_t en, int v, uint32_t w0, uint32_t w1, uint32_t w2) {
-            uint32_t* q = &rl2[(size_t)(en * 4)];
-            q[0] = w0; q[1] = w2; q[3] = 0u;   // (q[2]: normal entries of the entry's workgroup, written below)
-            rl2[(size_t)(std::max<int64_t>(nentries, 1) * 4 + en * kLdsWaves + v)] = w1;
-        };
-        for (int wg = 0; wg < nwg; ++wg)   // record word 2: how many NORMAL entries the entry's workgroup has (its dense entries follow them: val_permute_kernel)
-            for (int64_t en = wg_first[(size_t)wg]; en < wg_first[(size_t)wg + 1]; ++en) rl2[(size_t)(en * 4 + 2)] = (uint32_t)(rbase[(size_t)wg + 1] - rbase[(size_t)wg]);
-        for (int wg = 0; wg < nwg; ++wg) {
-            const int64_t k0 = rbase[(size_t)wg], k1 = rbase[(size_t)wg + 1];
-            std::vector<int64_t> dk;   // the workgroup's dense pairs, in order
-            for (int64_t k = k0; k < k1; ++k) if (nd[(size_t)k]) dk.push_back(k);
-            for (int64_t k = k0; k < k1; ++k) {
-                const uint32_t r = (uint32_t)rlist[(size_t)k];
-                const uint32_t nextr = k + 1 < k1 ? (uint32_t)rlist[(size_t)k + 1] : (dk.empty() ? 0xffffffffu : (uint32_t)rlist[(size_t)dk[0]]);
-                for (int v = 0; v < kLdsWaves; ++v) put(ent2[(size_t)k * 2], v, r | (k > k0 ? 0x40000000u : 0u), 0u, nextr);
-            }
-            for (size_t gi = 0; gi < dk.size(); ++gi) {
-                const int64_t k = dk[gi];
-                const uint32_t r = (uint32_t)rlist[(size_t)k];
-                const uint32_t nextr = gi + 1 < dk.size() ? (uint32_t)rlist[(size_t)dk[gi + 1]] : 0xffffffffu;
-                for (int64_t d = 0; d < nd[(size_t)k]; ++d)
-                    for (int v = 0; v < kLdsWaves; ++v) {
-                        uint32_t desc = 0u;   // tiles of every window slot among this wavefront's extras [maxw d, maxw (d + 1))
-                        for (int j = 0; j < maxw; ++j) {
-                            const size_t c = (size_t)((k * kLdsWaves + v) * maxw + j);
-                            const int64_t lo = xbase[c], hi = lo + (cnt[c] > 1u ? cnt[c] - 1u : 0u);
-                            const int64_t a0 = std::max<int64_t>(lo, d * maxw), a1 = std::min<int64_t>(hi, (d + 1) * maxw);
-                            if (a1 > a0) desc |= (uint32_t)(a1 - a0) << (4 * j);
-                        }
-                        put(ent2[(size_t)k * 2 + 1] + d, v, r | 0x80000000u | (d == 0 ? 0x40000000u : 0u), desc, d == 0 ? nextr : 0xffffffffu);
-                    }
-            }
-        }
-        e = hipMalloc(&d_rl2, rl2.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_rl2, rl2.data(), rl2.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess && with_dense) {
-            e = hipMalloc(&d_xbase, xbase.size() * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemcpyAsync(d_xbase, xbase.data(), xbase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (xbase goes out of scope)
-        if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "flat stream entries: %s", hipGetErrorString(e)));
+    if (b.verbose) fprintf(stderr, "[tcgnn] cell stream %d: %lld tiles ordinary, %lld steps of the busiest wavefronts; flat would take %lld steps (+%lld columns cold; %lld dense pairs keep %lld columns "
+                                   "in %lld dense entries, %lld steps) / %lld (+%lld): %s\n", b.slot,
+                           (long long)classic_tiles, (long long)classic_steps, (long long)(npairs * maxw), (long long)(over[0] - b.over_dense), (long long)b.ndense_pairs, (long long)b.over_dense,
+                           (long long)b.ndense_entries, (long long)b.dense_steps, (long long)(2 * npairs * maxw), (long long)over[1],
+                           b.flat_tpc ? (b.flat_tpc == 1 ? "flat, 1 tile per cell" : "flat, 2 tiles per cell") : "ordinary");
+}
+// step 6: ... nor flat where ONE window would leave a long remainder behind (a hub row: its cells overflow in every range, and the
+// remainder of a window is one wavefront's serial work - a 24 k-degree hub cost the flat walk 0.72 ms against 0.61): the remainder
+// is counted with the flat cap before anything is built (cell_cold_count_kernel).  The counts leave the dense pairs' overflow out:
+// they read the entry table, which therefore goes to the device first.
+static int cells_hub_row_trial(CellBuild& b) {
+    hipError_t e = hipSuccess;
+    if (b.with_dense()) {
+        b.ent = flat_entries(b.nwg, b.maxw, b.rbase, b.rlist, b.cnt, b.dense_mx, true, false);
+        e = b.d_ent.alloc(b.ent.ent2.size());
+        if (e == hipSuccess) e = hipMemcpyAsync(b.d_ent, b.ent.ent2.data(), b.ent.ent2.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+        if (e != hipSuccess) return fail(hip_rc(e), "flat stream entries: %s", hipGetErrorString(e));
     }
-    if (val && flat_tpc != 1)   // (spmm_lds_val_kernel walks flat streams with one tile per cell only; the caller keeps the gather walks)
-        return bail3(fail(TCGNN_ERR_UNSUPPORTED, "edge-valued LDS-resident SpMM: the single-edge cells of this graph are not uniform enough for a flat stream"));
-    hot_cols -= over_cols; cold_cols += over_cols;
+    if (!b.flat_tpc || test_knob("TCGNN_LDS_FLAT")) return TCGNN_OK;
+    DevBuf<uint32_t> d_trial;
+    std::vector<uint32_t> trial((size_t)b.p->nw_eff, 0u);
+    e = d_trial.alloc(trial.size());
+    if (e == hipSuccess) e = hipMemsetAsync(d_trial, 0, trial.size() * sizeof(uint32_t), b.stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cell_cold_count_kernel, dim3((unsigned)((b.nw + 255) / 256)), dim3(256), 0, b.stream, b.best.d_cellcols.ptr, b.d_kmap.ptr, b.best.d_sorder.ptr, b.nw, b.nranges, b.maxw,
+                           d_trial.ptr, (uint32_t)(32 * b.flat_tpc), b.d_ent.ptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(trial.data(), d_trial, trial.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
+    uint32_t worst = 0;
+    for (uint32_t c : trial) worst = std::max(worst, (c + 31u) / 32u);
+    if (worst > 16u) {
+        if (b.verbose) fprintf(stderr, "[tcgnn] cell stream %d: ordinary after all - one window would leave %u cold tiles behind\n", b.slot, worst);
+        b.flat_tpc = 0; b.over_cols = 0;
+    }
+    return TCGNN_OK;
+}
+// step 7: the entries of the stream as it will be built (flat_entries) and, flat streams, their records on the device
+static int cells_entries(CellBuild& b) {
+    if (!b.with_dense()) { (void)hipStreamSynchronize(b.stream); b.d_ent.reset(); }   // (the trial may have sent the stream back to ordinary)
+    FlatEntries ent = flat_entries(b.nwg, b.maxw, b.rbase, b.rlist, b.cnt, b.dense_mx, b.with_dense(), b.flat_tpc != 0);
+    hipError_t e = hipSuccess;
+    if (b.flat_tpc) {
+        e = b.d_rl2.alloc(ent.rl2.size());
+        if (e == hipSuccess) e = hipMemcpyAsync(b.d_rl2, ent.rl2.data(), ent.rl2.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b.stream);
+        if (e == hipSuccess && b.with_dense()) {
+            e = b.d_xbase.alloc(ent.xbase.size());
+            if (e == hipSuccess) e = hipMemcpyAsync(b.d_xbase, ent.xbase.data(), ent.xbase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b.stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    }
+    if (e != hipSuccess) return fail(hip_rc(e), "flat stream entries: %s", hipGetErrorString(e));
+    b.ent = std::move(ent);   // (behind a synchronisation: the table the trial read was copied from the old one)
+    return TCGNN_OK;
+}
+// step 8: the tiles (cell_init / cell_fill / cell_optimize) and, flat streams, their per-(pair, wavefront) metadata blocks
+// (flat_transpose), after which the ordinary tiles and the cell table go
+static int cells_fill_tiles(CellBuild& b) {
+    const tcgnn_plan* p = b.p;
+    const int flat_tpc = b.flat_tpc;
+    b.hot_cols -= b.over_cols; b.cold_cols += b.over_cols;
     uint64_t run = 0;
-    if (flat_tpc) run = (uint64_t)nentries * (uint64_t)per_wg * (uint64_t)flat_tpc;   // (positions are computed: the table is not kept)
-    else for (size_t k = 0; k < cnt.size(); ++k) { const uint32_t c = cnt[k]; cnt[k] = (uint32_t)run; run += c; }
-    if (run >= (1ull << 32)) return bail3(fail(TCGNN_ERR_BAD_GRAPH, "LDS-range SpMM: %llu tiles overflow the 32-bit cell table", (unsigned long long)run));
-    const int64_t ntiles = (int64_t)run;
-    const int64_t nwords = std::max<int64_t>(ntiles, 1) * kCellWords;
-    e = hipMalloc(&d_tiles, (size_t)nwords * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cnt, cnt.data(), cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell stream (%lld tiles): %s", (long long)ntiles, hipGetErrorString(e)));
-    hipLaunchKernelGGL(cell_init_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, stream, d_tiles, nwords, rows);
-    if (val) {   // (flat only: the caller gives the stream up otherwise)
-        e = hipMalloc(&d_eidx, (size_t)std::max<int64_t>(ntiles, 1) * 32 * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_eidx, 0xff, (size_t)std::max<int64_t>(ntiles, 1) * 32 * sizeof(int32_t), stream);
-        if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "edge index of the cell stream: %s", hipGetErrorString(e)));
+    if (flat_tpc) run = (uint64_t)b.ent.nentries * (uint64_t)b.per_wg * (uint64_t)flat_tpc;   // (positions are computed: the table is not kept)
+    else for (size_t k = 0; k < b.cnt.size(); ++k) { const uint32_t c = b.cnt[k]; b.cnt[k] = (uint32_t)run; run += c; }
+    if (run >= (1ull << 32)) return fail(TCGNN_ERR_BAD_GRAPH, "LDS-range SpMM: %llu tiles overflow the 32-bit cell table", (unsigned long long)run);
+    const int64_t ntiles = b.ntiles = (int64_t)run;
+    const int64_t nwords = b.nwords = std::max<int64_t>(ntiles, 1) * kCellWords;
+    hipError_t e = b.d_tiles.alloc((size_t)nwords);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d_cnt, b.cnt.data(), b.cnt.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b.stream);
+    if (e != hipSuccess) return fail(hip_rc(e), "cell stream (%lld tiles): %s", (long long)ntiles, hipGetErrorString(e));
+    hipLaunchKernelGGL(cell_init_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, b.stream, b.d_tiles.ptr, nwords, b.rows);
+    if (b.val) {   // (flat only: build_lds_cells gives the stream up otherwise)
+        e = b.d_eidx.alloc((size_t)std::max<int64_t>(ntiles, 1) * 32);
+        if (e == hipSuccess) e = hipMemsetAsync(b.d_eidx, 0xff, b.d_eidx.bytes, b.stream);
+        if (e != hipSuccess) return fail(hip_rc(e), "edge index of the cell stream: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(cell_fill_kernel, dim3((unsigned)nw), dim3(256), 0, stream, s_wb, d_sorder, s_cols, s_mask, nwg, nranges, p->Nc,
-                       maxw, rows, d_cnt, d_firstq, d_tiles, d_kmap, d_parts, d_cellcols, flat_tpc, s_eidx, d_eidx, d_ent, d_xbase);
-    if (ntiles > 0) hipLaunchKernelGGL(cell_optimize_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, stream, d_tiles, ntiles, rows, d_eidx);
+    hipLaunchKernelGGL(cell_fill_kernel, dim3((unsigned)b.nw), dim3(256), 0, b.stream, b.s_wb, b.best.d_sorder.ptr, b.s_cols, b.s_mask, b.nwg, b.nranges, p->Nc,
+                       b.maxw, b.rows, b.d_cnt.ptr, b.best.d_firstq.ptr, b.d_tiles.ptr, b.d_kmap.ptr, b.best.d_parts.ptr, b.best.d_cellcols.ptr, flat_tpc, b.s_eidx, b.d_eidx.ptr, b.d_ent.ptr, b.d_xbase.ptr);
+    if (ntiles > 0) hipLaunchKernelGGL(cell_optimize_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, b.stream, b.d_tiles.ptr, ntiles, b.rows, b.d_eidx.ptr);
     e = hipGetLastError();
-    if (e == hipSuccess && flat_tpc) {   // tiles -> per-(pair, wavefront) metadata blocks; the ordinary tiles and the cell table go
-        e = hipMalloc(&d_flat, (size_t)nwords * sizeof(uint32_t));
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(flat_transpose_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, stream, d_tiles, d_flat, nentries * kLdsWaves, maxw * flat_tpc, d_rl2);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_tiles); d_tiles = nullptr;
-        (void)hipFree(d_cnt); d_cnt = nullptr;
-        if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "flat cell stream: %s", hipGetErrorString(e)));
+    if (e != hipSuccess) return fail(hip_rc(e), "cell fill: %s", hipGetErrorString(e));
+    if (!flat_tpc) return TCGNN_OK;
+    e = b.d_flat.alloc((size_t)nwords);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(flat_transpose_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, b.stream, b.d_tiles.ptr, b.d_flat.ptr, b.ent.nentries * kLdsWaves, b.maxw * flat_tpc, b.d_rl2.ptr);
+        e = hipGetLastError();
     }
-    // ---- the cold remainder, re-condensed per window for the gather walk
-    int64_t cold_tiles = 0, cold_max = 0;
-    size_t cold_bytes = 0;
-    std::vector<int64_t> cptr;
-    if (e == hipSuccess && cold_cols > 0) {
-        const int nwe = p->nw_eff;
-        std::vector<uint32_t> coldc((size_t)nwe, 0);
-        e = hipMalloc(&d_coldcols, (size_t)nwe * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_coldcols, 0, (size_t)nwe * sizeof(uint32_t), stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(cell_cold_count_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, d_cellcols, d_kmap, d_sorder, nw, nranges, maxw, d_coldcols,
-                               (uint32_t)(32 * flat_tpc), d_ent);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(coldc.data(), d_coldcols, coldc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        cptr.assign((size_t)nwe + 1, 0);
-        for (int w = 0; w < nwe; ++w) { cptr[(size_t)w + 1] = cptr[(size_t)w] + (coldc[(size_t)w] + 31) / 32; cold_max = std::max<int64_t>(cold_max, (coldc[(size_t)w] + 31) / 32); }
-        cold_tiles = cptr[(size_t)nwe];
-        const size_t b_ptr = cptr.size() * sizeof(int64_t), b_c = (size_t)std::max<int64_t>(cold_tiles, 1) * kWbCols * 4, b_m = (size_t)std::max<int64_t>(cold_tiles, 1) * kWinRows * 4;
-        if (e == hipSuccess) e = hipMalloc(&d_cold_ptr, b_ptr);
-        if (e == hipSuccess) e = hipMalloc(&d_ccols, b_c);
-        if (e == hipSuccess) e = hipMalloc(&d_cmask, b_m);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_cold_ptr, cptr.data(), b_ptr, hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_cmask, 0, b_m, stream);
-        if (e == hipSuccess) {
-            // (padding columns of a window's last tile point at the all-zero sentinel row, like pack_kernel's)
-            const int64_t nfill = std::max<int64_t>(cold_tiles, 1) * kWbCols;
-            hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)std::min<int64_t>((nfill + 255) / 256, 65535)), dim3(256), 0, stream, d_ccols, nfill, p->Nc);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && val) {
-            e = hipMalloc(&d_cold_eidx, (size_t)std::max<int64_t>(cold_tiles, 1) * 32 * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(d_cold_eidx, 0xff, (size_t)std::max<int64_t>(cold_tiles, 1) * 32 * sizeof(int32_t), stream);
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(cell_cold_fill_kernel, dim3((unsigned)nw), dim3(256), 0, stream, s_wb, d_sorder, s_cols, s_mask, d_kmap, nranges, p->Nc,
-                               maxw, rows, d_cold_ptr, d_ccols, d_cmask, d_parts, d_firstq, (uint32_t)(32 * flat_tpc), s_eidx, d_cold_eidx, d_ent);
-            e = hipGetLastError();
-        }
-        cold_bytes = b_ptr + b_c + b_m;
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    b.d_tiles.reset();
+    b.d_cnt.reset();
+    if (e != hipSuccess) return fail(hip_rc(e), "flat cell stream: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 9: the cold remainder, re-condensed per window for the gather walk
+static int cells_cold_remainder(CellBuild& b) {
+    if (b.cold_cols <= 0) return TCGNN_OK;
+    const tcgnn_plan* p = b.p;
+    const int nwe = p->nw_eff;
+    const uint32_t cap = (uint32_t)(32 * b.flat_tpc);
+    std::vector<uint32_t> coldc((size_t)nwe, 0);
+    DevBuf<uint32_t> d_coldcols;
+    hipError_t e = d_coldcols.alloc((size_t)nwe);
+    if (e == hipSuccess) e = hipMemsetAsync(d_coldcols, 0, (size_t)nwe * sizeof(uint32_t), b.stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cell_cold_count_kernel, dim3((unsigned)((b.nw + 255) / 256)), dim3(256), 0, b.stream, b.best.d_cellcols.ptr, b.d_kmap.ptr, b.best.d_sorder.ptr, b.nw, b.nranges, b.maxw,
+                           d_coldcols.ptr, cap, b.d_ent.ptr);
+        e = hipGetLastError();
     }
-    // ---- a flat stream whose layout leaves 16 x NT KB of LDS: the remainder as per-wavefront record lists, multiplied inside the
-    //      flat kernel one tile per range (tcgnn_lds_flat.inc: cold_step) instead of by spmm_cold_planar_kernel afterwards
-    int32_t* d_wcold_ptr = nullptr;
-    uint32_t *d_wcold = nullptr, *d_wlist = nullptr;
-    constexpr int wcold_enabled = 1;
-    if (e == hipSuccess && !val && flat_tpc && cold_tiles > 0 && cold_tiles < (1ll << 28) && wcold_enabled && flat_cold_fits(lds_stream_nt(slot), maxw, flat_tpc)) {
-        std::vector<int32_t> wptr((size_t)nwg * kLdsWaves + 1, 0);
-        std::vector<uint32_t> wlist;
-        wlist.reserve((size_t)cold_tiles);
-        for (int g2 = 0; g2 < nwg; ++g2)
+    if (e == hipSuccess) e = hipMemcpyAsync(coldc.data(), d_coldcols, coldc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    b.cptr.assign((size_t)nwe + 1, 0);
+    for (int w = 0; w < nwe; ++w) { b.cptr[(size_t)w + 1] = b.cptr[(size_t)w] + (coldc[(size_t)w] + 31) / 32; b.cold_max = std::max<int64_t>(b.cold_max, (coldc[(size_t)w] + 31) / 32); }
+    b.cold_tiles = b.cptr[(size_t)nwe];
+    const size_t ncold = (size_t)std::max<int64_t>(b.cold_tiles, 1);
+    if (e == hipSuccess) e = b.d_cold_ptr.alloc(b.cptr.size());
+    if (e == hipSuccess) e = b.d_ccols.alloc(ncold * kWbCols);
+    if (e == hipSuccess) e = b.d_cmask.alloc(ncold * kWinRows);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d_cold_ptr, b.cptr.data(), b.d_cold_ptr.bytes, hipMemcpyHostToDevice, b.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(b.d_cmask, 0, b.d_cmask.bytes, b.stream);
+    if (e == hipSuccess) {
+        // (padding columns of a window's last tile point at the all-zero sentinel row, like pack_kernel's)
+        const int64_t nfill = (int64_t)ncold * kWbCols;
+        hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)std::min<int64_t>((nfill + 255) / 256, 65535)), dim3(256), 0, b.stream, b.d_ccols.ptr, nfill, p->Nc);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && b.val) {
+        e = b.d_cold_eidx.alloc(ncold * 32);
+        if (e == hipSuccess) e = hipMemsetAsync(b.d_cold_eidx, 0xff, b.d_cold_eidx.bytes, b.stream);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(cell_cold_fill_kernel, dim3((unsigned)b.nw), dim3(256), 0, b.stream, b.s_wb, b.best.d_sorder.ptr, b.s_cols, b.s_mask, b.d_kmap.ptr, b.nranges, p->Nc,
+                           b.maxw, b.rows, b.d_cold_ptr.ptr, b.d_ccols.ptr, b.d_cmask.ptr, b.best.d_parts.ptr, b.best.d_firstq.ptr, cap, b.s_eidx, b.d_cold_eidx.ptr, b.d_ent.ptr);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(hip_rc(e), "cell fill: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 10: a flat stream whose layout leaves 16 x NT KB of LDS: the remainder as per-wavefront record lists, multiplied inside the
+// flat kernel one tile per range (tcgnn_lds_flat.inc: cold_step) instead of by spmm_cold_planar_kernel afterwards.  Ends with the
+// synchronisation every host table of the build waits for.
+static int cells_wavefront_cold_lists(CellBuild& b) {
+    hipError_t e = hipSuccess;
+    if (!b.val && b.flat_tpc && b.cold_tiles > 0 && b.cold_tiles < (1ll << 28) && flat_cold_fits(lds_stream_nt(b.slot), b.maxw, b.flat_tpc)) {
+        std::vector<int32_t>& wptr = b.wptr;
+        std::vector<uint32_t>& wlist = b.wlist;
+        wptr.assign((size_t)b.nwg * kLdsWaves + 1, 0);
+        wlist.reserve((size_t)b.cold_tiles);
+        for (int g2 = 0; g2 < b.nwg; ++g2)
             for (int v = 0; v < kLdsWaves; ++v) {
                 wptr[(size_t)g2 * kLdsWaves + v] = (int32_t)wlist.size();
-                for (int j = 0; j < maxw; ++j) {
-                    const int w = sorder[(size_t)cell_position(g2, v, j, maxw)];
+                for (int j = 0; j < b.maxw; ++j) {
+                    const int w = b.best.sorder[(size_t)cell_position(g2, v, j, b.maxw)];
                     if (w < 0) continue;
-                    for (int64_t t = cptr[(size_t)w]; t < cptr[(size_t)w + 1]; ++t) wlist.push_back((uint32_t)t | ((uint32_t)j << 28));
+                    for (int64_t t = b.cptr[(size_t)w]; t < b.cptr[(size_t)w + 1]; ++t) wlist.push_back((uint32_t)t | ((uint32_t)j << 28));
                 }
             }
-        wptr[(size_t)nwg * kLdsWaves] = (int32_t)wlist.size();
-        e = hipMalloc(&d_wcold_ptr, wptr.size() * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_wlist, std::max<size_t>(wlist.size(), 1) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&d_wcold, std::max<size_t>(wlist.size(), 1) * 64 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_wcold_ptr, wptr.data(), wptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess && !wlist.empty()) e = hipMemcpyAsync(d_wlist, wlist.data(), wlist.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+        wptr[(size_t)b.nwg * kLdsWaves] = (int32_t)wlist.size();
+        DevBuf<uint32_t> d_wlist;
+        e = b.d_wcold_ptr.alloc(wptr.size());
+        if (e == hipSuccess) e = d_wlist.alloc(std::max<size_t>(wlist.size(), 1));
+        if (e == hipSuccess) e = b.d_wcold.alloc(std::max<size_t>(wlist.size(), 1) * 64);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.d_wcold_ptr, wptr.data(), wptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+        if (e == hipSuccess && !wlist.empty()) e = hipMemcpyAsync(d_wlist, wlist.data(), wlist.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b.stream);
         if (e == hipSuccess && !wlist.empty()) {
             const int64_t nwordsw = (int64_t)wlist.size() * 64;
-            hipLaunchKernelGGL(flat_cold_records_kernel, dim3((unsigned)((nwordsw + 255) / 256)), dim3(256), 0, stream, d_wlist, (int64_t)wlist.size(), d_ccols, d_cmask, d_wcold);
+            hipLaunchKernelGGL(flat_cold_records_kernel, dim3((unsigned)((nwordsw + 255) / 256)), dim3(256), 0, b.stream, d_wlist.ptr, (int64_t)wlist.size(), b.d_ccols.ptr, b.d_cmask.ptr, b.d_wcold.ptr);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_wlist);
-        if (e != hipSuccess) { (void)hipFree(d_wcold_ptr); (void)hipFree(d_wcold); d_wcold_ptr = nullptr; d_wcold = nullptr; }
-        else cold_bytes += wptr.size() * sizeof(int32_t) + wlist.size() * 256;
+        if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);   // host vectors must outlive their copies
-    if (e != hipSuccess) return bail3(fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "cell fill: %s", hipGetErrorString(e)));
-    (void)hipFree(d_firstq); (void)hipFree(d_paircols); (void)hipFree(d_kmap); (void)hipFree(d_cellcols); (void)hipFree(d_coldcols);
-    tcgnn_plan::CellStream& cs = p->lds[slot];
-    cs.d_order = d_sorder;
-    cs.d_cell_ptr = d_cnt; cs.d_cell_tiles = d_tiles;
-    cs.flat_tpc = flat_tpc; cs.d_flat = d_flat;
-    cs.d_wcold_ptr = d_wcold_ptr; cs.d_wcold = d_wcold;
-    cs.d_eidx = d_eidx; cs.d_cold_eidx = d_cold_eidx;
-    cs.nwg = nwg; cs.tiles = ntiles;
-    if (flat_tpc) {   // a flat stream is indexed by ENTRY: rbase[wg] = the workgroup's first entry
-        const std::vector<int32_t>& rbase_e = wg_first;
-        e = hipMemcpyAsync(d_rbase, rbase_e.data(), rbase_e.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return bail3(fail(TCGNN_ERR_HIP, "flat stream entries: %s", hipGetErrorString(e)));
-    }
-    (void)hipFree(d_ent); (void)hipFree(d_xbase); d_ent = nullptr; d_xbase = nullptr;
-    cs.npairs = (int32_t)nentries; cs.d_rbase = d_rbase; cs.d_rlist = d_rlist; cs.d_rl2 = d_rl2; cs.dense_entries = (int32_t)(nentries - npairs);
-    cs.cold_tiles = cold_tiles; cs.hot_cols = hot_cols; cs.cold_cols = cold_cols; cs.cold_max = cold_max;
-    cs.d_parts = d_parts; cs.nsplit = nsplit;
-    const char* const verbose_env = getenv("TCGNN_VERBOSE");   // (read per build: builds are rare, and tests switch it on)
-    const bool verbose = verbose_env && atoi(verbose_env) > 0;
-    if (verbose)
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);   // host vectors must outlive their copies
+    if (e != hipSuccess) return fail(hip_rc(e), "cell fill: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 11, the last fallible one: a flat stream is indexed by ENTRY: rbase[wg] = the workgroup's first entry
+static int cells_flat_rbase(CellBuild& b) {
+    if (!b.flat_tpc) return TCGNN_OK;
+    hipError_t e = hipMemcpyAsync(b.d_rbase, b.ent.wg_first.data(), b.ent.wg_first.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+    if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "flat stream entries: %s", hipGetErrorString(e));
+    return TCGNN_OK;
+}
+// step 12: publication.  Cannot fail, and is the only writer of plan->lds[slot]: every fallible operation lies before it, so a
+// failed build leaves the slot exactly as it found it (nothing the plan points at is ever freed by the build, nothing is freed
+// twice).  The stream's arrays leave their DevBufs for the plan, the bytes they hand over are what plan->bytes grows by, and nranges
+// is stored last, with release ordering: a reader that sees it sees the stream.  *build_only_bytes (if asked for): the part of
+// those bytes the caller will release again (the 32-bit edge index of the single-edge stream).
+static void cells_publish(CellBuild& b, size_t* build_only_bytes) {
+    tcgnn_plan::CellStream& cs = b.p->lds[b.slot];
+    const int64_t nentries = b.ent.nentries;
+    const bool wcold = b.d_wcold_ptr != nullptr;
+    size_t bytes = 0, build_only = 0;
+    bytes += b.best.d_sorder.release(cs.d_order);
+    bytes += b.d_cnt.release(cs.d_cell_ptr);
+    bytes += b.d_tiles.release(cs.d_cell_tiles);
+    bytes += b.d_flat.release(cs.d_flat);
+    bytes += b.d_wcold_ptr.release(cs.d_wcold_ptr);
+    bytes += b.d_wcold.release(cs.d_wcold);
+    build_only += b.d_eidx.release(cs.d_eidx);
+    build_only += b.d_cold_eidx.release(cs.d_cold_eidx);
+    bytes += b.d_rbase.release(cs.d_rbase);
+    bytes += b.d_rlist.release(cs.d_rlist);
+    bytes += b.d_rl2.release(cs.d_rl2);
+    bytes += b.best.d_parts.release(cs.d_parts);
+    bytes += b.d_cold_ptr.release(cs.d_cold_ptr);
+    bytes += b.d_ccols.release(cs.d_cold_cols);
+    bytes += b.d_cmask.release(cs.d_cold_mask);
+    cs.flat_tpc = b.flat_tpc;
+    cs.nwg = b.nwg; cs.tiles = b.ntiles;
+    cs.npairs = (int32_t)nentries; cs.dense_entries = (int32_t)(nentries - b.npairs);
+    cs.cold_tiles = b.cold_tiles; cs.hot_cols = b.hot_cols; cs.cold_cols = b.cold_cols; cs.cold_max = b.cold_max;
+    cs.nsplit = b.best.nsplit;
+    if (b.verbose)
         fprintf(stderr, "[tcgnn] cell stream %d (%d windows per wavefront, %d-row ranges): %d workgroups x %d ranges, %lld of %lld pairs hot (>= %u columns), "
                         "%lld columns hot / %lld cold, %lld tiles + %lld cold gather tiles, placement %s\n",
-                slot, maxw, rows, nwg, nranges, (long long)npairs, (long long)npairs_all, hot_min, (long long)hot_cols, (long long)cold_cols,
-                (long long)ntiles, (long long)cold_tiles, best.mode == kPlaceGlobal ? "longest-first over the graph" : "contiguous blocks");
-    if (verbose && flat_tpc) fprintf(stderr, "[tcgnn]   flat: %d tile(s) per cell, %lld entries (%lld dense), %lld columns beyond the cells' tiles moved to the cold remainder (%s)\n", flat_tpc,
-                                     (long long)nentries, (long long)(nentries - npairs), (long long)over_cols,
-                                     d_wcold_ptr ? "multiplied inside the kernel, one tile per range" : "added by spmm_cold_planar_kernel");
-    if (verbose && nsplit) fprintf(stderr, "[tcgnn]   %d windows split over several wavefronts\n", nsplit);
-    cs.d_cold_ptr = d_cold_ptr; cs.d_cold_cols = d_ccols; cs.d_cold_mask = d_cmask;
-    p->bytes += (flat_tpc ? 0 : (size_t)(ncell_hot + 1) * sizeof(uint32_t)) + (size_t)nwords * sizeof(uint32_t) + sorder.size() * sizeof(int32_t) +
-                (rbase.size() + rlist.size()) * sizeof(int32_t) + rl2.size() * sizeof(uint32_t) + cold_bytes + (nsplit ? sparts.size() * sizeof(uint32_t) : 0) +
-                (val ? (size_t)(std::max<int64_t>(ntiles, 1) + (cold_tiles > 0 ? cold_tiles : 0)) * 32 * sizeof(int32_t) : 0);
-    cs.nranges = nranges;
+                b.slot, b.maxw, b.rows, b.nwg, b.nranges, (long long)b.npairs, (long long)b.npairs_all, b.best.hot_min, (long long)b.hot_cols, (long long)b.cold_cols,
+                (long long)b.ntiles, (long long)b.cold_tiles, b.best.mode == kPlaceGlobal ? "longest-first over the graph" : "contiguous blocks");
+    if (b.verbose && b.flat_tpc) fprintf(stderr, "[tcgnn]   flat: %d tile(s) per cell, %lld entries (%lld dense), %lld columns beyond the cells' tiles moved to the cold remainder (%s)\n", b.flat_tpc,
+                                         (long long)nentries, (long long)(nentries - b.npairs), (long long)b.over_cols,
+                                         wcold ? "multiplied inside the kernel, one tile per range" : "added by spmm_cold_planar_kernel");
+    if (b.verbose && b.best.nsplit) fprintf(stderr, "[tcgnn]   %d windows split over several wavefronts\n", b.best.nsplit);
+    b.p->bytes += bytes + build_only;
+    if (build_only_bytes) *build_only_bytes = build_only;
+    cs.nranges.store(b.nranges, std::memory_order_release);
+}
+
+// the arrays of a cell stream, all of them: what tcgnn_plan_destroy frees
+static void release_cell_stream(tcgnn_plan::CellStream& cs) {
+    for (void* q : {(void*)cs.d_order, (void*)cs.d_rbase, (void*)cs.d_rlist, (void*)cs.d_rl2, (void*)cs.d_parts, (void*)cs.d_cold_ptr, (void*)cs.d_cold_cols, (void*)cs.d_cold_mask,
+                    (void*)cs.d_cell_ptr, (void*)cs.d_cell_tiles, (void*)cs.d_flat, (void*)cs.d_wcold_ptr, (void*)cs.d_wcold, (void*)cs.d_eidx, (void*)cs.d_cold_eidx, (void*)cs.d_eidx16,
+                    (void*)cs.d_cold_eidx16}) (void)hipFree(q);
+}
+
+static int build_lds_cells(tcgnn_plan* p, hipStream_t stream, int slot, size_t* build_only_bytes = nullptr) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    if (p->lds[slot].nranges > 0) return TCGNN_OK;
+    if (p->nw_eff <= 0 || p->Nc <= 0) return fail(TCGNN_ERR_INVALID_ARG, "LDS-range SpMM: empty graph");
+    CellBuild b;
+    b.p = p; b.stream = stream; b.slot = slot;
+    b.val = slot == kLdsValSlot;
+    if (b.val && !p->d_xwb_ptr) return fail(TCGNN_ERR_INVALID_ARG, "edge-valued LDS-resident SpMM: the single-edge stream has not been built");
+    b.s_wb = b.val ? p->d_xwb_ptr : p->d_wb_ptr;
+    b.s_cols = b.val ? p->d_xcols : p->d_cols;
+    b.s_mask = b.val ? p->d_xmask : p->d_mask;
+    b.s_eidx = b.val ? p->d_xeidx : nullptr;
+    b.maxw = lds_stream_maxw(slot);
+    b.rows = lds_stream_buf_rows(slot) - 8;
+    b.nranges = (p->Nc + b.rows - 1) / b.rows;
+    b.per_wg = kLdsWaves * b.maxw;
+    b.nwg = lds_workgroups(p, b.maxw);
+    b.nw = b.nwg * b.per_wg;
+    b.ncell = (int64_t)b.nwg * b.nranges * b.per_wg;
+    b.npairs_all = (int64_t)b.nwg * b.nranges;
+    b.verbose = verbose_level() > 0;
+    if (const int rc = cells_window_weights(b)) return rc;
+    if (const int rc = cells_choose_placement(b)) return rc;
+    if (const int rc = cells_hot_pairs(b)) return rc;
+    cells_dense_pairs(b);
+    cells_flat_or_ordinary(b);
+    if (const int rc = cells_hub_row_trial(b)) return rc;
+    if (const int rc = cells_entries(b)) return rc;
+    if (b.val && b.flat_tpc != 1)   // (spmm_lds_val_kernel walks flat streams with one tile per cell only; the caller keeps the gather walks)
+        return fail(TCGNN_ERR_UNSUPPORTED, "edge-valued LDS-resident SpMM: the single-edge cells of this graph are not uniform enough for a flat stream");
+    if (const int rc = cells_fill_tiles(b)) return rc;
+    if (const int rc = cells_cold_remainder(b)) return rc;
+    if (const int rc = cells_wavefront_cold_lists(b)) return rc;
+    if (const int rc = cells_flat_rbase(b)) return rc;
+    cells_publish(b, build_only_bytes);
     return TCGNN_OK;
 }
 
 // ---- the edge-valued LDS-resident walk (tcgnn_lds_val.inc): single-edge tile stream + its flat cell stream (slot kLdsValSlot).
 // Built on the first edge-valued call that would use it (allocates and synchronises: never inside a graph capture); the answer -
 // usable or not - is remembered in plan->val_choice.
+// step 1: the single-edge source stream, handed to the plan (build_lds_cells cuts slot kLdsValSlot from it).  *usable = false: the
+// graph has a window the stream cannot hold; *bytes: what the plan was handed.
+static int val_source_stream(tcgnn_plan* p, hipStream_t stream, bool* usable, size_t* bytes) {
+    const int nw = p->nw_eff;
+    *usable = false; *bytes = 0;
+    DevBuf<int32_t> d_ew, d_flags, d_xc, d_xe;
+    DevBuf<int64_t> d_xp;
+    DevBuf<uint32_t> d_xm;
+    std::vector<int32_t> ew((size_t)nw, 0);
+    hipError_t e = d_ew.alloc((size_t)nw);
+    if (e == hipSuccess) e = d_flags.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, sizeof(int32_t), stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(window_edges_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, p->rowptr, p->N, nw, d_ew.ptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ew.data(), d_ew, (size_t)nw * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    d_ew.reset();
+    std::vector<int64_t> xptr((size_t)nw + 1, 0);
+    for (int w = 0; w < nw; ++w) xptr[(size_t)w + 1] = xptr[(size_t)w] + (ew[(size_t)w] + kWbCols - 1) / kWbCols;
+    const int64_t total = std::max<int64_t>(xptr[(size_t)nw], 1);
+    if (e == hipSuccess) e = d_xp.alloc(xptr.size());
+    if (e == hipSuccess) e = d_xc.alloc((size_t)total * kWbCols);
+    if (e == hipSuccess) e = d_xe.alloc((size_t)total * kWbCols);
+    if (e == hipSuccess) e = d_xm.alloc((size_t)total * kWinRows);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_xp, xptr.data(), xptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_xe, 0xff, d_xe.bytes, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_xm, 0, d_xm.bytes, stream);
+    if (e == hipSuccess) {   // (padding slots point at the all-zero sentinel row, like pack_kernel's; filled on the device - ADVICE r04: a 460 MB host vector)
+        const int64_t nfill = total * kWbCols;
+        hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)std::min<int64_t>((nfill + 255) / 256, 65535)), dim3(256), 0, stream, d_xc.ptr, nfill, p->Nc);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (xptr must outlive its copy)
+    }
+    int32_t bad = 0;
+    if (e == hipSuccess && nw > 0) {
+        hipLaunchKernelGGL(expand_edges_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, p->d_mask, p->d_ebase, d_xp.ptr, d_xc.ptr, d_xm.ptr, d_xe.ptr, p->Nc, d_flags.ptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flags, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail(hip_rc(e), "single-edge tile stream: %s", hipGetErrorString(e));
+    if (bad) return TCGNN_OK;
+    *bytes = d_xp.release(p->d_xwb_ptr) + d_xc.release(p->d_xcols) + d_xm.release(p->d_xmask) + d_xe.release(p->d_xeidx);
+    p->total_xwb = xptr[(size_t)nw];
+    p->bytes += *bytes;
+    *usable = true;
+    return TCGNN_OK;
+}
+// step 3 (step 2 is build_lds_cells): CSR positions -> 16-bit offsets into each window's run of edges (half the index bytes per
+// call and in the plan); returns whether the stream can be used
+static bool val_index16(tcgnn_plan* p, hipStream_t stream) {
+    tcgnn_plan::CellStream& cs = p->lds[kLdsValSlot];
+    const size_t nt = (size_t)std::max<int64_t>(cs.tiles, 1), nc = (size_t)std::max<int64_t>(cs.cold_tiles, 1);
+    DevBuf<uint16_t> d_e16, d_cold_e16;
+    DevBuf<int32_t> d_bad;
+    int32_t bad = 0;
+    hipError_t e = d_e16.alloc(nt * 32);
+    if (e == hipSuccess) e = d_cold_e16.alloc(nc * 32);
+    if (e == hipSuccess) e = d_bad.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int32_t), stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_e16, 0xff, d_e16.bytes, stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(val_index16_kernel, dim3((unsigned)(cs.nwg * kLdsWaves * kLdsMaxW2)), dim3(256), 0, stream, p->rowptr, cs.d_order, cs.d_eidx, cs.d_rbase, d_e16.ptr, p->N,
+                           kLdsMaxW2, cs.cold_tiles > 0 ? cs.d_cold_ptr : nullptr, cs.d_cold_eidx, d_cold_e16.ptr, d_bad.ptr, cs.d_rl2, std::max(cs.npairs, 1));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess || bad) return false;
+    p->bytes += d_e16.release(cs.d_eidx16) + d_cold_e16.release(cs.d_cold_eidx16);
+    return true;
+}
 static int build_val_stream(tcgnn_plan* p, hipStream_t stream) {
     // (ADVICE r04: ONE lock over the whole build - the single-edge source, the cell stream cut from it and the frees behind it; two
     //  threads making a plan's first edge-valued call used to be able to build, and free, the same arrays twice)
     static std::mutex mu;
     std::lock_guard<std::mutex> lock(mu);
-    {
-        if (p->val_choice.load(std::memory_order_acquire) >= 0) return TCGNN_OK;
-        if (!p->d_xwb_ptr) {
-            const int nw = p->nw_eff;
-            int32_t *d_ew = nullptr, *d_flags = nullptr;
-            std::vector<int32_t> ew((size_t)nw, 0);
-            hipError_t e = hipMalloc(&d_ew, (size_t)nw * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc(&d_flags, sizeof(int32_t));
-            if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, sizeof(int32_t), stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(window_edges_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, stream, p->rowptr, p->N, nw, d_ew);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(ew.data(), d_ew, (size_t)nw * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            (void)hipFree(d_ew);
-            std::vector<int64_t> xptr((size_t)nw + 1, 0);
-            for (int w = 0; w < nw; ++w) xptr[(size_t)w + 1] = xptr[(size_t)w] + (ew[(size_t)w] + kWbCols - 1) / kWbCols;
-            const int64_t total = std::max<int64_t>(xptr[(size_t)nw], 1);
-            int64_t* d_xp = nullptr; int32_t *d_xc = nullptr, *d_xe = nullptr; uint32_t* d_xm = nullptr;
-            auto drop = [&]() { (void)hipFree(d_xp); (void)hipFree(d_xc); (void)hipFree(d_xe); (void)hipFree(d_xm); (void)hipFree(d_flags); };
-            if (e == hipSuccess) e = hipMalloc(&d_xp, xptr.size() * sizeof(int64_t));
-            if (e == hipSuccess) e = hipMalloc(&d_xc, (size_t)total * kWbCols * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc(&d_xe, (size_t)total * kWbCols * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc(&d_xm, (size_t)total * kWinRows * sizeof(uint32_t));
-            if (e == hipSuccess) e = hipMemcpyAsync(d_xp, xptr.data(), xptr.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_xe, 0xff, (size_t)total * kWbCols * sizeof(int32_t), stream);
-            if (e == hipSuccess) e = hipMemsetAsync(d_xm, 0, (size_t)total * kWinRows * sizeof(uint32_t), stream);
-            if (e == hipSuccess) {   // (padding slots point at the all-zero sentinel row, like pack_kernel's; filled on the device - ADVICE r04: a 460 MB host vector)
-                const int64_t nfill = total * kWbCols;
-                hipLaunchKernelGGL(fill_i32_kernel, dim3((unsigned)std::min<int64_t>((nfill + 255) / 256, 65535)), dim3(256), 0, stream, d_xc, nfill, p->Nc);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (xptr must outlive its copy)
-            }
-            int32_t bad = 0;
-            if (e == hipSuccess && nw > 0) {
-                hipLaunchKernelGGL(expand_edges_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, p->d_mask, p->d_ebase, d_xp, d_xc, d_xm, d_xe, p->Nc, d_flags);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flags, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess || bad) {
-                drop();
-                p->val_choice.store(0, std::memory_order_release);
-                return e == hipSuccess ? TCGNN_OK : fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "single-edge tile stream: %s", hipGetErrorString(e));
-            }
-            (void)hipFree(d_flags);
-            p->d_xwb_ptr = d_xp; p->d_xcols = d_xc; p->d_xmask = d_xm; p->d_xeidx = d_xe; p->total_xwb = xptr[(size_t)nw];
-            p->bytes += xptr.size() * sizeof(int64_t) + (size_t)total * (2 * kWbCols * sizeof(int32_t) + kWinRows * sizeof(uint32_t));
-        }
-    }
-    const int rc = build_lds_cells(p, stream, kLdsValSlot);
+    if (p->val_choice.load(std::memory_order_acquire) >= 0) return TCGNN_OK;
+    bool usable;
+    size_t source_bytes, eidx_bytes = 0;
+    const int src = val_source_stream(p, stream, &usable, &source_bytes);
+    if (!usable) { p->val_choice.store(0, std::memory_order_release); return src; }
+    const int rc = build_lds_cells(p, stream, kLdsValSlot, &eidx_bytes);
     tcgnn_plan::CellStream& cs = p->lds[kLdsValSlot];
-    bool ok = rc == TCGNN_OK && cs.nranges > 0 && cs.flat_tpc == 1 && cs.nsplit == 0 && cs.d_eidx;
-    if (ok) {   // CSR positions -> 16-bit offsets into each window's run of edges (half the index bytes per call and in the plan)
-        const size_t nt = (size_t)std::max<int64_t>(cs.tiles, 1), nc = (size_t)std::max<int64_t>(cs.cold_tiles, 1);
-        int32_t* d_bad = nullptr; int32_t bad = 0;
-        hipError_t e = hipMalloc(&cs.d_eidx16, nt * 32 * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc(&cs.d_cold_eidx16, nc * 32 * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMalloc(&d_bad, sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, sizeof(int32_t), stream);
-        if (e == hipSuccess) e = hipMemsetAsync(cs.d_eidx16, 0xff, nt * 32 * sizeof(uint16_t), stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(val_index16_kernel, dim3((unsigned)(cs.nwg * kLdsWaves * kLdsMaxW2)), dim3(256), 0, stream, p->rowptr, cs.d_order, cs.d_eidx, cs.d_rbase, cs.d_eidx16, p->N,
-                               kLdsMaxW2, cs.cold_tiles > 0 ? cs.d_cold_ptr : nullptr, cs.d_cold_eidx, cs.d_cold_eidx16, d_bad, cs.d_rl2, std::max(cs.npairs, 1));
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_bad);
-        ok = e == hipSuccess && !bad;
-        if (ok) p->bytes += (nt + nc) * 32 * sizeof(uint16_t);
-    }
-    if (cs.d_eidx) {
+    const bool ok = rc == TCGNN_OK && cs.nranges > 0 && cs.flat_tpc == 1 && cs.nsplit == 0 && cs.d_eidx && val_index16(p, stream);
+    if (cs.d_eidx) {   // (the 32-bit index is build-time only)
         (void)hipStreamSynchronize(stream);
-        p->bytes -= (size_t)(std::max<int64_t>(cs.tiles, 1) + (cs.cold_tiles > 0 ? cs.cold_tiles : 0)) * 32 * sizeof(int32_t);
+        p->bytes -= eidx_bytes;
         (void)hipFree(cs.d_eidx); (void)hipFree(cs.d_cold_eidx); cs.d_eidx = nullptr; cs.d_cold_eidx = nullptr;
     }
     // (the single-edge source is only needed to cut the cell stream: 0.9 GB on the Reddit shape, released here)
     (void)hipStreamSynchronize(stream);
-    p->bytes -= ((size_t)p->nw_eff + 1) * sizeof(int64_t) + (size_t)std::max<int64_t>(p->total_xwb, 1) * (2 * kWbCols * sizeof(int32_t) + kWinRows * sizeof(uint32_t));
+    p->bytes -= source_bytes;
     (void)hipFree(p->d_xwb_ptr); (void)hipFree(p->d_xcols); (void)hipFree(p->d_xmask); (void)hipFree(p->d_xeidx);
     p->d_xwb_ptr = nullptr; p->d_xcols = nullptr; p->d_xmask = nullptr; p->d_xeidx = nullptr;
     p->val_choice.store(ok ? 1 : 0, std::memory_order_release);

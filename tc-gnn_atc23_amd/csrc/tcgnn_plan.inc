@@ -11,24 +11,24 @@ static int build_sync_tables(tcgnn_plan* p, hipStream_t stream) {
     tcgnn_plan::SyncTables& t = p->sync;
     const int nw = p->nw_eff;
     if (nw < kXcds * 256 || !p->d_cols || p->total_wb < 1) return TCGNN_OK;
-    const char* const verbose = getenv("TCGNN_VERBOSE");
+    const bool verbose = verbose_level() > 0;
     t.nwx = (nw + kXcds - 1) / kXcds;
     t.S = kSyncSlice;
     t.R = (t.nwx + t.S - 1) / t.S;
     t.kmax = kSyncKmax;
     const int nslices = kXcds * t.R;
     const int nfb0 = (int)((((int64_t)p->Nc + 1) >> kSyncFbShift0) + 1);
-    uint32_t* d_hist = nullptr;
+    DevBuf<uint32_t> d_hist;
     std::vector<uint32_t> hist((size_t)nslices * nfb0);
-    hipError_t e = hipMalloc(&d_hist, hist.size() * sizeof(uint32_t));
+    hipError_t e = d_hist.alloc(hist.size());
     if (e == hipSuccess) e = hipMemsetAsync(d_hist, 0, hist.size() * sizeof(uint32_t), stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(sync_hist_kernel, dim3((unsigned)nw), dim3(64), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, kSyncFbShift0, nfb0, d_hist);
+        hipLaunchKernelGGL(sync_hist_kernel, dim3((unsigned)nw), dim3(64), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, kSyncFbShift0, nfb0, d_hist.ptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), d_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_hist);
+    d_hist.reset();
     if (e != hipSuccess) { (void)hipGetLastError(); return TCGNN_OK; }
     // hot buckets per slice: at least a quarter of a tile per window of the slice; coarser buckets until every slice's list fits
     std::vector<int32_t> hot((size_t)nslices * t.kmax, 0x7fffffff >> 12), nk((size_t)nslices, 0);
@@ -63,32 +63,31 @@ static int build_sync_tables(tcgnn_plan* p, hipStream_t stream) {
         if (fits) shift = sh;
     }
     if (shift < 0 || tiles_all <= 0) {
-        if (verbose && atoi(verbose) > 0) fprintf(stderr, "[tcgnn] sync walk: hot buckets do not fit %d entries per slice at any bucket size: not built\n", t.kmax);
+        if (verbose) fprintf(stderr, "[tcgnn] sync walk: hot buckets do not fit %d entries per slice at any bucket size: not built\n", t.kmax);
         return TCGNN_OK;
     }
     t.fb_shift = kSyncFbShift0 + shift;
     t.hot_frac = tiles_hot / tiles_all;
     t.avg_k = k_weighted / tiles_all;
-    if (verbose && atoi(verbose) > 0)
+    if (verbose)
         fprintf(stderr, "[tcgnn] sync walk: %d slices of %d windows, buckets of %d rows, %.1f hot buckets per slice (max %d), %.0f %% of the tiles inside them\n", nslices, t.S,
                 1 << t.fb_shift, t.avg_k, t.max_k, 100.0 * t.hot_frac);
     if (t.hot_frac < 0.5) return TCGNN_OK;
-    int32_t* d_hot = nullptr;
-    const size_t b_T = (size_t)nw * (t.kmax + 1) * sizeof(uint32_t);
-    e = hipMalloc(&d_hot, hot.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&t.d_nk, nk.size() * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&t.d_T, b_T);
+    DevBuf<int32_t> d_hot, d_nk;
+    DevBuf<uint32_t> d_T;
+    e = d_hot.alloc(hot.size());
+    if (e == hipSuccess) e = d_nk.alloc(nk.size());
+    if (e == hipSuccess) e = d_T.alloc((size_t)nw * (t.kmax + 1));
     if (e == hipSuccess) e = hipMemcpyAsync(d_hot, hot.data(), hot.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(t.d_nk, nk.data(), nk.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_nk, nk.data(), nk.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) {
         const int64_t total = (int64_t)nw * (t.kmax + 1);
-        hipLaunchKernelGGL(sync_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, t.kmax, t.fb_shift, d_hot, t.d_nk, t.d_T);
+        hipLaunchKernelGGL(sync_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, t.nwx, t.S, t.R, t.kmax, t.fb_shift, d_hot.ptr, d_nk.ptr, d_T.ptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);   // (host vectors above must outlive the copies)
-    (void)hipFree(d_hot);
-    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(t.d_T); (void)hipFree(t.d_nk); t.d_T = nullptr; t.d_nk = nullptr; return TCGNN_OK; }
-    p->bytes += b_T + nk.size() * sizeof(int32_t);
+    if (e != hipSuccess) { (void)hipGetLastError(); return TCGNN_OK; }
+    p->bytes += d_T.release(t.d_T) + d_nk.release(t.d_nk);
     t.ok = true;
     return TCGNN_OK;
 }
@@ -99,18 +98,17 @@ static int plan_read_weights(tcgnn_plan* p, hipStream_t stream, std::vector<int3
     const int nw = p->nw_eff;
     bp->assign((size_t)nw, 0);
     if (nw <= 0) return TCGNN_OK;
-    uint32_t* d_maxdeg = nullptr;
+    DevBuf<uint32_t> d_maxdeg;
     uint32_t h_maxdeg = 0;
-    hipError_t e = hipMalloc(&d_maxdeg, sizeof(uint32_t));
+    hipError_t e = d_maxdeg.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(d_maxdeg, 0, sizeof(uint32_t), stream);
     if (e == hipSuccess && p->N > 0) {
-        hipLaunchKernelGGL(max_degree_kernel, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)p->N + 255) / 256)), dim3(256), 0, stream, p->rowptr, p->N, d_maxdeg);
+        hipLaunchKernelGGL(max_degree_kernel, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)p->N + 255) / 256)), dim3(256), 0, stream, p->rowptr, p->N, d_maxdeg.ptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_maxdeg, d_maxdeg, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(bp->data(), p->bp, (size_t)nw * sizeof(int32_t), hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_maxdeg);
     if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "read blockPartition: %s", hipGetErrorString(e));
     p->max_degree = (int32_t)std::min<uint32_t>(h_maxdeg, 0x7fffffffu);
     return TCGNN_OK;
@@ -177,26 +175,25 @@ static int plan_allocate_and_pack(tcgnn_plan* p, hipStream_t stream, const std::
     const size_t n_wb = (size_t)std::max<int64_t>(p->total_wb, 1);
     const size_t b_ptr = ((size_t)nw + 1) * sizeof(int64_t), b_ord = (size_t)std::max(nw, 1) * sizeof(int32_t);
     const size_t b_cols = n_wb * kWbCols * sizeof(int32_t), b_mask = n_wb * kWinRows * sizeof(uint32_t), b_eb = n_wb * kWinRows * sizeof(int32_t);
-    int32_t* d_flags = nullptr;
+    DevBuf<int32_t> d_flags;
     hipError_t e = hipMalloc(&p->d_wb_ptr, b_ptr);
     if (e == hipSuccess) e = hipMalloc(&p->d_order, b_ord);
     if (e == hipSuccess) e = hipMalloc(&p->d_cols, b_cols);
     if (e == hipSuccess) e = hipMalloc(&p->d_mask, b_mask);
     if (e == hipSuccess) e = hipMalloc(&p->d_ebase, b_eb);
-    if (e == hipSuccess) e = hipMalloc(&d_flags, 2 * sizeof(int32_t));
-    if (e != hipSuccess) { (void)hipFree(d_flags); return fail(e == hipErrorOutOfMemory ? TCGNN_ERR_OOM : TCGNN_ERR_HIP, "plan allocation (%zu bytes): %s", b_ptr + b_ord + b_cols + b_mask + b_eb, hipGetErrorString(e)); }
+    if (e == hipSuccess) e = d_flags.alloc(2);
+    if (e != hipSuccess) { return fail(hip_rc(e), "plan allocation (%zu bytes): %s", b_ptr + b_ord + b_cols + b_mask + b_eb, hipGetErrorString(e)); }
     p->bytes = b_ptr + b_ord + b_cols + b_mask + b_eb;
     int32_t flags[2] = {0, 0};
     e = hipMemcpyAsync(p->d_wb_ptr, wb_ptr.data(), b_ptr, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && nw > 0) e = hipMemcpyAsync(p->d_order, order.data(), (size_t)nw * sizeof(int32_t), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 2 * sizeof(int32_t), stream);
     if (e == hipSuccess && nw > 0) {
-        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->rowptr, p->col, p->e2c, p->e2r, p->d_wb_ptr, p->N, p->Nc, p->d_cols, p->d_mask, p->d_ebase, d_flags);
+        hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->rowptr, p->col, p->e2c, p->e2r, p->d_wb_ptr, p->N, p->Nc, p->d_cols, p->d_mask, p->d_ebase, d_flags.ptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(flags, d_flags, sizeof flags, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream); // the host vectors must outlive the copies
-    (void)hipFree(d_flags);
     if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "plan build: %s", hipGetErrorString(e));
     if (flags[0]) return fail(TCGNN_ERR_BAD_GRAPH, "edgeToColumn / edgeToRow / edgeList hold ids outside the window, blockPartition or node range");
     p->canonical = flags[1] ? 0 : 1;
@@ -221,20 +218,19 @@ static int plan_symmetry(tcgnn_plan* p, hipStream_t stream) {
 static int plan_locality(tcgnn_plan* p, hipStream_t stream) {
     const int nw = p->nw_eff;
     if (nw <= 0) return TCGNN_OK;
-    unsigned long long* d_loc = nullptr;
+    DevBuf<unsigned long long> d_loc;
     unsigned long long h_loc[2] = {0, 0};
-    hipError_t e = hipMalloc(&d_loc, sizeof h_loc);
+    hipError_t e = d_loc.alloc(2);
     if (e == hipSuccess) e = hipMemsetAsync(d_loc, 0, sizeof h_loc, stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(locality_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, p->Nc, p->row_off, std::max(p->Nc / 16, kWinRows), d_loc);
+        hipLaunchKernelGGL(locality_kernel, dim3((unsigned)nw), dim3(256), 0, stream, p->d_wb_ptr, p->d_cols, nw, p->Nc, p->row_off, std::max(p->Nc / 16, kWinRows), d_loc.ptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_loc, d_loc, sizeof h_loc, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_loc);
     if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "plan build (locality): %s", hipGetErrorString(e));
     p->near_frac = h_loc[1] ? (double)h_loc[0] / (double)h_loc[1] : 0.0;
-    if (const char* v = getenv("TCGNN_VERBOSE")) if (atoi(v) > 0) fprintf(stderr, "[tcgnn] plan: %.0f %% of the condensed columns lie within num_cols / 16 rows of their window\n", 100.0 * p->near_frac);
+    if (verbose_level() > 0) fprintf(stderr, "[tcgnn] plan: %.0f %% of the condensed columns lie within num_cols / 16 rows of their window\n", 100.0 * p->near_frac);
     return TCGNN_OK;
 }
 // step 7: column buckets for the range-blocked SpMM: only when windows are long (>= 2 tiles per bucket on average) and numerous
@@ -289,11 +285,7 @@ int tcgnn_plan_destroy(tcgnn_plan* plan) {
     (void)hipFree(plan->d_wb_ptr); (void)hipFree(plan->d_order); (void)hipFree(plan->d_cols);
     (void)hipFree(plan->d_mask); (void)hipFree(plan->d_ebase); (void)hipFree(plan->d_bptr);
     (void)hipFree(plan->sync.d_T); (void)hipFree(plan->sync.d_nk);
-    for (auto& cs : plan->lds) {
-        (void)hipFree(cs.d_cell_ptr); (void)hipFree(cs.d_cell_tiles); (void)hipFree(cs.d_order); (void)hipFree(cs.d_rbase); (void)hipFree(cs.d_rlist); (void)hipFree(cs.d_rl2);
-        (void)hipFree(cs.d_cold_ptr); (void)hipFree(cs.d_cold_cols); (void)hipFree(cs.d_cold_mask); (void)hipFree(cs.d_parts); (void)hipFree(cs.d_flat);
-        (void)hipFree(cs.d_wcold_ptr); (void)hipFree(cs.d_wcold); (void)hipFree(cs.d_eidx); (void)hipFree(cs.d_cold_eidx); (void)hipFree(cs.d_eidx16); (void)hipFree(cs.d_cold_eidx16);
-    }
+    for (auto& cs : plan->lds) release_cell_stream(cs);
     (void)hipFree(plan->d_xwb_ptr); (void)hipFree(plan->d_xcols); (void)hipFree(plan->d_xmask); (void)hipFree(plan->d_xeidx); (void)hipFree(plan->d_sym);
     for (hipEvent_t e : plan->ev) (void)hipEventDestroy(e);
     delete plan;
@@ -321,8 +313,7 @@ int tcgnn_plan_create_sharded(const int32_t* d_nodePointer, const int32_t* d_edg
     p->rowptr = d_nodePointer; p->col = d_edgeList; p->bp = d_blockPartition; p->e2c = d_edgeToColumn; p->e2r = d_edgeToRow;
     auto bail = [&](int rc) { tcgnn_plan_destroy(p); return rc; };
     // TCGNN_VERBOSE=2: where plan creation spends its time (each mark synchronises the stream: a measurement aid, not the product's behaviour)
-    const char* const venv = getenv("TCGNN_VERBOSE");
-    const bool vtime = venv && atoi(venv) >= 2;
+    const bool vtime = verbose_level() >= 2;
     auto t_last = std::chrono::steady_clock::now();
     auto mark = [&](const char* what) {
         if (!vtime) return;

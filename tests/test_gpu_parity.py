@@ -710,6 +710,59 @@ def test_lds_resident_walk_splits_hub_windows_over_wavefronts(dev, T, D, hot, ca
         assert (np.abs(Yw.cpu().numpy() - ref_w) <= bound).all()
 
 
+@pytest.mark.parametrize("graph", ["powerlaw_n2061", "hub_rows_n9000"])
+def test_refused_edge_valued_stream_leaves_the_plan_as_it_found_it(dev, T, graph, monkeypatch):
+    """A failed cell-stream build leaves its slot of the plan exactly as it found it (cells_publish is the only writer and cannot
+    fail).  The one failure that needs no provoked error: the edge-valued stream of a graph with split hub windows, which keep the
+    ordinary stream, is refused (TCGNN_ERR_UNSUPPORTED inside the library, its text left in tcgnn_last_error; build_val_stream
+    answers such a refusal by settling the plan on the gather walks, so tcgnn_plan_prepare_val itself returns TCGNN_OK, forced mode
+    or not).  plan_bytes is then back at what it was before the attempt (the single-edge source released, nothing of a cell
+    stream left behind), a second prepare finds the question settled, forward_AGNN takes the gather walk, and the plan is
+    destroyed cleanly.  hub_rows_n9000 must take that path.  powerlaw_n2061 splits its hub windows only where the chip has few
+    enough CUs for a window to exceed a wavefront's share (on the 256 CUs of the MI355X it does not: measured, the stream is
+    built): there the stream must be in the plan's bytes and forward_AGNN must run on it."""
+    import tcgnn_capi as c
+    if graph == "powerlaw_n2061":
+        rp, col = graphs.powerlaw_graph(2061, 9.0, seed=22)
+    else:
+        rp, col = graphs.hub_rows_graph(9000, seed=5, full_rows=20, half_rows=4, background=250000)
+    n, nnz = len(rp) - 1, len(col)
+    (bp, e2c, e2r), meta = meta_for(dev, rp, col)
+    rng = np.random.default_rng(64)
+    X = rng.standard_normal((n, 64)).astype(np.float32)
+    att = rng.standard_normal(nnz).astype(np.float32)
+    tX, tatt = to_dev(dev, X, att)
+    monkeypatch.setenv("TCGNN_LDS_FLAT", "1")
+    T.clear_plan_cache()
+    try:
+        c.check(c.lib.tcgnn_set_spmm_mode(3), "tcgnn_set_spmm_mode")
+        T.prepare([64], *meta)                                # (the binary walk's streams of this width: theirs to keep)
+        before = T.plan_info(*meta)["plan_bytes"]
+        T.prepare([64], *meta, edge_valued=True)
+        refusal = c.lib.tcgnn_last_error().decode("utf-8", "replace")
+        after = T.plan_info(*meta)["plan_bytes"]
+        T.prepare([64], *meta, edge_valued=True)              # settled either way: nothing is built, nothing released
+        again = T.plan_info(*meta)["plan_bytes"]
+        Y = T.forward_AGNN(tX, meta[0], meta[1], tatt.view(1, -1), *meta[2:])[0].cpu().numpy()
+        kernel = T.last_kernel(*meta)
+        at_end = T.plan_info(*meta)["plan_bytes"]
+    finally:
+        c.lib.tcgnn_set_spmm_mode(0)
+        T.clear_plan_cache()
+    print("%s: plan_bytes %d before, %d after prepare(edge_valued=True), kernel %s" % (graph, before, after, kernel))
+    refused = kernel == "spmm_kernel"
+    assert refused or graph == "powerlaw_n2061", kernel
+    if refused:
+        assert "edge-valued LDS-resident SpMM: the single-edge cells of this graph are not uniform enough for a flat stream" in refusal, refusal
+        assert after == before, (before, after)
+    else:
+        assert "spmm_lds_val_kernel" in kernel and after > before, (kernel, before, after)
+    assert again == after and at_end == after, (after, again, at_end)
+    ref = O.spmm_val(X, rp, col, att, bp, e2c, e2r, round_mode=O.ROUND_TF32)
+    Y64, absY = O.spmm_f64(X, rp, col, att)
+    assert_parity(Y, ref, Y64, absY, "forward_AGNN behind a refused / built edge-valued stream")
+
+
 @pytest.mark.parametrize("D", [16, 32, 41, 64, 100, 128, 160])
 @pytest.mark.parametrize("flat", ["1", "2"])
 @pytest.mark.parametrize("shape", ["dense", "denser", "ragged"])
