@@ -72,7 +72,7 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, i = lane & 15;
     const int64_t stride = a.stride;
-    const int kx = scale_exp_from_bits(a.hdr[0]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
     const bool two_step = kx > 63 || kx < -63;                     // score = acc * 2^(-2kx), in two factors if needed
     const float inv_a = two_step ? pow2f(-kx) : pow2f(-2 * kx), inv_b = two_step ? pow2f(-kx) : 1.0f;
     const float wv = a.w ? a.w[0] : 1.0f;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
     // backward: the recorded max |ef|.  Rounding to a 10-bit mantissa does not depend on the scale.
     float att_bound;
     if constexpr (BWD) att_bound = fabsf(wv) * __uint_as_float(a.ef_absmax[0]);
-    else { const float xm = __uint_as_float(a.hdr[0]); att_bound = fabsf(wv) * (float)a.Dpad * xm * xm; }
+    else { const float xm = __uint_as_float(a.hdr[kHdrMaxX]); att_bound = fabsf(wv) * (float)a.Dpad * xm * xm; }
     const int ka = scale_exp_from_bits(__float_as_uint(att_bound));
     // r05: ONE scale per ROW of A.  The edge weights of a power-law graph under the reference's unscaled weights spread over 2^30 and
     // more ACROSS the matrix (hub x hub scores against leaf x leaf), and with one scale for all of them the small rows' weights fell
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT 
             for (int q = 0; q < 8; ++q) m = fmaxf(m, fabsf((float)v[q]));
         }
         m = fmaxf(m, __shfl_xor(m, 16)); m = fmaxf(m, __shfl_xor(m, 32));
-        const float xm = __uint_as_float(a.hdr[0]);
+        const float xm = __uint_as_float(a.hdr[kHdrMaxX]);
         const float bound = fabsf(wv) * (float)a.Dpad * xm * (m * pow2f(-kx));
         const int k = scale_exp_from_bits(__float_as_uint(bound));
         if (g == 0 && row < a.N) a.rowka[row] = k;
@@ -639,5 +639,5 @@ __global__ __launch_bounds__(kReduceThreads) void agnn_reduce_kernel(const doubl
         if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = (float)(sh[0] + (extra ? extra[0] : 0.0));   // (extra: wide_patch_kernel's correction, header words 10-11; zero unless the call was patched)
+    if (threadIdx.x == 0) out[0] = (float)(sh[0] + (extra ? extra[0] : 0.0));   // (extra: wide_patch_kernel's correction, the double at header word kHdrDwExtra; zero unless the call was patched)
 }

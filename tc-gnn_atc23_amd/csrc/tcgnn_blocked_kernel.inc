@@ -11,8 +11,8 @@ __global__ __launch_bounds__(256, (NT <= 4 ? 4 : 2)) void TCGNN_KERNEL_NAME(TCGN
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, i = lane & 15;
     const int coloff = (a.chunk0 + (int)blockIdx.y) * kMaxChunkDims;
-    const int kx = scale_exp_from_bits(a.hdr[0]);
-    const int ka = VAL ? scale_exp_from_bits(a.hdr[1]) : 0;
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
+    const int ka = VAL ? scale_exp_from_bits(a.hdr[kHdrMaxVal]) : 0;
     const float inv1 = pow2f(-kx), inv2 = VAL ? pow2f(-ka) : 1.0f;
     using TW = TileWalker<NT, VAL>;
     char* atab = smem + 4 * TW::WAVE_LDS;

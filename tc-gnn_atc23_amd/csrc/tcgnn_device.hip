@@ -28,9 +28,12 @@
 //   partial accumulators of the wavefronts are summed through LDS in a fixed order.
 //
 // File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator; in include order):
-//   tcgnn_device.hip          HIP_TRY, DevBuf (owner of one device allocation), struct tcgnn_plan, KernelTimer, device helpers (the range guard's rule, host and device), launch tables, switches
-//                             and walk predicates, stage_features, sync_chosen; behind the includes the C ABI of the operators and tcgnn_range_mode
-//   tcgnn_pack_stage.inc      plan-time kernels (pack, locality, longest row) and the staging pass (abs-max, fp16 images)
+//   tcgnn_device.hip          HIP_TRY, DevBuf (owner of one device allocation), struct tcgnn_plan, KernelTimer, device helpers, launch tables, switches
+//                             and walk predicates, sync_chosen; behind the includes the C ABI of the operators
+//   tcgnn_stage.inc           the staging pass, device and host: the header's words by name, the range guard's rule, abs-max kernels and every
+//                             fp16 converter (row-major, planar, slice), image and workspace sizes, Guard, fill_header, one converter launcher
+//                             per layout, stage_features; the C ABI of the caller-staged images and tcgnn_range_mode
+//   tcgnn_pack.inc            plan-time kernels (fill, longest row, locality, pack)
 //   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
 //   tcgnn_heads.inc           multi-head edge-valued SpMM: HeadsWalker (TileWalker with one A fragment per head), spmm_heads_kernel, spmm_heads_csr_kernel
 //   tcgnn_sync_walk.inc       slice-synchronised range walk: SyncArgs, spmm_sync_kernel's two forms from tcgnn_sync_kernel.inc, table kernels
@@ -216,16 +219,9 @@ struct KernelTimer {
 // ------------------------------------------------------------------------------------------
 // small device helpers
 // ------------------------------------------------------------------------------------------
+static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static constexpr int kXcds = 8;   // workgroups are dealt to the XCDs round-robin in launch order: workgroup b runs on XCD b % 8 (observed, used for speed only)
 
-// Power-of-two exponent k such that absmax * 2^k lies in [2^14, 2^15): fp16-safe (max 65504) with
-// 29 binades of normal range below the largest element.  0 for all-zero / non-finite data.
-__device__ __forceinline__ int scale_exp_from_bits(uint32_t b) {
-    if (b == 0u || b >= 0x7f800000u) return 0;
-    int e = (int)(b >> 23) - 127;
-    int k = 14 - e;
-    return k > 126 ? 126 : (k < -126 ? -126 : k);
-}
 __device__ __forceinline__ float relu_if(int on, float v) { return on ? fmaxf(v, 0.0f) : v; }
 // tcgnn_spmm_scaled's epilogue in the final store: Y[r, c] = relu(fl32(fl32(s * rs[r]) + bias[c])).  Each pointer may be null (that
 // step is left out).  No contraction into an FMA: the result must equal torch's separate multiply and add bit for bit.
@@ -235,101 +231,6 @@ __device__ __forceinline__ float epi_apply(int relu, const Epi& e, int64_t row, 
     if (e.rs) v = v * e.rs[row];
     if (e.bias) v = v + e.bias[col];
     return relu_if(relu, v);
-}
-__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
-
-// ---- the within-matrix range guard -------------------------------------------------------
-// The fp16 operand image carries ONE power-of-two scale per matrix: an element more than 2^28 below the largest loses mantissa
-// bits (fp16 subnormal) and one more than 2^39 below it is flushed to zero, where the reference's TF32 keeps fp32's exponent
-// (TCGNN_kernel.cu:438-444).  The absolute error that leaves per element is <= max|X| * 2^-39, which stays far inside the
-// contract's |d| <= 1e-3 max(1, |ref|) whenever max|X| < 2^8 - whatever the small elements are.  A matrix that holds BOTH an
-// element >= 2^8 and a nonzero one more than 2^28 below the maximum is "wide": for it every fp16-path kernel returns at once and
-// a fallback kernel launched behind it (plain fp32, operands rounded exactly like the reference's, CSR order) does the work; for
-// every other matrix the fallback returns at once.  The decision is made on the device from the staging pass's header words -
-// word k: bits of max |.| (k = 0: X, 1: edge values), word k + 2: 0x7f800000 - bits of the smallest nonzero |.| (0: none seen) -
-// so no call synchronises or reads anything back.
-// How large is "large": what an element below max 2^-28 loses is at most max 2^-39 in absolute terms, and a result may collect at
-// most k such errors - k = min(cap, n_tiny), cap = the longest row of the graph (SpMM) or 2 D (SDDMM, fused AGNN: the terms of one
-// dot product), n_tiny = how many elements of the matrix lose bits at all (counted by the conversion pass: ONE stray 1e-5 in a
-// matrix of 1e4's - what a training epoch's activations look like, tools/probe_training_ranges.py - costs one error, not cap).
-// The sum must stay inside the contract's 1e-3 max(1, |ref|) whatever the result is, i.e. below 2^-10:
-//   binary SpMM        k max 2^-39 <= 2^-10                 -> wide iff     log2 max  >= 29 - log2 k
-//   SDDMM / fused AGNN k max^2 2^-39 <= 2^-10               -> wide iff 2 * log2 max  >= 29 - log2 k
-//   edge-valued SpMM   2 k max|A| max|X| 2^-39 <= 2^-10     -> wide iff log2 max|A| + log2 max|X| >= 28 - log2 k
-// Header words (written by the staging pass): 4 = cap for X (0: guard off / an image the caller staged: never wide), 5 = cap for
-// the edge values, 6 = n_tiny of X, 7 = the power of max in the bound (1 or 2).
-// (host and device: tcgnn_range_mode reports the decision with the same four functions on a copy of the header words)
-__host__ __device__ __forceinline__ bool range_spread(const uint32_t* hdr, int k, int& emax) {
-    const uint32_t mx = hdr[k], mi = hdr[k + 2];
-    emax = (int)(mx >> 23);
-    if (mi == 0u || mx == 0u || mx >= 0x7f800000u) return false;
-    return emax - (int)((0x7f800000u - mi) >> 23) > 28;
-}
-__host__ __device__ __forceinline__ int ceil_log2_u32(uint32_t k) {
-#ifdef __HIP_DEVICE_COMPILE__
-    return k <= 1u ? 0 : 32 - __clz((int)(k - 1u));
-#else
-    return k <= 1u ? 0 : 32 - __builtin_clz(k - 1u);
-#endif
-}
-__host__ __device__ __forceinline__ bool range_is_wide(const uint32_t* hdr, int) {   // the feature matrix alone (binary SpMM, SDDMM, fused AGNN)
-    int emax;
-    const uint32_t cap = hdr[4], n = hdr[6];
-    if (!range_spread(hdr, 0, emax) || cap == 0u || n == 0u) return false;
-    return (int)hdr[7] * (emax - 127) >= 29 - ceil_log2_u32(n < cap ? n : cap);
-}
-__host__ __device__ __forceinline__ bool range_is_wide_val(const uint32_t* hdr) {
-    int ex, ea;
-    const bool sx = range_spread(hdr, 0, ex), sa = range_spread(hdr, 1, ea);
-    const uint32_t cap = hdr[5];
-    if (!(sx || sa) || cap == 0u || hdr[0] == 0u || hdr[1] == 0u) return false;
-    const uint32_t n = hdr[6], k = (sa || n >= cap) ? cap : (n ? n : 1u);   // (edge values that lose bits are not counted: the longest row bounds them)
-    return (ex - 127) + (ea - 127) >= 28 - ceil_log2_u32(k);
-}
-// ---- SDDMM and the fused AGNN pair at guard level 2: the way through a "wide" matrix (r04: a few dirty rows; r05: any number).
-// What makes a matrix wide is elements that lose bits in the image, i.e. DIRTY ROWS of X - one stray 1e-5 among 1e4's in a training
-// epoch (tools/probe_training_ranges.py), hub rows by the hundred on a power-law graph under the reference's unscaled weights.  The
-// conversion pass marks them in a bitmap behind the image (one bit per row of X; header word 8 counts them).  The MFMA kernels run
-// as usual and wide_patch_kernel - one launch behind them, returning at once when nothing is wide - scans the edges and recomputes,
-// in fp32 with the reference's operand rounding, every edge that touches a dirty row (its score, and what it contributes to the
-// aggregate and to d_w), a wavefront per such edge: cost proportional to the dirty edges, 0.2 ms of scan when anything is wide at
-// all.  r04 kept a list of at most 48 rows and left a matrix with more to the documented bound (VERDICT r04 "the default guard level
-// leaves a hole"): the hole is closed.  Level 3 (strict, header word 9): the MFMA kernels return and the same launch does all the
-// work in plain fp32 (wide_dense_body).  The aggregation operators, whose bound is linear and never reached in training, keep
-// their own fallback kernels (spmm_wide_fallback_kernel, the fp32-MFMA walk).
-__device__ __forceinline__ bool wide2_dense(const uint32_t* hdr) { return range_is_wide(hdr, 0) && hdr[9] != 0u; }   // (strict level: plain fp32)
-// conversion pass: a thread that met an element losing bits marks the row; the first to mark a row counts it
-__device__ __forceinline__ void note_dirty_row(uint32_t* hdr, uint32_t* bitmap, uint32_t nt, int64_t row) {
-    if (!bitmap || !nt) return;
-    const uint32_t bit = 1u << (row & 31);
-    if (!(atomicOr(bitmap + (row >> 5), bit) & bit)) atomicAdd(hdr + 8, 1u);
-}
-// conversion pass: this thread's count of elements that lose bits (nonzero, below fp16's normal range once scaled) -> hdr[6]
-__device__ __forceinline__ void count_tiny(uint32_t* cnt, uint32_t mine) {   // mine <= 15; lanes that left the kernel early count as 0
-    if (!cnt) return;
-    uint32_t total = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) total += (uint32_t)__popcll(__ballot((mine >> b) & 1u)) << b;
-    if (total && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(1)) - 1) atomicAdd(cnt, total);
-}
-// (decided on the SOURCE element and its scaled fp32 value, not on the converted half: an element more than 2^39 below the maximum
-//  converts to exactly 0 and must still count - ADVICE r03: one 1e12 among O(1) data had n_tiny = 0 and stayed on the MFMA path)
-__device__ __forceinline__ uint32_t is_tiny(float x, float s) { return (x != 0.0f && fabsf(x * s) < 6.103515625e-5f) ? 1u : 0u; }
-
-// Round to a 10-bit mantissa, nearest with ties AWAY from zero: bit-for-bit what the reference's
-// wmma::__float_to_tf32 (cvt.rna.tf32.f32, TCGNN_kernel.cu:441-444) does.  The result has at most
-// 11 significant bits, so the following fp32 -> fp16 conversion is exact for every element within
-// 2^-28 of the (scaled) maximum; fp16's default nearest-EVEN would differ on ties (about one
-// element in 2^13), which shows up as 2^-10-sized output differences.
-__device__ __forceinline__ float round_rna10(float x) {   // the same rounding kept in fp32 (fallback kernels)
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7f800000u) != 0x7f800000u) u = (u + 0x1000u) & 0xffffe000u;
-    return __uint_as_float(u);
-}
-__device__ __forceinline__ _Float16 to_half_rna(float x) {
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7f800000u) != 0x7f800000u) u = (u + 0x1000u) & 0xffffe000u;
-    return (_Float16)__uint_as_float(u);
 }
 
 // LDS image of one tile: 32 gathered rows x (NT*16) halves, addressed in 16-byte slots.
@@ -379,7 +280,8 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
     return __builtin_bit_cast(half4, v);
 }
 
-#include "tcgnn_pack_stage.inc"
+#include "tcgnn_stage.inc"
+#include "tcgnn_pack.inc"
 
 #include "tcgnn_gather_spmm.inc"
 #include "tcgnn_sync_walk.inc"
@@ -589,36 +491,10 @@ static constexpr int g_lds_dbg = 0;
 static constexpr int g_lds_fill_quota = 1;     // (r03: the wavefronts with an empty last slot take the range fills, -0.5 %)
 static int g_spmm_mode = [] { const char* e = getenv("TCGNN_SPMM_MODE"); return e ? atoi(e) : 0; }();
 static inline int spmm_mode_of(const tcgnn_plan* p) { const int m = p ? (int)p->spmm_mode.load(std::memory_order_relaxed) : -1; return m >= 0 ? m : g_spmm_mode; }
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 static constexpr size_t kBlockedMinBytes = 6u << 20;   // below this X16 is (nearly) L2-resident anyway
 static constexpr size_t kRangeTargetBytes = 1u << 20;  // X16 bytes per column range: wavefronts drift by a range or two
                                                         // and the 4 MB L2 also streams metadata (sweep: 0.5-1.5 MB best at D=64)
-static constexpr size_t kHdrBytes = 256;
 
-// Row pitch of the fp16 image in halves: a gathered row should touch as few 128-byte lines as
-// possible (a 96-byte row at pitch 96 straddles two lines three times out of four: D = 41..48 ran
-// slower than D = 64), so rows up to 128 B are padded to a power of two and longer ones to whole lines.
-static int x16_pitch(int dpad) {
-    const int bytes = dpad * 2;
-    if (bytes > 128) return ((bytes + 127) / 128 * 128) / 2;   // whole lines (D = 602: 1280 B, not the 2048 B of the next power of two)
-    int p = 32;
-    while (p < bytes) p <<= 1;   // power of two: 32 B .. 128 B inside one line
-    return p / 2;
-}
-// The gather walks address X16 through a structured buffer descriptor whose record stride (the row pitch in bytes) is a
-// 14-bit field: a wider row would wrap it (stride 0 + the swizzle bit set) and every gather would silently read the wrong row.
-static constexpr int kMaxStructStride = 16383;
-// ... and whose index * stride + offset is formed in 32 bits: an image of 4 GB or more (a papers100M-sized shard: 111 M rows of
-// 128 B) wraps.  The kernels then form 64-bit lane addresses instead (one v_mad_u64_u32 per gathered piece).
-static int32_t image_is_big(int32_t rows, int pitch_halves) { return ((uint64_t)rows + 1) * (uint64_t)pitch_halves * 2u >= (1ull << 32) ? 1 : 0; }
-static size_t image_bytes(const tcgnn_plan* plan, int pitch_halves) { return ((size_t)plan->Nc + 1) * pitch_halves * sizeof(_Float16); }   // (the rows a walk gathers from, + the zero row)
-static bool pitch_fits_descriptor(int D) { return x16_pitch(round_up(D, 16)) * 2 <= kMaxStructStride; }
-
-// (behind the image: the dirty-row bitmap of the range guard, one bit per row of X - wide_patch_kernel)
-static size_t image_body_bytes(int32_t N, int32_t D) { return ((((size_t)N + 1) * (size_t)x16_pitch(round_up(D, 16)) * sizeof(_Float16)) + 255) / 256 * 256; }
-static size_t dirty_bitmap_bytes(int32_t N) { return ((((size_t)N + 1 + 31) / 32) * 4 + 255) / 256 * 256; }
-static size_t workspace_bytes_for(int32_t N, int32_t D) { return kHdrBytes + image_body_bytes(N, D) + dirty_bitmap_bytes(N); }
-static uint32_t* dirty_bitmap_of(void* ws, int32_t N, int32_t D) { return reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + kHdrBytes + image_body_bytes(N, D)); }
 // the fused AGNN backward keeps one double per workgroup (per window; the XCD-sliced walk: per slice and four windows) behind the fp16 image
 static constexpr int kAgnnMaxSlices = 16;   // two rounds of eight (= XCDs)
 static size_t agnn_partial_bytes(const tcgnn_plan* plan) {
@@ -653,113 +529,12 @@ static int range_count(const tcgnn_plan* plan, size_t x16_bytes, size_t range_by
     while (nranges < plan->nbuckets && x16_bytes / nranges > range_bytes) nranges <<= 1;
     return nranges;
 }
-// ---- range guard parameters (range_is_wide): cap = how many lost-precision terms one result can collect at most - the longest row
-// of the graph (SpMM) or 2 D (SDDMM / fused AGNN) - and the power of max|X| in the error bound.  cap 0 = guard off
-// (tcgnn_set_range_guard(0), TCGNN_RANGE_GUARD=0).
-static int g_range_guard = [] { const char* e = getenv("TCGNN_RANGE_GUARD"); return e ? atoi(e) : 2; }();   // (r04: 2 - the usual wide input of SDDMM / fused AGNN costs one patch launch; 3 = strict)
-static inline int range_guard_of(const tcgnn_plan* p) { const int g = p ? (int)p->range_guard.load(std::memory_order_relaxed) : -1; return g >= 0 ? g : g_range_guard; }
-struct Guard { uint32_t cap, pow; };
-static Guard guard_spmm(const tcgnn_plan* p) { return {range_guard_of(p) ? (uint32_t)std::max(p->max_degree, 1) : 0u, 1u}; }
-// (level 1, the default: the aggregation operators - binary and edge-valued SpMM, the fused dense update - whose bound is linear in
-//  max|X| and which a training epoch never reaches; level 2 adds SDDMM and the fused AGNN pair, whose bound is QUADRATIC in max|X|:
-//  an AGNN epoch of the reference's unscaled recipe crosses 2^14.5 with a single lost element now and then, and each such call
-//  costs ~25 ms in the CSR fallbacks against 2 ms - so those two answer to the documented bound unless asked to be strict)
-static Guard guard_sddmm(const tcgnn_plan* p, int D) { const int lv = range_guard_of(p); return {lv >= 2 ? (uint32_t)(2 * std::max(D, 1)) : 0u, 2u | (lv >= 3 ? 0x100u : 0u)}; }   // (bit 8: strict, header word 9)
-
-// absmax(X) [+ absmax(val)] into the header's range words: X gated / column-scaled like the image will be (nx elements, 0: the words
-// exist already); the edge values under the SpMM's own cap
-static void launch_absmax(const tcgnn_plan* plan, const float* d_X, const float* d_gate, const float* d_cs, int64_t nx, int32_t D, const float* d_val, uint32_t* hdr, const Guard& gx,
-                          hipStream_t stream) {
-    if (nx > 0) {
-        const int grid = absmax_grid(nx);
-        if (d_cs && d_gate) hipLaunchKernelGGL(absmax_scaled_kernel<true>, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, d_cs, nx, (int64_t)D, hdr, hdr + 2, gx.cap, gx.pow);
-        else if (d_cs) hipLaunchKernelGGL(absmax_scaled_kernel<false>, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, d_cs, nx, (int64_t)D, hdr, hdr + 2, gx.cap, gx.pow);
-        else if (d_gate) hipLaunchKernelGGL(absmax_gated_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, d_gate, nx, hdr, hdr + 2, gx.cap, gx.pow);
-        else hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_X, nx, hdr, hdr + 2, gx.cap, gx.pow);
-    }
-    if (d_val && plan->E > 0) {
-        const int grid = absmax_grid(plan->E);
-        hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, stream, d_val, plan->E, hdr + 1, hdr + 3, guard_spmm(plan).cap, 0u);
-    }
-}
-
 // ---- what every hot-path entry point asks of the caller's buffers BEFORE it enqueues anything (include/tcgnn.h "Alignment"): a
 // refused call has touched neither the outputs nor the workspace.
 // [N, D] outputs: spmm_cold_planar_kernel and spmm_cold_val_kernel read-modify-write Y as float4 wherever D % 4 == 0, and
 // agnn_slice_sum_kernel stores it that way - on the host, so that no kernel carries a pointer test
 static int check_output_aligned(const char* call, const char* what, const void* p) {
     if (reinterpret_cast<uintptr_t>(p) & 15) return fail(TCGNN_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned, got %p", call, what, p);
-    return TCGNN_OK;
-}
-// the workspace the header prescribes for the call (tcgnn_workspace_bytes / tcgnn_sddmm2_workspace_bytes), whichever walk will run:
-// a walk that needs less than that does not make a smaller buffer legal
-static int check_workspace(const char* call, const void* ws, size_t ws_bytes, size_t need) {
-    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(TCGNN_ERR_WORKSPACE, "%s: workspace needs %zu bytes 256-aligned, got %zu at %p", call, need, ws_bytes, ws);
-    return TCGNN_OK;
-}
-
-struct StagedImage { const uint32_t* hdr = nullptr; const _Float16* x16 = nullptr; int dpad = 0, pitch = 0; };
-struct StageOpts {
-    bool planar = false;                 // [dpad / 16 planes][Nc + 1][16 halves] for the LDS-resident kernels instead of row-major
-    const float* d_gate = nullptr;
-    // ldx > 0: X (and the gate) is a column block of a wider row-major matrix with that row stride; the scale words in the
-    // header were then computed over the WHOLE matrix by the caller (block_of_wider = true: no memset, no absmax pass here), so
-    // every block is rounded exactly as the undivided call would round it.
-    int64_t ldx = 0; bool block_of_wider = false;
-    // hdr_from: the scale words of an image of the same matrix staged a moment ago (the planar one of a plan with a cold remainder):
-    // copied instead of recomputed, so both images are rounded with the same scale without a second pass over X
-    const uint32_t* hdr_from = nullptr;
-    const Guard* guard = nullptr;        // (null: the binary SpMM's bound; else the caller's operator has its own)
-    const float* d_cs = nullptr;         // (tcgnn_spmm_scaled): the operand is d_cs[row] * X'[row, :] - absmax, tiny count and image all of that product
-};
-// enqueue absmax(X) [+ absmax(val)] + convert; *out: the fp16 image
-static int stage_features(const tcgnn_plan* plan, const float* d_X, const float* d_val, int32_t D, void* ws, size_t ws_bytes, hipStream_t stream, const StageOpts& o, StagedImage* out) {
-    const bool planar = o.planar;
-    const float* const d_gate = o.d_gate; const float* const d_cs = o.d_cs;
-    const int64_t ldx = o.ldx;
-    const uint32_t* const hdr_from = o.hdr_from;
-    const Guard gx = o.guard ? *o.guard : guard_spmm(plan);
-    const size_t need = workspace_bytes_for(plan->Nc, D);
-    if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(TCGNN_ERR_WORKSPACE, "workspace: need %zu bytes 256-aligned, got %zu at %p", need, ws_bytes, ws);
-    uint32_t* hdr = static_cast<uint32_t*>(ws);
-    _Float16* x16 = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + kHdrBytes);
-    const int dpad = round_up(D, 16);
-    const int pitch = x16_pitch(dpad);
-    const bool block_of_wider = o.block_of_wider || hdr_from;
-    if (hdr_from) HIP_TRY(hipMemcpyAsync(hdr, hdr_from, 32, hipMemcpyDeviceToDevice, stream));
-    else if (!block_of_wider) HIP_TRY(hipMemsetAsync(hdr, 0, 64, stream));   // (words 0 .. 7: range words; 8: dirty-row count)
-    if (!block_of_wider) launch_absmax(plan, d_X, d_gate, d_cs, (int64_t)plan->Nc * D, D, d_val, hdr, gx, stream);
-    const int64_t chunks = ((int64_t)plan->Nc + 1) * (dpad / 8);
-    const unsigned cgrid = (unsigned)((chunks + 255) / 256);
-    uint32_t* const tiny = hdr_from ? nullptr : hdr + 6;   // (a second image of the same matrix: its elements are counted already)
-    const bool vec = (D % 4 == 0) && (ldx % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_X) & 15) == 0);
-    if (planar && d_cs) {   // (scaled: the rows kernel where X is whole float4 rows, else one chunk per thread - the same image either way)
-        if (vec && D % 16 == 0 && (!d_gate || (reinterpret_cast<uintptr_t>(d_gate) & 15) == 0)) {
-            const int64_t threads = ((int64_t)plan->Nc + 1) * (D / 4);
-            hipLaunchKernelGGL(convert_planar_rows_scaled_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d_X, d_cs, plan->Nc, D, x16, hdr, d_gate, tiny);
-        } else if (vec) hipLaunchKernelGGL((convert_planar_scaled_kernel<true>), dim3(cgrid), dim3(256), 0, stream, d_X, d_cs, plan->Nc, D, dpad / 16, x16, hdr, d_gate, tiny);
-        else hipLaunchKernelGGL((convert_planar_scaled_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, d_cs, plan->Nc, D, dpad / 16, x16, hdr, d_gate, tiny);
-    } else if (planar) {   // [dpad / 16 planes][Nc + 1][16 halves] for the LDS-resident range kernel (same chunk count: no pitch padding)
-        if (vec && D % 16 == 0 && (!d_gate || (reinterpret_cast<uintptr_t>(d_gate) & 15) == 0)) {
-            const int64_t threads = ((int64_t)plan->Nc + 1) * (D / 4);
-            hipLaunchKernelGGL(convert_planar_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, d_X, plan->Nc, D, x16, hdr, d_gate, tiny);
-        } else if (vec) hipLaunchKernelGGL((convert_planar_kernel<true>), dim3(cgrid), dim3(256), 0, stream, d_X, plan->Nc, D, dpad / 16, x16, hdr, d_gate, tiny);
-        else if ((size_t)D * 64 * sizeof(float) <= 48 * 1024)
-            hipLaunchKernelGGL(convert_planar_tiled_kernel, dim3((unsigned)(((int64_t)plan->Nc + 1 + 63) / 64)), dim3(256), (size_t)D * 64 * sizeof(float), stream,
-                               d_X, plan->Nc, D, dpad / 16, x16, hdr, d_gate, tiny);
-        else     hipLaunchKernelGGL((convert_planar_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, plan->Nc, D, dpad / 16, x16, hdr, d_gate, tiny);
-    } else {
-        uint32_t* const dirty = (tiny && (gx.pow & 0xffu) == 2u && gx.cap) ? dirty_bitmap_of(ws, plan->Nc, D) : nullptr;   // (SDDMM / fused AGNN at guard level 2: dirty rows for wide_patch_kernel)
-        if (dirty) HIP_TRY(hipMemsetAsync(dirty, 0, dirty_bitmap_bytes(plan->Nc), stream));
-        if (d_cs && vec) hipLaunchKernelGGL((convert_scaled_kernel<true>), dim3(cgrid), dim3(256), 0, stream, d_X, d_cs, plan->Nc, D, dpad, pitch, x16, hdr, d_gate, ldx, tiny, dirty);
-        else if (d_cs)   hipLaunchKernelGGL((convert_scaled_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, d_cs, plan->Nc, D, dpad, pitch, x16, hdr, d_gate, ldx, tiny, dirty);
-        else if (vec) hipLaunchKernelGGL((convert_kernel<true>), dim3(cgrid), dim3(256), 0, stream, d_X, plan->Nc, D, dpad, pitch, x16, hdr, d_gate, ldx, tiny, dirty);
-        else     hipLaunchKernelGGL((convert_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, plan->Nc, D, dpad, pitch, x16, hdr, d_gate, ldx, tiny, dirty);
-    }
-    HIP_TRY(hipGetLastError());
-    out->hdr = hdr; out->x16 = x16; out->dpad = dpad; out->pitch = pitch;
     return TCGNN_OK;
 }
 
@@ -848,19 +623,6 @@ int tcgnn_agnn_pair_backward(const tcgnn_plan* plan, const float* d_dY, const fl
     return run_agnn(agnn_call(plan, d_dY, d_w, const_cast<float*>(d_ef), const_cast<uint32_t*>(d_ef_absmax), d_G, d_dw, D, ws, ws_bytes, stream, true));
 }
 
-// which way the last staged call on this workspace went: the range guard's own rule (range_is_wide / range_is_wide_val) on the header words
-int tcgnn_range_mode(const void* d_workspace, void* stream_v, int32_t* wide_x, int32_t* wide_val) {
-    if (!d_workspace || !wide_x) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_range_mode: null argument");
-    uint32_t h[10];
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    HIP_TRY(hipMemcpyAsync(h, d_workspace, sizeof(h), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    *wide_x = range_is_wide(h, 0) ? 1 : 0;
-    if (*wide_x && h[7] == 2u) *wide_x = h[9] ? 1 : 2;   // (SDDMM / fused AGNN: a few dirty rows - MFMA kernel + wide_patch_kernel; many - fp32 only at the strict level)
-    if (wide_val) *wide_val = range_is_wide_val(h) ? 1 : 0;
-    return TCGNN_OK;
-}
-
 size_t tcgnn_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
     if (!plan || D < 1) return 0;
     // (the fused AGNN calls' reduction slots and the partial score streams of the LDS-resident SDDMM ride along)
@@ -923,35 +685,9 @@ int tcgnn_spmm_gemm(const tcgnn_plan* plan, const float* d_X, const float* d_W, 
     return run_spmm(c);
 }
 
-int tcgnn_x16_pitch(int32_t D) { return D < 1 ? 0 : x16_pitch(round_up(D, 16)); }
-
-int tcgnn_stage_absmax(const float* d_X, int64_t n, uint32_t* d_word, void* stream_v) {
-    if (n < 0 || (n > 0 && !d_X) || !d_word) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_stage_absmax: null argument");
-    if (n == 0) return TCGNN_OK;
-    const int grid = absmax_grid(n);
-    hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kAbsmaxThreads), 0, static_cast<hipStream_t>(stream_v), d_X, n, d_word, (uint32_t*)nullptr, 0u, 0u);
-    HIP_TRY(hipGetLastError());
-    return TCGNN_OK;
-}
-
-int tcgnn_stage_rows(const float* d_X, int32_t rows, int32_t D, const uint32_t* d_absmax_word, void* d_dst, void* stream_v) {
-    if (rows < 0 || D < 1 || (rows > 0 && !d_X) || !d_absmax_word || !d_dst) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_stage_rows: bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_dst) & 15) != 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_stage_rows: destination must be 16-byte aligned");
-    const int dpad = round_up(D, 16), pitch = x16_pitch(dpad);
-    const int64_t chunks = ((int64_t)rows + 1) * (dpad / 8);
-    const unsigned cgrid = (unsigned)((chunks + 255) / 256);
-    hipStream_t stream = static_cast<hipStream_t>(stream_v);
-    const bool vec = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_X) & 15) == 0);
-    _Float16* dst = static_cast<_Float16*>(d_dst);
-    if (vec) hipLaunchKernelGGL((convert_kernel<true>), dim3(cgrid), dim3(256), 0, stream, d_X, rows, D, dpad, pitch, dst, d_absmax_word, (const float*)nullptr);
-    else     hipLaunchKernelGGL((convert_kernel<false>), dim3(cgrid), dim3(256), 0, stream, d_X, rows, D, dpad, pitch, dst, d_absmax_word, (const float*)nullptr);
-    HIP_TRY(hipGetLastError());
-    return TCGNN_OK;
-}
-
 int tcgnn_spmm_staged(const tcgnn_plan* plan, const void* d_image, float* d_Y, int32_t D, void* stream) {
     if (!d_image || (reinterpret_cast<uintptr_t>(d_image) & 255)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_spmm_staged: the image must be 256-byte aligned");
-    // Every MFMA kernel opens with the range guard's test on header words 2, 4, 6, 7; a caller-staged image carries no range words
+    // Every MFMA kernel opens with the range guard's test on the header's range words (kHdrLoX, kHdrCapX, kHdrTiny, kHdrPow); a caller-staged image carries no range words
     // (never "wide": there is no fp32 X to fall back to).  The gather walks are told so (SpmmArgs::unguarded) and never look at
     // bytes 4 .. 255 of the header: the image is READ-ONLY to this call, as the signature says - one staged image may be shared by
     // several streams or ranks (r04 cleared those words with a memset on the caller's image, a write racing with other readers).
@@ -978,19 +714,6 @@ static bool lds_takes_staged(const tcgnn_plan* plan, int32_t D, hipStream_t stre
 int tcgnn_spmm_staged_layout(const tcgnn_plan* plan, int32_t D, void* stream) {
     if (!plan || D < 1) return 0;
     return lds_takes_staged(plan, D, static_cast<hipStream_t>(stream)) ? 1 : 0;
-}
-
-int tcgnn_stage_rows_planar(const float* d_X, int32_t rows, int32_t D, const uint32_t* d_absmax_word, void* d_dst, int64_t plane_rows, void* stream_v) {
-    if (rows < 0 || D < 1 || (rows > 0 && !d_X) || !d_absmax_word || !d_dst || plane_rows < rows) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_stage_rows_planar: bad argument");
-    if ((reinterpret_cast<uintptr_t>(d_dst) & 31) != 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_stage_rows_planar: destination must be 32-byte aligned");
-    const int nplanes = round_up(D, 16) / 16;
-    const int64_t chunks = (int64_t)rows * 2 * nplanes;
-    if (chunks > 0) {
-        hipLaunchKernelGGL(convert_planar_slice_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream_v), d_X, rows, D, nplanes,
-                           static_cast<_Float16*>(d_dst), plane_rows, d_absmax_word);
-        HIP_TRY(hipGetLastError());
-    }
-    return TCGNN_OK;
 }
 
 int tcgnn_spmm_staged_planar(const tcgnn_plan* plan, const void* d_image, float* d_Y, int32_t D, void* stream) {

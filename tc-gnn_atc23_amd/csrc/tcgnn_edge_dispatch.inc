@@ -124,7 +124,7 @@ static void launch_slice_sum(const tcgnn_plan* plan, const float* ypart, float* 
 // tcgnn_spmm_val on the XCD-sliced walk (route_spmm's kValSliced): the backward kernel with the score half off - w = 1, ef = the caller's
 // values, their abs-max from this call's header, one scale (no rowka) - and the slice sum
 static int launch_val_sliced(const tcgnn_plan* plan, const StagedImage& im, const float* d_val, float* d_Y, int32_t D, void* ws, int ns, hipStream_t stream) {
-    AgnnArgs a = agnn_args(plan, im, D, nullptr, const_cast<float*>(d_val), const_cast<uint32_t*>(im.hdr) + 1, agnn_addends_of(ws, plan, D), agnn_partial_of(ws, plan, D));
+    AgnnArgs a = agnn_args(plan, im, D, nullptr, const_cast<float*>(d_val), const_cast<uint32_t*>(im.hdr) + kHdrMaxVal, agnn_addends_of(ws, plan, D), agnn_partial_of(ws, plan, D));
     a.gsel = plan->nbuckets / ns; a.nslices = ns; a.valonly = 1; a.rot = agnn_rot(plan);
     KernelTimer timer(plan, stream, "agnn_kernel (XCD-sliced, values only) + agnn_slice_sum_kernel");
     HIP_TRY((launch_agnn<4, true, 0>(im.dpad / 16, a, ns * ((plan->nw_eff + 3) / 4), stream)));
@@ -225,8 +225,8 @@ static int run_agnn(const AgnnCall& c) {
         default:                    e = launch_agnn_per_window(c, a, &nslots); break;
     }
     HIP_TRY(e);
-    // (the d_w correction of the patch: a double in header words 10-11, zeroed with the header by the staging pass)
-    double* const dw_extra = reinterpret_cast<double*>(const_cast<uint32_t*>(im.hdr) + 10);
+    // (the d_w correction of the patch: the double at header word kHdrDwExtra, zeroed with the header by fill_header)
+    double* const dw_extra = reinterpret_cast<double*>(const_cast<uint32_t*>(im.hdr) + kHdrDwExtra);
     const int guard_level = range_guard_of(plan);
     if (guard_level >= 2) {
         // a few dirty rows (what training produces): the MFMA kernel above ran, the edges that touch them are recomputed here

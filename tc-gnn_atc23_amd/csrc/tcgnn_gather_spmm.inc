@@ -480,8 +480,8 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, const Epi& epi) {
     const int coloff = (a.chunk0 + (int)blockIdx.y) * kMaxChunkDims; // first feature column of this pass
     const int64_t tb = a.wb_ptr[w], te = a.wb_ptr[w + 1];
     if (a.accumulate && !a.relu && !EPI && tb == te) return;   // nothing to add to what the LDS-resident kernel stored
-    const int kx = scale_exp_from_bits(a.hdr[0]);
-    const int ka = VAL ? scale_exp_from_bits(a.hdr[1]) : 0;
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
+    const int ka = VAL ? scale_exp_from_bits(a.hdr[kHdrMaxVal]) : 0;
 
     floatx4 acc[NT];
 #pragma unroll

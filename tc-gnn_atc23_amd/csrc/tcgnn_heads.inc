@@ -200,8 +200,8 @@ __global__ __launch_bounds__(256, ((G * FB + 1) / 2 <= 4 ? 4 : 2)) void spmm_hea
     const int head0 = h.head0 + (int)blockIdx.y * G;
     const int coloff = head0 * (FB * 8);   // first feature column of this pass (a multiple of 16: route_heads only forms such passes)
     const int64_t tb = a.wb_ptr[w], te = a.wb_ptr[w + 1];
-    const int kx = scale_exp_from_bits(a.hdr[0]);
-    const int ka = scale_exp_from_bits(a.hdr[1]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
+    const int ka = scale_exp_from_bits(a.hdr[kHdrMaxVal]);
 
     floatx4 acc[NT], acc2[NT];
 #pragma unroll

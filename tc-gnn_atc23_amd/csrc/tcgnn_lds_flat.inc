@@ -447,7 +447,7 @@ __global__ __launch_bounds__(256, 2) void spmm_cold_planar_kernel(const ColdPlan
     }
     const int64_t row = (int64_t)w * kWinRows + r;
     if (!live || row >= a.N) return;
-    const float inv = pow2f(-scale_exp_from_bits(a.hdr[0]));
+    const float inv = pow2f(-scale_exp_from_bits(a.hdr[kHdrMaxX]));
     float* dst = a.y + row * a.D + plane * 16;
     if (plane * 16 + 16 <= a.D && (a.D & 3) == 0) {
 #pragma unroll

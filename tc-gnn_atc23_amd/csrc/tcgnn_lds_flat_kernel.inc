@@ -19,7 +19,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
     const int coloff = chunk_id * kLdsChunkDims;
     const uint32_t lds0 = (uint32_t)(uintptr_t)((LDS_AS char*)smem);
     const uint32_t pad0 = lds0 + 2 * BUFB + (uint32_t)wave * (2 * PADB);
-    const int kx = scale_exp_from_bits(a.hdr[0]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
 
     // (the window ids are read again in the epilogue instead of living through the walk: eight scalar registers the entry words and
     //  the dense walk need - the kernel spilled scalars into a vector register's lanes)

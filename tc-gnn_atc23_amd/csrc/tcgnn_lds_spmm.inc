@@ -402,169 +402,6 @@ template <int NT, int PLANE> __device__ __forceinline__ void lds_cell_block(uint
     else lds_cell_block4<PLANE>(ad0, ad1, idaddr, maddr, lo, hi, idw, m);
 }
 
-// fp32 X -> PLANAR fp16 image for the LDS kernel: plane p = columns 16p .. 16p+15 of every row, [planes][N + 1][16]
-// halves (32-byte records; row N all zero).  A column range of one plane is then one contiguous run of memory (each
-// LDS-DMA instruction moves 1 KB of consecutive bytes), and inside LDS a row's 16-column slices sit a whole plane apart:
-// the transposed read of slice s is the SAME address register with the immediate offset s * plane.
-// One thread per 16-byte chunk; writes are consecutive.  Rounding as convert_kernel.
-// (CS: tcgnn_spmm_scaled's column scale, as in convert_body)
-template <bool VEC, bool CS>
-__device__ __forceinline__ void convert_planar_body(const float* __restrict__ X, int32_t N, int32_t D, int32_t nplanes,
-                                                    _Float16* __restrict__ X16, const uint32_t* __restrict__ hdr,
-                                                    const float* __restrict__ G, uint32_t* __restrict__ tiny, const float* __restrict__ cs) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t per_plane = ((int64_t)N + 1) * 2;
-    if (q >= per_plane * nplanes) return;
-    const int p = (int)(q / per_plane);
-    const int64_t rem = q - (int64_t)p * per_plane;
-    const int64_t row = rem >> 1;
-    const int d0 = p * 16 + (int)(rem & 1) * 8;
-    const float s = pow2f(scale_exp_from_bits(hdr[0]));
-    half8 o;
-    uint32_t nt = 0;   // (range guard: elements that lose bits in the image - counted on the source values, is_tiny)
-    if (row < N && VEC && d0 + 8 <= D) {
-        const float4* src = reinterpret_cast<const float4*>(X + row * D + d0);
-        const float4 a = src[0], b = src[1];
-        float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        if constexpr (CS) {
-            const float c = cs[row];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = c * v[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool on = !G || G[row * D + d0 + j] > 0.0f;
-            o[j] = on ? to_half_rna(v[j] * s) : (_Float16)0.0f;
-            nt += on ? is_tiny(v[j], s) : 0u;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int d = d0 + j;
-            const bool on = row < N && d < D && (!G || G[row * D + d] > 0.0f);
-            const float v = on ? (CS ? cs[row] * X[row * D + d] : X[row * D + d]) : 0.0f;
-            o[j] = to_half_rna(v * s);
-            nt += is_tiny(v, s);
-        }
-    }
-    *reinterpret_cast<half8*>(X16 + q * 8) = o;
-    count_tiny(tiny, nt);
-}
-
-template <bool VEC>
-__global__ __launch_bounds__(256) void convert_planar_kernel(const float* __restrict__ X, int32_t N, int32_t D, int32_t nplanes,
-                                                             _Float16* __restrict__ X16, const uint32_t* __restrict__ hdr,
-                                                             const float* __restrict__ G = nullptr, uint32_t* __restrict__ tiny = nullptr) {
-    convert_planar_body<VEC, false>(X, N, D, nplanes, X16, hdr, G, tiny, nullptr);
-}
-template <bool VEC>
-__global__ __launch_bounds__(256) void convert_planar_scaled_kernel(const float* __restrict__ X, const float* __restrict__ cs, int32_t N, int32_t D, int32_t nplanes,
-                                                                    _Float16* __restrict__ X16, const uint32_t* __restrict__ hdr,
-                                                                    const float* __restrict__ G, uint32_t* __restrict__ tiny) {
-    convert_planar_body<VEC, true>(X, N, D, nplanes, X16, hdr, G, tiny, cs);
-}
-
-// The same image for D % 16 == 0 (no padding columns), read the way X lies in memory: one thread per float4, so a wavefront
-// reads 1 KB of consecutive bytes and writes, per plane, the 32-byte records of consecutive rows - whole lines.  (The
-// chunk-per-thread version above reads 64-byte pieces a row apart and touches every line of X twice, from two planes: 30 us
-// for Reddit at D = 64 against 17 us this way.)  The all-zero sentinel row is written by the threads past the last float4.
-template <bool CS>
-__device__ __forceinline__ void convert_planar_rows_body(const float* __restrict__ X, int32_t N, int32_t D, _Float16* __restrict__ X16,
-                                                         const uint32_t* __restrict__ hdr, const float* __restrict__ G, uint32_t* __restrict__ tiny,
-                                                         const float* __restrict__ cs) {
-    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int q = D >> 2;                              // float4 per row
-    const int64_t total = (int64_t)N * q;
-    if (f >= total + q) return;
-    const int64_t row = f / q;                         // (row == N: the sentinel row)
-    const int c4 = (int)(f - row * q);
-    half4 o = {(_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
-    uint32_t nt = 0;   // (range guard)
-    if (f < total) {
-        const float s = pow2f(scale_exp_from_bits(hdr[0]));
-        float4 v = reinterpret_cast<const float4*>(X)[f];
-        if (G) {
-            const float4 gt = reinterpret_cast<const float4*>(G)[f];
-            if (!(gt.x > 0.0f)) v.x = 0.0f;
-            if (!(gt.y > 0.0f)) v.y = 0.0f;
-            if (!(gt.z > 0.0f)) v.z = 0.0f;
-            if (!(gt.w > 0.0f)) v.w = 0.0f;
-        }
-        if constexpr (CS) {
-            const float c = cs[row];
-            v.x = c * v.x; v.y = c * v.y; v.z = c * v.z; v.w = c * v.w;
-        }
-        o[0] = to_half_rna(v.x * s); o[1] = to_half_rna(v.y * s); o[2] = to_half_rna(v.z * s); o[3] = to_half_rna(v.w * s);
-        nt = is_tiny(v.x, s) + is_tiny(v.y, s) + is_tiny(v.z, s) + is_tiny(v.w, s);
-    }
-    const int plane = c4 >> 2;
-    *reinterpret_cast<half4*>(X16 + (((int64_t)plane * ((int64_t)N + 1) + row) * 16 + (c4 & 3) * 4)) = o;
-    count_tiny(tiny, nt);
-}
-
-__global__ __launch_bounds__(256) void convert_planar_rows_kernel(const float* __restrict__ X, int32_t N, int32_t D, _Float16* __restrict__ X16,
-                                                                  const uint32_t* __restrict__ hdr, const float* __restrict__ G, uint32_t* __restrict__ tiny) {
-    convert_planar_rows_body<false>(X, N, D, X16, hdr, G, tiny, nullptr);
-}
-__global__ __launch_bounds__(256) void convert_planar_rows_scaled_kernel(const float* __restrict__ X, const float* __restrict__ cs, int32_t N, int32_t D, _Float16* __restrict__ X16,
-                                                                         const uint32_t* __restrict__ hdr, const float* __restrict__ G, uint32_t* __restrict__ tiny) {
-    convert_planar_rows_body<true>(X, N, D, X16, hdr, G, tiny, cs);
-}
-
-// A SLICE of rows into the planes of a caller's image (tcgnn_stage_rows_planar: a rank of a row-sharded run converts only ITS rows;
-// plane p of the image starts plane_rows records behind plane p - 1).  One thread per 16-byte chunk, rounding as convert_kernel; no
-// sentinel row, no range words: the caller's image holds zeros wherever nobody writes.
-__global__ __launch_bounds__(256) void convert_planar_slice_kernel(const float* __restrict__ X, int32_t rows, int32_t D, int32_t nplanes, _Float16* __restrict__ dst,
-                                                                   int64_t plane_rows, const uint32_t* __restrict__ word) {
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t per_plane = (int64_t)rows * 2;
-    if (q >= per_plane * nplanes) return;
-    const int p = (int)(q / per_plane);
-    const int64_t rem = q - (int64_t)p * per_plane;
-    const int64_t row = rem >> 1;
-    const int d0 = p * 16 + (int)(rem & 1) * 8;
-    const float s = pow2f(scale_exp_from_bits(word[0]));
-    half8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int d = d0 + j;
-        o[j] = to_half_rna((d < D ? X[row * D + d] : 0.0f) * s);
-    }
-    *reinterpret_cast<half8*>(dst + (((int64_t)p * plane_rows + row) * 2 + (rem & 1)) * 8) = o;
-}
-
-// The same conversion for row lengths that rule out 16-byte loads (D % 4 != 0, e.g. Reddit's 41 classes): a workgroup stages
-// 64 rows x D floats through LDS with coalesced scalar loads (the per-thread version above reads 32-byte pieces 4*D bytes
-// apart: 58 us against 23 us for the vector path at the same size), then every thread emits 16-byte planar chunks.
-__global__ __launch_bounds__(256) void convert_planar_tiled_kernel(const float* __restrict__ X, int32_t N, int32_t D, int32_t nplanes,
-                                                                   _Float16* __restrict__ X16, const uint32_t* __restrict__ hdr,
-                                                                   const float* __restrict__ G, uint32_t* __restrict__ tiny) {
-    extern __shared__ float stage[];                 // [64][D]
-    constexpr int ROWS = 64;
-    const int64_t row0 = (int64_t)blockIdx.x * ROWS;
-    const int64_t nrows = (int64_t)N + 1 - row0 < ROWS ? (int64_t)N + 1 - row0 : ROWS;   // includes the sentinel row N
-    const float s = pow2f(scale_exp_from_bits(hdr[0]));
-    const int64_t total = nrows * D;
-    uint32_t nt = 0;                                 // (range guard: counted where every source element is seen once)
-    for (int64_t k = threadIdx.x; k < total; k += blockDim.x) {
-        const int64_t e = row0 * D + k;
-        float v = 0.0f;
-        if (e < (int64_t)N * D && (!G || G[e] > 0.0f)) { const float x = X[e]; v = x * s; nt += is_tiny(x, s); }
-        stage[k] = v;
-    }
-    __syncthreads();
-    const int chunks = nplanes * 2;                  // 16-byte chunks per row
-    for (int64_t c = threadIdx.x; c < nrows * chunks; c += blockDim.x) {
-        const int r = (int)(c / chunks), ch = (int)(c % chunks);
-        const int p = ch >> 1, d0 = p * 16 + (ch & 1) * 8;
-        half8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = d0 + j < D ? to_half_rna(stage[(int64_t)r * D + d0 + j]) : (_Float16)0.0f;
-        *reinterpret_cast<half8*>(X16 + (((int64_t)p * ((int64_t)N + 1) + row0 + r) * 2 + (ch & 1)) * 8) = o;
-    }
-    if (tiny && nt) atomicAdd(tiny, nt);   // (range guard; a loop of uneven trip counts: one atomic per thread that saw any - rare)
-}
-
 // LDS-DMA of one column range: NT planes x (BR / 32) instructions of 1 KB (rows 32b .. 32b+31 of a plane; lane l: row l/2,
 // half l%2: 1 KB of consecutive source bytes -> 1 KB of consecutive LDS), dealt round-robin to the 16 wavefronts (wavefront
 // w issues instructions w, w + 16, w + 32 ...; four dedicated loaders measured slower: 0.58 vs 0.49 ms of fill alone).
@@ -631,7 +468,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void spmm_lds_kernel(const SpmmLdsA
     const int coloff = chunk_id * kLdsChunkDims;   // first feature column of this pass
     const uint32_t lds0 = (uint32_t)(uintptr_t)((LDS_AS char*)smem);
     const uint32_t pad0 = lds0 + 2 * BUFB + (uint32_t)wave * (2 * kLdsPadB);
-    const int kx = scale_exp_from_bits(a.hdr[0]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
 
     int wj[MAXW];
     uint32_t pj[MAXW];   // split hub windows: part | parts << 8 | scratch index << 16 (0: a whole window)

@@ -18,7 +18,7 @@
 // range fill, is the cold remainder, added from the planar image by spmm_cold_val_kernel.
 //
 // Numerics: values are rounded to a 10-bit mantissa with the reference's rule and scaled by the power of two of max |value|
-// (header word 1), exactly as the gather walks' TileWalker<NT, true> does; products are exact in fp32; sums run in range order.
+// (header word kHdrMaxVal), exactly as the gather walks' TileWalker<NT, true> does; products are exact in fp32; sums run in range order.
 
 struct SpmmValArgs {
     const uint32_t* blocks;     // plan: [npairs][16 wavefronts][32 T words] ids + masks (as SpmmFlatArgs::blocks)
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(kValThreads) void val_permute_kernel(const float* _
     __syncthreads();
     if (threadIdx.x == 0) { int32_t a = 0; for (int j = 0; j < kValWpb; ++j) { offs[j] = a; a += lens[j]; } offs[kValWpb] = a; }
     __syncthreads();
-    const float s = pow2f(scale_exp_from_bits(hdr[1]));
+    const float s = pow2f(scale_exp_from_bits(hdr[kHdrMaxVal]));
     const bool staged = offs[kValWpb] <= kValSpanHalves;
     if (staged) {
         // The four runs as ONE index space (element t of the span lies in window j = the number of run starts at or below t): sixteen
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void spmm_lds_val_kernel(const Spmm
     const uint32_t lds0 = (uint32_t)(uintptr_t)((LDS_AS char*)smem);
     const uint32_t pad0 = lds0 + 2 * BUFB + (uint32_t)wave * (2 * PADB);
     const uint32_t vpad0 = lds0 + 2 * BUFB + kLdsWaves * 2 * PADB + (uint32_t)wave * (2 * PADV);
-    const int kx = scale_exp_from_bits(a.hdr[0]), ka = scale_exp_from_bits(a.hdr[1]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]), ka = scale_exp_from_bits(a.hdr[kHdrMaxVal]);
 
     int wj[MAXW];
     floatx4 acc[MAXW][NT];
@@ -595,7 +595,7 @@ __global__ __launch_bounds__(256, 2) void spmm_cold_val_kernel(const ColdValArgs
     }
     const int64_t row = (int64_t)w * kWinRows + r;
     if (!live || row >= a.N) return;
-    const float inv = pow2f(-scale_exp_from_bits(a.hdr[0])), inv2 = pow2f(-scale_exp_from_bits(a.hdr[1]));   // (|kx + ka| may exceed 126: two factors)
+    const float inv = pow2f(-scale_exp_from_bits(a.hdr[kHdrMaxX])), inv2 = pow2f(-scale_exp_from_bits(a.hdr[kHdrMaxVal]));   // (|kx + ka| may exceed 126: two factors)
     float* dst = a.y + row * a.D + plane * 16;
     if (plane * 16 + 16 <= a.D && (a.D & 3) == 0) {
 #pragma unroll

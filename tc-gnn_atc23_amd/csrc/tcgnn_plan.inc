@@ -1,7 +1,7 @@
 // tcgnn_plan.inc - the plan's lifetime: tcgnn_plan_create[_sharded] as a sequence of named steps, tcgnn_plan_destroy, tcgnn_plan_get_info,
 // tcgnn_plan_prepare[_val], kernel timing, and the mode / range-guard setters.  Included by tcgnn_device.hip behind the dispatchers,
 // whose predicates tcgnn_plan_prepare[_val] ask (lds_wanted, ensure_lds_streams, val_lds_wanted, ensure_val_stream); struct tcgnn_plan
-// itself is in tcgnn_device.hip, the plan-time kernels in tcgnn_pack_stage.inc, the cell-stream builds in tcgnn_lds_plan.inc.
+// itself is in tcgnn_device.hip, the plan-time kernels in tcgnn_pack.inc, the cell-stream builds in tcgnn_lds_plan.inc.
 
 // ---- tables of the slice-synchronised range walk (tcgnn_sync_walk.inc), built at plan creation for graphs whose numbering has
 // locality (near_frac > 0.5: the walks that rely on it are the ones this one replaces) and whose windows are alike.  Two small kernels, one

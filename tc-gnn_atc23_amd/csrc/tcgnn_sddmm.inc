@@ -28,15 +28,15 @@ struct SddmmArgs {
     const _Float16* xa16;
     const uint32_t* hdr_a;
 };
-// tcgnn_sddmm2's range guard (level >= 2: hdr_z[4] = 2 D, else 0): the whole call goes the fp32 way when either operand holds elements
-// that lose bits in its image (range_spread, counted in word 6) and k max|X| max|Z| 2^-39 could leave 2^-10 - range_is_wide's rule for
+// tcgnn_sddmm2's range guard (level >= 2: Z's kHdrCapX = 2 D, else 0): the whole call goes the fp32 way when either operand holds elements
+// that lose bits in its image (range_spread, counted in kHdrTiny) and k max|X| max|Z| 2^-39 could leave 2^-10 - range_is_wide's rule for
 // SDDMM with the product of the two maxima in place of the square of one
 __device__ __forceinline__ bool sddmm2_wide(const uint32_t* hx, const uint32_t* hz) {
     int ex, ez;
-    const bool sx = range_spread(hx, 0, ex) && hx[6] != 0u, sz = range_spread(hz, 0, ez) && hz[6] != 0u;
-    const uint32_t cap = hz[4];
-    if (!(sx || sz) || cap == 0u || hx[0] == 0u || hz[0] == 0u) return false;
-    const uint32_t n = (sx ? hx[6] : 0u) + (sz ? hz[6] : 0u);
+    const bool sx = range_spread(hx, 0, ex) && hx[kHdrTiny] != 0u, sz = range_spread(hz, 0, ez) && hz[kHdrTiny] != 0u;
+    const uint32_t cap = hz[kHdrCapX];
+    if (!(sx || sz) || cap == 0u || hx[kHdrMaxX] == 0u || hz[kHdrMaxX] == 0u) return false;
+    const uint32_t n = (sx ? hx[kHdrTiny] : 0u) + (sz ? hz[kHdrTiny] : 0u);
     return (ex - 127) + (ez - 127) >= 29 - ceil_log2_u32(n < cap ? n : cap);
 }
 
@@ -71,12 +71,12 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, i = lane & 15;
     const int64_t stride = a.stride;
-    const int kx = scale_exp_from_bits(a.hdr[0]);
+    const int kx = scale_exp_from_bits(a.hdr[kHdrMaxX]);
     // ef = acc * 2^(-2kx); one multiply unless 2kx leaves the fp32 exponent range (then two)
     bool two_step = kx > 63 || kx < -63;
     float inv_a = two_step ? pow2f(-kx) : pow2f(-2 * kx), inv_b = two_step ? pow2f(-kx) : 1.0f;
     if constexpr (TWO) {   // ef = acc * 2^-(ka + kx); with ka = kx exactly the factors above
-        const int ka = scale_exp_from_bits(a.hdr_a[0]);
+        const int ka = scale_exp_from_bits(a.hdr_a[kHdrMaxX]);
         two_step = ka + kx > 126 || ka + kx < -126;
         inv_a = two_step ? pow2f(-ka) : pow2f(-(ka + kx));
         inv_b = two_step ? pow2f(-kx) : 1.0f;
@@ -363,8 +363,8 @@ __global__ __launch_bounds__(WAVES * 64) void sddmm_wide_kernel(const SddmmArgs 
     const int w = a.order[blockIdx.x];
     const int64_t tb = a.wb_ptr[w], te = a.wb_ptr[w + 1];
     const int64_t stride = a.stride;
-    const float inv = pow2f(-scale_exp_from_bits(a.hdr[0]));
-    const float inv_w = TWO ? pow2f(-scale_exp_from_bits(a.hdr_a[0])) : inv;   // (the window operand's scale)
+    const float inv = pow2f(-scale_exp_from_bits(a.hdr[kHdrMaxX]));
+    const float inv_w = TWO ? pow2f(-scale_exp_from_bits(a.hdr_a[kHdrMaxX])) : inv;   // (the window operand's scale)
     const int ksteps = (a.Dpad + 31) >> 5;
     const half8 hz = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t arow = (int64_t)w * kWinRows + i;

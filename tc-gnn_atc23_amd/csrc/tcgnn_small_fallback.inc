@@ -263,8 +263,8 @@ __device__ __forceinline__ void wide_dense_body(const PatchArgs& a, double* part
 static constexpr int kPatchBitmapWords = 15360, kPatchUnroll = 4, kPatchQueue = 128, kPatchRowDriven = 256;
 __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, double* partial, int32_t npartial) {
     if (!range_is_wide(a.hdr, 0)) return;
-    if (a.hdr[9]) { wide_dense_body(a, partial, npartial); return; }   // (the strict level: the MFMA kernel returned at once, everything in plain fp32)
-    if (!a.hdr[8]) return;                                             // (lost elements in no row that was marked: nothing to patch)
+    if (a.hdr[kHdrStrict]) { wide_dense_body(a, partial, npartial); return; }   // (the strict level: the MFMA kernel returned at once, everything in plain fp32)
+    if (!a.hdr[kHdrDirtyRows]) return;                                             // (lost elements in no row that was marked: nothing to patch)
     __shared__ uint32_t sbm[kPatchBitmapWords];
     __shared__ int32_t q_elo[4][kPatchQueue], q_ehi[4][kPatchQueue], q_r[4][kPatchQueue], q_c[4][kPatchQueue];   // per wavefront: edge, row (-2: read it), column | dirty-column flag << 31
     const int nwords = (a.Nc + 1 + 31) >> 5;
@@ -276,9 +276,9 @@ __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, doub
     const uint32_t* const bm = in_lds ? sbm : a.bitmap;   // (generic pointer: the branch is kernel-uniform)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t gw = (int64_t)blockIdx.x * 4 + wv, nwaves = (int64_t)gridDim.x * 4;
-    const float inv = pow2f(-scale_exp_from_bits(a.hdr[0]));
+    const float inv = pow2f(-scale_exp_from_bits(a.hdr[kHdrMaxX]));
     auto dirty = [&](int64_t x) -> bool { return x >= 0 && x <= a.Nc && ((bm[x >> 5] >> (x & 31)) & 1u); };
-    if (in_lds && a.sym && a.row_off == 0 && a.N == a.Nc && a.hdr[8] <= (uint32_t)kPatchRowDriven && a.sym[0] == 1) {   // (kernel-uniform)
+    if (in_lds && a.sym && a.row_off == 0 && a.N == a.Nc && a.hdr[kHdrDirtyRows] <= (uint32_t)kPatchRowDriven && a.sym[0] == 1) {   // (kernel-uniform)
         __shared__ int32_t dlist[kPatchRowDriven];
         __shared__ int32_t dcount;
         if (threadIdx.x == 0) dcount = 0;
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, doub
             }
         }
         __syncthreads();
-        const int nd = dcount < kPatchRowDriven ? dcount : kPatchRowDriven;   // (hdr[8] counted every marked row once: dcount <= hdr[8])
+        const int nd = dcount < kPatchRowDriven ? dcount : kPatchRowDriven;   // (hdr[kHdrDirtyRows] counted every marked row once: dcount <= hdr[kHdrDirtyRows])
         const int g8 = lane >> 3;
         for (int i = 0; i < nd; ++i) {
             const int32_t d = dlist[i];

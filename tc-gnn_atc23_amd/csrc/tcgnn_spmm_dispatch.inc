@@ -244,13 +244,8 @@ static int run_spmm(const SpmmCall& c);
 // every block rounded with the scale of the whole matrix (absmax over all of X / the edge values here, once)
 static int run_column_blocks(const SpmmCall& c) {
     const tcgnn_plan* const plan = c.plan;
-    const size_t need = workspace_bytes_for(plan->Nc, c.D);
-    if (!c.ws || c.ws_bytes < need || (reinterpret_cast<uintptr_t>(c.ws) & 255))
-        return fail(TCGNN_ERR_WORKSPACE, "workspace: need %zu bytes 256-aligned, got %zu at %p", need, c.ws_bytes, c.ws);
-    uint32_t* whdr = static_cast<uint32_t*>(c.ws);
-    HIP_TRY(hipMemsetAsync(whdr, 0, 32, c.stream));
-    launch_absmax(plan, c.d_X, c.d_gate, c.sc.col, (int64_t)plan->Nc * c.D, c.D, c.d_val, whdr, guard_spmm(plan), c.stream);
-    HIP_TRY(hipGetLastError());
+    if (const int rc = check_workspace("staging", c.ws, c.ws_bytes, workspace_bytes_for(plan->Nc, c.D))) return rc;
+    if (const int rc = fill_header(plan, static_cast<uint32_t*>(c.ws), c.d_X, c.d_gate, c.sc.col, c.D, guard_spmm(plan), c.d_val, plan->E, c.stream)) return rc;
     for (int c0 = 0; c0 < c.D; c0 += kMaxGatherBlockDims) {
         SpmmCall b = c;
         b.d_X = c.d_X + c0; b.d_Y = c.d_Y + c0; b.D = std::min(kMaxGatherBlockDims, c.D - c0);
@@ -502,17 +497,12 @@ static size_t heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F
         default:                return workspace_bytes_for(plan->Nc, std::min(F, kMaxGatherBlockDims));
     }
 }
-// max |edge_val| over all H E values into header words 1 / 3 / 5: ONE scale and one range-guard decision for the whole call
-static void launch_absmax_heads_val(const HeadsCall& c, uint32_t* hdr) {
-    const int64_t n = (int64_t)c.H * c.plan->E;
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n)), dim3(kAbsmaxThreads), 0, c.stream, c.d_val, n, hdr + 1, hdr + 3, guard_spmm(c.plan).cap, 0u);
-}
 static int launch_heads_fused(const HeadsCall& c) {
     const tcgnn_plan* const plan = c.plan;
     const int32_t D = c.H * c.F;
     StagedImage im;
     if (const int rc = stage_features(plan, c.d_X, nullptr, D, c.ws, c.ws_bytes, c.stream, StageOpts{}, &im)) return rc;
-    launch_absmax_heads_val(c, static_cast<uint32_t*>(c.ws));
+    launch_absmax_val(plan, c.d_val, (int64_t)c.H * plan->E, static_cast<uint32_t*>(c.ws), c.stream);   // (max |edge_val| over all H E values: one scale for the whole call)
     HIP_TRY(hipGetLastError());
     {
         KernelTimer timer(plan, c.stream, "spmm_heads_kernel");
@@ -532,11 +522,8 @@ static int launch_heads_fused(const HeadsCall& c) {
 static int run_heads_one_by_one(const HeadsCall& c) {
     const tcgnn_plan* const plan = c.plan;
     const int32_t D = c.H * c.F;
-    uint32_t* whdr = static_cast<uint32_t*>(c.ws);
-    HIP_TRY(hipMemsetAsync(whdr, 0, 64, c.stream));
-    launch_absmax(plan, c.d_X, nullptr, nullptr, (int64_t)plan->Nc * D, D, nullptr, whdr, guard_spmm(plan), c.stream);
-    launch_absmax_heads_val(c, whdr);
-    HIP_TRY(hipGetLastError());
+    // (X's scale over all of X and max |edge_val| over all H E values: every head rounded as the fused walk rounds it)
+    if (const int rc = fill_header(plan, static_cast<uint32_t*>(c.ws), c.d_X, nullptr, nullptr, D, guard_spmm(plan), c.d_val, (int64_t)c.H * plan->E, c.stream)) return rc;
     for (int h = 0; h < c.H; ++h)
         for (int c0 = 0; c0 < c.F; c0 += kMaxGatherBlockDims) {   // (a head wider than one gather launch covers: its own column blocks)
             SpmmCall b;

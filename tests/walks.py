@@ -119,7 +119,7 @@ def transposed_csr(rp, col):
 
 
 # ---- the range-major walks cut the fp16 image into column ranges of TCGNN_RANGE_KB; mirrors of x16_pitch and of range_count
-# (tcgnn_device.hip: the one loop route_sddmm, the SpMM dispatcher and launch_agnn_range_major pick the number of ranges with), so that a test can
+# (x16_pitch: tcgnn_stage.inc; range_count: tcgnn_device.hip, the one loop route_sddmm, the SpMM dispatcher and launch_agnn_range_major pick the number of ranges with), so that a test can
 # force eight of them and say so
 def image_bytes(n, D):
     row = (D + 15) // 16 * 16 * 2
