@@ -7,6 +7,15 @@
 //  line with the one before this file existed: template kernels are listed in the order their launch tables are first used.  Nothing
 //  else depends on the order - move the sections freely, the listing then holds the same kernels in another order.)
 
+// wide_patch_kernel's arguments that both operators take from the plan.  The kernel's row-driven branch is a shortcut of its scan with
+// the same scores bit for bit: TCGNN_PATCH_ROWS=0, read per call, hands it no symmetry word, so the same input takes the scan (tests
+// compare the two).  rows: what the windows of the plan cover - behind them the outputs keep the zeros run_sddmm / run_agnn wrote.
+static const int32_t* patch_sym_of(const tcgnn_plan* plan) {
+    const char* const env = test_knob("TCGNN_PATCH_ROWS");
+    return env && atoi(env) == 0 ? nullptr : plan->d_sym;
+}
+static int32_t patch_rows_of(const tcgnn_plan* plan) { return (int32_t)std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows); }
+
 // ------------------------------------------------------------------------------------------
 // the fused AGNN pair
 // ------------------------------------------------------------------------------------------
@@ -230,7 +239,7 @@ static int run_agnn(const AgnnCall& c) {
     const int guard_level = range_guard_of(plan);
     if (guard_level >= 2) {
         // a few dirty rows (what training produces): the MFMA kernel above ran, the edges that touch them are recomputed here
-        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, c.d_w, c.d_Y, c.d_absmax, dw_extra, plan->N, plan->Nc, D, plan->row_off, bwd ? 2 : 1, plan->E, plan->d_sym};
+        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, c.d_w, c.d_Y, c.d_absmax, dw_extra, plan->N, plan->Nc, D, plan->row_off, bwd ? 2 : 1, plan->E, patch_sym_of(plan), patch_rows_of(plan)};
         // (many: the same launch does all the work in plain fp32 - wide_dense_body; one launch per call either way, returning at once
         //  unless the staged matrix is "wide")
         HIP_TRY(launch_wide_patch(pa, stream, partial, nslots));
@@ -349,7 +358,7 @@ static int launch_sddmm_guard_tail(const SddmmCall& c, const StagedImage& im, co
         hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048)), dim3(256), 0, c.stream, imw.hdr, im.hdr, plan->rowptr, plan->col, c.d_Xw, c.d_X, c.d_ef,
                            rows, c.D, plan->row_off);
     } else if (range_guard_of(plan) >= 2) {   // a few dirty rows: the patch behind the MFMA kernel; many: the CSR fallback (each returns at once otherwise)
-        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, c.D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, nullptr, nullptr, nullptr, nullptr, plan->N, plan->Nc, c.D, plan->row_off, 0, plan->E, plan->d_sym};
+        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, c.D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, nullptr, nullptr, nullptr, nullptr, plan->N, plan->Nc, c.D, plan->row_off, 0, plan->E, patch_sym_of(plan), patch_rows_of(plan)};
         HIP_TRY(launch_wide_patch(pa, c.stream));
     }
     HIP_TRY(hipGetLastError());

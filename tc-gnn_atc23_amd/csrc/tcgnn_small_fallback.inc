@@ -143,6 +143,7 @@ struct PatchArgs {
     float* ef; const float* w; float* Y; uint32_t* efmax; double* dw_extra;
     int32_t N, Nc, D, row_off, mode; int64_t E;
     const int32_t* sym;   // device word: 1 = the plan's graph is structurally symmetric (symmetry_kernel, plan creation); nullptr: not known
+    int32_t rows;         // min(N, nw_eff * 16): the rows of the windows the plan was given.  Behind them ef, Y / G and d_w keep the caller's zeros
 };
 // one thread per edge (r, c): is (c, r) an edge too?  (canonical CSR: column ids sorted inside a row - a binary search.)  sym[0] starts at 1.
 // r06: only the edges ABOVE the diagonal search for their mirror; sym[1] collects (edges above) - (edges below).  Mirrors of distinct
@@ -221,7 +222,7 @@ __device__ __forceinline__ void wide_dense_body(const PatchArgs& a, double* part
     uint32_t m = 0u;
     const float w = a.w ? a.w[0] : 1.0f;
     if ((int)blockIdx.x < nb)
-    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < a.N; row += (int64_t)nb * 4) {
+    for (int64_t row = (int64_t)blockIdx.x * 4 + wave; row < a.rows; row += (int64_t)nb * 4) {   // (rows behind the windows: the caller's zeros stay)
         const float* xr = a.X + (row + a.row_off) * a.D;
         const int64_t e0 = a.rowptr[row], e1 = a.rowptr[row + 1];
         if (a.mode != 2 || a.dw_extra)
@@ -260,6 +261,11 @@ __device__ __forceinline__ void wide_dense_body(const PatchArgs& a, double* part
 // neighbour n of d, the mirror edge (n, d) - a binary search in row n: up to kPatchRowDriven dirty rows are patched that way, every
 // wavefront of the grid taking eight edges of a row at a time (both sides), in ~10 us.  More rows, an asymmetric or rectangular
 // plan, a bitmap beyond LDS: the scan.
+// r15: which wavefront takes which eight edges of a dirty row is a function of the ROW ID.  It was a function of the row's position in
+// dlist, and dlist is filled in the order this workgroup's wavefronts won an LDS atomic: two workgroups that numbered the rows
+// differently left a chunk to no wavefront or to several (modes 1 and 2 then add the correction twice).  dlist's order now decides
+// nothing but the order of the loop.  Rows behind the windows the plan was given (PatchArgs::rows) keep their zeros on every way:
+// a dirty row there is patched on the mirror side only - the edges (n, d) of covered rows n.
 static constexpr int kPatchBitmapWords = 15360, kPatchUnroll = 4, kPatchQueue = 128, kPatchRowDriven = 256;
 __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, double* partial, int32_t npartial) {
     if (!range_is_wide(a.hdr, 0)) return;
@@ -297,19 +303,19 @@ __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, doub
         for (int i = 0; i < nd; ++i) {
             const int32_t d = dlist[i];
             const int64_t e0 = a.rowptr[d], deg = (int64_t)a.rowptr[d + 1] - e0;
-            const int64_t first = (gw + (int64_t)i * 257) % nwaves;          // (consecutive dirty rows start at different wavefronts)
+            const int64_t first = (gw + (int64_t)d * 257) % nwaves;          // (by the row id, the same in every workgroup; neighbouring dirty rows start at different wavefronts)
             for (int64_t j0 = first * 8; j0 < 2 * deg; j0 += nwaves * 8) {   // (wave-uniform trip count: patch_edge_group shuffles inside its groups of eight)
                 const int64_t j = j0 + g8;
                 const bool valid = j < 2 * deg, mirror = j >= deg;
                 const int64_t erow = e0 + (valid ? (mirror ? j - deg : j) : 0);
                 const int32_t n = valid ? a.col[erow] : 0;
                 const bool ndirty = dirty(n);
-                int64_t e = erow; int64_t r = d; int32_t c = n; bool cd = ndirty, on = valid;
+                int64_t e = erow; int64_t r = d; int32_t c = n; bool cd = ndirty, on = valid && d < a.rows;
                 if (mirror) {   // the edge (n, d): where d sits in row n.  Row n dirty as well: its own row side takes that edge
                     int32_t lo = valid ? a.rowptr[n] : 0, hi = valid ? a.rowptr[n + 1] : 0;
                     const int32_t end = hi;
                     while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (a.col[mid] < d) lo = mid + 1; else hi = mid; }
-                    on = valid && !ndirty && lo < end && a.col[lo] == d;
+                    on = valid && !ndirty && n < a.rows && lo < end && a.col[lo] == d;
                     e = lo; r = n; c = d; cd = true;
                 }
                 patch_edge_group(a, on, e, r, c, cd, lane & 7, inv);
@@ -327,7 +333,7 @@ __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, doub
         int32_t r = q_r[wv][k];
         const uint32_t cw = (uint32_t)q_c[wv][k];
         if (mine && r == -2) r = a.e2r[e];                // (a hit by its column alone: its row is read now)
-        const bool on = mine && r >= 0 && r < a.N;
+        const bool on = mine && r >= 0 && r < a.rows;
         patch_edge_group(a, on, e, (int64_t)r, (int32_t)(cw & 0x7fffffffu), (cw >> 31) != 0u, lane & 7, inv);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
     };
@@ -352,7 +358,7 @@ __global__ __launch_bounds__(256) void wide_patch_kernel(const PatchArgs a, doub
             int32_t r = -2;
             const bool cd = dirty(c[u]);
             bool hit = e < a.E && cd;
-            if (rows_dirty && e < a.E) { r = a.e2r[e]; hit = r >= 0 && r < a.N && (cd || dirty((int64_t)r + a.row_off)); }
+            if (rows_dirty && e < a.E) { r = a.e2r[e]; hit = r >= 0 && r < a.rows && (cd || dirty((int64_t)r + a.row_off)); }
             const uint64_t m = __ballot(hit);
             if (!m) continue;
             if (hit) {

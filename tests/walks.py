@@ -146,7 +146,7 @@ def expected_ranges(n, D, column_buckets, range_kb):
 
 # ---- forcing a walk, and judging what it returned (tests/test_gpu_structures.py; kept here for the GPU tests that force walks through ctypes)
 KNOBS = ("TCGNN_LDS_FLAT", "TCGNN_LDS_DENSE_COLS", "TCGNN_SDDMM_XCD", "TCGNN_RM_IDENT", "TCGNN_AGNN_SLICED", "TCGNN_AGNN_ROT", "TCGNN_RANGE_KB",
-         "TCGNN_LDS_HOT_COLS", "TCGNN_SYNC")
+         "TCGNN_LDS_HOT_COLS", "TCGNN_SYNC", "TCGNN_PATCH_ROWS")
 
 
 def forced(T, monkeypatch, mode, env, body, ctx):
