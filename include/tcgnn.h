@@ -452,6 +452,33 @@ int tcgnn_gat_softmax_backward(const int32_t* d_nodePointer, const int32_t* d_ed
 int tcgnn_edge_colsum(const int32_t* d_nodePointer_t, const int32_t* d_perm, int32_t num_nodes, int64_t num_edges,
                       int32_t num_heads, const float* d_val, float* d_out, void* stream);
 
+/* ---- element-wise maximum over a node's incoming edges (GraphSAGE's max / pool aggregation; no counterpart in the reference) ----
+ *
+ * CSR row = destination node, column = source node; X, Y, dY, dX are fp32 [num_nodes, D] row-major, arg is int32 [num_nodes, D].
+ * Planless like tcgnn_edge_softmax: device pointers, the caller's stream, no allocation, no synchronisation (capturable in a HIP
+ * graph); no atomics and every order fixed: bit-identical on repetition.  X is read as fp32 - no fp16 image, no range guard: the
+ * forward is EXACT.
+ *   tcgnn_segment_max           the winner of two (value, CSR position) pairs is the greater value; among equal values (-0.0 == +0.0)
+ *                               the smaller position; a NaN beats every number, among NaNs the smaller position wins - numpy.argmax over
+ *                               the row's slice.  Y[i,d] has the BITS of X[col(arg[i,d]), d] (sign of zero, NaN payload).  Duplicate
+ *                               column ids in a row are distinct positions.  An empty row: Y = 0, arg = -1.  d_arg may be NULL.
+ *   tcgnn_segment_max_backward  the gradient with respect to X over the rows of A^T: d_nodePointer_t, d_edgeList_t and d_perm are what
+ *                               tcgnn_transpose_ws wrote.  fp64 sums, rounded once.  A source node nobody chose: 0.
+ * Rows are read with 16-byte loads when D % 4 == 0 and the base address (d_X; d_arg in backward) is 16-byte aligned, with 4-byte loads
+ * otherwise: the same results either way.  Row pointers are clamped to [0, num_edges] and a descending pair is an empty row.  For
+ * every read they index, a column id is clamped to the nearer end of [0, num_nodes) and a perm entry outside [0, num_edges) reads
+ * position 0: safe reads either way, values of no meaning for an array that holds such entries.  Nothing outside [0, num_nodes * D) of
+ * Y / arg / dX is written, and every element of them is.  num_nodes = 0, num_edges = 0 or D = 0 returns TCGNN_OK (Y / dX zeroed and
+ * arg set to -1 where they have elements and the pointer is given); a negative size, num_edges >= 2^31 or a null array otherwise:
+ * TCGNN_ERR_INVALID_ARG before anything is written. */
+/* Y[i,d] = max over e in row i of X[col(e), d];  arg[i,d] = the CSR position e that supplied it (-1 and Y = 0 for an empty row) */
+int tcgnn_segment_max(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                      const float* d_X, int32_t D, float* d_Y, int32_t* d_arg /* may be NULL */, void* stream);
+/* dX[j,d] = sum over eT in row j of A^T, in a fixed order, of dY[i,d] where i = edgeList_t[eT] and arg[i,d] == perm[eT] */
+int tcgnn_segment_max_backward(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm,
+                               int32_t num_nodes, int64_t num_edges, const int32_t* d_arg, const float* d_dY, int32_t D,
+                               float* d_dX, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

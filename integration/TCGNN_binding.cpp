@@ -448,6 +448,55 @@ torch::Tensor edge_colsum(torch::Tensor val, torch::Tensor nodePointer, torch::T
   return out;
 }
 
+// ---- not in the reference: element-wise maximum over a node's incoming edges (tcgnn_segment_max / _backward; the ctypes module's
+// forward_max and backward_max) ---------------------------------------------------------------------------------------------------
+namespace {
+// (N, E, D) of a max-aggregation call, after the checks of the ctypes module
+std::tuple<int32_t, int64_t, int32_t> max_args(const torch::Tensor& t, const char* name, const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  const int64_t N = nodePointer.numel() - 1;
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == N, name, " must be [num_nodes, embedding_dim]");
+  TORCH_CHECK(nodePointer.device() == t.device() && edgeList.device() == t.device(), name, ", nodePointer and edgeList must be on one device");
+  return {(int32_t)N, edgeList.numel(), (int32_t)t.size(1)};
+}
+torch::Tensor out_like(const c10::optional<torch::Tensor>& out, const torch::Tensor& t, const char* name) {
+  if (!out.has_value()) return torch::empty_like(t);
+  TORCH_CHECK(out->is_cuda() && out->is_contiguous() && out->scalar_type() == torch::kFloat32 && out->sizes() == t.sizes() && out->device() == t.device(),
+              "out must be a contiguous fp32 tensor of ", name, "'s shape on its device");
+  return *out;
+}
+}  // namespace
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> forward_max(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList, bool return_arg,
+                                                                    c10::optional<torch::Tensor> out) {
+  auto [N, E, D] = max_args(input, "input", nodePointer, edgeList);
+  torch::Tensor Y = out_like(out, input, "input");
+  DeviceGuard guard(input.device());
+  c10::optional<torch::Tensor> arg;
+  if (return_arg) arg = torch::empty({(int64_t)N, (int64_t)D}, input.options().dtype(torch::kInt32));
+  tcgnn_check(tcgnn_segment_max(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, input.data_ptr<float>(), D, Y.data_ptr<float>(),
+                                arg.has_value() ? arg->data_ptr<int>() : nullptr, current_stream(input)), "tcgnn_segment_max");
+  return {Y, arg};
+}
+
+torch::Tensor backward_max(torch::Tensor dY, torch::Tensor arg, torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<torch::Tensor> out) {
+  auto [N, E, D] = max_args(dY, "dY", nodePointer, edgeList);
+  CHECK_INPUT(arg);
+  TORCH_CHECK(arg.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(arg.sizes() == dY.sizes() && arg.device() == dY.device(), "arg must have the shape and device of dY");
+  torch::Tensor dX = out_like(out, dY, "dY");
+  DeviceGuard guard(dY.device());
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_segment_max_backward(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E, arg.data_ptr<int>(),
+                                         dY.data_ptr<float>(), D, dX.data_ptr<float>(), current_stream(dY)), "tcgnn_segment_max_backward");
+  return dX;
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -567,4 +616,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("el"), py::arg("er"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2, py::arg("out") = py::none());
   m.def("edge_colsum", &edge_colsum, "per-source-node sums of per-edge values, [N, heads] (not in the reference)", py::arg("val"), py::arg("nodePointer"),
         py::arg("edgeList"));
+  m.def("forward_max", &forward_max, "element-wise maximum over every node's incoming edges: (Y, arg) (not in the reference)", py::arg("input"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("return_arg") = true, py::arg("out") = py::none());
+  m.def("backward_max", &backward_max, "backward of forward_max: dX (not in the reference)", py::arg("dY"), py::arg("arg"), py::arg("nodePointer"),
+        py::arg("edgeList"), py::arg("out") = py::none());
 }

@@ -36,7 +36,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads",
-           "cache_stats", "drop_scales"]
+           "forward_max", "backward_max", "cache_stats", "drop_scales"]
 
 
 def _stream(device):
@@ -260,7 +260,8 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
     return out
 
 
-def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1):
+def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1,
+            max_aggregation=False):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
@@ -275,7 +276,11 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True, attention=True and heads=H: the
     edge-valued streams of A and A^T at that width (what a layer of ONE head runs on), the two-image SDDMM workspace, with A^T's
     plan the transposed CSR edge_colsum sums over, and - heads > 1 - the workspace of forward_heads at H heads of every width in
-    `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream."""
+    `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream.
+    max_aggregation=True (a model with forward_max / backward_max: SAGEConv's max and pool aggregators): the transposed CSR backward_max
+    walks, built now (transpose_graph: the graph's one transpose) - the two calls are planless and need nothing else."""
+    if max_aggregation:
+        transpose_graph(nodePointer, edgeList)
     e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     plans = [e.handle]
     dev = nodePointer.device
@@ -831,6 +836,53 @@ def edge_colsum(val, nodePointer, edgeList):
     N, H = nodePointer.numel() - 1, val.size(0)
     out = torch.empty(N, H, dtype=torch.float32, device=val.device)
     _call(_c.lib.tcgnn_edge_colsum, val.device, rp_t.data_ptr(), perm.data_ptr(), N, E, H, val.data_ptr(), out.data_ptr())
+    return out
+
+
+# ---- additions (not in the reference module): element-wise maximum over a node's incoming edges (GraphSAGE max / pool) -----
+
+def _max_args(t, name, nodePointer, edgeList):
+    _check_input(t, name)
+    _check_float(t, name)
+    for g, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(g, n)
+        _check_int(g, n)
+    N = nodePointer.numel() - 1
+    if N < 0:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    if t.dim() != 2 or t.size(0) != N:
+        raise RuntimeError("%s must be [num_nodes, embedding_dim] with num_nodes = %d, got %s" % (name, N, tuple(t.shape)))
+    if any(g.device != t.device for g in (nodePointer, edgeList)):
+        raise RuntimeError("%s, nodePointer and edgeList must be on one device" % name)
+    return N, edgeList.numel(), t.size(1)
+
+
+def forward_max(input, nodePointer, edgeList, return_arg=True, out=None):
+    """Not in the reference module: (Y, arg) with Y[i, d] = the maximum of input[col(e), d] over the edges e of row i and arg[i, d]
+    (int32) the CSR position that supplied it (tcgnn_segment_max).  Exact: input is read as fp32 and Y holds the winner's bits; among
+    equal values the smallest position wins, a NaN beats every number (numpy.argmax over the row's slice).  A row without edges:
+    Y = 0, arg = -1.  return_arg=False: arg is None (nothing is written for it).  Deterministic, no atomics."""
+    N, E, D = _max_args(input, "input", nodePointer, edgeList)
+    out = _out_like(out, input, "input")
+    arg = torch.empty(N, D, dtype=torch.int32, device=input.device) if return_arg else None
+    _call(_c.lib.tcgnn_segment_max, input.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, input.data_ptr(), D, out.data_ptr(), _ptr(arg))
+    return out, arg
+
+
+def backward_max(dY, arg, nodePointer, edgeList, out=None):
+    """Not in the reference module: the gradient of forward_max with respect to its input (tcgnn_segment_max_backward),
+        dX[j, d] = the sum of dY[i, d] over the edges (i <- j) at CSR position e with arg[i, d] == e,
+    a walk over the rows of A^T in a fixed order (fp64 sums, no atomics); a node nobody chose gets 0.  The transposed CSR is the
+    module's cached one (transpose_graph): built at the first call for a graph, or by prepare(..., max_aggregation=True)."""
+    N, E, D = _max_args(dY, "dY", nodePointer, edgeList)
+    _check_input(arg, "arg")
+    _check_int(arg, "arg")
+    if arg.shape != dY.shape or arg.device != dY.device:
+        raise RuntimeError("arg must have the shape and device of dY")
+    out = _out_like(out, dY, "dY")
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_segment_max_backward, dY.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, arg.data_ptr(), dY.data_ptr(), D,
+          out.data_ptr())
     return out
 
 

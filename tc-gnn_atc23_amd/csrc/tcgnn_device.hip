@@ -303,6 +303,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 
 #include "tcgnn_edge_softmax.inc"
 #include "tcgnn_gat.inc"
+#include "tcgnn_segment_max.inc"
 
 // ------------------------------------------------------------------------------------------
 // launch tables

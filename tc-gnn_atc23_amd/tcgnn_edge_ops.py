@@ -8,13 +8,14 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     gat_attention(el, er, rowptr, col, slope)  P[h] = softmax by row of leaky_relu(el[col e, h] + er[row e, h])   (multi-head GAT)
                                   bwd: g as above per head; ds = g lrelu'(raw); d_er = row sums of ds; d_el = column sums of ds
     aggregate_heads(P, Z, meta)   Y[:, head h] = A_val(P[h]) Z[:, head h], all heads in one call   bwd: dP[h] = sddmm(dY_h, Z_h),  dZ through A^T, one call
+    aggregate_max(X, rowptr, col) Y[i, d] = max over row i of X[col e, d] (0 for an empty row)     bwd: dX[j, d] = sum of dY[i, d] over the edges that won (i, d)
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
-The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=) and
-forward_heads(transpose=).  A backend without them is an error - there is no composed fallback in this module (a stand-in backend
+The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
+forward_heads(transpose=), forward_max and backward_max.  A backend without them is an error - there is no composed fallback in this module (a stand-in backend
 installed with tcgnn_layers.set_backend is given forward_heads there, if it has none).
 """
 import torch
@@ -131,6 +132,30 @@ class _AggregateHeads(torch.autograd.Function):
             rp, col, bp, e2c, e2r = ctx.meta
             d_z = b.forward_heads(d_y, rp, col, P, bp, e2c, e2r, H, transpose=True)[0]
         return (d_p, d_z) + (None,) * 5
+
+
+class _AggregateMax(torch.autograd.Function):
+    """Y = forward_max(X); the winning CSR positions (int32 [N, D]) are what is saved - X is not needed again."""
+
+    @staticmethod
+    def forward(ctx, X, row_pointers, column_index):
+        Y, arg = _L.backend().forward_max(X.contiguous(), row_pointers, column_index)
+        ctx.graph = (row_pointers, column_index)
+        ctx.save_for_backward(arg)
+        return Y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        arg, = ctx.saved_tensors
+        d_x = _L.backend().backward_max(d_y.contiguous(), arg, *ctx.graph) if ctx.needs_input_grad[0] else None
+        return d_x, None, None
+
+
+def aggregate_max(X, row_pointers, column_index):
+    """Y[i, d] = the maximum of X[col e, d] over the edges e of CSR row i (a node's incoming edges); a row without edges gives 0.
+    Exact (fp32 in, the winner's bits out); among equal values the first edge of the row wins, and only it receives the gradient:
+    dX[j, d] = the sum of dY[i, d] over the edges (i <- j) that won element (i, d) - a fixed-order walk over A^T, no atomics."""
+    return _AggregateMax.apply(X, row_pointers, column_index)
 
 
 def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):

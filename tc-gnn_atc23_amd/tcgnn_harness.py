@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "sage"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -54,6 +54,9 @@ def build_parser():
                    "not in the reference, whose layer aggregates with the raw scores")
     p.add_argument("--heads", type=int, default=1, help="GAT only: attention heads of the hidden layers, which concatenate `heads` heads of "
                    "hidden / heads features (it must divide); the output layer has one head of `classes` (not in the reference)")
+    p.add_argument("--aggregator", type=str, default="mean", choices=["mean", "max", "pool"],
+                   help="SAGE only: GraphSAGE's neighbour aggregation - 'mean', or the element-wise maximum over a node's incoming edges of the "
+                   "features ('max') or of a learned projection of them ('pool') (not in the reference)")
     return p
 
 
@@ -128,7 +131,7 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference", heads=1):
+                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean"):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -138,7 +141,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     directed (not in the reference): every layer with directed=True (backward through A^T), and A^T's plan prepared with A's.
     attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers.
     heads (GAT only, not in the reference): the hidden layers are GATConv(., hidden / heads, heads=heads) - concatenated back to `hidden` -
-    and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths."""
+    and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths.
+    aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks."""
     import tcgnn_layers as L
     heads = int(heads)
     if heads != 1 and model_name != "gat":
@@ -150,7 +154,12 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         def conv_cls(a, b):
             return L.GATConv(a, b // heads, heads=heads)
         out_cls = L.GATConv
+    elif model_name == "sage":
+        def conv_cls(a, b, **kw):
+            return L.SAGEConv(a, b, aggregator=aggregator, **kw)
     else:
+        if aggregator != "mean":
+            raise ValueError("aggregator applies to the SAGE model only")
         conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv}[model_name]
     torch.manual_seed(seed)
     if model_name != "gcn" and (norm != "none" or bias):
@@ -176,7 +185,12 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         return loss
 
     prep = getattr(L.backend(), "prepare", None)
-    if prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
+    if prep is not None and meta[0].is_cuda and model_name == "sage":
+        # a mean layer aggregates at min(in, out), the max layers take no plan-based aggregation at all
+        dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
+        prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
+             **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
+    elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
         prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
              **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if model_name == "gat" else
                 {"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
@@ -266,7 +280,8 @@ def run(args, quiet=False):
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
-                      attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1))
+                      attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
+                      aggregator=getattr(args, "aggregator", "mean"))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

@@ -10,6 +10,7 @@ gnn_conv.py:26-247, so a model written against the reference runs against this f
                         bwd: G = A_att dY; dX = G W^T; dW = X^T G;
                              da = (sddmm(dY)[None,:] @ col[:,None].float())^T
     SAG / GCNConv / GINConv / AGNNConv modules, n_heads = 1                                    (:10, :167-247)
+    GATConv, SAGEConv (not in the reference: DGL's layers of those names)
 
 The reference's backward uses A, not A^T (it assumes a symmetric graph) and does not propagate
 through ef into H; both are reproduced because the golden fixtures captured from gnn_conv.py
@@ -353,6 +354,25 @@ class TCGNNFunction_Scaled(torch.autograd.Function):
         return (d_input, tall_tn_mm(X, g), d_bias) + (None,) * 9
 
 
+class TCGNNFunction_ScaledSAG(torch.autograd.Function):
+    """Normalised neighbour aggregation on its own: Y = r * (A X), r fp32 [N] (mean aggregation with r = 1 / in_deg).
+    bwd: dX = A (r * dY) - A^T (r * dY) with directed=True - one forward_scaled with r as the column scale."""
+
+    @staticmethod
+    def forward(ctx, X, row_scale, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, directed=False):
+        ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.bwd = _bwd_kw(directed)
+        ctx.row_scale = row_scale
+        return backend().forward_scaled(X.contiguous(), *ctx.meta, row_scale=row_scale)[0]
+
+    @staticmethod
+    def backward(ctx, d_output):
+        d_input = None
+        if ctx.needs_input_grad[0]:
+            d_input = backend().forward_scaled(d_output.contiguous(), *ctx.meta, col_scale=ctx.row_scale, **ctx.bwd)[0]
+        return (d_input,) + (None,) * 7
+
+
 def degree_scales(row_pointers, column_index, norm):
     """(row_scale, col_scale) of DGL's GraphConv normalisation (TCGNN.degree_scales; cached beside the graph's plan)."""
     fn = getattr(backend(), "degree_scales", None)
@@ -616,3 +636,62 @@ class GATConv(torch.nn.Module):
         if not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
         return Y + self.bias if self.bias is not None else Y
+
+
+SAGE_AGGREGATORS = ("mean", "max", "pool")
+
+
+class SAGEConv(torch.nn.Module):
+    """Not in the reference: GraphSAGE's layer after DGL's SAGEConv,
+        out = X W_self + agg(X) W_neigh + b,
+    with aggregator
+        'mean'  agg(X) = D_in^-1 A X: forward_scaled with the 'right' row scale; W_neigh is applied BEFORE aggregating when
+                output_dim < input_dim (fewer columns through the aggregation; the same matrix).  The backward aggregates with A -
+                with A^T when directed=True, as the other layers do;
+        'max'   agg(X) = tcgnn_edge_ops.aggregate_max(X): the element-wise maximum over a node's incoming edges (0 where there are none);
+        'pool'  agg(X) = aggregate_max(relu(X W_pool + b_pool)), W_pool [input_dim, input_dim].
+    The max paths are exact and back-propagate through A^T on every graph, whatever `directed` says.  `weights` is W_neigh,
+    `weights_self` W_self; Glorot initialisation with the ReLU gain as in DGL, biases zero.  No feature dropout, no normalisation."""
+
+    def __init__(self, input_dim, output_dim, aggregator="mean", bias=True, directed=False):
+        super().__init__()
+        if aggregator not in SAGE_AGGREGATORS:
+            raise ValueError("aggregator must be one of %s, got %r ('lstm' and 'gcn' are not built)" % (", ".join(SAGE_AGGREGATORS), aggregator))
+        self.aggregator = aggregator
+        self.directed = bool(directed)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        self.weights_self = torch.nn.Parameter(torch.empty(input_dim, output_dim))
+        if aggregator == "pool":
+            self.weights_pool = torch.nn.Parameter(torch.empty(input_dim, input_dim))
+            self.bias_pool = torch.nn.Parameter(torch.zeros(input_dim))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(output_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        torch.nn.init.xavier_uniform_(self.weights, gain=gain)
+        torch.nn.init.xavier_uniform_(self.weights_self, gain=gain)
+        if self.aggregator == "pool":
+            torch.nn.init.xavier_uniform_(self.weights_pool, gain=gain)
+            self.bias_pool.data.zero_()
+        if self.bias is not None:
+            self.bias.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        out = dense_update(X, self.weights_self)
+        if self.aggregator == "mean":
+            r, _ = degree_scales(row_pointers, column_index, "right")
+            if self.weights.shape[1] < self.weights.shape[0]:
+                out = out + TCGNNFunction_ScaledSAG.apply(dense_update(X, self.weights), r, *meta, self.directed)
+            else:
+                out = out + dense_update(TCGNNFunction_ScaledSAG.apply(X, r, *meta, self.directed), self.weights)
+        else:
+            if self.aggregator == "pool":
+                X = torch.relu(dense_update(X, self.weights_pool) + self.bias_pool)
+            out = out + dense_update(E.aggregate_max(X, row_pointers, column_index), self.weights)
+        return out + self.bias if self.bias is not None else out
