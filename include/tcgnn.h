@@ -262,6 +262,16 @@ int tcgnn_set_range_guard(int32_t level);
 int tcgnn_plan_set_range_guard(tcgnn_plan* plan, int32_t level);
 int tcgnn_range_mode(const void* d_workspace, void* stream, int32_t* wide_x, int32_t* wide_val);
 
+/* One-pass staging.  A call that stages X as the planar image of the LDS-resident kernels (D a multiple of 16, X and the gate 16-byte
+ * aligned) reads X once: the plan remembers the power-of-two scale of the last matrix staged per kind of call, the pass converts
+ * with it while it takes the abs-max, and a second, short launch checks the guess - converting again only when max |X| has crossed a
+ * power of two (a "miss").  Results do not depend on it: image, header and Y are bit for bit those of the two-pass staging.
+ * tcgnn_set_stage_onepass(0) keeps every call on the two-pass staging (process-wide, read per call; the environment variable
+ * TCGNN_STAGE_ONEPASS sets the initial value, default 1).  tcgnn_plan_stage_stats reports how many of the plan's calls so far hit and
+ * missed; it reads two device words back and synchronises `stream` (a test / diagnosis aid, like tcgnn_range_mode). */
+int tcgnn_set_stage_onepass(int32_t on);
+int tcgnn_plan_stage_stats(const tcgnn_plan* plan, void* stream, int64_t* hits, int64_t* misses);
+
 /* Measurement aid: reserve HIP event pairs for up to `max_calls` kernel calls (0 = off).  While
  * enabled, tcgnn_spmm / tcgnn_spmm_val / tcgnn_sddmm bracket their main kernel (not the fp16
  * staging pass) with events recorded on the caller's stream, without synchronising.

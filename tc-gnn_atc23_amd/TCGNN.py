@@ -336,6 +336,21 @@ def set_range_guard(level):
     _c.check(_c.lib.tcgnn_set_range_guard(int(level)), "tcgnn_set_range_guard")
 
 
+def set_stage_onepass(on):
+    """Not part of the reference API: 0 keeps every call on the two-pass staging (memset + abs-max + convert), 1 (default) stages the
+    planar image in one pass over X where that applies (include/tcgnn.h: tcgnn_set_stage_onepass).  Results do not depend on it."""
+    _c.check(_c.lib.tcgnn_set_stage_onepass(int(on)), "tcgnn_set_stage_onepass")
+
+
+def stage_stats(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow):
+    """Not part of the reference API: (hits, misses) of the one-pass staging over this graph's calls so far - calls whose remembered
+    scale held, and calls that converted again.  Synchronises the current stream: a test / diagnosis aid."""
+    plan = _plan_of((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
+    h, m = _c._i64(0), _c._i64(0)
+    _c.check(_c.lib.tcgnn_plan_stage_stats(plan, _stream(nodePointer.device), _c.ctypes.byref(h), _c.ctypes.byref(m)), "tcgnn_plan_stage_stats")
+    return (h.value, m.value)
+
+
 def kernel_timing(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, max_calls=None):
     """Not part of the reference API.  kernel_timing(meta..., max_calls=K) arms HIP-event timing of
     the main kernel for the next K calls on this graph; kernel_timing(meta...) (no max_calls) waits

@@ -32,7 +32,8 @@
 //                             and walk predicates, sync_chosen; behind the includes the C ABI of the operators
 //   tcgnn_stage.inc           the staging pass, device and host: the header's words by name, the range guard's rule, abs-max kernels and every
 //                             fp16 converter (row-major, planar, slice), image and workspace sizes, Guard, fill_header, one converter launcher
-//                             per layout, stage_features; the C ABI of the caller-staged images and tcgnn_range_mode
+//                             per layout, the one-pass staging of the planar image (stage_fused_kernel + stage_settle_kernel), stage_features;
+//                             the C ABI of the caller-staged images, tcgnn_range_mode and tcgnn_plan_stage_stats
 //   tcgnn_pack.inc            plan-time kernels (fill, longest row, locality, pack)
 //   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
 //   tcgnn_heads.inc           multi-head edge-valued SpMM: HeadsWalker (TileWalker with one A fragment per head), spmm_heads_kernel, spmm_heads_csr_kernel
@@ -129,6 +130,9 @@ struct tcgnn_plan {
     uint32_t* d_bptr = nullptr;   // [nw_eff][nbuckets + 1] tile offset of the first tile whose first column is in bucket >= k
     int32_t num_cus = 256;
     size_t bytes = 0;
+    // one-pass staging (tcgnn_stage.inc): kStageHintEntries guess words - the scale exponent of the last matrix staged per kind of call,
+    // 0 = none - then the hit and the miss counter.  Device words, zeroed at creation; a guess and two statistics, never state a result depends on
+    uint32_t* d_stage = nullptr;
     // tables of the slice-synchronised range walk (tcgnn_sync_walk.inc; r06): graphs whose communities exceed an XCD's L2
     struct SyncTables {
         int32_t S = 0, R = 0, nwx = 0, kmax = 0, fb_shift = 0;

@@ -278,6 +278,17 @@ static int plan_first_cell_streams(tcgnn_plan* p, hipStream_t stream) {
     return TCGNN_OK;
 }
 
+// the one-pass staging's guess words and counters (tcgnn_stage.inc): "no guess" everywhere, no call counted
+static int plan_stage_words(tcgnn_plan* p, hipStream_t stream) {
+    hipError_t e = hipMalloc(&p->d_stage, kStageWords * sizeof(uint32_t));
+    if (e != hipSuccess) { p->d_stage = nullptr; return fail(hip_rc(e), "plan build (staging words): %s", hipGetErrorString(e)); }
+    e = hipMemsetAsync(p->d_stage, 0, kStageWords * sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "plan build (staging words): %s", hipGetErrorString(e));
+    p->bytes += kStageWords * sizeof(uint32_t);
+    return TCGNN_OK;
+}
+
 extern "C" {
 
 int tcgnn_plan_destroy(tcgnn_plan* plan) {
@@ -287,6 +298,7 @@ int tcgnn_plan_destroy(tcgnn_plan* plan) {
     (void)hipFree(plan->sync.d_T); (void)hipFree(plan->sync.d_nk);
     for (auto& cs : plan->lds) release_cell_stream(cs);
     (void)hipFree(plan->d_xwb_ptr); (void)hipFree(plan->d_xcols); (void)hipFree(plan->d_xmask); (void)hipFree(plan->d_xeidx); (void)hipFree(plan->d_sym);
+    (void)hipFree(plan->d_stage);
     for (hipEvent_t e : plan->ev) (void)hipEventDestroy(e);
     delete plan;
     return TCGNN_OK;
@@ -322,6 +334,7 @@ int tcgnn_plan_create_sharded(const int32_t* d_nodePointer, const int32_t* d_edg
         fprintf(stderr, "[tcgnn] plan_create: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
     };
+    if (const int rc = plan_stage_words(p, stream)) return bail(rc);
     std::vector<int64_t> wb_ptr;
     if (const int rc = plan_read_weights(p, stream, &p->h_bp)) return bail(rc);   // (h_bp stays: the placement of the LDS-resident walks weighs windows by it)
     mark("blockPartition to the host");
@@ -403,6 +416,12 @@ int tcgnn_plan_set_range_guard(tcgnn_plan* plan, int32_t level) {
 int tcgnn_set_range_guard(int32_t level) {
     if (level < 0 || level > 3) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_set_range_guard: 0 (off), 1 (SpMM operators), 2 (+ SDDMM / fused AGNN with a few lost elements, default) or 3 (strict)");
     g_range_guard = level;
+    return TCGNN_OK;
+}
+
+int tcgnn_set_stage_onepass(int32_t on) {
+    if (on < 0 || on > 1) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_set_stage_onepass: 0 (memset + abs-max + convert for every call) or 1 (one pass where it applies, default)");
+    g_stage_onepass = on;
     return TCGNN_OK;
 }
 

@@ -1,8 +1,9 @@
 // tcgnn_stage.inc - the staging pass every hot-path operator starts with, device and host: an abs-max pass writes the range words of
 // the workspace's header, a conversion pass writes the scaled fp16 image behind it.  Included by tcgnn_device.hip, ahead of every kernel.
 // In this order: the header's words; the scale and the rounding; the range guard's rule; the abs-max kernels and the converters
-// (row-major, planar, slice); image and workspace sizes; Guard; check_workspace; fill_header; one converter launcher per layout;
-// stage_features; the C ABI of the caller-staged images and tcgnn_range_mode.
+// (row-major, planar, the planar image in one pass over X, slice); image and workspace sizes; Guard; check_workspace; fill_header; one
+// converter launcher per layout; launch_stage_onepass; stage_features; the C ABI of the caller-staged images, tcgnn_range_mode and
+// tcgnn_plan_stage_stats.
 
 // ---- the header: kHdrBytes at the start of a workspace (and of a caller-staged image, which carries word kHdrMaxX alone), 32-bit words.
 // Every file names a word through this enum.  The X and the edge-value word of a pair are neighbours: range_spread and absmax_body
@@ -426,6 +427,183 @@ __global__ __launch_bounds__(256) void convert_planar_rows_scaled_kernel(const f
     convert_planar_rows_body<true>(X, N, D, X16, hdr, G, tiny, cs);
 }
 
+// ---- the planar image of whole aligned float4 rows in ONE pass over X (stage_features: where launch_convert_planar would take the
+// rows kernel).  The second read of X above exists only because the power-of-two scale is not known during the first, and from call to
+// call it rarely changes: it moves when max |X| crosses a power of two.  So the plan remembers, per kind of call, the scale exponent
+// of the last matrix staged (tcgnn_plan::d_stage, a guess and nothing more), and
+//   stage_fused_kernel   (pass 1) reads X once, abs-max as absmax_body and - with a usable guess - conversion as
+//                        convert_planar_rows_body with s = 2^guess; every workgroup leaves {max bits, lo word, tiny count, the guess
+//                        word it converted with} in its own 16-byte slot behind the dirty-row bitmap; workgroup 0 clears the header;
+//   stage_settle_kernel  (pass 2, the same grid) reduces the slots (4 KB at most), writes the header words, and returns when every
+//                        workgroup converted with the true exponent (a HIT); on a MISS it stores the true exponent as the next guess
+//                        and converts X with it, as the two-pass path would have.
+// Plain stores in pass 1, the stream's order between the passes: no workgroup waits for another.  A hit is an EQUAL exponent - a
+// neighbouring scale would change which elements are tiny - so image, header and everything behind them are bit for bit what
+// memset + absmax + convert_planar_rows produce.  The guess word is read by every workgroup of pass 1 on its own: a second stream
+// storing into it meanwhile makes the slots disagree, which is a miss.
+constexpr int kStageSlots = 256;          // absmax_grid's ceiling, and this path's: one slot per workgroup of pass 1
+constexpr int kStageHintEntries = 16;     // direct-mapped by stage_hint_index
+enum StageWord : int { kStageHits = kStageHintEntries, kStageMisses = kStageHintEntries + 1, kStageWords = kStageHintEntries + 2 };   // tcgnn_plan::d_stage
+// a guess word: 0 = none, else the exponent + 127 (scale_exp_from_bits returns -126 .. 126: words 1 .. 253)
+__device__ __forceinline__ bool stage_hint_usable(uint32_t w) { return w - 1u < 253u; }
+__device__ __forceinline__ uint32_t stage_hint_word(int k) { return (uint32_t)(k + 127); }
+static inline int stage_hint_index(int32_t D, bool gated, bool scaled, uint32_t pow) {
+    const uint32_t key = (uint32_t)(D >> 4) | (gated ? 0x100u : 0u) | (scaled ? 0x200u : 0u) | ((pow & 0xffu) << 10);
+    return (int)((key * 0x9e3779b1u) >> 28);
+}
+// float4 f of X -> (row, float4 of the row), stepped by the grid's stride without a division per step
+struct RowWalk {
+    int32_t row, c4, q, drow, dc;
+    __device__ __forceinline__ RowWalk(uint32_t f, uint32_t stride, int32_t q_) : q(q_) {
+        row = (int32_t)(f / (uint32_t)q_); c4 = (int32_t)(f - (uint32_t)row * (uint32_t)q_);
+        drow = (int32_t)(stride / (uint32_t)q_); dc = (int32_t)(stride - (uint32_t)drow * (uint32_t)q_);
+    }
+    __device__ __forceinline__ void step() { row += drow; c4 += dc; if (c4 >= q) { c4 -= q; ++row; } }
+};
+__device__ __forceinline__ _Float16* planar_rows_record(_Float16* X16, int32_t N, int64_t row, int c4) {   // (convert_planar_rows_body's store address)
+    return X16 + (((int64_t)(c4 >> 2) * ((int64_t)N + 1) + row) * 16 + (c4 & 3) * 4);
+}
+// workgroup-wide maxima of four words and sum of a fifth, in every thread
+__device__ __forceinline__ void stage_reduce(uint32_t (&mx)[4], uint32_t& sum) {
+    __shared__ uint32_t part[kAbsmaxThreads / 64][5];
+    __syncthreads();   // (a second reduction of one kernel: nobody still reads the first one's words)
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mx[j] = max(mx[j], (uint32_t)__shfl_xor((int)mx[j], off));
+        sum += (uint32_t)__shfl_xor((int)sum, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) part[threadIdx.x >> 6][j] = mx[j];
+        part[threadIdx.x >> 6][4] = sum;
+    }
+    __syncthreads();
+    const int nwv = (int)(blockDim.x >> 6);
+    sum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mx[j] = 0;
+    for (int w = 0; w < nwv; ++w) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) mx[j] = max(mx[j], part[w][j]);
+        sum += part[w][4];
+    }
+}
+// The grid-stride walk both passes share, four 16-byte loads in flight per thread as in absmax_body.  ABS: the abs-max side - m and
+// lo exactly as absmax_body's see() (tlo = the smallest b - 1 seen: zero wraps to the top, Inf and NaN lie at 0x7f7fffff or above, so a
+// value below that is the smallest nonzero finite magnitude, less one).  CONV: the conversion side - convert_planar_rows_body element
+// by element with scale s, the sentinel row included; nt counts the tiny elements.
+template <bool GATED, bool CS, bool ABS, bool CONV>
+__device__ __forceinline__ void stage_walk(const float* __restrict__ X, const float* __restrict__ G, const float* __restrict__ cs, int32_t N, int32_t D,
+                                           _Float16* __restrict__ X16, float s, uint32_t& m, uint32_t& tlo, uint32_t& nt) {
+    const int q = D >> 2;                                // float4 per row
+    const int64_t n4 = (int64_t)N * q;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t gsz = (int64_t)gridDim.x * blockDim.x;   // (at most 2^18: kStageSlots workgroups of kAbsmaxThreads)
+    const float4* p4 = reinterpret_cast<const float4*>(X);
+    const float4* g4 = reinterpret_cast<const float4*>(G);
+    const float4 one = {1.f, 1.f, 1.f, 1.f};
+    auto see = [&](float f, float gt) {
+        const uint32_t b = (!GATED || gt > 0.0f) ? __float_as_uint(f) & 0x7fffffffu : 0u;
+        m = max(m, b);
+        tlo = min(tlo, b - 1u);
+    };
+    auto take = [&](float4 v, const float4& gt, float c, int32_t row, int32_t c4) {
+        if constexpr (ABS) {
+            if constexpr (CS) { see(c * v.x, gt.x); see(c * v.y, gt.y); see(c * v.z, gt.z); see(c * v.w, gt.w); }
+            else { see(v.x, gt.x); see(v.y, gt.y); see(v.z, gt.z); see(v.w, gt.w); }
+        }
+        if constexpr (CONV) {
+            if constexpr (GATED) {
+                if (!(gt.x > 0.0f)) v.x = 0.0f;
+                if (!(gt.y > 0.0f)) v.y = 0.0f;
+                if (!(gt.z > 0.0f)) v.z = 0.0f;
+                if (!(gt.w > 0.0f)) v.w = 0.0f;
+            }
+            if constexpr (CS) { v.x = c * v.x; v.y = c * v.y; v.z = c * v.z; v.w = c * v.w; }
+            half4 o;
+            o[0] = to_half_rna(v.x * s); o[1] = to_half_rna(v.y * s); o[2] = to_half_rna(v.z * s); o[3] = to_half_rna(v.w * s);
+            nt += is_tiny(v.x, s) + is_tiny(v.y, s) + is_tiny(v.z, s) + is_tiny(v.w, s);
+            *reinterpret_cast<half4*>(planar_rows_record(X16, N, row, c4)) = o;
+        }
+    };
+    RowWalk w((uint32_t)gid, (uint32_t)gsz, q);
+    int64_t k = gid;
+    for (; k + 3 * gsz < n4; k += 4 * gsz) {
+        const int32_t r0 = w.row, c0 = w.c4; w.step();
+        const int32_t r1 = w.row, c1 = w.c4; w.step();
+        const int32_t r2 = w.row, c2 = w.c4; w.step();
+        const int32_t r3 = w.row, c3 = w.c4; w.step();
+        const float4 v0 = p4[k], v1 = p4[k + gsz], v2 = p4[k + 2 * gsz], v3 = p4[k + 3 * gsz];
+        float4 t0 = one, t1 = one, t2 = one, t3 = one;
+        if constexpr (GATED) { t0 = g4[k]; t1 = g4[k + gsz]; t2 = g4[k + 2 * gsz]; t3 = g4[k + 3 * gsz]; }
+        float s0 = 1.f, s1 = 1.f, s2 = 1.f, s3 = 1.f;
+        if constexpr (CS) { s0 = cs[r0]; s1 = cs[r1]; s2 = cs[r2]; s3 = cs[r3]; }
+        take(v0, t0, s0, r0, c0); take(v1, t1, s1, r1, c1); take(v2, t2, s2, r2, c2); take(v3, t3, s3, r3, c3);
+    }
+    if (k < n4) {   // the last, partial round: its loads in flight together as well
+        const bool b1 = k + gsz < n4, b2 = k + 2 * gsz < n4;
+        const int32_t r0 = w.row, c0 = w.c4; w.step();
+        const int32_t r1 = w.row, c1 = w.c4; w.step();
+        const int32_t r2 = w.row, c2 = w.c4;
+        const float4 v0 = p4[k], v1 = b1 ? p4[k + gsz] : one, v2 = b2 ? p4[k + 2 * gsz] : one;
+        float4 t0 = one, t1 = one, t2 = one;
+        if constexpr (GATED) { t0 = g4[k]; if (b1) t1 = g4[k + gsz]; if (b2) t2 = g4[k + 2 * gsz]; }
+        float s0 = 1.f, s1 = 1.f, s2 = 1.f;
+        if constexpr (CS) { s0 = cs[r0]; if (b1) s1 = cs[r1]; if (b2) s2 = cs[r2]; }
+        take(v0, t0, s0, r0, c0);
+        if (b1) take(v1, t1, s1, r1, c1);
+        if (b2) take(v2, t2, s2, r2, c2);
+    }
+    if constexpr (CONV) {   // the all-zero sentinel row N of every plane
+        const half4 zero = {(_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
+        for (int64_t t = gid; t < q; t += gsz) *reinterpret_cast<half4*>(planar_rows_record(X16, N, N, (int)t)) = zero;
+    }
+}
+template <bool GATED, bool CS>
+__global__ __launch_bounds__(kAbsmaxThreads) void stage_fused_kernel(const float* __restrict__ X, const float* __restrict__ G, const float* __restrict__ cs, int32_t N, int32_t D,
+                                                                     _Float16* __restrict__ X16, uint32_t* __restrict__ hdr, uint4* __restrict__ slots,
+                                                                     const uint32_t* __restrict__ hint) {
+    const uint32_t hw = *hint;
+    const bool conv = stage_hint_usable(hw);
+    uint32_t m = 0, tlo = 0xffffffffu, nt = 0;
+    if (conv) stage_walk<GATED, CS, true, true>(X, G, cs, N, D, X16, pow2f((int)hw - 127), m, tlo, nt);
+    else      stage_walk<GATED, CS, true, false>(X, G, cs, N, D, X16, 1.0f, m, tlo, nt);
+    uint32_t mx[4] = {m, ~tlo, 0u, 0u};
+    stage_reduce(mx, nt);
+    if (threadIdx.x == 0) {
+        const uint32_t t = ~mx[1];
+        slots[blockIdx.x] = make_uint4(mx[0], t < 0x7f7fffffu ? 0x7f800000u - (t + 1u) : 0u, nt, conv ? hw : 0u);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned)kHdrWords) hdr[threadIdx.x] = 0u;   // (the only stores of this kernel into the header)
+}
+template <bool GATED, bool CS>
+__global__ __launch_bounds__(kAbsmaxThreads) void stage_settle_kernel(const float* __restrict__ X, const float* __restrict__ G, const float* __restrict__ cs, int32_t N, int32_t D,
+                                                                      _Float16* __restrict__ X16, uint32_t* __restrict__ hdr, const uint4* __restrict__ slots, int32_t nslots,
+                                                                      uint32_t* __restrict__ stage, int32_t hint_index, uint32_t guard_cap, uint32_t guard_pow) {
+    uint32_t mx[4] = {0u, 0u, 0u, 0u}, tiny = 0;   // max bits, lo word, the largest guess word and the complement of the smallest
+    if ((int)threadIdx.x < nslots) {
+        const uint4 p = slots[threadIdx.x];
+        mx[0] = p.x; mx[1] = p.y; mx[2] = p.w; mx[3] = ~p.w; tiny = p.z;
+    }
+    stage_reduce(mx, tiny);
+    const int k = scale_exp_from_bits(mx[0]);
+    const bool hit = mx[2] == stage_hint_word(k) && ~mx[3] == mx[2];   // every workgroup of pass 1 converted, and with the true exponent
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hdr[kHdrMaxX] = mx[0]; hdr[kHdrLoX] = mx[1]; hdr[kHdrCapX] = guard_cap;
+        hdr[kHdrPow] = guard_pow & 0xffu; hdr[kHdrStrict] = guard_pow >> 8;
+        if (hit) hdr[kHdrTiny] = tiny;
+        else stage[hint_index] = stage_hint_word(k);
+        atomicAdd(stage + (hit ? kStageHits : kStageMisses), 1u);
+    }
+    if (hit) return;
+    uint32_t m = 0, tlo = 0, nt = 0;
+    stage_walk<GATED, CS, false, true>(X, G, cs, N, D, X16, pow2f(k), m, tlo, nt);
+    uint32_t none[4] = {0u, 0u, 0u, 0u};
+    stage_reduce(none, nt);
+    if (threadIdx.x == 0 && nt) atomicAdd(hdr + kHdrTiny, nt);   // (cleared by pass 1; workgroup 0 leaves it alone on a miss)
+}
+
 // A SLICE of rows into the planes of a caller's image (tcgnn_stage_rows_planar: a rank of a row-sharded run converts only ITS rows;
 // plane p of the image starts plane_rows records behind plane p - 1).  One thread per 16-byte chunk, rounding as convert_kernel; no
 // sentinel row, no range words: the caller's image holds zeros wherever nobody writes.
@@ -502,8 +680,12 @@ static bool pitch_fits_descriptor(int D) { return x16_pitch(round_up(D, 16)) * 2
 // (behind the image: the dirty-row bitmap of the range guard, one bit per row of X - wide_patch_kernel)
 static size_t image_body_bytes(int32_t N, int32_t D) { return ((((size_t)N + 1) * (size_t)x16_pitch(round_up(D, 16)) * sizeof(_Float16)) + 255) / 256 * 256; }
 static size_t dirty_bitmap_bytes(int32_t N) { return ((((size_t)N + 1 + 31) / 32) * 4 + 255) / 256 * 256; }
-static size_t workspace_bytes_for(int32_t N, int32_t D) { return kHdrBytes + image_body_bytes(N, D) + dirty_bitmap_bytes(N); }
+// (behind the bitmap: the one-pass staging's slot array, 16 bytes per workgroup of stage_fused_kernel - rewritten by every call that
+//  takes that path before it is read, so the workspace carries nothing from call to call)
+static constexpr size_t kStageSlotBytes = (size_t)kStageSlots * sizeof(uint4);
+static size_t workspace_bytes_for(int32_t N, int32_t D) { return kHdrBytes + image_body_bytes(N, D) + dirty_bitmap_bytes(N) + kStageSlotBytes; }
 static uint32_t* dirty_bitmap_of(void* ws, int32_t N, int32_t D) { return reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + kHdrBytes + image_body_bytes(N, D)); }
+static uint4* stage_slots_of(void* ws, int32_t N, int32_t D) { return reinterpret_cast<uint4*>(static_cast<char*>(ws) + kHdrBytes + image_body_bytes(N, D) + dirty_bitmap_bytes(N)); }
 
 // ---- range guard parameters (range_is_wide): cap = how many lost-precision terms one result can collect at most - the longest row
 // of the graph (SpMM) or 2 D (SDDMM / fused AGNN) - and the power of max|X| in the error bound.  cap 0 = guard off
@@ -589,6 +771,35 @@ static void launch_convert_planar(const float* d_X, const float* d_cs, const flo
     else hipLaunchKernelGGL((convert_planar_kernel<false>), cgrid, block, 0, stream, d_X, N, D, nplanes, x16, hdr, d_gate, tiny);
 }
 
+// ---- the planar image in one pass over X (stage_fused_kernel + stage_settle_kernel).  tcgnn_set_stage_onepass(0) /
+// TCGNN_STAGE_ONEPASS=0: every call stages with memset + abs-max + convert.
+static int g_stage_onepass = [] { const char* e = getenv("TCGNN_STAGE_ONEPASS"); return e ? atoi(e) : 1; }();
+// header cleared, range words of X written, image converted: what fill_header (without the edge values) + launch_convert_planar's rows
+// kernel leave.  The caller checked onepass_takes.
+static void launch_stage_onepass(const tcgnn_plan* plan, const float* d_X, const float* d_cs, const float* d_gate, int32_t D, const Guard& gx, void* ws, hipStream_t stream) {
+    const int32_t N = plan->Nc;
+    uint32_t* const hdr = static_cast<uint32_t*>(ws);
+    _Float16* const x16 = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + kHdrBytes);
+    uint4* const slots = stage_slots_of(ws, N, D);
+    // (a finer grid than absmax_grid's: a workgroup from one full round of float4 per thread, not four - at 16 columns the Reddit shape
+    //  gave absmax_grid 57 workgroups, too few for a pass that also converts: 7 us slower than the two-pass staging, measured)
+    const int nslots = (int)std::min<int64_t>(kStageSlots, (int64_t)N * (D / 4) / ((int64_t)kAbsmaxThreads * 4) + 1);
+    const int idx = stage_hint_index(D, d_gate != nullptr, d_cs != nullptr, gx.pow);
+    const dim3 grid(nslots), block(kAbsmaxThreads);
+    uint32_t* const stage = plan->d_stage;
+#define TCGNN_STAGE_ONEPASS_LAUNCH(GATED, CS)                                                                                                           \
+    do {                                                                                                                                                \
+        hipLaunchKernelGGL((stage_fused_kernel<GATED, CS>), grid, block, 0, stream, d_X, d_gate, d_cs, N, D, x16, hdr, slots, (const uint32_t*)(stage + idx)); \
+        hipLaunchKernelGGL((stage_settle_kernel<GATED, CS>), grid, block, 0, stream, d_X, d_gate, d_cs, N, D, x16, hdr, (const uint4*)slots, (int32_t)nslots, \
+                           stage, (int32_t)idx, gx.cap, gx.pow);                                                                                        \
+    } while (0)
+    if (d_gate && d_cs) TCGNN_STAGE_ONEPASS_LAUNCH(true, true);
+    else if (d_gate)    TCGNN_STAGE_ONEPASS_LAUNCH(true, false);
+    else if (d_cs)      TCGNN_STAGE_ONEPASS_LAUNCH(false, true);
+    else                TCGNN_STAGE_ONEPASS_LAUNCH(false, false);
+#undef TCGNN_STAGE_ONEPASS_LAUNCH
+}
+
 struct StagedImage { const uint32_t* hdr = nullptr; const _Float16* x16 = nullptr; int dpad = 0, pitch = 0; };
 struct StageOpts {
     bool planar = false;                 // [dpad / 16 planes][Nc + 1][16 halves] for the LDS-resident kernels instead of row-major
@@ -603,12 +814,24 @@ struct StageOpts {
     const Guard* guard = nullptr;        // (null: the binary SpMM's bound; else the caller's operator has its own)
     const float* d_cs = nullptr;         // (tcgnn_spmm_scaled): the operand is d_cs[row] * X'[row, :] - absmax, tiny count and image all of that product
 };
+// the one-pass path takes a call where launch_convert_planar takes the rows kernel and the header is this call's own to fill
+static bool onepass_takes(const tcgnn_plan* plan, const float* d_X, int32_t D, const StageOpts& o) {
+    return g_stage_onepass && plan->d_stage && o.planar && !o.hdr_from && !o.block_of_wider && (int64_t)plan->Nc * D > 0 && rows_are_float4(d_X, D, 0) && D % 16 == 0 &&
+           (!o.d_gate || (reinterpret_cast<uintptr_t>(o.d_gate) & 15) == 0);
+}
 // enqueue absmax(X) [+ absmax(val)] + convert; *out: the fp16 image
 static int stage_features(const tcgnn_plan* plan, const float* d_X, const float* d_val, int32_t D, void* ws, size_t ws_bytes, hipStream_t stream, const StageOpts& o, StagedImage* out) {
     const Guard gx = o.guard ? *o.guard : guard_spmm(plan);
     if (const int rc = check_workspace("staging", ws, ws_bytes, workspace_bytes_for(plan->Nc, D))) return rc;
     uint32_t* hdr = static_cast<uint32_t*>(ws);
     _Float16* x16 = reinterpret_cast<_Float16*>(static_cast<char*>(ws) + kHdrBytes);
+    if (onepass_takes(plan, d_X, D, o)) {
+        launch_stage_onepass(plan, d_X, o.d_cs, o.d_gate, D, gx, ws, stream);
+        launch_absmax_val(plan, d_val, plan->E, hdr, stream);   // (its words were cleared by pass 1)
+        HIP_TRY(hipGetLastError());
+        out->hdr = hdr; out->x16 = x16; out->dpad = round_up(D, 16); out->pitch = x16_pitch(out->dpad);
+        return TCGNN_OK;
+    }
     if (o.hdr_from) HIP_TRY(hipMemcpyAsync(hdr, o.hdr_from, kHdrRangeBytes, hipMemcpyDeviceToDevice, stream));
     else if (!o.block_of_wider) { if (const int rc = fill_header(plan, hdr, d_X, o.d_gate, o.d_cs, D, gx, d_val, plan->E, stream)) return rc; }
     uint32_t* const tiny = o.hdr_from ? nullptr : hdr + kHdrTiny;   // (a second image of the same matrix: its elements are counted already)
@@ -668,6 +891,19 @@ int tcgnn_range_mode(const void* d_workspace, void* stream_v, int32_t* wide_x, i
     *wide_x = range_is_wide(h, 0) ? 1 : 0;
     if (*wide_x && h[kHdrPow] == 2u) *wide_x = h[kHdrStrict] ? 1 : 2;   // (SDDMM / fused AGNN: a few dirty rows - MFMA kernel + wide_patch_kernel; many - fp32 only at the strict level)
     if (wide_val) *wide_val = range_is_wide_val(h) ? 1 : 0;
+    return TCGNN_OK;
+}
+
+// how the one-pass staging of this plan's calls went so far: calls whose guess of the scale held / calls that converted again
+int tcgnn_plan_stage_stats(const tcgnn_plan* plan, void* stream_v, int64_t* hits, int64_t* misses) {
+    if (!plan || !hits || !misses) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_plan_stage_stats: null argument");
+    uint32_t h[2] = {0u, 0u};
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    if (plan->d_stage) {
+        HIP_TRY(hipMemcpyAsync(h, plan->d_stage + kStageHits, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    *hits = h[0]; *misses = h[1];
     return TCGNN_OK;
 }
 

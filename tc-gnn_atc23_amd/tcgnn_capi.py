@@ -58,6 +58,8 @@ SIGNATURES = {
     "tcgnn_set_spmm_mode": (ctypes.c_int, [_i32]),
     "tcgnn_set_range_guard": (ctypes.c_int, [_i32]),
     "tcgnn_range_mode": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32)]),
+    "tcgnn_set_stage_onepass": (ctypes.c_int, [_i32]),
+    "tcgnn_plan_stage_stats": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "tcgnn_plan_set_timing": (ctypes.c_int, [_vp, _i32]),
     "tcgnn_plan_last_kernel": (ctypes.c_char_p, [_vp]),
     "tcgnn_plan_read_timing": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_float), _i32, ctypes.POINTER(_i32)]),
