@@ -414,6 +414,33 @@ size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D);
 int tcgnn_sddmm2(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t D,
                  void* d_workspace, size_t workspace_bytes, void* stream);
 
+/* The two-operand SDDMM for H heads at once (multi-head dot-product attention scores; the gradient of tcgnn_spmm_heads with respect
+ * to its edge values):
+ *   ef[h, e] = <X[row(e), hF:(h+1)F], Z[col(e), hF:(h+1)F]>   for h < H and every CSR edge e.
+ * X (the window operand) and Z (the gathered operand) are fp32 [N, H F] row-major; d_ef is fp32 [H, E] head-major - what
+ * tcgnn_gat_softmax writes and tcgnn_spmm_heads reads.  The contract is tcgnn_sddmm2's and tcgnn_spmm_heads': every element of
+ * ef[0:H, 0:E] is written and nothing else (scores of row windows the plan was not handed: 0); the caller owns the workspace -
+ * tcgnn_sddmm_heads_workspace_bytes(plan, H, F) bytes, 256-byte aligned - and the call neither allocates nor synchronises
+ * (capturable in a HIP graph); a repeated call returns the same bits, and so does every walk; X, Z and ef may sit at any 4-byte
+ * boundary.  X and Z are each rounded with ONE power-of-two scale over all H F columns, and the range guard (tcgnn_sddmm2's rule on
+ * the two headers, with H F terms a score - the conservative count) decides once for the whole call: behind every level >= 2 call,
+ * fused or head by head, ONE launch of the fp32 CSR kernel covers all heads and returns at once unless an operand is wide.
+ * The library picks its way from the plan and (H, F) alone - tcgnn_plan_last_kernel tells which:
+ *   H == 1                                 exactly tcgnn_sddmm2 (bit-identical, every walk it has);
+ *   H >= 2, F in {8, 16, 32, 64}, H F <= 128, canonical CSR with row windows, E >= 4, an image below 4 GB
+ *                                          "sddmm_heads_kernel" (with tcgnn_sddmm2's suffix for the walk): each operand staged once,
+ *                                          and on tcgnn_sddmm2's walk for H F columns one gather of the neighbour rows feeds the dot
+ *                                          products of every head of a pass (at most 4 heads and 128 columns a pass);
+ *   a non-canonical CSR or E < 4           one plain-fp32 CSR launch for all heads;
+ *   otherwise                              head by head inside the library, each head a column block of X and Z on tcgnn_sddmm2's
+ *                                          walks for F columns (one abs-max pass per operand for the whole call; F > 128:
+ *                                          "sddmm_wide_kernel").
+ * H < 1, F < 1, H F beyond int32 or a null array with E > 0: TCGNN_ERR_INVALID_ARG.  N = 0 or E = 0: TCGNN_OK.  A workspace too
+ * small or misaligned: TCGNN_ERR_WORKSPACE before anything is enqueued. */
+size_t tcgnn_sddmm_heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F);
+int tcgnn_sddmm_heads(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t H, int32_t F,
+                      void* d_workspace, size_t workspace_bytes, void* stream);
+
 /* ---- softmax over a node's incoming edges (DGL's edge_softmax; no counterpart in the reference) ------------------------------
  *
  * A row is the segment nodePointer[r] .. nodePointer[r + 1] of the edge array (softmax by destination node).  Planless, like

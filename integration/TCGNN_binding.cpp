@@ -318,6 +318,30 @@ std::vector<torch::Tensor> sddmm2_forward(torch::Tensor X, torch::Tensor Z, torc
   return {ef};
 }
 
+// Not in the reference: the two-operand SDDMM for every head at once, ef[h, e] = <X[row e, hF:(h+1)F], Z[col e, hF:(h+1)F]>, [heads, E]
+// (tcgnn_sddmm_heads; TCGNN.forward_ef_heads of the ctypes module)
+std::vector<torch::Tensor> sddmm_heads_forward(torch::Tensor X, torch::Tensor Z, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                               torch::Tensor blockPartition, torch::Tensor edgeToColumn, torch::Tensor edgeToRow, int64_t heads) {
+  CHECK_INPUT(X); CHECK_INPUT(Z); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  CHECK_INPUT(blockPartition); CHECK_INPUT(edgeToColumn); CHECK_INPUT(edgeToRow);
+  TORCH_CHECK(X.scalar_type() == torch::kFloat32 && Z.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  check_rows(X, nodePointer);
+  TORCH_CHECK(Z.sizes() == X.sizes() && Z.device() == X.device(), "Z must have the shape and device of X");
+  const int64_t E = edgeList.numel(), D = X.size(1);
+  TORCH_CHECK(heads >= 1 && D % heads == 0, "X has ", D, " columns, which ", heads, " heads do not divide");
+  DeviceGuard guard(X.device());
+  auto ef = torch::empty({heads, E}, X.options());
+  if (E == 0) return {ef};
+  if (D == 0) return {ef.zero_()};
+  auto* plan = plan_for(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow);
+  const int H = (int)heads, F = (int)(D / heads);
+  void* ws = nullptr;
+  const size_t need = tcgnn_sddmm_heads_workspace_bytes(plan, H, F);
+  torch::Tensor buf = aligned_scratch(need, X, &ws);
+  tcgnn_check(tcgnn_sddmm_heads(plan, X.data_ptr<float>(), Z.data_ptr<float>(), ef.data_ptr<float>(), H, F, ws, need, current_stream(X)), "tcgnn_sddmm_heads");
+  return {ef};
+}
+
 namespace {
 const float* beta_ptr(const c10::optional<torch::Tensor>& beta, const torch::Tensor& like) {
   if (!beta.has_value()) return nullptr;
@@ -606,7 +630,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row_scale") = py::none(), py::arg("col_scale") = py::none(), py::arg("bias") = py::none(), py::arg("relu") = false,
         py::arg("gate") = py::none(), py::arg("transpose") = false);
   m.def("forward_ef2", &sddmm2_forward, "SDDMM with two operands, ef[e] = <X[row e], Z[col e]> (not in the reference)");
-  m.def("edge_softmax", &edge_softmax, "softmax over every node's incoming edges (not in the reference)", py::arg("score"), py::arg("nodePointer"),
+  m.def("forward_ef_heads", &sddmm_heads_forward, "two-operand SDDMM for every head at once, ef[heads, E] (not in the reference)", py::arg("X"), py::arg("Z"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("blockPartition"), py::arg("edgeToColumn"), py::arg("edgeToRow"), py::arg("heads"));
+  m.def("edge_softmax", &edge_softmax,"softmax over every node's incoming edges (not in the reference)", py::arg("score"), py::arg("nodePointer"),
         py::arg("beta") = py::none(), py::arg("out") = py::none());
   m.def("edge_softmax_backward", &edge_softmax_backward, "backward of edge_softmax: (ds, dbeta) (not in the reference)", py::arg("p"), py::arg("dp"),
         py::arg("nodePointer"), py::arg("beta") = py::none(), py::arg("score") = py::none(), py::arg("need_dbeta") = false, py::arg("out") = py::none());

@@ -35,7 +35,7 @@ from tcgnn_graph_cache import GraphCache, TransposedCsr, TransposedPlan, graph_k
 __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGNN", "backward", "backward_ef",
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
-           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads",
+           "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "cache_stats", "drop_scales"]
 
 
@@ -272,10 +272,10 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     attention=True (a model with softmax-attention layers: forward_ef2, edge_softmax, edge_softmax_backward): the workspace grown to
     forward_ef2's two images at every width and the scratch of edge_softmax_backward's d_beta, on the current stream - a step that
     uses them then allocates nothing outside torch's pool and never synchronises.
-    A GAT model (gat_softmax, gat_softmax_backward, edge_colsum, and forward_heads / the per-head forward_ef2 calls of
-    tcgnn_edge_ops.aggregate_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True, attention=True and heads=H: the
+    A GAT or TransformerConv model (gat_softmax, gat_softmax_backward, edge_colsum, forward_heads and the forward_ef_heads calls of
+    tcgnn_edge_ops.aggregate_heads / sddmm_heads) passes the PER-HEAD widths with edge_valued=True, transpose=True, attention=True and heads=H: the
     edge-valued streams of A and A^T at that width (what a layer of ONE head runs on), the two-image SDDMM workspace, with A^T's
-    plan the transposed CSR edge_colsum sums over, and - heads > 1 - the workspace of forward_heads at H heads of every width in
+    plan the transposed CSR edge_colsum sums over, and - heads > 1 - the workspaces of forward_ef_heads and of forward_heads at H heads of every width in
     `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream.
     max_aggregation=True (a model with forward_max / backward_max: SAGEConv's max and pool aggregators): the transposed CSR backward_max
     walks, built now (transpose_graph: the graph's one transpose) - the two calls are planless and need nothing else."""
@@ -290,6 +290,8 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
         if attention:
             for d in widths:
                 _buffer("workspace", _c.lib.tcgnn_sddmm2_workspace_bytes(e.handle, d), dev, stream)
+                if int(heads) > 1:
+                    _buffer("workspace", _c.lib.tcgnn_sddmm_heads_workspace_bytes(e.handle, int(heads), d), dev, stream)
             _buffer("softmax", _c.lib.tcgnn_edge_softmax_workspace_bytes(max(nodePointer.numel() - 1, 0), edgeList.numel()), dev, stream)
         if transpose:
             own = _transposed_plan(e).own
@@ -710,6 +712,30 @@ def forward_ef2(X, Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeT
     out = torch.empty(edgeList.numel(), dtype=torch.float32, device=X.device)
     if out.numel() and D:
         _run(_c.lib.tcgnn_sddmm2, meta, X.device, D, (X.data_ptr(), Z.data_ptr(), out.data_ptr(), D), need=_c.lib.tcgnn_sddmm2_workspace_bytes)
+    elif out.numel():
+        out.zero_()
+    return [out]
+
+
+def forward_ef_heads(X, Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, heads):
+    """Not in the reference module: forward_ef2 for every head at once (tcgnn_sddmm_heads),
+        ef[h, e] = <X[row(e), hF:(h+1)F], Z[col(e), hF:(h+1)F]>,   F = X.size(1) / heads,
+    fp32 [heads, E], head-major - the layout gat_softmax returns and forward_heads takes: the scores of multi-head dot-product
+    attention, and forward_heads' gradient with respect to its edge values, forward_ef_heads(dY, input).  One call whatever the
+    shape: the library takes the fused walk - one gather of the neighbour rows feeds every head's dot product - where it covers
+    (heads, F) and goes head by head itself elsewhere (include/tcgnn.h; last_kernel tells).  Each operand is rounded with one scale
+    over all its columns.  heads = 1 is forward_ef2 bit for bit."""
+    meta = _six(X, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow)
+    _check_like(Z, "Z", X, "X")
+    D = X.size(1)
+    H = int(heads)
+    if H < 1 or D % H:
+        raise RuntimeError("X has %d columns, which %d heads do not divide" % (D, H))
+    out = torch.empty((H, edgeList.numel()), dtype=torch.float32, device=X.device)
+    if out.numel() and D:
+        F = D // H
+        _run(_c.lib.tcgnn_sddmm_heads, meta, X.device, D, (X.data_ptr(), Z.data_ptr(), out.data_ptr(), H, F),
+             need=lambda plan, _: _c.lib.tcgnn_sddmm_heads_workspace_bytes(plan, H, F))
     elif out.numel():
         out.zero_()
     return [out]

@@ -452,6 +452,25 @@ static hipError_t launch_sddmm_ks(int ks, const SddmmArgs& args, int nwg, hipStr
     return args.xa16 ? launch_sddmm_two<WAVES, BLOCKED, true>(ks, args, nwg, stream) : launch_sddmm_two<WAVES, BLOCKED, false>(ks, args, nwg, stream);
 }
 
+// tcgnn_sddmm_heads: npass passes (grid.y) of g heads of hf columns each, from args.head0 on.  The instantiated (hf, g): every pass
+// sddmm_heads_passes forms - hf = 8, 16, 32 with 2, 3 or 4 heads, hf = 64 with 2
+template <int WAVES, bool BLOCKED>
+static hipError_t launch_sddmm_heads(int hf, int g, const SddmmArgs& args, int nwg, int npass, hipStream_t stream) {
+    const dim3 grid((unsigned)nwg, (unsigned)npass), block(WAVES * 64);
+#define TCGNN_SDDMM_HEADS_CASE(f, n)                                                                                                                  \
+    if (hf == f && g == n) {                                                                                                                          \
+        hipLaunchKernelGGL((sddmm_kernel<sddmm_heads_ks(f, n), WAVES, BLOCKED, true, f, n>), grid, block, (size_t)WAVES * sddmm_heads_wave_lds(f, n), \
+                           stream, args);                                                                                                             \
+        return hipGetLastError();                                                                                                                     \
+    }
+    TCGNN_SDDMM_HEADS_CASE(8, 2) TCGNN_SDDMM_HEADS_CASE(8, 3) TCGNN_SDDMM_HEADS_CASE(8, 4)
+    TCGNN_SDDMM_HEADS_CASE(16, 2) TCGNN_SDDMM_HEADS_CASE(16, 3) TCGNN_SDDMM_HEADS_CASE(16, 4)
+    TCGNN_SDDMM_HEADS_CASE(32, 2) TCGNN_SDDMM_HEADS_CASE(32, 3) TCGNN_SDDMM_HEADS_CASE(32, 4)
+    TCGNN_SDDMM_HEADS_CASE(64, 2)
+#undef TCGNN_SDDMM_HEADS_CASE
+    return hipErrorInvalidValue;
+}
+
 static constexpr int kAgnnMaxW = 2;   // windows owned by a wavefront of the range-major fused kernel
 template <int WAVES, bool BWD, int MAXW>
 static hipError_t launch_agnn(int nt, const AgnnArgs& args, int nwg, hipStream_t stream) {
@@ -767,6 +786,17 @@ size_t tcgnn_sddmm2_workspace_bytes(const tcgnn_plan* plan, int32_t D) {
 int tcgnn_sddmm2(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t D, void* ws, size_t ws_bytes, void* stream_v) {
     if (!plan || D < 1 || (plan->N > 0 && !(d_X && d_Z)) || (plan->E > 0 && !d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm2: null argument or D < 1");
     return run_sddmm(sddmm_call("tcgnn_sddmm2", plan, d_X, d_Z, d_ef, D, ws, ws_bytes, stream_v));
+}
+
+size_t tcgnn_sddmm_heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    if (!plan || H < 1 || F < 1 || (int64_t)H * F > INT32_MAX) return 0;
+    return sddmm_heads_workspace_bytes(plan, H, F);
+}
+
+int tcgnn_sddmm_heads(const tcgnn_plan* plan, const float* d_X, const float* d_Z, float* d_ef, int32_t H, int32_t F, void* ws, size_t ws_bytes, void* stream_v) {
+    SddmmHeadsCall c;
+    c.plan = plan; c.d_X = d_X; c.d_Z = d_Z; c.d_ef = d_ef; c.H = H; c.F = F; c.ws = ws; c.ws_bytes = ws_bytes; c.stream = static_cast<hipStream_t>(stream_v);
+    return run_sddmm_heads(c);
 }
 
 } // extern "C"

@@ -1,5 +1,5 @@
-// tcgnn_edge_dispatch.inc - host side of the two edge operators, in the shape of tcgnn_spmm_dispatch.inc: SDDMM (tcgnn_sddmm, tcgnn_sddmm2)
-// and the fused AGNN pair.  Per operator: the request (SddmmCall / AgnnCall), ONE routing decision made before anything is staged
+// tcgnn_edge_dispatch.inc - host side of the two edge operators, in the shape of tcgnn_spmm_dispatch.inc: SDDMM (tcgnn_sddmm, tcgnn_sddmm2,
+// and at the end of the file tcgnn_sddmm_heads with its own route on top of run_sddmm) and the fused AGNN pair.  Per operator: the request (SddmmCall / AgnnCall), ONE routing decision made before anything is staged
 // (route_sddmm / route_agnn: plan facts, mode, width and the per-call test knobs), one launcher per walk, the range guard's tail, run_*.
 // Included by tcgnn_device.hip in front of tcgnn_spmm_dispatch.inc: tcgnn_spmm_val's XCD-sliced walk asks agnn_plan_walk and runs
 // launch_val_sliced, and tcgnn_workspace_bytes sizes the slice addends with agnn_slices - one predicate, one AgnnArgs builder for all.
@@ -262,6 +262,10 @@ struct SddmmCall {
     void* ws = nullptr; size_t ws_bytes = 0;
     hipStream_t stream = nullptr;
     const char* name = "";   // the entry point, for messages
+    // tcgnn_sddmm_heads on its fused walk: H heads of F columns (D = H F, d_ef [H, E]); 0: one head.  ld > 0: the operands are column
+    // blocks of wider row-major matrices of that row stride, whose headers the caller filled over the whole matrices (hdr_filled)
+    int32_t H = 0, F = 0;
+    int64_t ld = 0; bool hdr_filled = false;
     int dpad() const { return round_up(D, 16); }
     int ks() const { return (dpad() + 31) / 32; }
 };
@@ -272,6 +276,35 @@ struct SddmmRoute { SddmmWalk walk = SddmmWalk::kPerWindow; int nranges = 0, xcd
 static int sddmm_range_major_wgs(const tcgnn_plan* plan, int ks, int nranges) {
     const int64_t items = (int64_t)nranges * plan->nw_eff;
     return (int)std::min<int64_t>((items + 3) / 4, (int64_t)plan->num_cus * wgs_per_cu(4 * sddmm_wave_lds(ks), 4));
+}
+// The passes of the fused multi-head walk: H heads in ceil(H / kSddmmMaxHeadsPerPass) passes of at most 128 columns, as even as they
+// come - `nbig` passes of g + 1 heads, then the others of g (5 = 3 + 2, 7 = 4 + 3, 8 = 4 + 4) - so that no pass is a single head.
+struct SddmmHeadsPasses { int g = 0, nbig = 0, n = 0; };
+static SddmmHeadsPasses sddmm_heads_passes(int H, int F) {
+    const int gmax = std::min(kSddmmMaxHeadsPerPass, 128 / F);
+    SddmmHeadsPasses p;
+    p.n = (H + gmax - 1) / gmax; p.g = H / p.n; p.nbig = H % p.n;
+    return p;
+}
+// resident workgroups per CU of a fused pass: LDS, and the registers its launch bound leaves (three wavefronts a SIMD at one K-step, else two)
+static int sddmm_heads_wgs_per_cu(int F, int g) { return wgs_per_cu(4 * sddmm_heads_wave_lds(F, g), sddmm_heads_ks(F, g) <= 1 ? 3 : 2); }
+static int sddmm_heads_wgs_per_cu(const SddmmCall& c) {   // (of the call's widest pass; passes share the CUs - grid.y)
+    const SddmmHeadsPasses p = sddmm_heads_passes(c.H, c.F);
+    return std::max(1, sddmm_heads_wgs_per_cu(c.F, p.nbig ? p.g + 1 : p.g) / p.n);
+}
+// launch every pass of a fused call on `nwg` workgroups each: the passes of g + 1 heads in one launch, those of g in another
+template <int WAVES, bool BLOCKED>
+static hipError_t launch_sddmm_heads_passes(const SddmmCall& c, SddmmArgs a, int nwg) {
+    const SddmmHeadsPasses p = sddmm_heads_passes(c.H, c.F);
+    a.E = c.plan->E;
+    hipError_t e = hipSuccess;
+    if (p.nbig) { a.head0 = 0; e = launch_sddmm_heads<WAVES, BLOCKED>(c.F, p.g + 1, a, nwg, p.nbig, c.stream); }
+    if (e == hipSuccess && p.n > p.nbig) { a.head0 = p.nbig * (p.g + 1); e = launch_sddmm_heads<WAVES, BLOCKED>(c.F, p.g, a, nwg, p.n - p.nbig, c.stream); }
+    return e;
+}
+static int sddmm_heads_range_major_wgs(const SddmmCall& c, int nranges) {
+    const int64_t items = (int64_t)nranges * c.plan->nw_eff;
+    return (int)std::min<int64_t>((items + 3) / 4, (int64_t)c.plan->num_cus * sddmm_heads_wgs_per_cu(c));
 }
 // One walk selection for both calls.  Beyond 128 columns (ks > 4: sddmm_wide_kernel) only the per-window walk exists.
 static SddmmRoute route_sddmm(const SddmmCall& c) {
@@ -305,7 +338,7 @@ static SddmmRoute route_sddmm(const SddmmCall& c) {
     const char* const ienv = test_knob("TCGNN_RM_IDENT");
     r.ident = (ienv ? atoi(ienv) : 1) && windows_balanced(plan) ? 1 : 0;
     r.xcd = (xknob && (xknob >= 2 || r.ident || plan->near_frac <= 0.2 || r.nranges >= 4 * kXcds) && r.nranges % kXcds == 0 &&
-             sddmm_range_major_wgs(plan, ks, r.nranges) >= kXcds) ? 1 : 0;
+             (c.H ? sddmm_heads_range_major_wgs(c, r.nranges) : sddmm_range_major_wgs(plan, ks, r.nranges)) >= kXcds) ? 1 : 0;
     return r;
 }
 // the kernel arguments every walk starts from (imw: tcgnn_sddmm2's window operand, empty for one operand)
@@ -323,36 +356,49 @@ static SddmmArgs sddmm_args(const SddmmCall& c, const StagedImage& im, const Sta
 static hipError_t launch_sddmm_sync(const SddmmCall& c, SddmmArgs a) {
     const tcgnn_plan* const plan = c.plan;
     const int ks = c.ks();
-    KernelTimer timer(plan, c.stream, "sddmm_kernel (slice-synchronised)");
+    KernelTimer timer(plan, c.stream, c.H ? "sddmm_heads_kernel (slice-synchronised)" : "sddmm_kernel (slice-synchronised)");
     a.use_sync = 1;
     a.sync = sync_args(plan, a.stride * 2);
-    const int nwg = kXcds * std::max(1, std::min((plan->sync.S + 3) / 4, plan->num_cus / kXcds * wgs_per_cu(4 * sddmm_wave_lds(ks), ks <= 2 ? 4 : 3)));
+    const int per_cu = c.H ? sddmm_heads_wgs_per_cu(c) : wgs_per_cu(4 * sddmm_wave_lds(ks), ks <= 2 ? 4 : 3);
+    const int nwg = kXcds * std::max(1, std::min((plan->sync.S + 3) / 4, plan->num_cus / kXcds * per_cu));
     hipError_t e = hipSuccess;
     for (int r = 0; r < plan->sync.R && e == hipSuccess; ++r) {
         a.sync.round = r;
-        e = launch_sddmm_ks<4, true>(ks, a, nwg, c.stream);
+        e = c.H ? launch_sddmm_heads_passes<4, true>(c, a, nwg) : launch_sddmm_ks<4, true>(ks, a, nwg, c.stream);
     }
     return e;
 }
 static hipError_t launch_sddmm_range_major(const SddmmCall& c, const SddmmRoute& r, SddmmArgs a) {
-    KernelTimer timer(c.plan, c.stream, "sddmm_kernel");
+    KernelTimer timer(c.plan, c.stream, c.H ? "sddmm_heads_kernel" : "sddmm_kernel");
     a.nranges = r.nranges;
     a.gsel = c.plan->nbuckets / r.nranges;
     a.ident = r.ident;
     a.xcd = r.xcd;
-    int nwg = sddmm_range_major_wgs(c.plan, c.ks(), r.nranges);
+    int nwg = c.H ? sddmm_heads_range_major_wgs(c, r.nranges) : sddmm_range_major_wgs(c.plan, c.ks(), r.nranges);
     if (r.xcd) nwg -= nwg % kXcds;
+    if (c.H) return launch_sddmm_heads_passes<4, true>(c, a, nwg);
     return launch_sddmm_ks<4, true>(c.ks(), a, nwg, c.stream);
 }
 static hipError_t launch_sddmm_per_window(const SddmmCall& c, const SddmmArgs& a) {
     const tcgnn_plan* const plan = c.plan;
-    KernelTimer timer(plan, c.stream, c.ks() <= 4 ? "sddmm_kernel" : "sddmm_wide_kernel");
+    KernelTimer timer(plan, c.stream, c.H ? "sddmm_heads_kernel" : (c.ks() <= 4 ? "sddmm_kernel" : "sddmm_wide_kernel"));
+    if (c.H) return plan->waves == 4 ? launch_sddmm_heads_passes<4, false>(c, a, plan->nw_eff) : launch_sddmm_heads_passes<1, false>(c, a, plan->nw_eff);
     return plan->waves == 4 ? launch_sddmm_ks<4, false>(c.ks(), a, plan->nw_eff, c.stream) : launch_sddmm_ks<1, false>(c.ks(), a, plan->nw_eff, c.stream);
+}
+// sddmm_heads_csr_kernel for all H heads of [.., H F] operands on `rows` rows: a capped grid, the kernel strides over rows and heads
+static void launch_sddmm_heads_csr(const tcgnn_plan* plan, const uint32_t* hx, const uint32_t* hz, const float* d_X, const float* d_Z, float* d_ef, int32_t rows, int32_t H,
+                                   int32_t F, hipStream_t stream) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(sddmm_heads_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048), (unsigned)std::min(H, 1024)), dim3(256), 0, stream, hx, hz, plan->rowptr, plan->col,
+                       d_X, d_Z, d_ef, rows, H, F, (int64_t)H * F, plan->E, plan->row_off);
 }
 // the range guard's tail, behind the launchers (returns at once unless X is "wide")
 static int launch_sddmm_guard_tail(const SddmmCall& c, const StagedImage& im, const StagedImage& imw) {
     const tcgnn_plan* const plan = c.plan;
-    if (range_guard_of(plan) >= 2 && c.d_Xw) {   // two operands: the whole call in fp32 when either is wide (sddmm2_wide; returns at once otherwise)
+    if (c.ld) return TCGNN_OK;   // (a head's column block of tcgnn_sddmm_heads: ONE tail for all heads, behind the last of them - run_sddmm_heads)
+    if (range_guard_of(plan) >= 2 && c.H) {   // tcgnn_sddmm_heads, fused: every head in ONE launch
+        launch_sddmm_heads_csr(plan, imw.hdr, im.hdr, c.d_Xw, c.d_X, c.d_ef, patch_rows_of(plan), c.H, c.F, c.stream);
+    } else if (range_guard_of(plan) >= 2 && c.d_Xw) {   // two operands: the whole call in fp32 when either is wide (sddmm2_wide; returns at once otherwise)
         // (the rows of the windows the plan was given: what lies behind them stays as the memset left it, as on the MFMA path)
         const int32_t rows = (int32_t)std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows);
         hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048)), dim3(256), 0, c.stream, imw.hdr, im.hdr, plan->rowptr, plan->col, c.d_Xw, c.d_X, c.d_ef,
@@ -377,9 +423,9 @@ static int run_sddmm(const SddmmCall& c) {
         HIP_TRY(hipGetLastError());
         return TCGNN_OK;
     }
-    if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(c.d_ef, 0, (size_t)plan->E * sizeof(float), c.stream));
-    const Guard gsd = guard_sddmm(plan, D);
-    StageOpts so; so.guard = &gsd;
+    if ((int64_t)plan->nw_eff * kWinRows < plan->N) HIP_TRY(hipMemsetAsync(c.d_ef, 0, (size_t)plan->E * std::max(c.H, 1) * sizeof(float), c.stream));
+    const Guard gsd = guard_sddmm(plan, D);   // (a fused multi-head call: D = H F where a score has F terms - the conservative cap, one decision for every head)
+    StageOpts so; so.guard = &gsd; so.ldx = c.ld; so.block_of_wider = c.hdr_filled;
     StagedImage im, imw;
     if (const int rc = stage_features(plan, c.d_X, nullptr, D, c.ws, c.ws_bytes, c.stream, so, &im)) return rc;
     if (c.d_Xw) {   // the window operand's image behind the gathered operand's: its own header, its own scale
@@ -391,4 +437,82 @@ static int run_sddmm(const SddmmCall& c) {
     const hipError_t e = r.walk == SddmmWalk::kSync ? launch_sddmm_sync(c, a) : (r.walk == SddmmWalk::kRangeMajor ? launch_sddmm_range_major(c, r, a) : launch_sddmm_per_window(c, a));
     HIP_TRY(e);
     return launch_sddmm_guard_tail(c, im, imw);
+}
+
+// ------------------------------------------------------------------------------------------
+// tcgnn_sddmm_heads: ef[h, e] = <X[row e, hF:(h+1)F], Z[col e, hF:(h+1)F]> for H heads, ef [H, E] head-major.  One decision
+// (route_sddmm_heads), from the plan and (H, F) alone, before anything is staged; tcgnn_sddmm_heads_workspace_bytes asks the same function.
+// ------------------------------------------------------------------------------------------
+struct SddmmHeadsCall {
+    const tcgnn_plan* plan = nullptr;
+    const float *d_X = nullptr, *d_Z = nullptr;   // X: the window operand, Z: the gathered one; both [Nc, H F]
+    float* d_ef = nullptr;                        // [H, E]
+    int32_t H = 0, F = 0;
+    void* ws = nullptr; size_t ws_bytes = 0;
+    hipStream_t stream = nullptr;
+};
+// kSingle: H == 1 is tcgnn_sddmm2 itself (run_sddmm, every walk it has); kFused: sddmm_kernel's multi-head form ("sddmm_heads_kernel") on
+// route_sddmm's walk at width H F - each operand staged once, one walk of the tile stream per pass of up to four heads; kCsr: a plan
+// without a tile stream, or fewer than four edges - sddmm_heads_csr_kernel, all heads in one launch; kPerHead: head by head inside the
+// library - each head a column block of X and Z (run_sddmm with ld, the headers filled once over the whole matrices) into its row of ef
+enum class SddmmHeadsWay { kSingle, kFused, kCsr, kPerHead };
+// the fused form's head widths (each with 2 .. 4 heads a pass, F = 64 with 2: launch_sddmm_heads); H F <= 128, and an image one
+// buffer descriptor addresses (the big-image lane addresses stay the single-head kernel's)
+static bool sddmm_heads_fused_width(int32_t F) { return F == 8 || F == 16 || F == 32 || F == 64; }
+static SddmmHeadsWay route_sddmm_heads(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    if (H == 1) return SddmmHeadsWay::kSingle;
+    if (!plan->canonical || plan->E < 4) return SddmmHeadsWay::kCsr;
+    const int64_t D = (int64_t)H * F;
+    if (sddmm_heads_fused_width(F) && D <= 128 && plan->nw_eff > 0 && !image_is_big(plan->Nc, x16_pitch(round_up((int)D, 16)))) return SddmmHeadsWay::kFused;
+    return SddmmHeadsWay::kPerHead;
+}
+static size_t sddmm_heads_workspace_bytes(const tcgnn_plan* plan, int32_t H, int32_t F) {
+    switch (route_sddmm_heads(plan, H, F)) {
+        case SddmmHeadsWay::kSingle: return tcgnn_sddmm2_workspace_bytes(plan, F);
+        case SddmmHeadsWay::kFused:  return 2 * workspace_bytes_for(plan->Nc, H * F);   // the two images of all columns
+        // two images of one head's block at a time.  (kCsr stages nothing, but is handed the same buffer: what a caller must
+        //  provide is checked alike on every route)
+        default:                     return 2 * workspace_bytes_for(plan->Nc, F);
+    }
+}
+static int run_sddmm_heads(const SddmmHeadsCall& h) {
+    const tcgnn_plan* const plan = h.plan;
+    if (!plan || h.H < 1 || h.F < 1 || (int64_t)h.H * h.F > INT32_MAX) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm_heads: null plan, H < 1, F < 1 or H * F beyond int32");
+    if (plan->E > 0 && plan->N > 0 && !(h.d_X && h.d_Z && h.d_ef)) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sddmm_heads: null array");
+    if (plan->E == 0 || plan->N == 0) return TCGNN_OK;
+    const int32_t D = h.H * h.F;
+    SddmmCall c;
+    c.plan = plan; c.d_Xw = h.d_X; c.d_X = h.d_Z; c.d_ef = h.d_ef; c.ws = h.ws; c.ws_bytes = h.ws_bytes; c.stream = h.stream; c.name = "tcgnn_sddmm_heads";
+    const SddmmHeadsWay way = route_sddmm_heads(plan, h.H, h.F);
+    if (way == SddmmHeadsWay::kSingle) { c.D = h.F; return run_sddmm(c); }   // exactly tcgnn_sddmm2
+    if (const int rc = check_workspace("tcgnn_sddmm_heads", h.ws, h.ws_bytes, sddmm_heads_workspace_bytes(plan, h.H, h.F))) return rc;
+    if (way == SddmmHeadsWay::kFused) { c.D = D; c.H = h.H; c.F = h.F; return run_sddmm(c); }
+    if (way == SddmmHeadsWay::kCsr) {
+        // (a canonical plan: the rows of the windows it was handed, what lies behind them zero; a non-canonical one has no windows - every row)
+        const int32_t rows = plan->canonical ? patch_rows_of(plan) : plan->N;
+        if (rows < plan->N) HIP_TRY(hipMemsetAsync(h.d_ef, 0, (size_t)plan->E * h.H * sizeof(float), h.stream));
+        launch_sddmm_heads_csr(plan, nullptr, nullptr, h.d_X, h.d_Z, h.d_ef, rows, h.H, h.F, h.stream);
+        HIP_TRY(hipGetLastError());
+        return TCGNN_OK;
+    }
+    // head by head: ONE abs-max per operand for the whole call (every head rounded with the scales the fused walk would use), Z's
+    // header where run_sddmm stages the gathered operand and X's where it stages the window operand of an F-column call
+    const Guard gsd = guard_sddmm(plan, D);
+    const size_t first = workspace_bytes_for(plan->Nc, h.F);
+    if (const int rc = fill_header(plan, static_cast<uint32_t*>(h.ws), h.d_Z, nullptr, nullptr, D, gsd, nullptr, 0, h.stream)) return rc;
+    if (const int rc = fill_header(plan, reinterpret_cast<uint32_t*>(static_cast<char*>(h.ws) + first), h.d_X, nullptr, nullptr, D, gsd, nullptr, 0, h.stream)) return rc;
+    for (int k = 0; k < h.H; ++k) {
+        SddmmCall b = c;
+        b.d_Xw = h.d_X + (int64_t)k * h.F; b.d_X = h.d_Z + (int64_t)k * h.F; b.d_ef = h.d_ef + (int64_t)k * plan->E;
+        b.D = h.F; b.ld = D; b.hdr_filled = true;
+        if (const int rc = run_sddmm(b)) return rc;
+    }
+    // the range guard's tail, ONE launch behind the last head for all of them.  Every head's MFMA kernel asked sddmm2_wide with the
+    // lost-element counts of the blocks converted so far; the counts only grow and the rule is monotone in them, so where any head's
+    // kernel stood back the tail - which sees the whole call's counts - does the work, and where it runs it rewrites every head
+    if (range_guard_of(plan) >= 2)
+        launch_sddmm_heads_csr(plan, reinterpret_cast<const uint32_t*>(static_cast<char*>(h.ws) + first), static_cast<const uint32_t*>(h.ws), h.d_X, h.d_Z, h.d_ef,
+                               patch_rows_of(plan), h.H, h.F, h.stream);
+    HIP_TRY(hipGetLastError());
+    return TCGNN_OK;
 }

@@ -27,6 +27,10 @@ struct SddmmArgs {
     // own image and header - same pitch and row count as x16, its own power-of-two scale.  x16 / hdr are then the gathered operand's
     const _Float16* xa16;
     const uint32_t* hdr_a;
+    // tcgnn_sddmm_heads (the HF > 0 instantiations only, behind everything above): ef is [H][E] head-major, E floats a head; pass
+    // blockIdx.y of a launch takes the G heads from head0 + blockIdx.y G on - columns (head0 + blockIdx.y G) HF .. of both images
+    int64_t E;
+    int32_t head0;
 };
 // tcgnn_sddmm2's range guard (level >= 2: Z's kHdrCapX = 2 D, else 0): the whole call goes the fp32 way when either operand holds elements
 // that lose bits in its image (range_spread, counted in kHdrTiny) and k max|X| max|Z| 2^-39 could leave 2^-10 - range_is_wide's rule for
@@ -50,6 +54,16 @@ static constexpr int kSddmmStageCap = 64;
 // where LDS would otherwise allow a single workgroup per CU (latency is then hidden by wavefront count only).
 static constexpr int sddmm_nbuf(int ks) { return TCGNN_SDDMM_NBUF(ks); }
 static constexpr int sddmm_wave_lds(int ks) { return sddmm_nbuf(ks) * (2 * ks * 1024) + kPadBytes + 16 * kSddmmStageCap * 4 + 256; }
+// The multi-head form (tcgnn_sddmm_heads; HF = columns of a head, G = heads of a pass): one staging area PER HEAD, so the cap is the
+// smallest a tile allows - a tile adds at most 32 results to a row - and the flush is decided from the tile's masks BEFORE it is
+// staged (a row that could overflow flushes first) instead of after it with 32 slots kept free.  At most kSddmmMaxHeadsPerPass heads
+// and 128 columns a pass: 2 x 4 KB or 8 KB of operand buffers + 4 x 2 KB of staging = 16.8 KB a wavefront, two four-wavefront
+// workgroups per CU at the worst shapes (4 x 16, 4 x 32), three at 4 x 8 (DESIGN.md 4.11 has the table).
+static constexpr int kSddmmHeadsStageCap = 32, kSddmmMaxHeadsPerPass = 4;
+static constexpr int sddmm_heads_ks(int hf, int g) { return (hf * g + 31) / 32; }
+static constexpr int sddmm_heads_wave_lds(int hf, int g) {
+    return sddmm_nbuf(sddmm_heads_ks(hf, g)) * (2 * sddmm_heads_ks(hf, g) * 1024) + kPadBytes + g * 16 * kSddmmHeadsStageCap * 4 + 256;
+}
 
 // KS = number of 32-wide k steps (D <= 32*KS <= 128).  The 16 window rows (MFMA A operand) stay in
 // registers.  Neighbour rows are the B operand, which for X * X^T is contiguous per lane: lane
@@ -59,14 +73,27 @@ static constexpr int sddmm_wave_lds(int ks) { return sddmm_nbuf(ks) * (2 * ks * 
 // gather of the NEXT tile (both 16-column halves) is in flight while the current one is multiplied
 // and scattered, without any VGPR holding a load in flight (see "memory pipeline discipline").
 // TWO (tcgnn_sddmm2): the window rows come from a second image, a.xa16, scaled by its own header word; everything else is the same code
-template <int KS, int WAVES, bool BLOCKED, bool TWO = false>
-__global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(const SddmmArgs a) {
+// HF > 0 (tcgnn_sddmm_heads, with TWO; reported as "sddmm_heads_kernel"): the KS K-steps are the G HF columns of one pass of G heads,
+// HF columns each, and every head has its own accumulator, staging area and row of ef.  Lane (i, g) of K-step ks holds the pass's
+// columns 32 ks + 8 g .. + 7, which belong to ONE head: a head's accumulator takes the K-steps its columns touch - HF = 64 two, HF = 32
+// one; HF = 8 / 16: four / two heads share a K-step, which is then issued once per head with an A fragment whose lanes outside that
+// head's column groups are zero (built once per window in load_a: the tile loop gains MFMA issues and the staging writes of G times
+// the outputs, no other VALU work).  Gather, metadata DMA, LDS landing layout and the three walks are the single-head kernel's.
+template <int KS, int WAVES, bool BLOCKED, bool TWO = false, int HF = 0, int G = 1>
+__global__ __launch_bounds__(WAVES * 64, (HF > 0 ? (KS <= 1 ? 3 : 2) : (KS <= 2 ? 4 : 3))) void sddmm_kernel(const SddmmArgs a) {
+    static_assert(HF == 0 || (TWO && (HF == 8 || HF == 16 || HF == 32 || HF == 64) && G >= 1 && G <= kSddmmMaxHeadsPerPass && KS == sddmm_heads_ks(HF, G) && KS <= 4),
+                  "a pass of the multi-head form: G heads of HF columns in KS K-steps");
     if constexpr (TWO) { if (sddmm2_wide(a.hdr_a, a.hdr)) return; }   // (sddmm2_csr_kernel, launched behind this kernel, does the work)
     else if (wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BUF_BYTES = 2 * KS * 1024;               // both halves of one tile
-    constexpr int WAVE_LDS = sddmm_wave_lds(KS);
-    constexpr int CAP = kSddmmStageCap;                    // staged outputs per row before a flush
+    constexpr int WAVE_LDS = HF > 0 ? sddmm_heads_wave_lds(HF, G) : sddmm_wave_lds(KS);
+    constexpr int CAP = HF > 0 ? kSddmmHeadsStageCap : kSddmmStageCap;   // staged outputs per row before a flush
+    constexpr int KPH = HF > 32 ? HF / 32 : 1;             // HF > 0: K-steps a head's accumulator takes
+    constexpr int NA = HF > 0 ? G * KPH : KS;              // A fragments a window keeps: one per K-step; HF > 0: one per (head, K-step of the head)
+    constexpr int STG_HEAD = 16 * CAP * 4;                 // staging bytes of one head
+    const int head0 = HF > 0 ? a.head0 + (int)blockIdx.y * G : 0;
+    const int coloff = head0 * HF;                         // first column of this pass in both images (a multiple of 8)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int g = lane >> 4, i = lane & 15;
@@ -92,7 +119,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
     uint32_t boff[KS];
     bool bok[KS];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) { bok[ks] = ks * 32 + 8 * g < a.Dpad; boff[ks] = bok[ks] ? (uint32_t)(ks * 32 + 8 * g) * 2u : 0u; }
+    for (int ks = 0; ks < KS; ++ks) { bok[ks] = coloff + ks * 32 + 8 * g < a.Dpad; boff[ks] = (uint32_t)(coloff + (bok[ks] ? ks * 32 + 8 * g : 0)) * 2u; }
     // WL (KS = 2, rows of one 128-byte line; r03): whole-line gathers, as in agnn_kernel - instruction q takes the eight rows of tile
     // columns 8q .. 8q+7 (lane L: row slot L >> 3, the chunk that belongs at position L & 7) into block q, row-major; chunk c of row
     // slot rho lies at position c ^ 2 (rho >> 1), which spreads the sixteen lanes of every ds_read_b128 lane group of the operand
@@ -116,7 +143,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
 #pragma unroll
         for (int q = 0; q < NI; ++q) {
             const uint32_t c = (uint32_t)(lane % CPR) ^ wl_sw((uint32_t)(lane / CPR), (uint32_t)q);
-            choff[q] = ((int)(c * 8u) < a.Dpad) ? c * 16u : 0u;
+            choff[q] = (uint32_t)coloff * 2u + ((coloff + (int)(c * 8u) < a.Dpad) ? c * 16u : 0u);
         }
     }
     uint32_t qaddr[1 + 2 * KS];                                                                   // edge offsets, then my landing slots
@@ -135,21 +162,32 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
     // tiles are consecutive in ef, so results are staged per row in LDS and each row is flushed as one
     // contiguous store (about one store per tile instead of eight, ~10x fewer write requests).
     const uint32_t stg = pad + kPadBytes;
-    const uint32_t junk = stg + 16u * CAP * 4u + (uint32_t)lane * 4u;
+    const uint32_t junk = stg + (uint32_t)(HF > 0 ? G : 1) * STG_HEAD + (uint32_t)lane * 4u;
     const uint32_t stg_row[4] = {stg + (uint32_t)(4 * g + 0) * CAP * 4u, stg + (uint32_t)(4 * g + 1) * CAP * 4u,
                                  stg + (uint32_t)(4 * g + 2) * CAP * 4u, stg + (uint32_t)(4 * g + 3) * CAP * 4u};
     const uint32_t flush_base = stg + (uint32_t)lane * 4u;        // lane j reads the j-th staged result of every row
 
   // A operand of window w: row i, halves 32*ks + 8g .. +7 (rows past N read the zero sentinel row)
-  auto load_a = [&](const int w, half8 (&af)[KS]) __attribute__((always_inline)) {
+  // (HF > 0: fragment k KPH + j is head k's j-th K-step; where heads share a K-step, the lanes of the other heads' column groups are zero)
+  auto load_a = [&](const int w, half8 (&af)[NA]) __attribute__((always_inline)) {
     int64_t arow = (int64_t)w * kWinRows + i;
     arow = arow < a.N ? arow + a.row_off : a.Nc;
-    const _Float16* ap = (TWO ? a.xa16 : a.x16) + arow * stride + 8 * g;
+    const _Float16* ap = (TWO ? a.xa16 : a.x16) + arow * stride + coloff + 8 * g;
+    if constexpr (HF > 0) {
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+#pragma unroll
+            for (int j = 0; j < KPH; ++j) {
+                const int ks = (k * HF) / 32 + j;
+                af[k * KPH + j] = ((32 * ks + 8 * g) / HF == k && coloff + ks * 32 + 8 * g < a.Dpad) ? *reinterpret_cast<const half8*>(ap + ks * 32) : hz;
+            }
+        return;
+    }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) af[ks] = (ks * 32 + 8 * g < a.Dpad) ? *reinterpret_cast<const half8*>(ap + ks * 32) : hz;
   };
   // one run: CONSECUTIVE tiles t .. te-1 of window w (step must be 1: the staging relies on it); af = load_a(w)
-  auto run_a = [&](const int w, const half8 (&af)[KS], int64_t t, const int64_t te, const int64_t step) __attribute__((always_inline)) {
+  auto run_a = [&](const int w, const half8 (&af)[NA], int64_t t, const int64_t te, const int64_t step) __attribute__((always_inline)) {
     if (t >= te) return;
     // edges of this window live in ef[e_w0 .. ): 32-bit offsets from a wave-uniform base
     const int64_t wrow = (int64_t)w * kWinRows;
@@ -160,6 +198,23 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
     uint32_t rstart[4] = {~0u, ~0u, ~0u, ~0u};                   // window-relative ef position of each row's first staged result
     auto flush = [&]() {
         uint32_t vals[16];
+        if constexpr (HF > 0) {   // every head's runs: the same counts and positions, head k's staging area into its row of ef
+#pragma unroll
+            for (int k = 0; k < G; ++k) {
+                lds_rows_block8<CAP * 4, 0>(flush_base + (uint32_t)(k * STG_HEAD), vals);
+                lds_rows_block8<CAP * 4, 8>(flush_base + (uint32_t)(k * STG_HEAD), vals + 8);
+                char* const ef_h = ef_w + (int64_t)(head0 + k) * a.E * 4;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const uint32_t c_r = (uint32_t)__builtin_amdgcn_readlane((int)cnt[r & 3], 16 * (r >> 2));
+                    const uint32_t s_r = (uint32_t)__builtin_amdgcn_readlane((int)rstart[r & 3], 16 * (r >> 2));
+                    if ((uint32_t)lane < c_r) *reinterpret_cast<uint32_t*>(ef_h + ((s_r + (uint32_t)lane) << 2)) = vals[r];
+                }
+            }
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) { cnt[ii] = 0u; rstart[ii] = ~0u; }
+            return;
+        }
         lds_rows_block8<CAP * 4, 0>(flush_base, vals);
         lds_rows_block8<CAP * 4, 8>(flush_base, vals + 8);
 #pragma unroll
@@ -224,11 +279,39 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
         if (flush_pending) { flush(); flush_pending = false; }
         // ---- tile tcur
         const uint32_t mm[4] = {cur.m4[0], cur.m4[1], cur.m4[2], cur.m4[3]};
+        if constexpr (HF > 0) {   // (CAP = 32: the masks say before the multiply whether every row has room for this tile)
+            const uint32_t fill = max(max(cnt[0] + (uint32_t)__popc(mm[0]), cnt[1] + (uint32_t)__popc(mm[1])), max(cnt[2] + (uint32_t)__popc(mm[2]), cnt[3] + (uint32_t)__popc(mm[3])));
+            if (__any(fill > (uint32_t)CAP)) flush();
+        }
         const uint32_t e0 = (uint32_t)e_w0;   // window-relative edge positions (a window holds far fewer than 2^32 edges)
         const uint32_t rbase[4] = {cur.eb4[0] - e0, cur.eb4[1] - e0, cur.eb4[2] - e0, cur.eb4[3] - e0};
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const uint32_t anyrow = ((mm[0] | mm[1] | mm[2] | mm[3]) >> (16 * sub)) & 0xffffu;
+            if constexpr (HF > 0) {
+              if (__any(anyrow != 0u)) {
+                floatx4 acch[G];
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    acch[k] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int j = 0; j < KPH; ++j)
+                        acch[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[k * KPH + j], __builtin_bit_cast(half8, q[1 + sub * KS + (k * HF) / 32 + j]), acch[k], 0, 0, 0);
+                }
+                const int bit = 16 * sub + i;
+#pragma unroll
+                for (int ii = 0; ii < 4; ++ii) {
+                    const bool on = (mm[ii] >> bit) & 1u;
+                    const uint32_t slot = on ? stg_row[ii] + ((cnt[ii] + (uint32_t)__popc(mm[ii] & below[sub])) << 2) : junk;
+#pragma unroll
+                    for (int k = 0; k < G; ++k) {
+                        float v = acch[k][ii] * inv_a;
+                        if (two_step) v *= inv_b;
+                        lds_write_b32(on ? slot + (uint32_t)(k * STG_HEAD) : junk, v);
+                    }
+                }
+              }
+            } else
             if (__any(anyrow != 0u)) {              // skip a 16-column half no edge lands in
                 floatx4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -256,7 +339,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
         // a tile adds at most 32 results to a row: flush while every row still has room for one more tile
         const uint32_t fullest = max(max(cnt[0], cnt[1]), max(cnt[2], cnt[3]));
         if (!more) flush();
-        else flush_pending = __any(fullest > (uint32_t)(CAP - 32));
+        else if constexpr (HF == 0) flush_pending = __any(fullest > (uint32_t)(CAP - 32));
         cur.m4 = m4n;
         cur.eb4 = q[0];
         tcur = tn;
@@ -286,7 +369,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
   };
   auto run = [&](const int w, int64_t t, const int64_t te, const int64_t step) __attribute__((always_inline)) {
     if (t >= te) return;
-    half8 af[KS];
+    half8 af[NA];
     load_a(w, af);
     run_a(w, af, t, te, step);
   };
@@ -304,7 +387,7 @@ __global__ __launch_bounds__(WAVES * 64, (KS <= 2 ? 4 : 3)) void sddmm_kernel(co
             //  (window, phase) run cost 4 KB of mostly missing lines and a round trip in front of each of the ~5-tile runs - 4.4 GB per call on
             //  the products shape; every trip walks the phases again, the wavefronts still together)
             for (int w = w_lo + wid; w < w_hi; w += nwv) {
-                half8 af[KS];
+                half8 af[NA];
                 load_a(w, af);
                 const uint32_t* Tw = a.sync.T + (int64_t)w * ts;
                 const int64_t tb = a.wb_ptr[w];
@@ -417,6 +500,34 @@ __global__ __launch_bounds__(256) void sddmm2_csr_kernel(const uint32_t* __restr
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
             if (lane == 0) ef[e] = s;
+        }
+    }
+}
+
+// tcgnn_sddmm_heads in plain fp32: sddmm2_csr_kernel's body per head - head h reads columns h F .. of X and Z (row stride ld = H F)
+// and writes ef + h E, the same sums in the same order as the single-head kernel on that head's columns.  ONE launch for all heads
+// (heads from blockIdx.y in steps of grid.y, rows from blockIdx.x in steps of grid.x: any H and N under a capped grid): the path of
+// non-canonical plans and of fewer than four edges (hx == nullptr), and the range guard's way behind the MFMA kernels of the fused
+// and of the head-by-head route (returns at once unless sddmm2_wide holds on the two headers, which decide for the whole call).
+__global__ __launch_bounds__(256) void sddmm_heads_csr_kernel(const uint32_t* __restrict__ hx, const uint32_t* __restrict__ hz, const int32_t* __restrict__ rowptr,
+                                                              const int32_t* __restrict__ col, const float* __restrict__ X, const float* __restrict__ Z, float* ef,
+                                                              int32_t N, int32_t H, int32_t F, int64_t ld, int64_t E, int32_t row_off) {
+    if (hx && !sddmm2_wide(hx, hz)) return;
+    const int lane = threadIdx.x & 63;
+    for (int64_t h = blockIdx.y; h < H; h += gridDim.y) {
+        const float* const Xh = X + h * F;
+        const float* const Zh = Z + h * F;
+        float* const efh = ef + h * E;
+        for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < N; row += (int64_t)gridDim.x * 4) {
+            const float* xr = Xh + (row + row_off) * ld;
+            for (int64_t e = rowptr[row]; e < rowptr[row + 1]; ++e) {
+                const float* xc = Zh + (int64_t)col[e] * ld;
+                float s = 0.f;
+                for (int d = lane; d < F; d += 64) s += round_rna10(xr[d]) * round_rna10(xc[d]);
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+                if (lane == 0) efh[e] = s;
+            }
         }
     }
 }

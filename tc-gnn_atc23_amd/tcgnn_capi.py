@@ -81,6 +81,8 @@ SIGNATURES = {
     "tcgnn_sddmm": (ctypes.c_int, [_vp, _vp, _vp, _i32, _vp, _sz, _vp]),
     "tcgnn_sddmm2_workspace_bytes": (_sz, [_vp, _i32]),
     "tcgnn_sddmm2": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "tcgnn_sddmm_heads_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "tcgnn_sddmm_heads": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _sz, _vp]),
     "tcgnn_edge_softmax_workspace_bytes": (_sz, [_i32, _i64]),
     "tcgnn_edge_softmax": (ctypes.c_int, [_i32p, _i32, _i64, _vp, _vp, _vp, _vp]),
     "tcgnn_edge_softmax_backward": (ctypes.c_int, [_i32p, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

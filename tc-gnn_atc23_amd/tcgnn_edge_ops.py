@@ -7,7 +7,9 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate(P, H, meta)         Y = A_val(P) H                           bwd: dP = sddmm(dY, H),  dH = A_val(P)^T dY
     gat_attention(el, er, rowptr, col, slope)  P[h] = softmax by row of leaky_relu(el[col e, h] + er[row e, h])   (multi-head GAT)
                                   bwd: g as above per head; ds = g lrelu'(raw); d_er = row sums of ds; d_el = column sums of ds
-    aggregate_heads(P, Z, meta)   Y[:, head h] = A_val(P[h]) Z[:, head h], all heads in one call   bwd: dP[h] = sddmm(dY_h, Z_h),  dZ through A^T, one call
+    aggregate_heads(P, Z, meta)   Y[:, head h] = A_val(P[h]) Z[:, head h], all heads in one call   bwd: dP = sddmm_heads(dY, Z), dZ through A^T, one call each
+    sddmm_heads(X, Z, meta, H)    ef[h, e] = <X[row e, head h], Z[col e, head h]>, [H, E], one call  bwd: dX = A_val(d_ef) Z, dZ = A_val(d_ef)^T X per head, one call each
+    edge_softmax_heads(S, rowptr, beta)  edge_softmax of every row of S [H, E] (head by head on the one-head operator, one [H, E] result)
     aggregate_max(X, rowptr, col) Y[i, d] = max over row i of X[col e, d] (0 for an empty row)     bwd: dX[j, d] = sum of dY[i, d] over the edges that won (i, d)
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
@@ -15,8 +17,8 @@ edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, als
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_max and backward_max.  A backend without them is an error - there is no composed fallback in this module (a stand-in backend
-installed with tcgnn_layers.set_backend is given forward_heads there, if it has none).
+forward_heads(transpose=), forward_ef_heads, forward_max and backward_max.  A backend without them is an error - there is no composed fallback in this module (a
+stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
 
@@ -108,8 +110,8 @@ class _GATAttention(torch.autograd.Function):
 
 
 class _AggregateHeads(torch.autograd.Function):
-    """Y = forward_heads(Z, P): one call for all heads, and one over A^T for dZ.  dP is written row by row into one [heads, E] tensor,
-    a forward_ef2 per head (a multi-head SDDMM does not exist yet)."""
+    """Y = forward_heads(Z, P): one call for all heads, and one over A^T for dZ.  dP [heads, E] is ONE forward_ef_heads(dY, Z) call, the
+    multi-head SDDMM (a stand-in backend without it was given the per-head definition by tcgnn_layers.set_backend)."""
 
     @staticmethod
     def forward(ctx, P, Z, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
@@ -123,15 +125,71 @@ class _AggregateHeads(torch.autograd.Function):
     def backward(ctx, d_y):
         P, Z = ctx.saved_tensors
         b = _L.backend()
-        H, F = P.shape[0], Z.shape[1] // P.shape[0]
+        H = P.shape[0]
         d_y = d_y.contiguous()
         d_p = d_z = None
         if ctx.needs_input_grad[0]:
-            d_p = torch.stack([b.forward_ef2(d_y[:, h * F:(h + 1) * F].contiguous(), Z[:, h * F:(h + 1) * F].contiguous(), *ctx.meta)[0] for h in range(H)])
+            d_p = b.forward_ef_heads(d_y, Z, *ctx.meta, H)[0]
         if ctx.needs_input_grad[1]:
             rp, col, bp, e2c, e2r = ctx.meta
             d_z = b.forward_heads(d_y, rp, col, P, bp, e2c, e2r, H, transpose=True)[0]
         return (d_p, d_z) + (None,) * 5
+
+
+def _into(row, result):
+    """`result` is `row` where the backend wrote through out= (TCGNN, the binding); a stand-in that returns a tensor of its own is copied"""
+    if result.data_ptr() != row.data_ptr():
+        row.copy_(result)
+
+
+class _SDDMMHeads(torch.autograd.Function):
+    """ef = forward_ef_heads(X, Z): one call for all heads; dX = forward_heads(Z, d_ef) and dZ = forward_heads(X, d_ef) over A^T, one call each."""
+
+    @staticmethod
+    def forward(ctx, X, Z, heads, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        ctx.meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        ctx.heads = heads
+        X, Z = X.contiguous(), Z.contiguous()
+        ctx.save_for_backward(X, Z)
+        return _L.backend().forward_ef_heads(X, Z, *ctx.meta, heads)[0]
+
+    @staticmethod
+    def backward(ctx, d_ef):
+        X, Z = ctx.saved_tensors
+        rp, col, bp, e2c, e2r = ctx.meta
+        b = _L.backend()
+        d_ef = d_ef.contiguous()
+        d_x = b.forward_heads(Z, rp, col, d_ef, bp, e2c, e2r, ctx.heads)[0] if ctx.needs_input_grad[0] else None
+        d_z = b.forward_heads(X, rp, col, d_ef, bp, e2c, e2r, ctx.heads, transpose=True)[0] if ctx.needs_input_grad[1] else None
+        return (d_x, d_z) + (None,) * 6
+
+
+class _EdgeSoftmaxHeads(torch.autograd.Function):
+    """edge_softmax of every head's row of S [H, E] with one beta (a constant: no d_beta), written into one [H, E] tensor through out="""
+
+    @staticmethod
+    def forward(ctx, S, row_pointers, beta):
+        S = S.contiguous()
+        b1 = beta.detach().reshape(1).contiguous() if beta is not None else None
+        b = _L.backend()
+        P = torch.empty_like(S)
+        for h in range(S.shape[0]):
+            _into(P[h], b.edge_softmax(S[h], row_pointers, b1, out=P[h]))
+        ctx.rowptr = row_pointers
+        ctx.has_beta = b1 is not None
+        ctx.save_for_backward(*([P] + ([b1] if ctx.has_beta else [])))
+        return P
+
+    @staticmethod
+    def backward(ctx, d_p):
+        P = ctx.saved_tensors[0]
+        b1 = ctx.saved_tensors[1] if ctx.has_beta else None
+        b = _L.backend()
+        d_p = d_p.contiguous()
+        d_s = torch.empty_like(P)
+        for h in range(P.shape[0]):
+            _into(d_s[h], b.edge_softmax_backward(P[h], d_p[h], ctx.rowptr, beta=b1, out=d_s[h])[0])
+        return d_s, None, None
 
 
 class _AggregateMax(torch.autograd.Function):
@@ -167,10 +225,28 @@ def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):
 def aggregate_heads(P, Z, meta):
     """Y[:, hF:(h+1)F] = A_val(P[h]) Z[:, hF:(h+1)F] for P [heads, E] and Z [N, heads * F]: the multi-head aggregation, one
     forward_heads call of the backend (the library's multi-head edge-valued SpMM: one gather feeds every head where its fused walk
-    covers the shape).  dZ is one forward_heads call over A^T, dP[h] a forward_ef2 per head; both exact."""
+    covers the shape).  dZ is one forward_heads call over A^T, dP one forward_ef_heads call (the multi-head SDDMM); both exact."""
     if P.dim() != 2 or Z.dim() != 2 or P.shape[0] < 1 or Z.shape[1] % P.shape[0]:
         raise RuntimeError("P must be [heads, E] and Z [N, heads * F], got %s and %s" % (tuple(P.shape), tuple(Z.shape)))
     return _AggregateHeads.apply(P, Z, *meta)
+
+
+def sddmm_heads(X, Z, meta, heads):
+    """ef[h, e] = <X[row e, hF:(h+1)F], Z[col e, hF:(h+1)F]> for X, Z [N, heads * F]: the scores of multi-head dot-product attention,
+    [heads, E] head-major, one forward_ef_heads call of the backend (the library's multi-head SDDMM: one gather feeds every head's
+    dot product where its fused walk covers the shape).  dX and dZ are one forward_heads call each (dZ over A^T); both exact."""
+    heads = int(heads)
+    if X.dim() != 2 or X.shape != Z.shape or heads < 1 or X.shape[1] % heads:
+        raise RuntimeError("X and Z must both be [N, heads * F], got %s and %s for %d heads" % (tuple(X.shape), tuple(Z.shape), heads))
+    return _SDDMMHeads.apply(X, Z, heads, *meta)
+
+
+def edge_softmax_heads(S, row_pointers, beta=None):
+    """softmax of beta * S[h] over every CSR row, for every head h of S [heads, E]; beta: a one-element CONSTANT tensor (a scale such
+    as 1 / sqrt(F): it gets no gradient) or None = 1.  Head by head on the one-head operator, into one [heads, E] tensor."""
+    if S.dim() != 2:
+        raise RuntimeError("S must be [heads, E], got %s" % (tuple(S.shape),))
+    return _EdgeSoftmaxHeads.apply(S, row_pointers, beta)
 
 
 def sddmm(X, Z, meta):

@@ -45,12 +45,24 @@ def _heads_of_single(module):
     return forward_heads
 
 
+def _ef_heads_of_single(module):
+    """forward_ef_heads by its definition, forward_ef2 on each head's columns: what set_backend gives a stand-in that has no such call"""
+    def forward_ef_heads(X, Z, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, heads):
+        F = X.shape[1] // heads
+        return [torch.stack([module.forward_ef2(X[:, h * F:(h + 1) * F].contiguous(), Z[:, h * F:(h + 1) * F].contiguous(), nodePointer, edgeList,
+                                                blockPartition, edgeToColumn, edgeToRow)[0] for h in range(heads)])]
+    return forward_ef_heads
+
+
 def set_backend(module):
     """Install a stand-in for the TCGNN module (host tests: pure-torch or scipy objects).  One that has forward_AGNN but no
-    forward_heads is given the latter by its definition; the product's own backends (TCGNN, the binding) have the call."""
+    forward_heads, or forward_ef2 but no forward_ef_heads, is given the missing call by its definition; the product's own backends
+    (TCGNN, the binding) have both."""
     global _backend
     if module is not None and hasattr(module, "forward_AGNN") and not hasattr(module, "forward_heads"):
         module.forward_heads = _heads_of_single(module)
+    if module is not None and hasattr(module, "forward_ef2") and not hasattr(module, "forward_ef_heads"):
+        module.forward_ef_heads = _ef_heads_of_single(module)
     _backend = module
 
 
@@ -635,6 +647,69 @@ class GATConv(torch.nn.Module):
         Y = E.aggregate_heads(P, Z, meta)
         if not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
+        return Y + self.bias if self.bias is not None else Y
+
+
+class TransformerConv(torch.nn.Module):
+    """Not in the reference: multi-head dot-product attention after PyG's TransformerConv (DGL's DotGatConv), without edge features
+    and without the beta gate:
+        Q = X W_q + b_q,  K = X W_k + b_k,  V = X W_v + b_v   [N, heads * output_dim] each;
+        S[h, e] = <Q[row e, head h], K[col e, head h]>;   P[h] = softmax by row of S[h] / sqrt(output_dim);   Y_h = A_val(P[h]) V_h
+    (tcgnn_edge_ops.sddmm_heads - one multi-head SDDMM call -, edge_softmax_heads and aggregate_heads; gradients exact on any graph).
+    The heads are concatenated ([N, heads * output_dim]) or, with concat=False, averaged ([N, output_dim]); with root_weight X W_root is
+    added, then the output bias: a node without incoming edges gets the root term and the bias only.  bias=False drops b_q, b_k, b_v
+    and the output bias.  Glorot-uniform weights, zero biases.  No attention dropout."""
+
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, bias=True):
+        super().__init__()
+        if heads < 1:
+            raise ValueError("heads must be >= 1, got %r" % (heads,))
+        self.heads, self.output_dim, self.concat = int(heads), int(output_dim), bool(concat)
+        wide = self.heads * self.output_dim
+        out = wide if self.concat else self.output_dim
+        for name in ("q", "k", "v"):
+            setattr(self, "weights_" + name, torch.nn.Parameter(torch.empty(input_dim, wide)))
+            if bias:
+                setattr(self, "bias_" + name, torch.nn.Parameter(torch.zeros(wide)))
+            else:
+                self.register_parameter("bias_" + name, None)
+        if root_weight:
+            self.weights_root = torch.nn.Parameter(torch.empty(input_dim, out))
+        else:
+            self.register_parameter("weights_root", None)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(out))
+        else:
+            self.register_parameter("bias", None)
+        # (the softmax's scale: a constant of the layer, on its device - no tensor is made per step and it gets no gradient)
+        self.register_buffer("scale", torch.tensor([self.output_dim ** -0.5], dtype=torch.float32), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for p in (self.weights_q, self.weights_k, self.weights_v, self.weights_root):
+            if p is not None:
+                torch.nn.init.xavier_uniform_(p)
+        for b in (self.bias_q, self.bias_k, self.bias_v, self.bias):
+            if b is not None:
+                b.data.zero_()
+
+    def _project(self, X, W, b):
+        Y = dense_update(X, W)
+        return Y + b if b is not None else Y
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        Q = self._project(X, self.weights_q, self.bias_q)
+        K = self._project(X, self.weights_k, self.bias_k)
+        V = self._project(X, self.weights_v, self.bias_v)
+        S = E.sddmm_heads(Q, K, meta, self.heads)
+        P = E.edge_softmax_heads(S, row_pointers, self.scale.to(S.dtype))
+        Y = E.aggregate_heads(P, V, meta)
+        if not self.concat:
+            Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
+        if self.weights_root is not None:
+            Y = Y + dense_update(X, self.weights_root)
         return Y + self.bias if self.bias is not None else Y
 
 

@@ -9,8 +9,12 @@ Graphs: sbm_reddit, R-MAT at the Reddit shape, and an SBM graph at the ogbn-prod
                   B = 4 (N + 1) + 4 E + 8 N H + 4 H E
   aggregate       aggregate_heads (ONE multi-head edge-valued SpMM, forward; forward + backward) against ONE binary forward at width H F;
                   heads_walk names the kernel the multi-head call ran
-  epoch           a GAT epoch, 2 layers, hidden = H F
-    python tools/bench_gat.py [--epochs K] [--skip-epochs] [--graphs a,b] [--configs 8x8,4x32,2x64]"""
+  sddmm           forward_ef_heads (ONE multi-head SDDMM) against the loop it replaces - H forward_ef2 calls on contiguous copies of the
+                  heads' column blocks, stacked - and aggregate_heads' dP alone (backward with respect to the edge values only);
+                  sddmm_walk names the kernel the multi-head call ran.  (forward_ef_heads_ms is null on a tree from before the call
+                  existed: the tool is run on the parent commit's tree as well, for the A/B figures of DESIGN.md 4.11)
+  epoch           a GAT epoch and a TransformerConv epoch, 2 layers, hidden = H F
+    python tools/bench_gat.py [--epochs K] [--skip-epochs] [--skip-attention] [--graphs a,b] [--configs 8x8,4x32,2x64]"""
 import argparse
 import json
 import os
@@ -137,10 +141,38 @@ def aggregate_times(graph, n, meta, heads, feat, dev):
          aggregate_heads_forward_backward_ms=t_hb, binary_walk=walk_1, heads_walk=walk_h)
 
 
+def sddmm_times(graph, n, meta, heads, feat, dev):
+    E = meta[1].numel()
+    g = torch.Generator(device=dev).manual_seed(feat + 1)
+    X = torch.randn(n, heads * feat, device=dev, generator=g)
+    Z = torch.randn(n, heads * feat, device=dev, generator=g)
+    P = torch.rand(heads, E, device=dev, generator=g)
+
+    def per_head():
+        return torch.stack([TCGNN.forward_ef2(X[:, h * feat:(h + 1) * feat].contiguous(), Z[:, h * feat:(h + 1) * feat].contiguous(), *meta)[0] for h in range(heads)])
+    fused = getattr(TCGNN, "forward_ef_heads", None)
+    with torch.no_grad():
+        t_loop = median_ms(per_head)
+        walk_1 = TCGNN.last_kernel(*meta)
+        t_heads = median_ms(lambda: fused(X, Z, *meta, heads)) if fused else None
+        walk_h = TCGNN.last_kernel(*meta) if fused else None
+        diff = float((fused(X, Z, *meta, heads)[0] - per_head()).abs().max()) if fused else None
+
+    def dp_only():
+        p = P.detach().requires_grad_(True)
+        torch.autograd.grad(E_ops.aggregate_heads(p, Z, meta), (p,), X)
+    with torch.no_grad():
+        t_fwd = median_ms(lambda: E_ops.aggregate_heads(P, Z, meta), reps=10, warmup=3)
+    t_dp = median_ms(dp_only, reps=10, warmup=3) - t_fwd
+    emit(graph=graph, what="sddmm", heads=heads, features=feat, forward_ef_heads_ms=t_heads, per_head_forward_ef2_ms=t_loop, aggregate_heads_dP_ms=t_dp,
+         sddmm_walk=walk_h, per_head_walk=walk_1, max_abs_difference_from_the_per_head_loop=diff)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--skip-epochs", action="store_true")
+    ap.add_argument("--skip-attention", action="store_true", help="leave out the gat_softmax measurements and their torch compositions")
     ap.add_argument("--graphs", type=str, default="sbm_reddit,rmat_reddit,sbm_products")
     ap.add_argument("--configs", type=str, default=",".join("%dx%d" % c for c in CONFIGS), help="heads x features per head, e.g. 8x8,4x32,2x64")
     args = ap.parse_args()
@@ -155,16 +187,22 @@ def main():
         for heads, feat in [tuple(int(v) for v in c.split("x")) for c in args.configs.split(",")]:
             TCGNN.prepare([feat, heads * feat], *meta, transpose=True, edge_valued=True, attention=True)
             TCGNN.prepare([feat], *meta, transpose=True, edge_valued=True, heads=heads)
-            with torch.no_grad():
-                attention_times(graph, n, rp, col, heads, dev)
-            torch.cuda.empty_cache()
+            if not args.skip_attention:
+                with torch.no_grad():
+                    attention_times(graph, n, rp, col, heads, dev)
+                torch.cuda.empty_cache()
             aggregate_times(graph, n, meta, heads, feat, dev)
+            torch.cuda.empty_cache()
+            sddmm_times(graph, n, meta, heads, feat, dev)
             torch.cuda.empty_cache()
             if not args.skip_epochs:
                 x = torch.randn(n, in_dim, device=dev)
                 y = torch.randint(0, classes, (n,), device=dev)
                 r = H.time_training("gat", meta, x, y, in_dim, heads * feat, classes, 2, args.epochs, heads=heads)
-                emit(graph=graph, what="epoch", heads=heads, features=feat, hidden=heads * feat, train_ms=r["train_ms"], final_loss=r["final_loss"])
+                emit(graph=graph, what="epoch", model="gat", heads=heads, features=feat, hidden=heads * feat, train_ms=r["train_ms"], final_loss=r["final_loss"])
+                if hasattr(TCGNN, "forward_ef_heads"):
+                    r = H.time_training("transformer", meta, x, y, in_dim, heads * feat, classes, 2, args.epochs, heads=heads)
+                    emit(graph=graph, what="epoch", model="transformer", heads=heads, features=feat, hidden=heads * feat, train_ms=r["train_ms"], final_loss=r["final_loss"])
                 del x, y
                 torch.cuda.empty_cache()
         TCGNN.clear_plan_cache()
