@@ -57,10 +57,24 @@ static constexpr int agnn_wave_lds(int ks, bool bwd) {
 // MAXW = 0: one workgroup per window, each wavefront a contiguous quarter of its tiles.
 // MAXW > 0: persistent wavefronts that own MAXW windows (accumulators in registers) and walk the column
 //           ranges in step, as spmm_blocked_kernel does, so the gathered rows stay L2-resident.
-template <int NT, int WAVES, bool BWD, int MAXW>
+static constexpr int kAgnnMaxW = 2;   // windows owned by a wavefront of the range-major fused kernel
 // (the backward pass of the range-major walk beyond 96 columns - taken on request only, tcgnn_set_spmm_mode(2) - needs more than the 256
 //  registers two wavefronts per SIMD leave once the per-row exponents are live: one wavefront per SIMD there)
-__global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 3 : ((BWD && MAXW > 1 && NT > 6) ? 1 : 2))) void agnn_kernel(const AgnnArgs a) {
+static constexpr LaunchGeom agnn_geom(int nt, int waves, bool bwd, int maxw) {
+    return {waves * 64, waves * agnn_wave_lds((nt + 1) / 2, bwd), nt <= 4 ? 3 : ((bwd && maxw > 1 && nt > 6) ? 1 : 2), maxw};
+}
+// EXCEPTION kept from before the geometry was stated once: a forced range-major backward pass beyond 96 columns sizes its persistent
+// grid for TWO workgroups per CU although its launch bound lets one be resident (material for a performance issue, not measured)
+static constexpr int agnn_range_major_wgs_per_cu(int nt, bool bwd) {
+    return (bwd && nt > 6) ? 2 : agnn_geom(nt, 4, bwd, kAgnnMaxW).wgs_per_cu();
+}
+// (pinned: resident four-wavefront workgroups per CU at 1 .. 8 tiles of width, as the persistent grids are sized)
+static_assert(widths_give([](int nt) { return agnn_range_major_wgs_per_cu(nt, false); }, {3, 3, 3, 3, 2, 2, 2, 2}), "agnn_kernel range-major, forward");
+static_assert(widths_give([](int nt) { return agnn_range_major_wgs_per_cu(nt, true); }, {3, 3, 3, 3, 2, 2, 2, 2}), "agnn_kernel range-major, backward");
+static_assert(widths_give([](int nt) { return agnn_geom(nt, 4, false, kAgnnMaxW).wgs_per_cu(); }, {3, 3, 3, 3, 2, 2, 2, 2}), "agnn_kernel slice-synchronised, forward");
+static_assert(widths_give([](int nt) { return agnn_geom(nt, 4, true, nt > 6 ? 1 : kAgnnMaxW).wgs_per_cu(); }, {3, 3, 3, 3, 2, 2, 2, 2}), "agnn_kernel slice-synchronised, backward");
+template <int NT, int WAVES, bool BWD, int MAXW>
+__global__ __launch_bounds__(agnn_geom(NT, WAVES, BWD, MAXW).threads, agnn_geom(NT, WAVES, BWD, MAXW).waves_per_simd) void agnn_kernel(const AgnnArgs a) {
     const bool valonly = BWD && a.valonly != 0;   // (kernel-uniform)
     if (valonly ? range_is_wide_val(a.hdr) : wide2_dense(a.hdr)) return;   // (range guard: the fp32 fallback launched behind this kernel does the work; a few dirty rows: wide_patch_kernel)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -640,4 +654,16 @@ __global__ __launch_bounds__(kReduceThreads) void agnn_reduce_kernel(const doubl
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = (float)(sh[0] + (extra ? extra[0] : 0.0));   // (extra: wide_patch_kernel's correction, the double at header word kHdrDwExtra; zero unless the call was patched)
+}
+
+template <int WAVES, bool BWD, int MAXW>
+static hipError_t launch_agnn(int nt, const AgnnArgs& args, int nwg, hipStream_t stream) {
+    return with_width<8>(nt, [&](auto NT) { return launch_kernel<agnn_kernel<NT, WAVES, BWD, MAXW>>(dim3((unsigned)nwg), agnn_geom(NT, WAVES, BWD, MAXW), stream, args); });
+}
+// the fused backward kernel beyond 96 columns on the slice-synchronised walk: one window per wavefront (MAXW = 1)
+static hipError_t launch_agnn_wide_one(int nt, const AgnnArgs& args, int nwg, hipStream_t stream) {
+    const dim3 grid((unsigned)nwg);
+    if (nt == 7) return launch_kernel<agnn_kernel<7, 4, true, 1>>(grid, agnn_geom(7, 4, true, 1), stream, args);
+    if (nt == 8) return launch_kernel<agnn_kernel<8, 4, true, 1>>(grid, agnn_geom(8, 4, true, 1), stream, args);
+    return hipErrorInvalidValue;
 }

@@ -28,22 +28,25 @@
 //   partial accumulators of the wavefronts are summed through LDS in a fixed order.
 //
 // File map (r04: one translation unit - the kernels are templates their launchers instantiate - cut by operator; in include order):
-//   tcgnn_device.hip          HIP_TRY, DevBuf (owner of one device allocation), struct tcgnn_plan, KernelTimer, device helpers, launch tables, switches
-//                             and walk predicates, sync_chosen; behind the includes the C ABI of the operators
+//   tcgnn_device.hip          HIP_TRY, DevBuf (owner of one device allocation), struct tcgnn_plan, KernelTimer, device helpers, switches
+//                             and walk predicates, sync_chosen; behind the includes the C ABI of the operators.  It launches nothing
+//   tcgnn_launch.inc          what the launch tables beside the kernels (*_geom, launch_*) share: LaunchGeom, with_width, launch_kernel, launch_plain_or_twin
 //   tcgnn_stage.inc           the staging pass, device and host: the header's words by name, the range guard's rule, abs-max kernels and every
 //                             fp16 converter (row-major, planar, slice), image and workspace sizes, Guard, fill_header, one converter launcher
 //                             per layout, the one-pass staging of the planar image (stage_fused_kernel + stage_settle_kernel), stage_features;
 //                             the C ABI of the caller-staged images, tcgnn_range_mode and tcgnn_plan_stage_stats
 //   tcgnn_pack.inc            plan-time kernels (fill, longest row, locality, pack)
-//   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc)
-//   tcgnn_heads.inc           multi-head edge-valued SpMM: HeadsWalker (TileWalker with one A fragment per head), spmm_heads_kernel, spmm_heads_csr_kernel
-//   tcgnn_sync_walk.inc       slice-synchronised range walk: SyncArgs, spmm_sync_kernel's two forms from tcgnn_sync_kernel.inc, table kernels
+//   tcgnn_gather_spmm.inc     TileWalker, spmm_kernel; spmm_blocked_kernel's two forms from tcgnn_blocked_kernel.inc (+ generated tcgnn_lds_blocks.inc);
+//                             launch_spmm_*, launch_blocked_*
+//   tcgnn_heads.inc           multi-head edge-valued SpMM: HeadsWalker (TileWalker with one A fragment per head), spmm_heads_kernel, spmm_heads_csr_kernel;
+//                             launch_heads_* (included behind tcgnn_small_fallback.inc)
+//   tcgnn_sync_walk.inc       slice-synchronised range walk: SyncArgs, spmm_sync_kernel's two forms from tcgnn_sync_kernel.inc, launch_sync_*, table kernels
 //   tcgnn_small_spmm.inc      spmm_small_kernel (single launch, fp32 MFMA on fp32 X; also the binary SpMM's range-guard fallback)
 //   tcgnn_lds_spmm.inc        LDS-resident SpMM, ordinary cell stream; cell-stream build kernels
 //   tcgnn_lds_flat.inc        LDS-resident SpMM, flat cell stream (the headline kernel; its forms from tcgnn_lds_flat_kernel.inc)
 //   tcgnn_lds_val.inc         LDS-resident edge-valued SpMM (single-edge stream, per-call slot values)
-//   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel (one and two operands), sddmm2_csr_kernel
-//   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction
+//   tcgnn_sddmm.inc           sddmm_kernel, sddmm_wide_kernel (one and two operands), sddmm2_csr_kernel; launch_sddmm_*
+//   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction; launch_agnn*
 //   tcgnn_small_fallback.inc  CSR kernels of non-canonical plans, the range guard's fallbacks, symmetry_kernel, wide_patch_kernel
 //   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
@@ -284,6 +287,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
     return __builtin_bit_cast(half4, v);
 }
 
+#include "tcgnn_launch.inc"
 #include "tcgnn_stage.inc"
 #include "tcgnn_pack.inc"
 
@@ -308,193 +312,6 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_edge_softmax.inc"
 #include "tcgnn_gat.inc"
 #include "tcgnn_segment_max.inc"
-
-// ------------------------------------------------------------------------------------------
-// launch tables
-// ------------------------------------------------------------------------------------------
-template <int NT, int WAVES, bool VAL>
-static hipError_t launch_spmm_one(const SpmmArgs& args, int nwin, int nchunks, hipStream_t stream, const Epi& epi) {
-    const size_t lds = (size_t)WAVES * TileWalker<NT, VAL>::WAVE_LDS + 4096;
-    if constexpr (!VAL) {   // (tcgnn_spmm_scaled's row scale / bias: the kernel with the epilogue)
-        if (epi.rs || epi.bias) {
-            hipLaunchKernelGGL((spmm_epi_kernel<NT, WAVES>), dim3((unsigned)nwin, (unsigned)nchunks), dim3(WAVES * 64), lds, stream, SpmmEpiArgs{args, epi});
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((spmm_kernel<NT, WAVES, VAL>), dim3((unsigned)nwin, (unsigned)nchunks), dim3(WAVES * 64), lds, stream, args);
-    return hipGetLastError();
-}
-
-template <int WAVES, bool VAL>
-static hipError_t launch_spmm_nt(int nt, const SpmmArgs& args, int nwin, int nchunks, hipStream_t stream, const Epi& epi) {
-    switch (nt) {
-        case 1: return launch_spmm_one<1, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 2: return launch_spmm_one<2, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 3: return launch_spmm_one<3, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 4: return launch_spmm_one<4, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 5: return launch_spmm_one<5, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 6: return launch_spmm_one<6, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 7: return launch_spmm_one<7, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        case 8: return launch_spmm_one<8, WAVES, VAL>(args, nwin, nchunks, stream, epi);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-static hipError_t launch_spmm_any(bool val, int waves, int nt, const SpmmArgs& args, int nwin, int nchunks, hipStream_t stream,
-                                  const Epi& epi = Epi{nullptr, nullptr}) {
-    if (waves == 4) return val ? launch_spmm_nt<4, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_nt<4, false>(nt, args, nwin, nchunks, stream, epi);
-    return val ? launch_spmm_nt<1, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_nt<1, false>(nt, args, nwin, nchunks, stream, epi);
-}
-
-// spmm_heads_kernel: G whole heads of 8 FB columns per pass - the shapes heads_per_pass (tcgnn_spmm_dispatch.inc) forms, full passes and remainders
-template <int G, int FB>
-static hipError_t launch_heads_one(const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
-    const size_t lds = (size_t)waves * HeadsWalker<G, FB>::WAVE_LDS;
-    static bool attr_set = false;   // (four wavefronts of a 4 x 16 pass hold 65 KB)
-    if (!attr_set) {
-        const hipError_t e = hipFuncSetAttribute((const void*)spmm_heads_kernel<G, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * HeadsWalker<G, FB>::WAVE_LDS);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((spmm_heads_kernel<G, FB>), dim3((unsigned)nwin, (unsigned)npass), dim3((unsigned)waves * 64), lds, stream, args);
-    return hipGetLastError();
-}
-static hipError_t launch_heads_any(int g, int fb, const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
-#define TCGNN_HEADS_CASE(G, FB) case (G) * 100 + (FB): return launch_heads_one<G, FB>(args, waves, nwin, npass, stream)
-    switch (g * 100 + fb) {
-        TCGNN_HEADS_CASE(1, 1); TCGNN_HEADS_CASE(2, 1); TCGNN_HEADS_CASE(3, 1); TCGNN_HEADS_CASE(4, 1);   // F = 8
-        TCGNN_HEADS_CASE(1, 2); TCGNN_HEADS_CASE(2, 2); TCGNN_HEADS_CASE(3, 2); TCGNN_HEADS_CASE(4, 2);   // F = 16
-        TCGNN_HEADS_CASE(1, 3); TCGNN_HEADS_CASE(2, 3);                                                   // F = 24
-        TCGNN_HEADS_CASE(1, 4); TCGNN_HEADS_CASE(2, 4);                                                   // F = 32
-        default: return hipErrorInvalidValue;
-    }
-#undef TCGNN_HEADS_CASE
-}
-
-// workgroups of a persistent grid resident on one CU: what its 160 KB of LDS hold, at most what the kernel's registers allow, at least one
-static constexpr int wgs_per_cu(int lds_per_wg, int by_regs) { return std::max(1, std::min(by_regs, (160 * 1024) / lds_per_wg)); }
-// windows owned by one wavefront of the range-blocked kernel (accumulators: MAXW * NT * 4 registers)
-static constexpr int blocked_maxw(int nt, bool val) { return (nt <= 4 && !val) ? 4 : 2; }
-
-template <int NT, bool VAL>
-static hipError_t launch_blocked_one(const SpmmBlockedArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
-    constexpr int MAXW = blocked_maxw(NT, VAL);
-    const size_t lds = (size_t)4 * TileWalker<NT, VAL>::WAVE_LDS + 4096;
-    if constexpr (!VAL) {   // (tcgnn_spmm_scaled's row scale / bias: the kernel with the epilogue)
-        if (epi.rs || epi.bias) {
-            hipLaunchKernelGGL((spmm_blocked_epi_kernel<NT, MAXW, false>), dim3((unsigned)nwg, (unsigned)nchunks), dim3(256), lds, stream, SpmmBlockedEpiArgs{args, epi});
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((spmm_blocked_kernel<NT, MAXW, VAL>), dim3((unsigned)nwg, (unsigned)nchunks), dim3(256), lds, stream, args);
-    return hipGetLastError();
-}
-
-static hipError_t launch_blocked_any(bool val, int nt, const SpmmBlockedArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
-#define TCGNN_BLK_CASE(n) case n: return val ? launch_blocked_one<n, true>(args, nwg, nchunks, stream, epi) : launch_blocked_one<n, false>(args, nwg, nchunks, stream, epi);
-    switch (nt) {
-        TCGNN_BLK_CASE(1) TCGNN_BLK_CASE(2) TCGNN_BLK_CASE(3) TCGNN_BLK_CASE(4)
-        TCGNN_BLK_CASE(5) TCGNN_BLK_CASE(6) TCGNN_BLK_CASE(7) TCGNN_BLK_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef TCGNN_BLK_CASE
-}
-
-// windows owned by one wavefront of the slice-synchronised walk, and its tile buffers.  Up to 64 columns: 4 windows, two buffers, 16 wavefronts
-// per CU (the grid is cut to what holds a slice).  Beyond: ONE 8 KB buffer per wavefront and 2 windows (64 accumulator registers of 168; three
-// spill 34-44 words at 128 columns), so that twelve wavefronts fit a CU instead of eight - 768 windows per XCD in flight: the slice (kSyncSlice).
-// (r06, later: the single-buffer kernels walk their runs as ONE pipeline - TileWalker::walk_list - whose three list cursors do not fit the
-//  168 registers of twelve wavefronts at 7-8 tiles of width: eight wavefronts of 3 windows, 256 registers - 768 windows per XCD again)
-static constexpr int sync_nbuf(int nt, bool val) { return nt <= 2 ? 2 : 1; }
-static constexpr int sync_maxw(int nt, bool val) { return 2; }
-static constexpr int sync_wgs_per_cu(int nt, bool val) {
-    return wgs_per_cu(4 * (sync_nbuf(nt, val) * nt * 1024 + kPadBytes + (val ? 2048 : 0) + (sync_nbuf(nt, val) == 1 ? 2048 : 0)) + 4096, nt <= 4 ? 4 : 2);
-}
-template <int NT, bool VAL>
-static hipError_t launch_sync_one(const SpmmSyncArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
-    constexpr int MAXW = sync_maxw(NT, VAL), NBUF = sync_nbuf(NT, VAL);
-    const size_t lds = (size_t)4 * TileWalker<NT, VAL, NBUF>::WAVE_LDS + 4096;
-    if constexpr (!VAL) {
-        if (epi.rs || epi.bias) {
-            hipLaunchKernelGGL((spmm_sync_epi_kernel<NT, MAXW, false, NBUF>), dim3((unsigned)nwg, (unsigned)nchunks), dim3(256), lds, stream, SpmmSyncEpiArgs{args, epi});
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((spmm_sync_kernel<NT, MAXW, VAL, NBUF>), dim3((unsigned)nwg, (unsigned)nchunks), dim3(256), lds, stream, args);
-    return hipGetLastError();
-}
-static hipError_t launch_sync_any(bool val, int nt, const SpmmSyncArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
-#define TCGNN_SYNC_CASE(n) case n: return val ? launch_sync_one<n, true>(args, nwg, nchunks, stream, epi) : launch_sync_one<n, false>(args, nwg, nchunks, stream, epi);
-    switch (nt) {
-        TCGNN_SYNC_CASE(1) TCGNN_SYNC_CASE(2) TCGNN_SYNC_CASE(3) TCGNN_SYNC_CASE(4)
-        TCGNN_SYNC_CASE(5) TCGNN_SYNC_CASE(6) TCGNN_SYNC_CASE(7) TCGNN_SYNC_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef TCGNN_SYNC_CASE
-}
-
-template <int WAVES, bool BLOCKED, bool TWO>
-static hipError_t launch_sddmm_two(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
-    const dim3 grid((unsigned)nwg), block(WAVES * 64);
-    const size_t lds = (size_t)WAVES * sddmm_wave_lds(ks <= 4 ? ks : 1);
-    switch (ks) {
-        case 1: hipLaunchKernelGGL((sddmm_kernel<1, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
-        case 2: hipLaunchKernelGGL((sddmm_kernel<2, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
-        case 3: hipLaunchKernelGGL((sddmm_kernel<3, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
-        case 4: hipLaunchKernelGGL((sddmm_kernel<4, WAVES, BLOCKED, TWO>), grid, block, lds, stream, args); break;
-        default: hipLaunchKernelGGL((sddmm_wide_kernel<WAVES, TWO>), grid, block, 0, stream, args); break;
-    }
-    return hipGetLastError();
-}
-// (args.xa16 set: tcgnn_sddmm2's instantiations, the window operand from its own image)
-template <int WAVES, bool BLOCKED>
-static hipError_t launch_sddmm_ks(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
-    return args.xa16 ? launch_sddmm_two<WAVES, BLOCKED, true>(ks, args, nwg, stream) : launch_sddmm_two<WAVES, BLOCKED, false>(ks, args, nwg, stream);
-}
-
-// tcgnn_sddmm_heads: npass passes (grid.y) of g heads of hf columns each, from args.head0 on.  The instantiated (hf, g): every pass
-// sddmm_heads_passes forms - hf = 8, 16, 32 with 2, 3 or 4 heads, hf = 64 with 2
-template <int WAVES, bool BLOCKED>
-static hipError_t launch_sddmm_heads(int hf, int g, const SddmmArgs& args, int nwg, int npass, hipStream_t stream) {
-    const dim3 grid((unsigned)nwg, (unsigned)npass), block(WAVES * 64);
-#define TCGNN_SDDMM_HEADS_CASE(f, n)                                                                                                                  \
-    if (hf == f && g == n) {                                                                                                                          \
-        hipLaunchKernelGGL((sddmm_kernel<sddmm_heads_ks(f, n), WAVES, BLOCKED, true, f, n>), grid, block, (size_t)WAVES * sddmm_heads_wave_lds(f, n), \
-                           stream, args);                                                                                                             \
-        return hipGetLastError();                                                                                                                     \
-    }
-    TCGNN_SDDMM_HEADS_CASE(8, 2) TCGNN_SDDMM_HEADS_CASE(8, 3) TCGNN_SDDMM_HEADS_CASE(8, 4)
-    TCGNN_SDDMM_HEADS_CASE(16, 2) TCGNN_SDDMM_HEADS_CASE(16, 3) TCGNN_SDDMM_HEADS_CASE(16, 4)
-    TCGNN_SDDMM_HEADS_CASE(32, 2) TCGNN_SDDMM_HEADS_CASE(32, 3) TCGNN_SDDMM_HEADS_CASE(32, 4)
-    TCGNN_SDDMM_HEADS_CASE(64, 2)
-#undef TCGNN_SDDMM_HEADS_CASE
-    return hipErrorInvalidValue;
-}
-
-static constexpr int kAgnnMaxW = 2;   // windows owned by a wavefront of the range-major fused kernel
-template <int WAVES, bool BWD, int MAXW>
-static hipError_t launch_agnn(int nt, const AgnnArgs& args, int nwg, hipStream_t stream) {
-    const dim3 grid((unsigned)nwg), block(WAVES * 64);
-    const size_t lds = (size_t)WAVES * agnn_wave_lds((nt + 1) / 2, BWD);
-#define TCGNN_AGNN_CASE(n) case n: hipLaunchKernelGGL((agnn_kernel<n, WAVES, BWD, MAXW>), grid, block, lds, stream, args); break;
-    switch (nt) {
-        TCGNN_AGNN_CASE(1) TCGNN_AGNN_CASE(2) TCGNN_AGNN_CASE(3) TCGNN_AGNN_CASE(4)
-        TCGNN_AGNN_CASE(5) TCGNN_AGNN_CASE(6) TCGNN_AGNN_CASE(7) TCGNN_AGNN_CASE(8)
-        default: return hipErrorInvalidValue;
-    }
-#undef TCGNN_AGNN_CASE
-    return hipGetLastError();
-}
-
-// the fused backward kernel beyond 96 columns on the slice-synchronised walk: one window per wavefront (MAXW = 1)
-static hipError_t launch_agnn_wide_one(int nt, const AgnnArgs& args, int nwg, hipStream_t stream) {
-    const dim3 grid((unsigned)nwg), block(256);
-    const size_t lds = (size_t)4 * agnn_wave_lds((nt + 1) / 2, true);
-    if (nt == 7) hipLaunchKernelGGL((agnn_kernel<7, 4, true, 1>), grid, block, lds, stream, args);
-    else if (nt == 8) hipLaunchKernelGGL((agnn_kernel<8, 4, true, 1>), grid, block, lds, stream, args);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-}
 
 // ---- run-time switches.  Product: TCGNN_SPMM_MODE / TCGNN_RANGE_GUARD (initial values of tcgnn_set_spmm_mode / tcgnn_set_range_guard,
 // include/tcgnn.h) and TCGNN_VERBOSE (plan statistics on stderr).  TEST AIDS, read through test_knob() only - tests/ forces every walk

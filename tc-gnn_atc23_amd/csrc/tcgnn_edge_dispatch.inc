@@ -3,9 +3,8 @@
 // (route_sddmm / route_agnn: plan facts, mode, width and the per-call test knobs), one launcher per walk, the range guard's tail, run_*.
 // Included by tcgnn_device.hip in front of tcgnn_spmm_dispatch.inc: tcgnn_spmm_val's XCD-sliced walk asks agnn_plan_walk and runs
 // launch_val_sliced, and tcgnn_workspace_bytes sizes the slice addends with agnn_slices - one predicate, one AgnnArgs builder for all.
-// (The fused pair comes first and launch_val_sliced is its first launcher only so that `make audit`'s listing could be compared line by
-//  line with the one before this file existed: template kernels are listed in the order their launch tables are first used.  Nothing
-//  else depends on the order - move the sections freely, the listing then holds the same kernels in another order.)
+// (Nothing depends on the order of the sections: `make audit`'s listing names template kernels in the order their launch tables are
+//  first used, and tools/compare_listings.py compares two listings kernel by kernel, whatever their order.)
 
 // wide_patch_kernel's arguments that both operators take from the plan.  The kernel's row-driven branch is a shortcut of its scan with
 // the same scores bit for bit: TCGNN_PATCH_ROWS=0, read per call, hands it no symmetry word, so the same input takes the scan (tests
@@ -15,6 +14,14 @@ static const int32_t* patch_sym_of(const tcgnn_plan* plan) {
     return env && atoi(env) == 0 ? nullptr : plan->d_sym;
 }
 static int32_t patch_rows_of(const tcgnn_plan* plan) { return (int32_t)std::min<int64_t>(plan->N, (int64_t)plan->nw_eff * kWinRows); }
+// wide_patch_kernel's arguments for an SDDMM call (mode 0); the fused pair adds w, Y, efmax, dw_extra and its mode.  What is not named is zero
+static PatchArgs patch_args(const tcgnn_plan* plan, const StagedImage& im, const float* d_X, float* d_ef, int32_t D, void* ws) {
+    PatchArgs pa{};
+    pa.hdr = im.hdr; pa.bitmap = dirty_bitmap_of(ws, plan->Nc, D); pa.rowptr = plan->rowptr; pa.col = plan->col; pa.e2r = plan->e2r;
+    pa.X = d_X; pa.x16 = im.x16; pa.pitch = im.pitch; pa.ef = d_ef;
+    pa.N = plan->N; pa.Nc = plan->Nc; pa.D = D; pa.row_off = plan->row_off; pa.E = plan->E; pa.sym = patch_sym_of(plan); pa.rows = patch_rows_of(plan);
+    return pa;
+}
 
 // ------------------------------------------------------------------------------------------
 // the fused AGNN pair
@@ -150,7 +157,7 @@ static hipError_t launch_agnn_sync(const AgnnCall& c, const AgnnRoute& r, AgnnAr
     a.use_sync = 1;
     a.sync = sync_args(plan, a.stride * 2);
     const int mw = r.sync_one ? 1 : kAgnnMaxW;
-    const int per_launch = kXcds * std::max(1, std::min((plan->sync.S + 4 * mw - 1) / (4 * mw), plan->num_cus / kXcds * wgs_per_cu(4 * agnn_wave_lds((nt + 1) / 2, c.bwd), nt <= 4 ? 3 : 2)));
+    const int per_launch = kXcds * std::max(1, std::min((plan->sync.S + 4 * mw - 1) / (4 * mw), plan->num_cus / kXcds * agnn_geom(nt, 4, c.bwd, mw).wgs_per_cu()));
     double* const partial = a.partial;
     hipError_t e = hipSuccess;
     for (int q = 0; q < plan->sync.R && e == hipSuccess; ++q) {
@@ -183,7 +190,7 @@ static hipError_t launch_agnn_range_major(const AgnnCall& c, AgnnArgs a, int* ns
     a.nranges = range_count(plan, image_bytes(plan, a.stride), 4 * kRangeTargetBytes);
     a.gsel = plan->nbuckets / a.nranges;
     a.ngroups = (plan->nw_eff + kAgnnMaxW - 1) / kAgnnMaxW;
-    *nslots = std::min((a.ngroups + 3) / 4, plan->num_cus * wgs_per_cu(4 * agnn_wave_lds((nt + 1) / 2, c.bwd), nt <= 4 ? 3 : 2));
+    *nslots = std::min((a.ngroups + 3) / 4, plan->num_cus * agnn_range_major_wgs_per_cu(nt, c.bwd));
     return c.bwd ? launch_agnn<4, true, kAgnnMaxW>(nt, a, *nslots, c.stream) : launch_agnn<4, false, kAgnnMaxW>(nt, a, *nslots, c.stream);
 }
 static hipError_t launch_agnn_per_window(const AgnnCall& c, const AgnnArgs& a, int* nslots) {
@@ -239,7 +246,8 @@ static int run_agnn(const AgnnCall& c) {
     const int guard_level = range_guard_of(plan);
     if (guard_level >= 2) {
         // a few dirty rows (what training produces): the MFMA kernel above ran, the edges that touch them are recomputed here
-        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, c.d_w, c.d_Y, c.d_absmax, dw_extra, plan->N, plan->Nc, D, plan->row_off, bwd ? 2 : 1, plan->E, patch_sym_of(plan), patch_rows_of(plan)};
+        PatchArgs pa = patch_args(plan, im, c.d_X, c.d_ef, D, c.ws);
+        pa.w = c.d_w; pa.Y = c.d_Y; pa.efmax = c.d_absmax; pa.dw_extra = dw_extra; pa.mode = bwd ? 2 : 1;
         // (many: the same launch does all the work in plain fp32 - wide_dense_body; one launch per call either way, returning at once
         //  unless the staged matrix is "wide")
         HIP_TRY(launch_wide_patch(pa, stream, partial, nslots));
@@ -275,7 +283,7 @@ struct SddmmRoute { SddmmWalk walk = SddmmWalk::kPerWindow; int nranges = 0, xcd
 // persistent grid of the range-major walk: what is resident at once, at most one wavefront per (range, window) item
 static int sddmm_range_major_wgs(const tcgnn_plan* plan, int ks, int nranges) {
     const int64_t items = (int64_t)nranges * plan->nw_eff;
-    return (int)std::min<int64_t>((items + 3) / 4, (int64_t)plan->num_cus * wgs_per_cu(4 * sddmm_wave_lds(ks), 4));
+    return (int)std::min<int64_t>((items + 3) / 4, (int64_t)plan->num_cus * sddmm_geom(ks, 4).wgs_per_cu());
 }
 // The passes of the fused multi-head walk: H heads in ceil(H / kSddmmMaxHeadsPerPass) passes of at most 128 columns, as even as they
 // come - `nbig` passes of g + 1 heads, then the others of g (5 = 3 + 2, 7 = 4 + 3, 8 = 4 + 4) - so that no pass is a single head.
@@ -286,11 +294,10 @@ static SddmmHeadsPasses sddmm_heads_passes(int H, int F) {
     p.n = (H + gmax - 1) / gmax; p.g = H / p.n; p.nbig = H % p.n;
     return p;
 }
-// resident workgroups per CU of a fused pass: LDS, and the registers its launch bound leaves (three wavefronts a SIMD at one K-step, else two)
-static int sddmm_heads_wgs_per_cu(int F, int g) { return wgs_per_cu(4 * sddmm_heads_wave_lds(F, g), sddmm_heads_ks(F, g) <= 1 ? 3 : 2); }
-static int sddmm_heads_wgs_per_cu(const SddmmCall& c) {   // (of the call's widest pass; passes share the CUs - grid.y)
+// resident workgroups per CU of a fused call: those of its widest pass (sddmm_heads_geom); the passes share the CUs - grid.y
+static int sddmm_heads_wgs_per_cu(const SddmmCall& c) {
     const SddmmHeadsPasses p = sddmm_heads_passes(c.H, c.F);
-    return std::max(1, sddmm_heads_wgs_per_cu(c.F, p.nbig ? p.g + 1 : p.g) / p.n);
+    return std::max(1, sddmm_heads_geom(c.F, p.nbig ? p.g + 1 : p.g, 4).wgs_per_cu() / p.n);
 }
 // launch every pass of a fused call on `nwg` workgroups each: the passes of g + 1 heads in one launch, those of g in another
 template <int WAVES, bool BLOCKED>
@@ -359,7 +366,7 @@ static hipError_t launch_sddmm_sync(const SddmmCall& c, SddmmArgs a) {
     KernelTimer timer(plan, c.stream, c.H ? "sddmm_heads_kernel (slice-synchronised)" : "sddmm_kernel (slice-synchronised)");
     a.use_sync = 1;
     a.sync = sync_args(plan, a.stride * 2);
-    const int per_cu = c.H ? sddmm_heads_wgs_per_cu(c) : wgs_per_cu(4 * sddmm_wave_lds(ks), ks <= 2 ? 4 : 3);
+    const int per_cu = c.H ? sddmm_heads_wgs_per_cu(c) : sddmm_geom(ks, 4).wgs_per_cu();
     const int nwg = kXcds * std::max(1, std::min((plan->sync.S + 3) / 4, plan->num_cus / kXcds * per_cu));
     hipError_t e = hipSuccess;
     for (int r = 0; r < plan->sync.R && e == hipSuccess; ++r) {
@@ -404,8 +411,7 @@ static int launch_sddmm_guard_tail(const SddmmCall& c, const StagedImage& im, co
         hipLaunchKernelGGL(sddmm2_csr_kernel, dim3((unsigned)std::min((rows + 3) / 4, 2048)), dim3(256), 0, c.stream, imw.hdr, im.hdr, plan->rowptr, plan->col, c.d_Xw, c.d_X, c.d_ef,
                            rows, c.D, plan->row_off);
     } else if (range_guard_of(plan) >= 2) {   // a few dirty rows: the patch behind the MFMA kernel; many: the CSR fallback (each returns at once otherwise)
-        const PatchArgs pa{im.hdr, dirty_bitmap_of(c.ws, plan->Nc, c.D), plan->rowptr, plan->col, plan->e2r, c.d_X, im.x16, im.pitch, c.d_ef, nullptr, nullptr, nullptr, nullptr, plan->N, plan->Nc, c.D, plan->row_off, 0, plan->E, patch_sym_of(plan), patch_rows_of(plan)};
-        HIP_TRY(launch_wide_patch(pa, c.stream));
+        HIP_TRY(launch_wide_patch(patch_args(plan, im, c.d_X, c.d_ef, c.D, c.ws), c.stream));
     }
     HIP_TRY(hipGetLastError());
     return TCGNN_OK;

@@ -168,12 +168,14 @@ __device__ __forceinline__ void lds_read8_b32(const uint32_t (&ad)[8], uint32_t 
 // columns): ONE buffer per wavefront - the B fragments of tile t are read into registers, then the gather of t+1 is issued into the same
 // buffer and flies under the MFMAs.  Half the LDS per wavefront: twelve wavefronts per CU instead of eight where the tile is 8 KB, and
 // what a CU has in flight is what this walk is bound by (PMC: wavefronts parked on the gather 64 % of their cycles at 74 % L2 hits).
+// LDS of one TileWalker wavefront: tile buffer(s), metadata pad, edge values (2 x 4 per lane), and with ONE buffer the run list of walk_list
+static constexpr int kTileMaxRuns = 128;
+static constexpr int tile_wave_lds(int nt, bool val, int nbuf) { return nbuf * nt * 1024 + kPadBytes + (val ? 2048 : 0) + (nbuf == 1 ? kTileMaxRuns * 16 : 0); }
 template <int NT, bool VAL, int NBUF = 2>
 struct TileWalker {
     static constexpr int TILE_BYTES = NT * 1024;
-    // (NBUF = 1 also carries a RUN LIST per wavefront: walk_list below)
-    static constexpr int kMaxRuns = 128, kRunListBytes = NBUF == 1 ? kMaxRuns * 16 : 0;
-    static constexpr int WAVE_LDS = NBUF * TILE_BYTES + kPadBytes + (VAL ? 2048 : 0) + kRunListBytes;  // tile buffer(s), metadata pad, edge values (2 x 4 per lane), run list
+    static constexpr int kMaxRuns = kTileMaxRuns;
+    static constexpr int WAVE_LDS = tile_wave_lds(NT, VAL, NBUF);
     static constexpr int NIDS = NT + 1 + (VAL ? 1 : 0);
     using Img = TileImage<NT>;
     const SpmmArgs& a;
@@ -467,6 +469,8 @@ struct TileWalker {
 // (second launch-bound argument = waves per SIMD: keeps the register budget at 128 / 256 so the
 // accumulators are allocated as VGPRs - with the default budget hipcc split them into AGPRs and
 // spent 24 v_accvgpr_* moves per tile shuffling them)
+// spmm_kernel's launch geometry: one workgroup of `waves` wavefronts per window; behind the wavefronts' LDS the 4 KB A table
+static constexpr LaunchGeom spmm_geom(int nt, int waves, bool val) { return {waves * 64, waves * tile_wave_lds(nt, val, 2) + 4096, nt <= 4 ? 4 : 2, 0}; }
 // EPI: tcgnn_spmm_scaled's row scale / bias in the final store - kernels of their own (spmm_epi_kernel), so that the plain ones
 // keep their code and registers
 template <int NT, int WAVES, bool VAL, bool EPI>
@@ -581,10 +585,25 @@ __device__ __forceinline__ void spmm_body(const SpmmArgs& a, const Epi& epi) {
     }
 }
 template <int NT, int WAVES, bool VAL>
-__global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 4 : 2)) void spmm_kernel(const SpmmArgs a) { spmm_body<NT, WAVES, VAL, false>(a, Epi{nullptr, nullptr}); }
+__global__ __launch_bounds__(spmm_geom(NT, WAVES, VAL).threads, spmm_geom(NT, WAVES, VAL).waves_per_simd) void spmm_kernel(const SpmmArgs a) { spmm_body<NT, WAVES, VAL, false>(a, Epi{nullptr, nullptr}); }
 struct SpmmEpiArgs { SpmmArgs a; Epi epi; };
 template <int NT, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, (NT <= 4 ? 4 : 2)) void spmm_epi_kernel(const SpmmEpiArgs e) { spmm_body<NT, WAVES, false, true>(e.a, e.epi); }
+__global__ __launch_bounds__(spmm_geom(NT, WAVES, false).threads, spmm_geom(NT, WAVES, false).waves_per_simd) void spmm_epi_kernel(const SpmmEpiArgs e) { spmm_body<NT, WAVES, false, true>(e.a, e.epi); }
+
+template <int WAVES, bool VAL>
+static hipError_t launch_spmm_waves(int nt, const SpmmArgs& args, int nwin, int nchunks, hipStream_t stream, const Epi& epi) {
+    const dim3 grid((unsigned)nwin, (unsigned)nchunks);
+    return with_width<8>(nt, [&](auto NT) {
+        constexpr LaunchGeom g = spmm_geom(NT, WAVES, VAL);
+        if constexpr (VAL) return launch_kernel<spmm_kernel<NT, WAVES, true>>(grid, g, stream, args);
+        else return launch_plain_or_twin<spmm_kernel<NT, WAVES, false>, spmm_epi_kernel<NT, WAVES>>(grid, g, stream, args, epi);
+    });
+}
+static hipError_t launch_spmm_any(bool val, int waves, int nt, const SpmmArgs& args, int nwin, int nchunks, hipStream_t stream,
+                                  const Epi& epi = Epi{nullptr, nullptr}) {
+    if (waves == 4) return val ? launch_spmm_waves<4, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_waves<4, false>(nt, args, nwin, nchunks, stream, epi);
+    return val ? launch_spmm_waves<1, true>(nt, args, nwin, nchunks, stream, epi) : launch_spmm_waves<1, false>(nt, args, nwin, nchunks, stream, epi);
+}
 
 // ------------------------------------------------------------------------------------------
 // Range-blocked SpMM for graphs whose fp16 feature image does not fit the 4 MB per-XCD L2.
@@ -622,6 +641,11 @@ __global__ void bucket_ptr_kernel(const int64_t* __restrict__ wb_ptr, const int3
     bptr[idx] = (uint32_t)lo;
 }
 
+// spmm_blocked_kernel's launch geometry: four persistent wavefronts, each owning maxw windows (accumulators: maxw * nt * 4 registers)
+static constexpr LaunchGeom blocked_geom(int nt, bool val) { return {256, 4 * tile_wave_lds(nt, val, 2) + 4096, nt <= 4 ? 4 : 2, (nt <= 4 && !val) ? 4 : 2}; }
+// (pinned: resident workgroups per CU at 1 .. 8 tiles of width)
+static_assert(widths_give([](int nt) { return blocked_geom(nt, false).wgs_per_cu(); }, {4, 4, 4, 4, 2, 2, 2, 2}), "spmm_blocked_kernel, binary A");
+static_assert(widths_give([](int nt) { return blocked_geom(nt, true).wgs_per_cu(); }, {4, 4, 4, 3, 2, 2, 2, 2}), "spmm_blocked_kernel, edge values");
 #define TCGNN_KERNEL_NAME spmm_blocked_kernel
 #define TCGNN_KERNEL_PARAM const SpmmBlockedArgs b
 #define TCGNN_KERNEL_PROLOGUE
@@ -642,3 +666,16 @@ struct SpmmBlockedEpiArgs { SpmmBlockedArgs b; Epi epi; };
 #undef TCGNN_KERNEL_PARAM
 #undef TCGNN_KERNEL_PROLOGUE
 #undef TCGNN_KERNEL_STORE
+
+template <int NT, bool VAL>
+static hipError_t launch_blocked_one(const SpmmBlockedArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
+    constexpr LaunchGeom g = blocked_geom(NT, VAL);
+    const dim3 grid((unsigned)nwg, (unsigned)nchunks);
+    if constexpr (VAL) return launch_kernel<spmm_blocked_kernel<NT, g.maxw, true>>(grid, g, stream, args);
+    else return launch_plain_or_twin<spmm_blocked_kernel<NT, g.maxw, false>, spmm_blocked_epi_kernel<NT, g.maxw, false>>(grid, g, stream, args, epi);
+}
+static hipError_t launch_blocked_any(bool val, int nt, const SpmmBlockedArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
+    return with_width<8>(nt, [&](auto NT) {
+        return val ? launch_blocked_one<NT, true>(args, nwg, nchunks, stream, epi) : launch_blocked_one<NT, false>(args, nwg, nchunks, stream, epi);
+    });
+}

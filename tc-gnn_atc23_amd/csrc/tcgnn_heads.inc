@@ -186,7 +186,9 @@ struct HeadsWalker : TileWalker<(G * FB + 1) / 2, true, 2> {
 // One workgroup per (window, pass); 1 or 4 wavefronts (blockDim.x / 64: the plan's workgroup shape) share the window's tiles round-robin
 // and their partial sums are combined through LDS in wavefront order.  (second launch-bound argument: as spmm_kernel's)
 template <int G, int FB>
-__global__ __launch_bounds__(256, ((G * FB + 1) / 2 <= 4 ? 4 : 2)) void spmm_heads_kernel(const SpmmHeadsArgs h) {
+static constexpr LaunchGeom heads_geom(int waves) { return {waves * 64, waves * HeadsWalker<G, FB>::WAVE_LDS, HeadsWalker<G, FB>::NT <= 4 ? 4 : 2, 0}; }
+template <int G, int FB>
+__global__ __launch_bounds__((heads_geom<G, FB>(4).threads), (heads_geom<G, FB>(4).waves_per_simd)) void spmm_heads_kernel(const SpmmHeadsArgs h) {
     const SpmmArgs& a = h.base;
     if (range_is_wide_val(a.hdr)) return;   // (range guard, the whole call: spmm_heads_wide_fallback_kernel, launched behind this kernel, does the work)
     using HW = HeadsWalker<G, FB>;
@@ -273,4 +275,22 @@ __global__ __launch_bounds__(256) void spmm_heads_wide_fallback_kernel(const uin
                                                                        int64_t E, int64_t ld) {
     const int64_t h = blockIdx.y;
     spmm_wide_fallback_body<false>(hdr, 1, rowptr, col, val + h * E, nullptr, X + h * F, nullptr, Y + h * F, N, F, ld, ld, 0, 0, nullptr, Epi{nullptr, nullptr});
+}
+
+// spmm_heads_kernel: G whole heads of 8 FB columns per pass - the shapes heads_per_pass (tcgnn_spmm_dispatch.inc) forms, full passes and remainders
+template <int G, int FB>
+static hipError_t launch_heads_one(const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
+    // (four wavefronts of a 4 x 16 pass hold 65 KB: the ceiling is raised to what four need, whatever this plan's workgroup shape)
+    return launch_kernel<spmm_heads_kernel<G, FB>, heads_geom<G, FB>(4).lds_bytes>(dim3((unsigned)nwin, (unsigned)npass), heads_geom<G, FB>(waves), stream, args);
+}
+static hipError_t launch_heads_any(int g, int fb, const SpmmHeadsArgs& args, int waves, int nwin, int npass, hipStream_t stream) {
+#define TCGNN_HEADS_CASE(G, FB) case (G) * 100 + (FB): return launch_heads_one<G, FB>(args, waves, nwin, npass, stream)
+    switch (g * 100 + fb) {
+        TCGNN_HEADS_CASE(1, 1); TCGNN_HEADS_CASE(2, 1); TCGNN_HEADS_CASE(3, 1); TCGNN_HEADS_CASE(4, 1);   // F = 8
+        TCGNN_HEADS_CASE(1, 2); TCGNN_HEADS_CASE(2, 2); TCGNN_HEADS_CASE(3, 2); TCGNN_HEADS_CASE(4, 2);   // F = 16
+        TCGNN_HEADS_CASE(1, 3); TCGNN_HEADS_CASE(2, 3);                                                   // F = 24
+        TCGNN_HEADS_CASE(1, 4); TCGNN_HEADS_CASE(2, 4);                                                   // F = 32
+        default: return hipErrorInvalidValue;
+    }
+#undef TCGNN_HEADS_CASE
 }

@@ -330,31 +330,15 @@ template __global__ void spmm_lds_flat_epi_kernel<4, 4, 2, false, false>(const S
 template __global__ void spmm_lds_flat_epi_kernel<1, 8, 2, false, false>(const SpmmFlatEpiArgs);
 template __global__ void spmm_lds_flat_epi_kernel<2, 8, 2, false, false>(const SpmmFlatEpiArgs);
 
+static constexpr LaunchGeom flat_geom(int nt, int maxw, int tpc) { return {kLdsWaves * 64, flat_lds_bytes(nt, maxw, tpc), kLdsWaves / 4, maxw}; }   // (as lds_geom)
+
 template <int NT, int MAXW, int TPC, bool DBG, bool WITH_DENSE>
 static hipError_t launch_flat_dbg(const SpmmFlatArgs& args, int nchunks, hipStream_t stream, const Epi& epi) {
-    if constexpr (!DBG) {
-        if (epi.rs || epi.bias) {   // tcgnn_spmm_scaled: the twin with the epilogue in its store
-            static bool epi_attr_set = false;
-            if (!epi_attr_set) {
-                hipError_t e = hipFuncSetAttribute((const void*)spmm_lds_flat_epi_kernel<NT, MAXW, TPC, DBG, WITH_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   flat_lds_bytes(NT, MAXW, TPC));
-                if (e != hipSuccess) return e;
-                epi_attr_set = true;
-            }
-            hipLaunchKernelGGL((spmm_lds_flat_epi_kernel<NT, MAXW, TPC, DBG, WITH_DENSE>), dim3((unsigned)args.nwg, (unsigned)nchunks), dim3(kLdsWaves * 64),
-                               flat_lds_bytes(NT, MAXW, TPC), stream, SpmmFlatEpiArgs{args, epi});
-            return hipGetLastError();
-        }
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)spmm_lds_flat_kernel<NT, MAXW, TPC, DBG, WITH_DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, flat_lds_bytes(NT, MAXW, TPC));
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((spmm_lds_flat_kernel<NT, MAXW, TPC, DBG, WITH_DENSE>), dim3((unsigned)args.nwg, (unsigned)nchunks), dim3(kLdsWaves * 64),
-                       flat_lds_bytes(NT, MAXW, TPC), stream, args);
-    return hipGetLastError();
+    constexpr LaunchGeom g = flat_geom(NT, MAXW, TPC);
+    const dim3 grid((unsigned)args.nwg, (unsigned)nchunks);
+    // (tcgnn_spmm_scaled: the twin with the epilogue in its store; it has no phase-timer instantiations)
+    if constexpr (DBG) return launch_kernel<spmm_lds_flat_kernel<NT, MAXW, TPC, true, WITH_DENSE>, g.lds_bytes>(grid, g, stream, args);
+    else return launch_plain_or_twin<spmm_lds_flat_kernel<NT, MAXW, TPC, false, WITH_DENSE>, spmm_lds_flat_epi_kernel<NT, MAXW, TPC, false, WITH_DENSE>, g.lds_bytes>(grid, g, stream, args, epi);
 }
 template <int NT, int MAXW, int TPC, bool DBG>
 static hipError_t launch_flat_dense(const SpmmFlatArgs& args, int nchunks, hipStream_t stream, bool dense, const Epi& epi) {
@@ -372,13 +356,8 @@ static hipError_t launch_flat_one(const SpmmFlatArgs& args, int nchunks, hipStre
 }
 template <int TPC>
 static hipError_t launch_flat_tpc(int maxw, int nt, const SpmmFlatArgs& args, int nchunks, hipStream_t stream, bool dense, const Epi& epi) {
-    if (maxw == kLdsMaxW2) return nt == 1 ? launch_flat_one<1, kLdsMaxW2, TPC>(args, nchunks, stream, dense, epi) : launch_flat_one<2, kLdsMaxW2, TPC>(args, nchunks, stream, dense, epi);
-    switch (nt) {
-        case 1: return launch_flat_one<1, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi);
-        case 2: return launch_flat_one<2, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi);
-        case 3: return launch_flat_one<3, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi);
-        default: return launch_flat_one<4, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi);
-    }
+    if (maxw == kLdsMaxW2) return with_width<2>(nt, [&](auto NT) { return launch_flat_one<NT, kLdsMaxW2, TPC>(args, nchunks, stream, dense, epi); });
+    return with_width<4>(nt, [&](auto NT) { return launch_flat_one<NT, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi); });
 }
 // dense: the stream has dense entries (CellStream::dense_entries > 0) - the instantiation that walks them
 static hipError_t launch_flat_any(int maxw, int nt, int tpc, const SpmmFlatArgs& args, int nchunks, hipStream_t stream, bool dense,

@@ -720,17 +720,12 @@ template __global__ void spmm_lds_kernel<2, 8, true>(const SpmmLdsArgs);
 
 static constexpr int lds_spmm_bytes(int nt, int maxw) { return 2 * nt * lds_buf_rows(nt, maxw) * 32 + kLdsWaves * 2 * lds_pad_tiles(maxw, lds_buf_rows(nt, maxw)) * 128; }
 
+static constexpr LaunchGeom lds_geom(int nt, int maxw) { return {kLdsWaves * 64, lds_spmm_bytes(nt, maxw), kLdsWaves / 4, maxw}; }   // (one workgroup per CU; the kernel's bound is the same kLdsWaves * 64)
+
 template <int NT, int MAXW, bool DBG>
 static hipError_t launch_lds_dbg(const SpmmLdsArgs& args, int nchunks, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)spmm_lds_kernel<NT, MAXW, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_spmm_bytes(NT, MAXW));
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((spmm_lds_kernel<NT, MAXW, DBG>), dim3((unsigned)args.nwg, (unsigned)nchunks), dim3(kLdsWaves * 64),
-                       lds_spmm_bytes(NT, MAXW), stream, args);
-    return hipGetLastError();
+    constexpr LaunchGeom g = lds_geom(NT, MAXW);
+    return launch_kernel<spmm_lds_kernel<NT, MAXW, DBG>, g.lds_bytes>(dim3((unsigned)args.nwg, (unsigned)nchunks), g, stream, args);
 }
 template <int NT, int MAXW>
 static hipError_t launch_lds_one(const SpmmLdsArgs& args, int nchunks, hipStream_t stream) {
@@ -740,11 +735,6 @@ static hipError_t launch_lds_one(const SpmmLdsArgs& args, int nchunks, hipStream
     return launch_lds_dbg<NT, MAXW, false>(args, nchunks, stream);
 }
 static hipError_t launch_lds_any(int maxw, int nt, const SpmmLdsArgs& args, int nchunks, hipStream_t stream) {
-    if (maxw == kLdsMaxW2) return nt == 1 ? launch_lds_one<1, kLdsMaxW2>(args, nchunks, stream) : launch_lds_one<2, kLdsMaxW2>(args, nchunks, stream);
-    switch (nt) {
-        case 1: return launch_lds_one<1, kLdsMaxW>(args, nchunks, stream);
-        case 2: return launch_lds_one<2, kLdsMaxW>(args, nchunks, stream);
-        case 3: return launch_lds_one<3, kLdsMaxW>(args, nchunks, stream);
-        default: return launch_lds_one<4, kLdsMaxW>(args, nchunks, stream);
-    }
+    if (maxw == kLdsMaxW2) return with_width<2>(nt, [&](auto NT) { return launch_lds_one<NT, kLdsMaxW2>(args, nchunks, stream); });
+    return with_width<4>(nt, [&](auto NT) { return launch_lds_one<NT, kLdsMaxW>(args, nchunks, stream); });
 }

@@ -536,17 +536,11 @@ __global__ __launch_bounds__(kLdsWaves * 64) void spmm_lds_val_kernel(const Spmm
     }
 }
 
+// (as lds_geom: eight windows a wavefront, two planes a pass)
+static constexpr LaunchGeom val_geom() { return {kLdsWaves * 64, val_lds_bytes(2, kLdsMaxW2), kLdsWaves / 4, kLdsMaxW2}; }
+static_assert(val_geom().lds_bytes <= 160 * 1024, "LDS of the edge-valued flat walk");
 static hipError_t launch_lds_val(const SpmmValArgs& args, int nchunks, hipStream_t stream) {
-    static bool attr_set = false;
-    constexpr int bytes = val_lds_bytes(2, kLdsMaxW2);
-    static_assert(bytes <= 160 * 1024, "LDS of the edge-valued flat walk");
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)spmm_lds_val_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(spmm_lds_val_kernel, dim3((unsigned)args.nwg, (unsigned)nchunks), dim3(kLdsWaves * 64), bytes, stream, args);
-    return hipGetLastError();
+    return launch_kernel<spmm_lds_val_kernel, val_geom().lds_bytes>(dim3((unsigned)args.nwg, (unsigned)nchunks), val_geom(), stream, args);
 }
 
 // The cold remainder of the edge-valued walk: spmm_cold_planar_kernel with a value per tile slot (lane k & 31 holds slot k's value,

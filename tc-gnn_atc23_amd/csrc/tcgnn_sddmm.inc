@@ -64,6 +64,16 @@ static constexpr int sddmm_heads_ks(int hf, int g) { return (hf * g + 31) / 32; 
 static constexpr int sddmm_heads_wave_lds(int hf, int g) {
     return sddmm_nbuf(sddmm_heads_ks(hf, g)) * (2 * sddmm_heads_ks(hf, g) * 1024) + kPadBytes + g * 16 * kSddmmHeadsStageCap * 4 + 256;
 }
+// Launch geometry of sddmm_kernel and of its multi-head form.  The persistent walks (range-major, slice-synchronised) take one window per
+// wavefront at a time; four wavefronts per SIMD up to 64 columns, three beyond - the multi-head form three at one K-step, else two.
+static constexpr LaunchGeom sddmm_geom(int ks, int waves) { return {waves * 64, waves * sddmm_wave_lds(ks), ks <= 2 ? 4 : 3, 1}; }
+static constexpr LaunchGeom sddmm_heads_geom(int hf, int g, int waves) { return {waves * 64, waves * sddmm_heads_wave_lds(hf, g), sddmm_heads_ks(hf, g) <= 1 ? 3 : 2, 1}; }
+// (pinned: resident four-wavefront workgroups per CU at 1 .. 4 K-steps, and for every instantiated pass of 2 .. 4 heads - index g - 1)
+static_assert(widths_give([](int ks) { return sddmm_geom(ks, 4).wgs_per_cu(); }, {4, 3, 3, 3}), "sddmm_kernel");
+static_assert(widths_give([](int g) { return g < 2 ? 0 : sddmm_heads_geom(8, g, 4).wgs_per_cu(); }, {0, 3, 3, 3}), "sddmm_kernel, heads of 8 columns");
+static_assert(widths_give([](int g) { return g < 2 ? 0 : sddmm_heads_geom(16, g, 4).wgs_per_cu(); }, {0, 3, 2, 2}), "sddmm_kernel, heads of 16 columns");
+static_assert(widths_give([](int g) { return g < 2 ? 0 : sddmm_heads_geom(32, g, 4).wgs_per_cu(); }, {0, 2, 2, 2}), "sddmm_kernel, heads of 32 columns");
+static_assert(widths_give([](int g) { return g < 2 ? 0 : sddmm_heads_geom(64, g, 4).wgs_per_cu(); }, {0, 2}), "sddmm_kernel, heads of 64 columns");
 
 // KS = number of 32-wide k steps (D <= 32*KS <= 128).  The 16 window rows (MFMA A operand) stay in
 // registers.  Neighbour rows are the B operand, which for X * X^T is contiguous per lane: lane
@@ -80,7 +90,7 @@ static constexpr int sddmm_heads_wave_lds(int hf, int g) {
 // head's column groups are zero (built once per window in load_a: the tile loop gains MFMA issues and the staging writes of G times
 // the outputs, no other VALU work).  Gather, metadata DMA, LDS landing layout and the three walks are the single-head kernel's.
 template <int KS, int WAVES, bool BLOCKED, bool TWO = false, int HF = 0, int G = 1>
-__global__ __launch_bounds__(WAVES * 64, (HF > 0 ? (KS <= 1 ? 3 : 2) : (KS <= 2 ? 4 : 3))) void sddmm_kernel(const SddmmArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (HF > 0 ? sddmm_heads_geom(HF, G, WAVES) : sddmm_geom(KS, WAVES)).waves_per_simd) void sddmm_kernel(const SddmmArgs a) {
     static_assert(HF == 0 || (TWO && (HF == 8 || HF == 16 || HF == 32 || HF == 64) && G >= 1 && G <= kSddmmMaxHeadsPerPass && KS == sddmm_heads_ks(HF, G) && KS <= 4),
                   "a pass of the multi-head form: G heads of HF columns in KS K-steps");
     if constexpr (TWO) { if (sddmm2_wide(a.hdr_a, a.hdr)) return; }   // (sddmm2_csr_kernel, launched behind this kernel, does the work)
@@ -530,4 +540,31 @@ __global__ __launch_bounds__(256) void sddmm_heads_csr_kernel(const uint32_t* __
             }
         }
     }
+}
+
+// (TWO: tcgnn_sddmm2's instantiations, the window operand from its own image.  Beyond 128 columns - ks > 4 - only sddmm_wide_kernel exists)
+template <int WAVES, bool BLOCKED, bool TWO>
+static hipError_t launch_sddmm_two(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
+    const dim3 grid((unsigned)nwg);
+    if (ks > 4) return launch_kernel<sddmm_wide_kernel<WAVES, TWO>>(grid, LaunchGeom{WAVES * 64, 0, 0, 0}, stream, args);
+    return with_width<4>(ks, [&](auto KS) { return launch_kernel<sddmm_kernel<KS, WAVES, BLOCKED, TWO>>(grid, sddmm_geom(KS, WAVES), stream, args); });
+}
+template <int WAVES, bool BLOCKED>
+static hipError_t launch_sddmm_ks(int ks, const SddmmArgs& args, int nwg, hipStream_t stream) {
+    return args.xa16 ? launch_sddmm_two<WAVES, BLOCKED, true>(ks, args, nwg, stream) : launch_sddmm_two<WAVES, BLOCKED, false>(ks, args, nwg, stream);
+}
+
+// tcgnn_sddmm_heads: npass passes (grid.y) of g heads of hf columns each, from args.head0 on.  The instantiated (hf, g): every pass
+// sddmm_heads_passes forms - hf = 8, 16, 32 with 2, 3 or 4 heads, hf = 64 with 2
+template <int WAVES, bool BLOCKED>
+static hipError_t launch_sddmm_heads(int hf, int g, const SddmmArgs& args, int nwg, int npass, hipStream_t stream) {
+    const dim3 grid((unsigned)nwg, (unsigned)npass);
+#define TCGNN_SDDMM_HEADS_CASE(f, n) \
+    if (hf == f && g == n) return launch_kernel<sddmm_kernel<sddmm_heads_ks(f, n), WAVES, BLOCKED, true, f, n>>(grid, sddmm_heads_geom(f, n, WAVES), stream, args);
+    TCGNN_SDDMM_HEADS_CASE(8, 2) TCGNN_SDDMM_HEADS_CASE(8, 3) TCGNN_SDDMM_HEADS_CASE(8, 4)
+    TCGNN_SDDMM_HEADS_CASE(16, 2) TCGNN_SDDMM_HEADS_CASE(16, 3) TCGNN_SDDMM_HEADS_CASE(16, 4)
+    TCGNN_SDDMM_HEADS_CASE(32, 2) TCGNN_SDDMM_HEADS_CASE(32, 3) TCGNN_SDDMM_HEADS_CASE(32, 4)
+    TCGNN_SDDMM_HEADS_CASE(64, 2)
+#undef TCGNN_SDDMM_HEADS_CASE
+    return hipErrorInvalidValue;
 }

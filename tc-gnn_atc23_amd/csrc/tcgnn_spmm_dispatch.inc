@@ -215,10 +215,35 @@ static int route_spmm(const SpmmCall& c, SpmmRoute* r) {
     r->walk = blocked ? Walk::kBlocked : Walk::kPerWindow;
     return TCGNN_OK;
 }
+// ---- kernel arguments: every builder names each field it sets; what is not named is zero
+static SpmmSmallArgs small_args(const SpmmCall& c, const uint32_t* guard_hdr) {
+    const tcgnn_plan* const plan = c.plan;
+    SpmmSmallArgs a{};
+    a.wb_ptr = plan->d_wb_ptr; a.cols = plan->d_cols; a.mask = plan->d_mask; a.x = c.d_X; a.gate = c.d_gate; a.y = c.d_Y;
+    a.N = plan->N; a.Nc = plan->Nc; a.D = c.D; a.relu = c.relu; a.nw = plan->nw_eff; a.guard = guard_hdr;
+    return a;
+}
+// the plan's tile stream over a row-major image: what the gather walks, the cold remainder of an ordinary cell stream and the fused
+// multi-head walk start from (whole rows of Y, binary A, no epilogue - each sets the rest)
+static SpmmArgs spmm_args(const tcgnn_plan* plan, const StagedImage& im, float* d_Y, int32_t D) {
+    SpmmArgs a{};
+    a.wb_ptr = plan->d_wb_ptr; a.order = plan->d_order; a.cols = plan->d_cols; a.mask = plan->d_mask; a.ebase = plan->d_ebase;
+    a.x16 = im.x16; a.hdr = im.hdr; a.y = d_Y;
+    a.N = plan->N; a.D = D; a.stride = im.pitch; a.E = plan->E; a.xrows = plan->Nc + 1; a.ldy = D;
+    a.big = image_is_big(plan->Nc, im.pitch);
+    return a;
+}
+// dpad columns as whole 128-column chunks, then one launch for the remainder: launch(tiles of width, first chunk, chunks)
+template <class F>
+static int for_column_chunks(int dpad, F&& launch) {
+    const int nfull = dpad / kMaxChunkDims, rem = (dpad % kMaxChunkDims) / 16;
+    if (nfull) HIP_TRY(launch(8, 0, nfull));
+    if (rem) HIP_TRY(launch(rem, nfull, 1));
+    return TCGNN_OK;
+}
 // ---- launchers: one per walk, each given the call, its route and the staged image
 static void launch_small_pair(const SpmmCall& c, unsigned grid_x, const uint32_t* guard_hdr) {   // (guard_hdr: as the range guard's fallback - returns at once unless wide)
-    const tcgnn_plan* const plan = c.plan;
-    const SpmmSmallArgs sa{plan->d_wb_ptr, plan->d_cols, plan->d_mask, c.d_X, c.d_gate, c.d_Y, plan->N, plan->Nc, c.D, c.relu, plan->nw_eff, guard_hdr};
+    const SpmmSmallArgs sa = small_args(c, guard_hdr);
     const dim3 grid(grid_x, (unsigned)((c.D + 63) / 64));
     if (c.scaled()) hipLaunchKernelGGL(spmm_small_scaled_kernel, grid, dim3(64), 0, c.stream, SpmmSmallScaledArgs{sa, c.sc.col, c.epi()});
     else hipLaunchKernelGGL(spmm_small_kernel, grid, dim3(64), 0, c.stream, sa);
@@ -264,17 +289,18 @@ static int launch_val_lds(const SpmmCall& c, const StagedImage& im) {
     _Float16* const vals = reinterpret_cast<_Float16*>(static_cast<char*>(c.ws) + image);
     _Float16* const cvals = vals + (size_t)std::max<int64_t>(cs.tiles, 1) * 32;
     KernelTimer timer(plan, stream, cs.cold_tiles > 0 ? "val_permute_kernel + spmm_lds_val_kernel + spmm_cold_val_kernel (cold remainder)" : "val_permute_kernel + spmm_lds_val_kernel");
-    {
-        static bool attr_set = false;
-        if (!attr_set) { HIP_TRY(hipFuncSetAttribute((const void*)val_permute_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kValSpanHalves * 2)); attr_set = true; }
-        hipLaunchKernelGGL(val_permute_kernel, dim3((unsigned)(cs.nwg * kLdsWaves * (kLdsMaxW2 / kValWpb))), dim3(kValThreads), kValSpanHalves * 2, stream, c.d_val, plan->rowptr, cs.d_order, cs.d_eidx16, cs.d_rbase, im.hdr,
-                           vals, plan->N, cs.cold_tiles > 0 ? cs.d_cold_ptr : nullptr, cs.d_cold_eidx16, cvals, cs.d_rl2, cs.dense_entries > 0 ? 1 : 0, std::max(cs.npairs, 1));
-        HIP_TRY(hipGetLastError());
-    }
-    const SpmmValArgs va{cs.d_flat, vals, cs.d_order, im.x16, im.hdr, c.d_Y, plan->N, c.D, im.dpad / 16, 0, plan->Nc + 1, plan->nw_eff, cs.nwg, cs.d_rbase, cs.d_rl2, std::max(cs.npairs, 1)};
+    constexpr LaunchGeom permute{kValThreads, kValSpanHalves * 2, 0, 0};
+    HIP_TRY((launch_kernel<val_permute_kernel, permute.lds_bytes>(dim3((unsigned)(cs.nwg * kLdsWaves * (kLdsMaxW2 / kValWpb))), permute, stream, c.d_val, plan->rowptr, cs.d_order, cs.d_eidx16, cs.d_rbase, im.hdr,
+                                                                 vals, plan->N, cs.cold_tiles > 0 ? cs.d_cold_ptr : nullptr, cs.d_cold_eidx16, cvals, cs.d_rl2, cs.dense_entries > 0 ? 1 : 0, std::max(cs.npairs, 1))));
+    SpmmValArgs va{};
+    va.blocks = cs.d_flat; va.vals = vals; va.order = cs.d_order; va.x16 = im.x16; va.hdr = im.hdr; va.y = c.d_Y;
+    va.N = plan->N; va.D = c.D; va.stride = im.dpad / 16; va.xrows = plan->Nc + 1; va.nw = plan->nw_eff; va.nwg = cs.nwg;
+    va.rbase = cs.d_rbase; va.rl2 = cs.d_rl2; va.nent = std::max(cs.npairs, 1);
     HIP_TRY(launch_lds_val(va, (im.dpad + 31) / 32, stream));   // (a three-plane remainder: its last chunk's second plane lies beyond the matrix - zeros)
     if (cs.cold_tiles > 0) {
-        const ColdValArgs ca{cs.d_cold_ptr, cs.d_cold_cols, cs.d_cold_mask, cvals, im.x16, im.hdr, c.d_Y, plan->N, c.D, plan->Nc + 1, plan->nw_eff, 0, im.dpad};
+        ColdValArgs ca{};
+        ca.cold_ptr = cs.d_cold_ptr; ca.ccols = cs.d_cold_cols; ca.cmask = cs.d_cold_mask; ca.cvals = cvals; ca.x16 = im.x16; ca.hdr = im.hdr; ca.y = c.d_Y;
+        ca.N = plan->N; ca.D = c.D; ca.xrows = plan->Nc + 1; ca.nw = plan->nw_eff; ca.ncols = im.dpad;
         hipLaunchKernelGGL(spmm_cold_val_kernel, dim3((unsigned)((plan->nw_eff + 3) / 4), (unsigned)((im.dpad + 63) / 64)), dim3(256), 0, stream, ca);
         HIP_TRY(hipGetLastError());
     }
@@ -285,15 +311,16 @@ static int launch_cold_rows(const SpmmCall& c, const tcgnn_plan::CellStream* col
     const tcgnn_plan* const plan = c.plan;
     const int pitch_r = x16_pitch(im.dpad);
     // (the per-tile metadata DMA fetches 16 edge-offset words too; binary SpMM never looks at them: the mask array stands in)
-    SpmmArgs a{cold->d_cold_ptr, plan->d_order, cold->d_cold_cols, cold->d_cold_mask, reinterpret_cast<const int32_t*>(cold->d_cold_mask), x16_rows, nullptr, im.hdr, c.d_Y, plan->N, c.D, pitch_r, 0, plan->E,
-               plan->Nc + 1, c.relu, (int32_t)c.D, image_is_big(plan->Nc, pitch_r), nullptr, 0, 1, 0};
+    SpmmArgs a = spmm_args(plan, im, c.d_Y, c.D);
+    a.wb_ptr = cold->d_cold_ptr; a.cols = cold->d_cold_cols; a.mask = cold->d_cold_mask; a.ebase = reinterpret_cast<const int32_t*>(cold->d_cold_mask);
+    a.x16 = x16_rows; a.stride = pitch_r; a.big = image_is_big(plan->Nc, pitch_r); a.relu = c.relu; a.accumulate = 1;
     constexpr int cold_w4 = 48;   // tiles per window from which 4 wavefronts share it (SBM Reddit shape, 25 cold tiles per window: 169 us with one wavefront, 202 with four)
     // (and a window with hundreds of cold tiles - a hub - is 0.25 us per tile of serial work for one wavefront)
     const int waves = (cold->cold_tiles >= (int64_t)cold_w4 * plan->nw_eff || cold->cold_max >= 512) ? 4 : 1;
-    const int nfull = im.dpad / kMaxChunkDims, rem = (im.dpad % kMaxChunkDims) / 16;
-    if (nfull) { a.chunk0 = 0; HIP_TRY(launch_spmm_any(false, waves, 8, a, plan->nw_eff, nfull, c.stream, c.epi())); }
-    if (rem) { a.chunk0 = nfull; HIP_TRY(launch_spmm_any(false, waves, rem, a, plan->nw_eff, 1, c.stream, c.epi())); }
-    return TCGNN_OK;
+    return for_column_chunks(im.dpad, [&](int nt, int chunk0, int nchunks) {
+        a.chunk0 = chunk0;
+        return launch_spmm_any(false, waves, nt, a, plan->nw_eff, nchunks, c.stream, c.epi());
+    });
 }
 static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& im) {
     const tcgnn_plan* const plan = c.plan;
@@ -314,7 +341,7 @@ static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& 
         x16_rows = rows.x16;
     }
     const tcgnn_plan::CellStream& cs0 = plan->lds[lds_stream_of(r.passes[0].nt, r.passes[0].maxw)];
-    const SpmmSmallArgs fb{plan->d_wb_ptr, plan->d_cols, plan->d_mask, c.d_X, c.d_gate, c.d_Y, plan->N, plan->Nc, D, c.relu, plan->nw_eff, r.own_fb ? im.hdr : nullptr};
+    const SpmmSmallArgs fb = small_args(c, r.own_fb ? im.hdr : nullptr);
     KernelTimer timer(plan, stream, r.cold ? "spmm_lds_kernel + spmm_kernel (cold remainder)" :
                                     (cs0.flat_tpc ? (flat_cold_behind(cs0) ? "spmm_lds_flat_kernel + spmm_cold_planar_kernel (cold remainder)" : "spmm_lds_flat_kernel") : "spmm_lds_kernel"));
     for (int i = 0; i < r.npass; ++i) {
@@ -324,75 +351,82 @@ static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& 
             const bool has_cold = flat_cold_behind(cs);
             // (tcgnn_spmm_scaled: with a remainder behind it this kernel stores raw sums and spmm_cold_planar_kernel, the final writer,
             //  applies row scale, bias and ReLU; otherwise its twin spmm_lds_flat_epi_kernel applies them in its own store)
-            SpmmFlatArgs f{cs.d_flat, cs.d_order, im.x16, im.hdr, c.d_Y, plan->N, D, im.dpad / 16, p.chunk0, plan->Nc + 1, plan->nw_eff, cs.nwg, g_lds_dbg,
-                           has_cold ? 0 : c.relu, cs.d_rbase, cs.d_rl2, std::max(cs.npairs, 1), c.d_W, c.D_out, r.accumulate, g_lds_fill_quota, cs.d_wcold_ptr, cs.d_wcold, fb};
+            SpmmFlatArgs f{};
+            f.blocks = cs.d_flat; f.order = cs.d_order; f.x16 = im.x16; f.hdr = im.hdr; f.y = c.d_Y;
+            f.N = plan->N; f.D = D; f.stride = im.dpad / 16; f.chunk0 = p.chunk0; f.xrows = plan->Nc + 1; f.nw = plan->nw_eff; f.nwg = cs.nwg;
+            f.dbg = g_lds_dbg; f.relu = has_cold ? 0 : c.relu; f.rbase = cs.d_rbase; f.rl2 = cs.d_rl2; f.nent = std::max(cs.npairs, 1);
+            f.w = c.d_W; f.dout = c.D_out; f.accumulate = r.accumulate; f.fill_quota = g_lds_fill_quota; f.wcold_ptr = cs.d_wcold_ptr; f.wcold = cs.d_wcold; f.fb = fb;
             HIP_TRY(launch_flat_any(p.maxw, p.nt, cs.flat_tpc, f, p.nchunks, stream, cs.dense_entries > 0, has_cold ? no_epi : epi));
             if (has_cold && !(g_lds_dbg & 16)) {
                 const int cd = lds_chunk_dims(p.maxw);
                 const int col0 = p.chunk0 * cd, ncols = std::min(p.nchunks * cd, im.dpad - col0);
-                const ColdPlanarArgs ca{cs.d_cold_ptr, cs.d_cold_cols, cs.d_cold_mask, im.x16, im.hdr, c.d_Y, plan->N, D, plan->Nc + 1, plan->nw_eff, col0, ncols, c.relu, epi};
+                ColdPlanarArgs ca{};
+                ca.cold_ptr = cs.d_cold_ptr; ca.ccols = cs.d_cold_cols; ca.cmask = cs.d_cold_mask; ca.x16 = im.x16; ca.hdr = im.hdr; ca.y = c.d_Y;
+                ca.N = plan->N; ca.D = D; ca.xrows = plan->Nc + 1; ca.nw = plan->nw_eff; ca.col0 = col0; ca.ncols = ncols; ca.relu = c.relu; ca.epi = epi;
                 hipLaunchKernelGGL(spmm_cold_planar_kernel, dim3((unsigned)((plan->nw_eff + 3) / 4), (unsigned)((ncols + 63) / 64)), dim3(256), 0, stream, ca);
                 HIP_TRY(hipGetLastError());
             }
             continue;
         }
-        SpmmLdsArgs l{cs.d_cell_ptr, cs.d_cell_tiles, cs.d_order, im.x16, im.hdr, c.d_Y, plan->N, D, im.dpad / 16, p.chunk0, plan->Nc + 1,
-                      cs.nranges, plan->nw_eff, cs.nwg, g_lds_dbg, r.cold ? 0 : c.relu, cs.d_rbase, cs.d_rlist, c.d_W, c.D_out, r.accumulate, cs.d_parts, fb,
-                      r.cold ? no_epi : epi};
+        SpmmLdsArgs l{};
+        l.cell_ptr = cs.d_cell_ptr; l.tiles = cs.d_cell_tiles; l.order = cs.d_order; l.x16 = im.x16; l.hdr = im.hdr; l.y = c.d_Y;
+        l.N = plan->N; l.D = D; l.stride = im.dpad / 16; l.chunk0 = p.chunk0; l.xrows = plan->Nc + 1; l.nranges = cs.nranges; l.nw = plan->nw_eff; l.nwg = cs.nwg;
+        l.dbg = g_lds_dbg; l.relu = r.cold ? 0 : c.relu; l.rbase = cs.d_rbase; l.rlist = cs.d_rlist;
+        l.w = c.d_W; l.dout = c.D_out; l.accumulate = r.accumulate; l.parts = cs.d_parts; l.fb = fb; l.epi = r.cold ? no_epi : epi;
         HIP_TRY(launch_lds_any(p.maxw, p.nt, l, p.nchunks, stream));
     }
     return r.cold ? launch_cold_rows(c, r.cold, im, x16_rows) : TCGNN_OK;
 }
-// the three gather walks share their kernel arguments and cover dpad columns as whole 128-column chunks + one launch for the rest
+// the three gather walks share their kernel arguments and cover dpad columns as for_column_chunks cuts them
 static SpmmArgs gather_args(const SpmmCall& c, const StagedImage& im) {
-    const tcgnn_plan* const plan = c.plan;
-    SpmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, im.x16, c.d_val, im.hdr, c.d_Y, plan->N, c.D, im.pitch, 0, plan->E, plan->Nc + 1, c.relu, (int32_t)c.stride(),
-               image_is_big(plan->Nc, im.pitch), c.d_W, c.D_out, 0, c.d_image ? 1 : 0};
-    if (c.d_W) a.ldy = c.D_out;
+    SpmmArgs a = spmm_args(c.plan, im, c.d_Y, c.D);
+    a.edge_val = c.d_val; a.relu = c.relu; a.ldy = c.d_W ? c.D_out : (int32_t)c.stride();
+    a.w = c.d_W; a.dout = c.D_out; a.unguarded = c.d_image ? 1 : 0;
     return a;
 }
 static int launch_sync(const SpmmCall& c, const StagedImage& im) {
     const tcgnn_plan* const plan = c.plan;
     const bool val = c.d_val != nullptr;
-    const int nfull = im.dpad / kMaxChunkDims, rem = (im.dpad % kMaxChunkDims) / 16;
     KernelTimer timer(plan, c.stream, "spmm_sync_kernel");
     SpmmSyncArgs sa{gather_args(c, im), sync_args(plan, im.pitch * 2)};
-    auto wgs = [&](int nt) {   // workgroups per launch: what holds a slice (S windows per XCD, 4 wavefronts x MAXW windows per workgroup), at most what is resident
-        const int per_xcd = std::min((plan->sync.S + 4 * sync_maxw(nt, val) - 1) / (4 * sync_maxw(nt, val)), plan->num_cus / kXcds * sync_wgs_per_cu(nt, val));
+    auto wgs = [&](int nt) {   // workgroups per launch: what holds a slice (S windows per XCD, 4 wavefronts x maxw windows per workgroup), at most what is resident
+        const LaunchGeom g = sync_geom(nt, val);
+        const int per_xcd = std::min((plan->sync.S + 4 * g.maxw - 1) / (4 * g.maxw), plan->num_cus / kXcds * g.wgs_per_cu());
         return kXcds * std::max(per_xcd, 1);
     };
     for (int r = 0; r < plan->sync.R; ++r) {   // one launch per slice round
         sa.s.round = r;
-        if (nfull) { sa.base.chunk0 = 0; HIP_TRY(launch_sync_any(val, 8, sa, wgs(8), nfull, c.stream, c.epi())); }
-        if (rem) { sa.base.chunk0 = nfull; HIP_TRY(launch_sync_any(val, rem, sa, wgs(rem), 1, c.stream, c.epi())); }
+        const int rc = for_column_chunks(im.dpad, [&](int nt, int chunk0, int nchunks) {
+            sa.base.chunk0 = chunk0;
+            return launch_sync_any(val, nt, sa, wgs(nt), nchunks, c.stream, c.epi());
+        });
+        if (rc) return rc;
     }
     return TCGNN_OK;
 }
 static int launch_blocked(const SpmmCall& c, const StagedImage& im) {
     const tcgnn_plan* const plan = c.plan;
     const bool val = c.d_val != nullptr;
-    const int nfull = im.dpad / kMaxChunkDims, rem = (im.dpad % kMaxChunkDims) / 16;
     KernelTimer timer(plan, c.stream, "spmm_blocked_kernel");
     const int nranges = range_count(plan, image_bytes(plan, im.pitch), kRangeTargetBytes);
     SpmmBlockedArgs b{gather_args(c, im), plan->d_bptr, plan->nbuckets, plan->nbuckets / nranges, nranges, plan->nw_eff, 0};
-    auto wgs = [&](int nt) {   // persistent grid = what is resident at once: LDS per workgroup (4 wavefronts: tile buffers,
-                               // pads, + the 4 KB A table) against 160 KB, and the register budget (4 or 2 workgroups per CU)
-        const int maxw = blocked_maxw(nt, val);
-        b.ngroups = (plan->nw_eff + maxw - 1) / maxw;
-        return std::min((b.ngroups + 3) / 4, plan->num_cus * wgs_per_cu(4 * (2 * nt * 1024 + kPadBytes + (val ? 1024 : 0)) + 4096, nt <= 4 ? 4 : 2));
-    };
-    if (nfull) { b.base.chunk0 = 0; const int n = wgs(8); HIP_TRY(launch_blocked_any(val, 8, b, n, nfull, c.stream, c.epi())); }
-    if (rem) { b.base.chunk0 = nfull; const int n = wgs(rem); HIP_TRY(launch_blocked_any(val, rem, b, n, 1, c.stream, c.epi())); }
-    return TCGNN_OK;
+    return for_column_chunks(im.dpad, [&](int nt, int chunk0, int nchunks) {
+        // persistent grid = what is resident at once: LDS per workgroup (4 wavefronts: tile buffers, pads, + the 4 KB A table)
+        // against 160 KB, and the register budget (4 or 2 workgroups per CU)
+        const LaunchGeom g = blocked_geom(nt, val);
+        b.base.chunk0 = chunk0;
+        b.ngroups = (plan->nw_eff + g.maxw - 1) / g.maxw;
+        return launch_blocked_any(val, nt, b, std::min((b.ngroups + 3) / 4, plan->num_cus * g.wgs_per_cu()), nchunks, c.stream, c.epi());
+    });
 }
 static int launch_per_window(const SpmmCall& c, const StagedImage& im) {
     const tcgnn_plan* const plan = c.plan;
-    const int nfull = im.dpad / kMaxChunkDims, rem = (im.dpad % kMaxChunkDims) / 16;
     KernelTimer timer(plan, c.stream, "spmm_kernel");
     SpmmArgs a = gather_args(c, im);
-    if (nfull) { a.chunk0 = 0; HIP_TRY(launch_spmm_any(c.d_val != nullptr, plan->waves, 8, a, plan->nw_eff, nfull, c.stream, c.epi())); }
-    if (rem) { a.chunk0 = nfull; HIP_TRY(launch_spmm_any(c.d_val != nullptr, plan->waves, rem, a, plan->nw_eff, 1, c.stream, c.epi())); }
-    return TCGNN_OK;
+    return for_column_chunks(im.dpad, [&](int nt, int chunk0, int nchunks) {
+        a.chunk0 = chunk0;
+        return launch_spmm_any(c.d_val != nullptr, plan->waves, nt, a, plan->nw_eff, nchunks, c.stream, c.epi());
+    });
 }
 // rows beyond the windows the caller described stay zero, like zeros_like - or hold the epilogue of an empty sum
 static int fill_uncovered_rows(const SpmmCall& c) {
@@ -506,8 +540,8 @@ static int launch_heads_fused(const HeadsCall& c) {
     HIP_TRY(hipGetLastError());
     {
         KernelTimer timer(plan, c.stream, "spmm_heads_kernel");
-        SpmmArgs a{plan->d_wb_ptr, plan->d_order, plan->d_cols, plan->d_mask, plan->d_ebase, im.x16, c.d_val, im.hdr, c.d_Y, plan->N, D, im.pitch, 0, plan->E, plan->Nc + 1, 0, D,
-                   0, nullptr, 0, 0, 0};
+        SpmmArgs a = spmm_args(plan, im, c.d_Y, D);   // (route_heads: never a big image)
+        a.edge_val = c.d_val;
         const int g = heads_per_pass(c.F), nfull = c.H / g, rem = c.H % g;
         if (nfull) HIP_TRY(launch_heads_any(g, c.F / 8, SpmmHeadsArgs{a, 0}, plan->waves, plan->nw_eff, nfull, c.stream));
         if (rem) HIP_TRY(launch_heads_any(rem, c.F / 8, SpmmHeadsArgs{a, nfull * g}, plan->waves, plan->nw_eff, 1, c.stream));

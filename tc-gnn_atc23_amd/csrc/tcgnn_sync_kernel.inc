@@ -2,7 +2,7 @@
 // spmm_sync_epi_kernel, the same walk with tcgnn_spmm_scaled's row scale / bias in the final store.  The macros expand, for the
 // plain kernel, to exactly the tokens it was written with, so its code does not change.
 template <int NT, int MAXW, bool VAL, int NBUF>
-__global__ __launch_bounds__(256, (NT <= 4 ? 4 : 2)) void TCGNN_KERNEL_NAME(TCGNN_KERNEL_PARAM) {
+__global__ __launch_bounds__(sync_geom(NT, VAL).threads, sync_geom(NT, VAL).waves_per_simd) void TCGNN_KERNEL_NAME(TCGNN_KERNEL_PARAM) {
     TCGNN_KERNEL_PROLOGUE
     if (!b.base.unguarded && (VAL ? range_is_wide_val(b.base.hdr) : range_is_wide(b.base.hdr, 0))) return;   // (range guard: the fp32 fallback launched behind this kernel does the work)
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -26,7 +26,10 @@
 // with one wavefront per window: same tile order per window).
 // ------------------------------------------------------------------------------------------
 static constexpr int kSyncKmax = 64;          // hot buckets a slice may list
-static constexpr int kSyncSlice = 768;        // windows of one XCD per launch = what its wavefronts hold at once beyond 64 columns (32 CUs x 12 wavefronts x 2 windows)
+// windows of one XCD per launch.  Up to 64 columns its wavefronts hold them at once (32 CUs x 16 wavefronts x 2 windows = 1024: the grid
+// is cut to the slice).  Beyond, 32 CUs x 8 wavefronts x 2 windows = 512 are resident and a slice round takes a second trip, a third
+// filled (the figure dates from a layout of 12 wavefronts x 2 windows per CU that the kernels no longer have: ADVICE r06)
+static constexpr int kSyncSlice = 768;
 static constexpr int kSyncFbShift0 = 11;      // finest bucket: 2048 rows
 
 struct SyncArgs {
@@ -52,6 +55,14 @@ __device__ __forceinline__ void sync_slice_of(const SyncArgs& s, int& x, int& w_
     nph = k <= s.m ? 1 : (k + s.m - 1) / s.m;
 }
 
+// spmm_sync_kernel's launch geometry.  Tile buffers per wavefront: two up to 32 columns; beyond, ONE and a run list - the kernel walks
+// its runs as one pipeline (TileWalker::walk_list).  A wavefront owns 2 windows at every width (three spilled 34-44 words at 128
+// columns).  Four wavefronts per SIMD up to 64 columns, two beyond: walk_list's three list cursors want the 256 registers.
+static constexpr int sync_nbuf(int nt) { return nt <= 2 ? 2 : 1; }
+static constexpr LaunchGeom sync_geom(int nt, bool val) { return {256, 4 * tile_wave_lds(nt, val, sync_nbuf(nt)) + 4096, nt <= 4 ? 4 : 2, 2}; }
+// (pinned: resident workgroups per CU at 1 .. 8 tiles of width)
+static_assert(widths_give([](int nt) { return sync_geom(nt, false).wgs_per_cu(); }, {4, 4, 4, 4, 2, 2, 2, 2}), "spmm_sync_kernel, binary A");
+static_assert(widths_give([](int nt) { return sync_geom(nt, true).wgs_per_cu(); }, {4, 4, 4, 4, 2, 2, 2, 2}), "spmm_sync_kernel, edge values");
 #define TCGNN_KERNEL_NAME spmm_sync_kernel
 #define TCGNN_KERNEL_PARAM const SpmmSyncArgs b
 #define TCGNN_KERNEL_PROLOGUE
@@ -72,6 +83,20 @@ struct SpmmSyncEpiArgs { SpmmSyncArgs b; Epi epi; };
 #undef TCGNN_KERNEL_PARAM
 #undef TCGNN_KERNEL_PROLOGUE
 #undef TCGNN_KERNEL_STORE
+
+template <int NT, bool VAL>
+static hipError_t launch_sync_one(const SpmmSyncArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
+    constexpr LaunchGeom g = sync_geom(NT, VAL);
+    constexpr int NBUF = sync_nbuf(NT);
+    const dim3 grid((unsigned)nwg, (unsigned)nchunks);
+    if constexpr (VAL) return launch_kernel<spmm_sync_kernel<NT, g.maxw, true, NBUF>>(grid, g, stream, args);
+    else return launch_plain_or_twin<spmm_sync_kernel<NT, g.maxw, false, NBUF>, spmm_sync_epi_kernel<NT, g.maxw, false, NBUF>>(grid, g, stream, args, epi);
+}
+static hipError_t launch_sync_any(bool val, int nt, const SpmmSyncArgs& args, int nwg, int nchunks, hipStream_t stream, const Epi& epi) {
+    return with_width<8>(nt, [&](auto NT) {
+        return val ? launch_sync_one<NT, true>(args, nwg, nchunks, stream, epi) : launch_sync_one<NT, false>(args, nwg, nchunks, stream, epi);
+    });
+}
 
 // ---- plan-time tables -----------------------------------------------------------------------
 // tiles of every slice per fine bucket (bucket of a tile = that of its first column: the stream is sorted by column inside a window)
