@@ -516,6 +516,50 @@ int tcgnn_segment_max_backward(const int32_t* d_nodePointer_t, const int32_t* d_
                                int32_t num_nodes, int64_t num_edges, const int32_t* d_arg, const float* d_dY, int32_t D,
                                float* d_dX, void* stream);
 
+/* ---- GATv2 attention (Brody et al.; DGL's / PyG's GATv2Conv; no counterpart in the reference) -------------------------------------
+ *
+ * CSR row = destination node, column = source node.  d_xl (read at col(e)) and d_xr (read at row(e)) are fp32 [num_nodes, H F]
+ * row-major and may be the same pointer; d_attn is fp32 [H, F]; per-edge arrays are head-major [H, num_edges] (a head's row is what
+ * tcgnn_spmm_heads takes).  Planless like tcgnn_gat_softmax: device pointers, the caller's stream, no allocation, no synchronisation
+ * (capturable in a HIP graph); no atomics and every reduction order fixed: bit-identical on repetition.  Everything is read as fp32 -
+ * no fp16 image, no range guard.  Any H >= 1 and F >= 1.
+ *   the activation term  z = fl32(xl[col e, hF+f] + xr[row e, hF+f]);  l = z > 0 ? z : fl32(z * negative_slope) - GAT's two roundings,
+ *                        the product contracted with nothing.
+ *   tcgnn_gatv2_softmax           s[h,e] = fl32(sum_f (double)attn[h,f] * (double)l): exact fp64 products, an fp64 sum in a fixed order,
+ *                                 rounded once; every neighbour row is gathered once and every score formed once.  p[h,.] = softmax of
+ *                                 those rounded scores over every CSR row, the maximum always subtracted - the exponential, the fp64 row sum
+ *                                 and the fp64 quotient are tcgnn_edge_softmax's with beta = 1.  The scores are parked in their slots of
+ *                                 d_p and normalised in place in the same launch.  d_score (may be NULL) receives the rounded scores; d_p
+ *                                 is bit-identical with and without it.
+ *   tcgnn_gatv2_softmax_backward  g = p * (float)((double)dp - sum_row p dp), the dot product in fp64 and fixed order, as
+ *                                 tcgnn_gat_softmax_backward forms it; d_g may alias d_dp.  With c = z > 0 ? attn[h,f] : fl32(attn[h,f] *
+ *                                 negative_slope):  d_dxr[i, hF+f] = fl32(sum_{e in row i} (double)fl32(g[h,e] * c)) - EVERY row is
+ *                                 written, an empty one with 0;  d_dattn[h,f] = fl32(sum_e (double)g[h,e] * (double)l), each workgroup's
+ *                                 fp64 partials in d_scratch (tcgnn_gatv2_workspace_bytes bytes, 8-byte aligned), added in workgroup order
+ *                                 by a second small launch.
+ *   tcgnn_gatv2_source_grad       over the rows of A^T (d_nodePointer_t, d_edgeList_t, d_perm: what tcgnn_transpose_ws wrote):
+ *                                 d_dxl[j, hF+f] = fl32(sum_{eT in row j} (double)fl32(g[h, perm eT] * c)), z = fl32(xl[j] + xr[col_t eT]);
+ *                                 a source nobody reads gets 0.
+ * Rows are read with 16-byte loads when F % 4 == 0 and d_xl, d_xr and d_attn are 16-byte aligned, with 4-byte loads otherwise: the
+ * same bits either way.  Row pointers are clamped to [0, num_edges] and a descending pair is an empty row.  For every read they index,
+ * a column id is clamped to the nearer end of [0, num_nodes) and a perm entry outside [0, num_edges) reads position 0: safe reads
+ * either way, values of no meaning for an array that holds such entries.  Nothing outside [0, num_edges) of a head's row of p / score /
+ * g and nothing outside [0, num_nodes * H * F) of the node arrays is written.  num_nodes = 0 or num_edges = 0 returns TCGNN_OK (d_dxr /
+ * d_dxl / d_dattn zeroed where they have elements and the pointer is given); H < 1, F < 1, a negative size, num_edges >= 2^31 or a null
+ * array where one is needed: TCGNN_ERR_INVALID_ARG before anything is written; a scratch buffer too small: TCGNN_ERR_WORKSPACE.  A hub
+ * row stays on one workgroup, as in tcgnn_edge_softmax and tcgnn_gat_softmax. */
+size_t tcgnn_gatv2_workspace_bytes(int32_t num_nodes, int64_t num_edges, int32_t H, int32_t F);
+int tcgnn_gatv2_softmax(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges, int32_t H,
+                        int32_t F, const float* d_xl, const float* d_xr, const float* d_attn, float negative_slope,
+                        float* d_score /* may be NULL */, float* d_p, void* stream);
+int tcgnn_gatv2_softmax_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                                 int32_t H, int32_t F, const float* d_xl, const float* d_xr, const float* d_attn,
+                                 float negative_slope, const float* d_p, const float* d_dp, float* d_g, float* d_dxr,
+                                 float* d_dattn, void* d_scratch, size_t scratch_bytes, void* stream);
+int tcgnn_gatv2_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm, int32_t num_nodes,
+                            int64_t num_edges, int32_t H, int32_t F, const float* d_xl, const float* d_xr, const float* d_attn,
+                            float negative_slope, const float* d_g, float* d_dxl, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

@@ -472,6 +472,73 @@ torch::Tensor edge_colsum(torch::Tensor val, torch::Tensor nodePointer, torch::T
   return out;
 }
 
+// ---- not in the reference: GATv2 attention (tcgnn_gatv2_softmax / _backward / tcgnn_gatv2_source_grad; the ctypes module's
+// gatv2_softmax, gatv2_softmax_backward and gatv2_source_grad) ----------------------------------------------------------------------
+namespace {
+// (N, E, H, F) of a GATv2 call, after the checks of the ctypes module
+std::tuple<int32_t, int64_t, int32_t, int32_t> gatv2_args(const torch::Tensor& xl, const torch::Tensor& xr, const torch::Tensor& attn,
+                                                          const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(attn); CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(xl.scalar_type() == torch::kFloat32 && xr.scalar_type() == torch::kFloat32 && attn.scalar_type() == torch::kFloat32,
+              "expected scalar type Float");
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  TORCH_CHECK(attn.dim() == 2 && attn.size(0) >= 1 && attn.size(1) >= 1, "attn must be [heads, features] (heads >= 1, features >= 1)");
+  const int64_t N = nodePointer.numel() - 1, H = attn.size(0), F = attn.size(1);
+  TORCH_CHECK(xl.dim() == 2 && xl.size(0) == N && xl.size(1) == H * F && xr.sizes() == xl.sizes(), "xl and xr must be [num_nodes, heads * features]");
+  TORCH_CHECK(xr.device() == xl.device() && attn.device() == xl.device() && nodePointer.device() == xl.device() && edgeList.device() == xl.device(),
+              "xl, xr, attn, nodePointer and edgeList must be on one device");
+  return {(int32_t)N, edgeList.numel(), (int32_t)H, (int32_t)F};
+}
+}  // namespace
+
+torch::Tensor gatv2_softmax(torch::Tensor xl, torch::Tensor xr, torch::Tensor attn, torch::Tensor nodePointer, torch::Tensor edgeList,
+                            double negative_slope, c10::optional<torch::Tensor> out, c10::optional<torch::Tensor> score_out) {
+  auto [N, E, H, F] = gatv2_args(xl, xr, attn, nodePointer, edgeList);
+  torch::Tensor p = out.has_value() ? *out : torch::empty({(int64_t)H, E}, xl.options());
+  check_head_major(p, "out", H, E, xl);
+  if (score_out.has_value()) check_head_major(*score_out, "score_out", H, E, xl);
+  DeviceGuard guard(xl.device());
+  tcgnn_check(tcgnn_gatv2_softmax(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, H, F, xl.data_ptr<float>(), xr.data_ptr<float>(),
+                                  attn.data_ptr<float>(), (float)negative_slope, score_out.has_value() ? score_out->data_ptr<float>() : nullptr,
+                                  p.data_ptr<float>(), current_stream(xl)), "tcgnn_gatv2_softmax");
+  return p;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gatv2_softmax_backward(torch::Tensor p, torch::Tensor dp, torch::Tensor xl, torch::Tensor xr,
+                                                                               torch::Tensor attn, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                                               double negative_slope, c10::optional<torch::Tensor> out) {
+  auto [N, E, H, F] = gatv2_args(xl, xr, attn, nodePointer, edgeList);
+  check_head_major(p, "p", H, E, xl);
+  check_head_major(dp, "dp", H, E, xl);
+  torch::Tensor g = out.has_value() ? *out : torch::empty_like(dp);
+  check_head_major(g, "out", H, E, xl);
+  DeviceGuard guard(xl.device());
+  torch::Tensor d_xr = torch::empty({(int64_t)N, (int64_t)H * F}, xl.options());
+  torch::Tensor d_attn = torch::empty({(int64_t)H, (int64_t)F}, xl.options());
+  void* scratch = nullptr;
+  const size_t need = tcgnn_gatv2_workspace_bytes(N, E, H, F);
+  torch::Tensor buf = aligned_scratch(need, xl, &scratch);
+  tcgnn_check(tcgnn_gatv2_softmax_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, H, F, xl.data_ptr<float>(), xr.data_ptr<float>(),
+                                           attn.data_ptr<float>(), (float)negative_slope, p.data_ptr<float>(), dp.data_ptr<float>(), g.data_ptr<float>(),
+                                           d_xr.data_ptr<float>(), d_attn.data_ptr<float>(), scratch, need, current_stream(xl)),
+              "tcgnn_gatv2_softmax_backward");
+  return {g, d_xr, d_attn};
+}
+
+torch::Tensor gatv2_source_grad(torch::Tensor g, torch::Tensor xl, torch::Tensor xr, torch::Tensor attn, torch::Tensor nodePointer,
+                                torch::Tensor edgeList, double negative_slope) {
+  auto [N, E, H, F] = gatv2_args(xl, xr, attn, nodePointer, edgeList);
+  check_head_major(g, "g", H, E, xl);
+  DeviceGuard guard(xl.device());
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  torch::Tensor d_xl = torch::empty({(int64_t)N, (int64_t)H * F}, xl.options());
+  tcgnn_check(tcgnn_gatv2_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E, H, F, xl.data_ptr<float>(),
+                                      xr.data_ptr<float>(), attn.data_ptr<float>(), (float)negative_slope, g.data_ptr<float>(), d_xl.data_ptr<float>(),
+                                      current_stream(xl)), "tcgnn_gatv2_source_grad");
+  return d_xl;
+}
+
 // ---- not in the reference: element-wise maximum over a node's incoming edges (tcgnn_segment_max / _backward; the ctypes module's
 // forward_max and backward_max) ---------------------------------------------------------------------------------------------------
 namespace {
@@ -646,4 +713,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("return_arg") = true, py::arg("out") = py::none());
   m.def("backward_max", &backward_max, "backward of forward_max: dX (not in the reference)", py::arg("dY"), py::arg("arg"), py::arg("nodePointer"),
         py::arg("edgeList"), py::arg("out") = py::none());
+  m.def("gatv2_softmax", &gatv2_softmax, "GATv2 attention, p[heads, E] (not in the reference)", py::arg("xl"), py::arg("xr"), py::arg("attn"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2, py::arg("out") = py::none(), py::arg("score_out") = py::none());
+  m.def("gatv2_softmax_backward", &gatv2_softmax_backward, "row side of gatv2_softmax's backward: (g, d_xr, d_attn) (not in the reference)", py::arg("p"),
+        py::arg("dp"), py::arg("xl"), py::arg("xr"), py::arg("attn"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2,
+        py::arg("out") = py::none());
+  m.def("gatv2_source_grad", &gatv2_source_grad, "source side of gatv2_softmax's backward: d_xl (not in the reference)", py::arg("g"), py::arg("xl"),
+        py::arg("xr"), py::arg("attn"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2);
 }

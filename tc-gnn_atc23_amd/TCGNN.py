@@ -36,7 +36,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
-           "forward_max", "backward_max", "cache_stats", "drop_scales"]
+           "forward_max", "backward_max", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad"]
 
 
 def _stream(device):
@@ -60,7 +60,7 @@ _cache = GraphCache(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8"), _c.lib.tcgnn_p
 _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
-          "softmax": (1, 256)}        # the fp64 partials of edge_softmax_backward's d_beta
+          "softmax": (1, 256)}        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
 
 
 def _buffer(kind, need, device, stream=None):
@@ -292,7 +292,10 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
                 _buffer("workspace", _c.lib.tcgnn_sddmm2_workspace_bytes(e.handle, d), dev, stream)
                 if int(heads) > 1:
                     _buffer("workspace", _c.lib.tcgnn_sddmm_heads_workspace_bytes(e.handle, int(heads), d), dev, stream)
-            _buffer("softmax", _c.lib.tcgnn_edge_softmax_workspace_bytes(max(nodePointer.numel() - 1, 0), edgeList.numel()), dev, stream)
+            N, E = max(nodePointer.numel() - 1, 0), edgeList.numel()
+            # (... and of gatv2_softmax_backward's d_attn at `heads` heads - and at the one head of an output layer - of every width)
+            _buffer("softmax", max([_c.lib.tcgnn_edge_softmax_workspace_bytes(N, E)] +
+                                   [_c.lib.tcgnn_gatv2_workspace_bytes(N, E, h, d) for d in widths for h in {1, max(int(heads), 1)}]), dev, stream)
         if transpose:
             own = _transposed_plan(e).own
             if own is not None:
@@ -822,11 +825,11 @@ def _gat_args(el, er, nodePointer, edgeList):
     return N, edgeList.numel(), el.size(1)
 
 
-def _head_major(t, name, H, E, like):
+def _head_major(t, name, H, E, like, of="el"):
     _check_input(t, name)
     _check_float(t, name)
     if tuple(t.shape) != (H, E) or t.device != like.device:
-        raise RuntimeError("%s must be a contiguous fp32 [heads, num_edges] = [%d, %d] tensor on the device of el, got %s" % (name, H, E, tuple(t.shape)))
+        raise RuntimeError("%s must be a contiguous fp32 [heads, num_edges] = [%d, %d] tensor on the device of %s, got %s" % (name, H, E, of, tuple(t.shape)))
 
 
 def gat_softmax(el, er, nodePointer, edgeList, negative_slope=0.2, out=None):
@@ -877,6 +880,84 @@ def edge_colsum(val, nodePointer, edgeList):
     N, H = nodePointer.numel() - 1, val.size(0)
     out = torch.empty(N, H, dtype=torch.float32, device=val.device)
     _call(_c.lib.tcgnn_edge_colsum, val.device, rp_t.data_ptr(), perm.data_ptr(), N, E, H, val.data_ptr(), out.data_ptr())
+    return out
+
+
+# ---- additions (not in the reference module): GATv2 attention ------------------------------------------------
+
+def _gatv2_args(xl, xr, attn, nodePointer, edgeList):
+    for t, n in ((xl, "xl"), (xr, "xr"), (attn, "attn")):
+        _check_input(t, n)
+        _check_float(t, n)
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    N = nodePointer.numel() - 1
+    if N < 0:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    if attn.dim() != 2 or attn.size(0) < 1 or attn.size(1) < 1:
+        raise RuntimeError("attn must be [heads, features] (heads >= 1, features >= 1), got %s" % (tuple(attn.shape),))
+    H, F = attn.size(0), attn.size(1)
+    if xl.dim() != 2 or xl.size(0) != N or xl.size(1) != H * F or xr.shape != xl.shape:
+        raise RuntimeError("xl and xr must be [num_nodes, heads * features] = [%d, %d], got %s and %s" % (N, H * F, tuple(xl.shape), tuple(xr.shape)))
+    if any(t.device != xl.device for t in (xr, attn, nodePointer, edgeList)):
+        raise RuntimeError("xl, xr, attn, nodePointer and edgeList must be on one device")
+    return N, edgeList.numel(), H, F
+
+
+def gatv2_softmax(xl, xr, attn, nodePointer, edgeList, negative_slope=0.2, out=None, score_out=None):
+    """Not in the reference module: GATv2's attention in one kernel (tcgnn_gatv2_softmax), p fp32 [heads, E] (the reference's
+    edgeAttention layout: p is what forward_heads takes),
+        s[h, e] = sum_f attn[h, f] leaky_relu(xl[col(e), hF + f] + xr[row(e), hF + f]),   p[h, .] = softmax of s[h, .] over every node's incoming edges.
+    xl / xr: fp32 [N, heads * F], the source- and the destination-side projection (they may be one tensor); attn: fp32 [heads, F].  No
+    [E, heads * F] tensor is formed: every neighbour row is gathered once, the score's sum is fp64 and rounded once.  score_out
+    (fp32 [heads, E]) receives the scores; p has the same bits with and without it.  Entries of positions no row covers are left as
+    allocated.  Deterministic: a second call returns the same bits."""
+    N, E, H, F = _gatv2_args(xl, xr, attn, nodePointer, edgeList)
+    if out is None:
+        out = torch.empty(H, E, dtype=torch.float32, device=xl.device)
+    else:
+        _head_major(out, "out", H, E, xl, "xl")
+    if score_out is not None:
+        _head_major(score_out, "score_out", H, E, xl, "xl")
+    _call(_c.lib.tcgnn_gatv2_softmax, xl.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, F, xl.data_ptr(), xr.data_ptr(), attn.data_ptr(),
+          float(negative_slope), _ptr(score_out), out.data_ptr())
+    return out
+
+
+def gatv2_softmax_backward(p, dp, xl, xr, attn, nodePointer, edgeList, negative_slope=0.2, out=None):
+    """Not in the reference module: the row side of gatv2_softmax's backward (tcgnn_gatv2_softmax_backward) - (g [heads, E], d_xr
+    [N, heads * F], d_attn [heads, F]) with z = xl[col e] + xr[row e] and
+        g = p (dp - sum_row p dp),   d_xr[i] = sum_{row i} g attn lrelu'(z),   d_attn[h, f] = sum_e g[h, e] leaky_relu(z)[hF + f]
+    out (g) may be dp itself.  d_xl is gatv2_source_grad(g, ...).  The partial sums of d_attn live in a buffer held per stream."""
+    N, E, H, F = _gatv2_args(xl, xr, attn, nodePointer, edgeList)
+    _head_major(p, "p", H, E, xl, "xl")
+    _head_major(dp, "dp", H, E, xl, "xl")
+    if out is None:
+        out = torch.empty_like(dp)
+    else:
+        _head_major(out, "out", H, E, xl, "xl")
+    dev = xl.device
+    d_xr = torch.empty(N, H * F, dtype=torch.float32, device=dev)
+    d_attn = torch.empty(H, F, dtype=torch.float32, device=dev)
+    scratch = _buffer("softmax", _c.lib.tcgnn_gatv2_workspace_bytes(N, E, H, F), dev)
+    _call(_c.lib.tcgnn_gatv2_softmax_backward, dev, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, H, F, xl.data_ptr(), xr.data_ptr(), attn.data_ptr(),
+          float(negative_slope), p.data_ptr(), dp.data_ptr(), out.data_ptr(), d_xr.data_ptr(), d_attn.data_ptr(), *scratch)
+    return out, d_xr, d_attn
+
+
+def gatv2_source_grad(g, xl, xr, attn, nodePointer, edgeList, negative_slope=0.2):
+    """Not in the reference module: the source side of gatv2_softmax's backward (tcgnn_gatv2_source_grad), fp32 [N, heads * F],
+        d_xl[j] = sum over the edges e with col(e) = j of g[., e] attn lrelu'(xl[j] + xr[row e])
+    - a walk over the rows of A^T in a fixed order (fp64 sums, no atomics); a node nobody reads gets 0.  g: what gatv2_softmax_backward
+    returned, in A's CSR order.  The transposed CSR is the module's cached one (transpose_graph): built at the first call for a graph,
+    or by prepare(..., transpose=True)."""
+    N, E, H, F = _gatv2_args(xl, xr, attn, nodePointer, edgeList)
+    _head_major(g, "g", H, E, xl, "xl")
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    out = torch.empty(N, H * F, dtype=torch.float32, device=xl.device)
+    _call(_c.lib.tcgnn_gatv2_source_grad, xl.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, H, F, xl.data_ptr(), xr.data_ptr(),
+          attn.data_ptr(), float(negative_slope), g.data_ptr(), out.data_ptr())
     return out
 
 

@@ -51,6 +51,8 @@
 //   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
+//   tcgnn_segment_max.inc     element-wise maximum over a row's edges and its backward over A^T (the wide-row gather: a lane group per neighbour row)
+//   tcgnn_gatv2.inc           GATv2 attention: fused score + softmax, the row-side backward (g, d_xr, d_attn), the source-side backward (d_xl)
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells (a cell stream in named steps over a
 //                             CellBuild; flat_entries, the entry records, is a pure host function; cells_publish cannot fail), build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
@@ -312,6 +314,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_edge_softmax.inc"
 #include "tcgnn_gat.inc"
 #include "tcgnn_segment_max.inc"
+#include "tcgnn_gatv2.inc"
 
 // ---- run-time switches.  Product: TCGNN_SPMM_MODE / TCGNN_RANGE_GUARD (initial values of tcgnn_set_spmm_mode / tcgnn_set_range_guard,
 // include/tcgnn.h) and TCGNN_VERBOSE (plan statistics on stderr).  TEST AIDS, read through test_knob() only - tests/ forces every walk

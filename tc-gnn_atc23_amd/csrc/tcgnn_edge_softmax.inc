@@ -104,13 +104,8 @@ __device__ __forceinline__ void es_fwd_row(const float* s, float* p, int64_t lo,
     }
 }
 
-__global__ __launch_bounds__(256) void edge_softmax_fwd_kernel(const int32_t* __restrict__ rowptr, int32_t N, int64_t E, const float* score,
-                                                               const float* __restrict__ beta, float* p) {
-    __shared__ int64_t sp[kEsRowsPerWg + 1];
-    __shared__ float redf[4];
-    __shared__ double redd[4];
-    es_load_rows(rowptr, N, E, sp);
-    const float b = beta ? beta[0] : 1.0f;
+// every row of the workgroup (sp: its 33 clamped row pointers), binned by length as the header says; score may be p itself
+__device__ __forceinline__ void es_fwd_rows(const int64_t* sp, const float* score, float* p, float b, float* redf, double* redd) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     {   // rows of 1 .. 16 edges: eight lanes each
         const int r = wave * kEsRowsPerWave + (lane >> 3);
@@ -145,6 +140,15 @@ __global__ __launch_bounds__(256) void edge_softmax_fwd_kernel(const int32_t* __
     }
 }
 
+__global__ __launch_bounds__(256) void edge_softmax_fwd_kernel(const int32_t* __restrict__ rowptr, int32_t N, int64_t E, const float* score,
+                                                               const float* __restrict__ beta, float* p) {
+    __shared__ int64_t sp[kEsRowsPerWg + 1];
+    __shared__ float redf[4];
+    __shared__ double redd[4];
+    es_load_rows(rowptr, N, E, sp);
+    es_fwd_rows(sp, score, p, beta ? beta[0] : 1.0f, redf, redd);
+}
+
 // ---- backward -----------------------------------------------------------------------------------------------------------------
 template <int W, int NK, bool DB>
 __device__ __forceinline__ void es_bwd_row(const float* __restrict__ p, const float* dp, const float* __restrict__ s, float* ds, int64_t lo,
@@ -172,16 +176,11 @@ __device__ __forceinline__ void es_bwd_row(const float* __restrict__ p, const fl
     }
 }
 
+// every row of the workgroup, binned as in forward; dbeta: this thread's share of sum s g (DB only).  score is read where DB
 template <bool DB>
-__global__ __launch_bounds__(256) void edge_softmax_bwd_kernel(const int32_t* __restrict__ rowptr, int32_t N, int64_t E, const float* __restrict__ p,
-                                                               const float* dp, const float* __restrict__ score, const float* __restrict__ beta,
-                                                               float* ds, double* __restrict__ partial) {
-    __shared__ int64_t sp[kEsRowsPerWg + 1];
-    __shared__ double redd[4];
-    es_load_rows(rowptr, N, E, sp);
-    const float b = beta ? beta[0] : 1.0f;
+__device__ __forceinline__ void es_bwd_rows(const int64_t* sp, const float* __restrict__ p, const float* dp, const float* __restrict__ score, float* ds,
+                                            float b, double* redd, double& dbeta) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    double dbeta = 0.0;
     {
         const int r = wave * kEsRowsPerWave + (lane >> 3);
         const int64_t lo = sp[r], len = sp[r + 1] - lo;
@@ -213,6 +212,17 @@ __global__ __launch_bounds__(256) void edge_softmax_bwd_kernel(const int32_t* __
             if constexpr (DB) dbeta += (double)score[e] * (double)g;
         }
     }
+}
+
+template <bool DB>
+__global__ __launch_bounds__(256) void edge_softmax_bwd_kernel(const int32_t* __restrict__ rowptr, int32_t N, int64_t E, const float* __restrict__ p,
+                                                               const float* dp, const float* __restrict__ score, const float* __restrict__ beta,
+                                                               float* ds, double* __restrict__ partial) {
+    __shared__ int64_t sp[kEsRowsPerWg + 1];
+    __shared__ double redd[4];
+    es_load_rows(rowptr, N, E, sp);
+    double dbeta = 0.0;
+    es_bwd_rows<DB>(sp, p, dp, score, ds, beta ? beta[0] : 1.0f, redd, dbeta);
     if constexpr (DB) {
         const double total = es_block_sum(dbeta, redd);
         if (threadIdx.x == 0) partial[blockIdx.x] = total;

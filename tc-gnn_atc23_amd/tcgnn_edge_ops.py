@@ -7,6 +7,8 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate(P, H, meta)         Y = A_val(P) H                           bwd: dP = sddmm(dY, H),  dH = A_val(P)^T dY
     gat_attention(el, er, rowptr, col, slope)  P[h] = softmax by row of leaky_relu(el[col e, h] + er[row e, h])   (multi-head GAT)
                                   bwd: g as above per head; ds = g lrelu'(raw); d_er = row sums of ds; d_el = column sums of ds
+    gatv2_attention(xl, xr, attn, rowptr, col, slope)  P[h] = softmax by row of <attn[h], leaky_relu(xl[col e, head h] + xr[row e, head h])>   (GATv2)
+                                  bwd: g as above per head; d_xr, d_attn by row and d_xl over A^T, from the backend's two GATv2 backward calls
     aggregate_heads(P, Z, meta)   Y[:, head h] = A_val(P[h]) Z[:, head h], all heads in one call   bwd: dP = sddmm_heads(dY, Z), dZ through A^T, one call each
     sddmm_heads(X, Z, meta, H)    ef[h, e] = <X[row e, head h], Z[col e, head h]>, [H, E], one call  bwd: dX = A_val(d_ef) Z, dZ = A_val(d_ef)^T X per head, one call each
     edge_softmax_heads(S, rowptr, beta)  edge_softmax of every row of S [H, E] (head by head on the one-head operator, one [H, E] result)
@@ -17,7 +19,7 @@ edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, als
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max and backward_max.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -107,6 +109,33 @@ class _GATAttention(torch.autograd.Function):
         ds, d_er = b.gat_softmax_backward(p, d_p, el, er, *ctx.graph, ctx.slope)
         d_el = b.edge_colsum(ds, *ctx.graph) if ctx.needs_input_grad[0] else None
         return d_el, (d_er if ctx.needs_input_grad[1] else None), None, None, None
+
+
+class _GATv2Attention(torch.autograd.Function):
+    """P = gatv2_softmax(xl, xr, attn); (g, d_xr, d_attn) = gatv2_softmax_backward, d_xl = gatv2_source_grad(g) over A^T.  shared: xl and xr
+    are ONE tensor (a layer with share_weights), given once - its gradient is the sum of both sides."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, attn, row_pointers, column_index, negative_slope, shared):
+        xl = xl.contiguous()
+        xr = xl if shared else xr.contiguous()
+        attn = attn.contiguous()
+        p = _L.backend().gatv2_softmax(xl, xr, attn, row_pointers, column_index, negative_slope)
+        ctx.graph = (row_pointers, column_index)
+        ctx.slope, ctx.shared = negative_slope, shared
+        ctx.save_for_backward(*((p, xl, attn) if shared else (p, xl, attn, xr)))
+        return p
+
+    @staticmethod
+    def backward(ctx, d_p):
+        p, xl, attn = ctx.saved_tensors[:3]
+        xr = xl if ctx.shared else ctx.saved_tensors[3]
+        b = _L.backend()
+        g, d_xr, d_attn = b.gatv2_softmax_backward(p, d_p.contiguous(), xl, xr, attn, *ctx.graph, ctx.slope)
+        d_xl = b.gatv2_source_grad(g, xl, xr, attn, *ctx.graph, ctx.slope) if ctx.needs_input_grad[0] else None
+        if ctx.shared:
+            return (d_xl + d_xr if d_xl is not None else None), None, (d_attn if ctx.needs_input_grad[2] else None), None, None, None, None
+        return d_xl, (d_xr if ctx.needs_input_grad[1] else None), (d_attn if ctx.needs_input_grad[2] else None), None, None, None, None
 
 
 class _AggregateHeads(torch.autograd.Function):
@@ -220,6 +249,17 @@ def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):
     """P[h, e] = softmax over every CSR row of leaky_relu(el[col e, h] + er[row e, h]): GAT's attention, [heads, E] (head-major: P[h] is
     what aggregate takes).  el / er: [N, heads].  bwd: (ds, d_er) from the backend's gat_softmax_backward, d_el = edge_colsum(ds)."""
     return _GATAttention.apply(el, er, row_pointers, column_index, float(negative_slope))
+
+
+def gatv2_attention(xl, xr, attn, row_pointers, column_index, negative_slope=0.2):
+    """P[h, e] = softmax over every CSR row of sum_f attn[h, f] leaky_relu(xl[col e, hF + f] + xr[row e, hF + f]): GATv2's attention,
+    [heads, E] head-major (what aggregate_heads takes).  xl / xr: [N, heads * F], attn: [heads, F].  One fused kernel forward (no
+    [E, heads * F] tensor), two backward: (g, d_xr, d_attn) by row, d_xl over A^T - exact on any graph.  When xl and xr are the same
+    tensor its gradient is the sum of both sides."""
+    if attn.dim() != 2 or xl.dim() != 2 or xl.shape != xr.shape or xl.shape[1] != attn.shape[0] * attn.shape[1]:
+        raise RuntimeError("xl and xr must be [N, heads * F] and attn [heads, F], got %s, %s and %s" % (tuple(xl.shape), tuple(xr.shape), tuple(attn.shape)))
+    shared = xl is xr
+    return _GATv2Attention.apply(xl, None if shared else xr, attn, row_pointers, column_index, float(negative_slope), shared)
 
 
 def aggregate_heads(P, Z, meta):

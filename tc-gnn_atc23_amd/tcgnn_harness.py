@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "sage", "transformer"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -52,7 +52,7 @@ def build_parser():
     p.add_argument("--attention", type=str, default="reference", choices=["reference", "softmax"],
                    help="AGNN only: 'softmax' normalises the cosine scores over every node's incoming edges (DGL's AGNNConv; exact gradients) - "
                    "not in the reference, whose layer aggregates with the raw scores")
-    p.add_argument("--heads", type=int, default=1, help="GAT and transformer only: attention heads of the hidden layers, which concatenate `heads` heads of "
+    p.add_argument("--heads", type=int, default=1, help="GAT, GATv2 and transformer only: attention heads of the hidden layers, which concatenate `heads` heads of "
                    "hidden / heads features (it must divide); the output layer has one head of `classes` (not in the reference)")
     p.add_argument("--aggregator", type=str, default="mean", choices=["mean", "max", "pool"],
                    help="SAGE only: GraphSAGE's neighbour aggregation - 'mean', or the element-wise maximum over a node's incoming edges of the "
@@ -140,12 +140,12 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     norm / bias (GCN only, not in the reference): GCNConv(norm=..., bias=...), DGL GraphConv's normalised layer.
     directed (not in the reference): every layer with directed=True (backward through A^T), and A^T's plan prepared with A's.
     attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers.
-    heads (GAT and transformer only, not in the reference): the hidden layers are GATConv / TransformerConv(., hidden / heads, heads=heads) -
+    heads (GAT, GATv2 and transformer only, not in the reference): the hidden layers are GATConv / GATv2Conv / TransformerConv(., hidden / heads, heads=heads) -
     concatenated back to `hidden` - and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths.
     aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks."""
     import tcgnn_layers as L
     heads = int(heads)
-    multi_head = model_name in ("gat", "transformer")
+    multi_head = model_name in ("gat", "gatv2", "transformer")
     if heads != 1 and not multi_head:
         raise ValueError("heads applies to the multi-head attention models - the transformer and the GAT model only")
     if multi_head and (heads < 1 or hidden % heads):
@@ -155,6 +155,10 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         def conv_cls(a, b):
             return L.GATConv(a, b // heads, heads=heads)
         out_cls = L.GATConv
+    elif model_name == "gatv2":
+        def conv_cls(a, b):
+            return L.GATv2Conv(a, b // heads, heads=heads)
+        out_cls = L.GATv2Conv
     elif model_name == "transformer":
         def conv_cls(a, b):
             return L.TransformerConv(a, b // heads, heads=heads)
@@ -177,7 +181,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
             raise ValueError("attention applies to the AGNN model only")
         conv_kwargs["attention"] = attention
     if multi_head:
-        conv_kwargs.pop("directed", None)   # (GATConv and TransformerConv back-propagate through A^T on every graph)
+        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv and TransformerConv back-propagate through A^T on every graph)
     model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 

@@ -10,7 +10,7 @@ gnn_conv.py:26-247, so a model written against the reference runs against this f
                         bwd: G = A_att dY; dX = G W^T; dW = X^T G;
                              da = (sddmm(dY)[None,:] @ col[:,None].float())^T
     SAG / GCNConv / GINConv / AGNNConv modules, n_heads = 1                                    (:10, :167-247)
-    GATConv, SAGEConv (not in the reference: DGL's layers of those names)
+    GATConv, GATv2Conv, SAGEConv (not in the reference: DGL's layers of those names)
 
 The reference's backward uses A, not A^T (it assumes a symmetric graph) and does not propagate
 through ef into H; both are reproduced because the golden fixtures captured from gnn_conv.py
@@ -645,6 +645,55 @@ class GATConv(torch.nn.Module):
         el, er = (Zh * self.attn_l).sum(-1), (Zh * self.attn_r).sum(-1)
         P = E.gat_attention(el, er, row_pointers, column_index, self.negative_slope)
         Y = E.aggregate_heads(P, Z, meta)
+        if not self.concat:
+            Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
+        return Y + self.bias if self.bias is not None else Y
+
+
+class GATv2Conv(torch.nn.Module):
+    """Not in the reference: DGL's GATv2Conv (Brody et al.) - GAT with the non-linearity IN FRONT of the attention vector, so that the
+    ranking of a node's neighbours depends on the node:
+        Zl = X W_l,  Zr = X W_r  [N, heads * output_dim]  (share_weights: W_r is W_l, one product);
+        P[h, e] = softmax by row of <attn_h, leaky_relu(Zl_h[col e] + Zr_h[row e])>;   Y_h = A_val(P[h]) Zl_h
+    (tcgnn_edge_ops.gatv2_attention - one fused kernel, no [E, heads * output_dim] tensor - and aggregate_heads; gradients exact on
+    any graph).  As in GATConv the projections carry no bias and there is one output bias; the heads are concatenated
+    ([N, heads * output_dim]) or, with concat=False, averaged ([N, output_dim]); then the bias is added: a node without incoming edges
+    gets the bias only.  Glorot initialisation as in GATConv (normal, gain sqrt 2; bias zero).  No dropout, no residual."""
+
+    def __init__(self, input_dim, output_dim, heads=1, negative_slope=0.2, concat=True, bias=True, share_weights=False):
+        super().__init__()
+        if heads < 1:
+            raise ValueError("heads must be >= 1, got %r" % (heads,))
+        self.heads, self.output_dim, self.negative_slope, self.concat = int(heads), int(output_dim), float(negative_slope), bool(concat)
+        self.share_weights = bool(share_weights)
+        self.weights = torch.nn.Parameter(torch.empty(input_dim, self.heads * self.output_dim))
+        if self.share_weights:
+            self.register_parameter("weights_r", None)
+        else:
+            self.weights_r = torch.nn.Parameter(torch.empty(input_dim, self.heads * self.output_dim))
+        self.attn = torch.nn.Parameter(torch.empty(1, self.heads, self.output_dim))
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(self.heads * self.output_dim if self.concat else self.output_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        torch.nn.init.xavier_normal_(self.weights, gain=gain)
+        if self.weights_r is not None:
+            torch.nn.init.xavier_normal_(self.weights_r, gain=gain)
+        torch.nn.init.xavier_normal_(self.attn, gain=gain)
+        if self.bias is not None:
+            self.bias.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        Zl = dense_update(X, self.weights)
+        Zr = Zl if self.share_weights else dense_update(X, self.weights_r)
+        P = E.gatv2_attention(Zl, Zr, self.attn.view(self.heads, self.output_dim), row_pointers, column_index, self.negative_slope)
+        Y = E.aggregate_heads(P, Zl, meta)
         if not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
         return Y + self.bias if self.bias is not None else Y
