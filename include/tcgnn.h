@@ -516,6 +516,36 @@ int tcgnn_segment_max_backward(const int32_t* d_nodePointer_t, const int32_t* d_
                                int32_t num_nodes, int64_t num_edges, const int32_t* d_arg, const float* d_dY, int32_t D,
                                float* d_dX, void* stream);
 
+/* ---- mean, standard deviation, maximum and minimum over a node's incoming edges in one walk (PNA's aggregators; no counterpart in
+ * the reference) ----
+ *
+ * The conventions of tcgnn_segment_max: the same arrays, clamps, alignment rule (d_X; in backward d_a, d_b, d_argmax and d_argmin,
+ * as far as they are given), degenerate sizes and refusals.  One gather of every neighbour row feeds all the outputs that are given.
+ *   tcgnn_segment_stats           for a row i with k > 0 edges and x_e = X[col(e), d]:  mean = sum x_e / k;  std = sqrt(max(var, 0) + eps)
+ *                                 with var the population variance (divided by k);  max / argmax exactly tcgnn_segment_max's;  min /
+ *                                 argmin the mirror image (numpy.argmin: the smaller value, among equal values the smaller position, a NaN
+ *                                 beats every number, among NaNs the first).  A row without edges: +0 in all four value outputs - std
+ *                                 included - and -1 in both args.  Any output may be NULL: nothing is computed or written for it;
+ *                                 d_argmax without d_max, d_argmin without d_min or no output at all is TCGNN_ERR_INVALID_ARG.
+ *                                 The moments are fp64 sums of t = x_e - s and t^2 from the fp32 inputs, s = X[col(rowptr[i]), d] the row's
+ *                                 first neighbour:  mean = s + S1 / k,  var = S2 / k - (S1 / k)^2, each rounded to fp32 once.
+ *   tcgnn_segment_stats_backward  over the rows of A^T (what tcgnn_transpose_ws wrote), with i = edgeList_t[eT] and e = perm[eT]:
+ *                                 dZ[j,d] = sum over eT in row j of  a[i,d] + b[i,d] Z[j,d] + [argmax[i,d] == e] dmax[i,d]
+ *                                                                    + [argmin[i,d] == e] dmin[i,d],
+ *                                 the terms formed and summed in fp64 in a fixed order, rounded once.  The caller folds the gradients of
+ *                                 mean and std into a and b per destination row (k > 0):  b = d_std / (k std),  a = d_mean / k - b mean.
+ *                                 Nullable groups: d_a;  d_b with d_Z;  d_argmax with d_dmax;  d_argmin with d_dmin - half of a group is
+ *                                 TCGNN_ERR_INVALID_ARG; with every group NULL dZ is zeroed.  dmax / dmin are read only where the arg
+ *                                 names the edge. */
+int tcgnn_segment_stats(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                        const float* d_X, int32_t D, float eps,
+                        float* d_mean, float* d_std, float* d_max, int32_t* d_argmax, float* d_min, int32_t* d_argmin, void* stream);
+int tcgnn_segment_stats_backward(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm,
+                                 int32_t num_nodes, int64_t num_edges, const float* d_Z,
+                                 const float* d_a, const float* d_b,
+                                 const int32_t* d_argmax, const float* d_dmax, const int32_t* d_argmin, const float* d_dmin,
+                                 int32_t D, float* d_dZ, void* stream);
+
 /* ---- GATv2 attention (Brody et al.; DGL's / PyG's GATv2Conv; no counterpart in the reference) -------------------------------------
  *
  * CSR row = destination node, column = source node.  d_xl (read at col(e)) and d_xr (read at row(e)) are fp32 [num_nodes, H F]

@@ -14,6 +14,8 @@
 #include <algorithm>
 #include <cstdio>
 #include <list>
+#include <map>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -588,6 +590,96 @@ torch::Tensor backward_max(torch::Tensor dY, torch::Tensor arg, torch::Tensor no
   return dX;
 }
 
+// ---- not in the reference: mean / std / max / min over a node's incoming edges in one walk (tcgnn_segment_stats / _backward; the
+// ctypes module's forward_stats and backward_stats, whose element-wise steps these repeat operation for operation) -----------------
+namespace {
+using TensorMap = std::map<std::string, c10::optional<torch::Tensor>>;
+bool stats_name(const std::string& a) { return a == "mean" || a == "std" || a == "max" || a == "min"; }
+const torch::Tensor* given(const TensorMap& m, const char* key) {
+  auto it = m.find(key);
+  return it != m.end() && it->second.has_value() ? &*it->second : nullptr;
+}
+const torch::Tensor& saved_tensor(const TensorMap& m, const char* key) {
+  const torch::Tensor* t = given(m, key);
+  TORCH_CHECK(t != nullptr, "saved has no '", key, "'");
+  return *t;
+}
+template <typename T>
+const T* ptr_or_null(const torch::Tensor* t) { return t ? t->data_ptr<T>() : nullptr; }
+}  // namespace
+
+py::dict forward_stats(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList, std::vector<std::string> aggregators, double eps,
+                       bool return_arg) {
+  if (aggregators.empty()) throw py::value_error("aggregators must name at least one of mean, std, max, min");
+  for (const std::string& a : aggregators)
+    if (!stats_name(a)) throw py::value_error("aggregators must be among mean, std, max, min, got '" + a + "'");
+  auto [N, E, D] = max_args(input, "input", nodePointer, edgeList);
+  DeviceGuard guard(input.device());
+  auto asked = [&](const char* a) { return std::find(aggregators.begin(), aggregators.end(), a) != aggregators.end(); };
+  std::map<std::string, torch::Tensor> out;
+  for (const char* a : {"mean", "std", "max", "min"})
+    if (asked(a)) out[a] = torch::empty({(int64_t)N, (int64_t)D}, input.options());
+  if (return_arg)
+    for (const char* a : {"max", "min"})
+      if (asked(a)) out[std::string("arg") + a] = torch::empty({(int64_t)N, (int64_t)D}, input.options().dtype(torch::kInt32));
+  auto f = [&](const char* k) { auto it = out.find(k); return it != out.end() ? it->second.data_ptr<float>() : nullptr; };
+  auto i = [&](const char* k) { auto it = out.find(k); return it != out.end() ? it->second.data_ptr<int>() : nullptr; };
+  if (N && D)   // (a tensor without elements has no address to give)
+    tcgnn_check(tcgnn_segment_stats(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, input.data_ptr<float>(), D, (float)eps, f("mean"), f("std"),
+                                    f("max"), i("argmax"), f("min"), i("argmin"), current_stream(input)), "tcgnn_segment_stats");
+  py::dict d;
+  for (auto& kv : out) d[py::str(kv.first)] = kv.second;
+  return d;
+}
+
+torch::Tensor backward_stats(TensorMap grads, TensorMap saved, torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<torch::Tensor> out) {
+  for (auto& kv : grads)
+    if (!stats_name(kv.first)) throw py::value_error("grads must be keyed by mean, std, max, min, got '" + kv.first + "'");
+  const torch::Tensor& Z = saved_tensor(saved, "Z");
+  auto [N, E, D] = max_args(Z, "Z", nodePointer, edgeList);
+  for (auto& kv : grads)
+    if (kv.second.has_value()) {
+      CHECK_INPUT((*kv.second));
+      TORCH_CHECK(kv.second->scalar_type() == torch::kFloat32, "expected scalar type Float");
+      TORCH_CHECK(kv.second->sizes() == Z.sizes() && kv.second->device() == Z.device(), "grads['", kv.first, "'] must have the shape and device of Z");
+    }
+  const torch::Tensor *g_mean = given(grads, "mean"), *g_std = given(grads, "std"), *g_max = given(grads, "max"), *g_min = given(grads, "min");
+  const torch::Tensor *argmax = nullptr, *argmin = nullptr;
+  for (auto [g, key, slot] : {std::make_tuple(g_max, "argmax", &argmax), std::make_tuple(g_min, "argmin", &argmin)})
+    if (g) {
+      const torch::Tensor& arg = saved_tensor(saved, key);
+      CHECK_INPUT(arg);
+      TORCH_CHECK(arg.scalar_type() == torch::kInt32, "expected scalar type Int");
+      TORCH_CHECK(arg.sizes() == Z.sizes() && arg.device() == Z.device(), key, " must have the shape and device of Z");
+      *slot = &arg;
+    }
+  torch::Tensor dZ = out_like(out, Z, "Z");
+  if (!(N && D)) return dZ;
+  DeviceGuard guard(Z.device());
+  torch::Tensor a, b;
+  if (g_mean || g_std) {
+    using torch::indexing::Slice;
+    using torch::indexing::None;
+    torch::Tensor hi = nodePointer.index({Slice(1, None)}), lo = nodePointer.index({Slice(None, -1)});
+    torch::Tensor has = (hi > lo).unsqueeze(1);
+    torch::Tensor inv_k = has.to(torch::kFloat32) / (hi - lo).clamp_min(1).to(torch::kFloat32).unsqueeze(1);
+    if (g_std) {
+      b = (*g_std * inv_k) / torch::where(has, saved_tensor(saved, "std"), 1.0);
+      const torch::Tensor& mean = saved_tensor(saved, "mean");
+      a = g_mean ? (*g_mean * inv_k - b * mean) : -(b * mean);
+    } else {
+      a = *g_mean * inv_k;
+    }
+  }
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_segment_stats_backward(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E,
+                                           b.defined() ? Z.data_ptr<float>() : nullptr, a.defined() ? a.data_ptr<float>() : nullptr,
+                                           b.defined() ? b.data_ptr<float>() : nullptr, ptr_or_null<int>(argmax), ptr_or_null<float>(g_max),
+                                           ptr_or_null<int>(argmin), ptr_or_null<float>(g_min), D, dZ.data_ptr<float>(), current_stream(Z)),
+              "tcgnn_segment_stats_backward");
+  return dZ;
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -713,6 +805,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("return_arg") = true, py::arg("out") = py::none());
   m.def("backward_max", &backward_max, "backward of forward_max: dX (not in the reference)", py::arg("dY"), py::arg("arg"), py::arg("nodePointer"),
         py::arg("edgeList"), py::arg("out") = py::none());
+  m.def("forward_stats", &forward_stats, "mean / std / max / min over every node's incoming edges in one walk: a dict (not in the reference)",
+        py::arg("input"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("aggregators") = std::vector<std::string>{"mean", "std", "max", "min"},
+        py::arg("eps") = 1e-5, py::arg("return_arg") = true);
+  m.def("backward_stats", &backward_stats, "backward of forward_stats: dZ (not in the reference)", py::arg("grads"), py::arg("saved"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("out") = py::none());
   m.def("gatv2_softmax", &gatv2_softmax, "GATv2 attention, p[heads, E] (not in the reference)", py::arg("xl"), py::arg("xr"), py::arg("attn"),
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2, py::arg("out") = py::none(), py::arg("score_out") = py::none());
   m.def("gatv2_softmax_backward", &gatv2_softmax_backward, "row side of gatv2_softmax's backward: (g, d_xr, d_attn) (not in the reference)", py::arg("p"),

@@ -36,7 +36,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
-           "forward_max", "backward_max", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad"]
+           "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad"]
 
 
 def _stream(device):
@@ -277,8 +277,9 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     edge-valued streams of A and A^T at that width (what a layer of ONE head runs on), the two-image SDDMM workspace, with A^T's
     plan the transposed CSR edge_colsum sums over, and - heads > 1 - the workspaces of forward_ef_heads and of forward_heads at H heads of every width in
     `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream.
-    max_aggregation=True (a model with forward_max / backward_max: SAGEConv's max and pool aggregators): the transposed CSR backward_max
-    walks, built now (transpose_graph: the graph's one transpose) - the two calls are planless and need nothing else."""
+    max_aggregation=True (a model with forward_max / backward_max: SAGEConv's max and pool aggregators - or with forward_stats /
+    backward_stats: PNAConv): the transposed CSR backward_max and backward_stats walk, built now (transpose_graph: the graph's one
+    transpose) - the calls are planless and need nothing else."""
     if max_aggregation:
         transpose_graph(nodePointer, edgeList)
     e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
@@ -1005,6 +1006,90 @@ def backward_max(dY, arg, nodePointer, edgeList, out=None):
     rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
     _call(_c.lib.tcgnn_segment_max_backward, dY.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, arg.data_ptr(), dY.data_ptr(), D,
           out.data_ptr())
+    return out
+
+
+# ---- additions (not in the reference module): mean / std / max / min over a node's incoming edges in one walk (PNA) --------
+
+STATS_AGGREGATORS = ("mean", "std", "max", "min")
+
+
+def _stats_names(aggregators):
+    names = (aggregators,) if isinstance(aggregators, str) else tuple(aggregators)
+    for a in names:
+        if a not in STATS_AGGREGATORS:
+            raise ValueError("aggregators must be among %s, got %r" % (", ".join(STATS_AGGREGATORS), a))
+    if not names:
+        raise ValueError("aggregators must name at least one of %s" % ", ".join(STATS_AGGREGATORS))
+    return names
+
+
+def forward_stats(input, nodePointer, edgeList, aggregators=STATS_AGGREGATORS, eps=1e-5, return_arg=True):
+    """Not in the reference module: the aggregators of PNA over every node's incoming edges from ONE gather of the neighbour rows
+    (tcgnn_segment_stats) - a dict with the keys named in `aggregators` (among 'mean', 'std', 'max', 'min'; fp32 [N, D]) and, with
+    return_arg, 'argmax' / 'argmin' (int32 [N, D]: the CSR position that supplied the value) for the extrema asked for.
+        mean = sum x / k;   std = sqrt(max(var, 0) + eps), var the population variance;   max / argmax as forward_max;
+        min / argmin its mirror image (numpy.argmin; a NaN beats every number).
+    input is read as fp32; the moments are fp64 sums shifted by the row's first neighbour, rounded once.  A row without edges: 0 in
+    every value (std too), -1 in the args.  Deterministic, no atomics.  An unknown aggregator name raises ValueError."""
+    names = _stats_names(aggregators)
+    N, E, D = _max_args(input, "input", nodePointer, edgeList)
+    dev = input.device
+    out = {a: torch.empty(N, D, dtype=torch.float32, device=dev) for a in STATS_AGGREGATORS if a in names}
+    if return_arg:
+        out.update({"arg" + a: torch.empty(N, D, dtype=torch.int32, device=dev) for a in ("max", "min") if a in names})
+    if N and D:   # (a tensor without elements has no address to give)
+        _call(_c.lib.tcgnn_segment_stats, dev, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, input.data_ptr(), D, float(eps),
+              *[_ptr(out.get(k)) for k in ("mean", "std", "max", "argmax", "min", "argmin")])
+    return out
+
+
+def backward_stats(grads, saved, nodePointer, edgeList, out=None):
+    """Not in the reference module: the gradient of forward_stats with respect to its input (tcgnn_segment_stats_backward), one
+    walk over the rows of A^T in a fixed order (fp64 terms and sums, no atomics).  grads: aggregator name -> dY fp32 [N, D] (entries
+    may be missing or None); saved: 'Z' (the forward's input) and, as far as those aggregators have a gradient, 'mean', 'std',
+    'argmax', 'argmin' as forward_stats returned them.  With k the row's edge count, on rows with k > 0
+        b = d_std / (k std),   a = d_mean / k - b mean      (both 0 on a row without edges)
+    are formed here with fp32 element-wise operations on [N, D] tensors, and
+        dZ[j, d] = sum over the edges (i <- j) at CSR position e of  a[i, d] + b[i, d] Z[j, d] + [argmax[i, d] == e] d_max[i, d]
+                                                                     + [argmin[i, d] == e] d_min[i, d].
+    Conditioning: mean is stored in fp32, so the std gradient a + b Z = b (Z - mean) loses about |mean| / std * 2^-24 of relative
+    accuracy - as in any fp32 implementation.  The transposed CSR is the module's cached one (transpose_graph): built at the first
+    call for a graph, or by prepare(..., max_aggregation=True)."""
+    for k in grads:
+        if k not in STATS_AGGREGATORS:
+            raise ValueError("grads must be keyed by %s, got %r" % (", ".join(STATS_AGGREGATORS), k))
+    g = {k: v for k, v in grads.items() if v is not None}
+    Z = saved["Z"]
+    N, E, D = _max_args(Z, "Z", nodePointer, edgeList)
+    for k, v in g.items():
+        _check_input(v, "grads[%r]" % k)
+        _check_float(v, "grads[%r]" % k)
+        if v.shape != Z.shape or v.device != Z.device:
+            raise RuntimeError("grads[%r] must have the shape and device of Z" % k)
+    for k in ("max", "min"):
+        if k in g:
+            arg = saved["arg" + k]
+            _check_input(arg, "arg" + k)
+            _check_int(arg, "arg" + k)
+            if arg.shape != Z.shape or arg.device != Z.device:
+                raise RuntimeError("arg%s must have the shape and device of Z" % k)
+    out = _out_like(out, Z, "Z")
+    if not (N and D):
+        return out
+    a = b = None
+    if "mean" in g or "std" in g:
+        has = (nodePointer[1:] > nodePointer[:-1]).unsqueeze(1)
+        inv_k = has.to(torch.float32) / (nodePointer[1:] - nodePointer[:-1]).clamp(min=1).to(torch.float32).unsqueeze(1)   # 1 / k, 0 on a row without edges
+        if "std" in g:
+            b = (g["std"] * inv_k) / torch.where(has, saved["std"], 1.0)   # (std is 0 on a row without edges: keep 0 / 0 out)
+            a = (g["mean"] * inv_k - b * saved["mean"]) if "mean" in g else -(b * saved["mean"])
+        else:
+            a = g["mean"] * inv_k
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_segment_stats_backward, Z.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, Z.data_ptr() if b is not None else None,
+          _ptr(a), _ptr(b), saved["argmax"].data_ptr() if "max" in g else None, _ptr(g.get("max")), saved["argmin"].data_ptr() if "min" in g else None,
+          _ptr(g.get("min")), D, out.data_ptr())
     return out
 
 

@@ -91,6 +91,8 @@ SIGNATURES = {
     "tcgnn_edge_colsum": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _i32, _vp, _vp, _vp]),
     "tcgnn_segment_max": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     "tcgnn_segment_max_backward": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i64, _vp, _vp, _i32, _vp, _vp]),
+    "tcgnn_segment_stats": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tcgnn_segment_stats_backward": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "tcgnn_gatv2_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),
     "tcgnn_gatv2_softmax": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _i32, _i32, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
     "tcgnn_gatv2_softmax_backward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _i32, _i32, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,

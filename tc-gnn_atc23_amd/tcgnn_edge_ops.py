@@ -13,13 +13,14 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     sddmm_heads(X, Z, meta, H)    ef[h, e] = <X[row e, head h], Z[col e, head h]>, [H, E], one call  bwd: dX = A_val(d_ef) Z, dZ = A_val(d_ef)^T X per head, one call each
     edge_softmax_heads(S, rowptr, beta)  edge_softmax of every row of S [H, E] (head by head on the one-head operator, one [H, E] result)
     aggregate_max(X, rowptr, col) Y[i, d] = max over row i of X[col e, d] (0 for an empty row)     bwd: dX[j, d] = sum of dY[i, d] over the edges that won (i, d)
+    aggregate_stats(Z, rowptr, col, aggregators)  mean / std / max / min over row i of Z[col e, d], one gather for all (PNA)     bwd: one walk over A^T for all of them
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max, backward_max and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -243,6 +244,41 @@ def aggregate_max(X, row_pointers, column_index):
     Exact (fp32 in, the winner's bits out); among equal values the first edge of the row wins, and only it receives the gradient:
     dX[j, d] = the sum of dY[i, d] over the edges (i <- j) that won element (i, d) - a fixed-order walk over A^T, no atomics."""
     return _AggregateMax.apply(X, row_pointers, column_index)
+
+
+class _AggregateStats(torch.autograd.Function):
+    """forward_stats(Z) of the named aggregators; saved: Z, mean and std (where std is asked for) and the args - nothing of size E."""
+
+    @staticmethod
+    def forward(ctx, Z, row_pointers, column_index, names, eps):
+        Z = Z.contiguous()
+        # (the gradient of std needs the mean: one more output of the same walk)
+        asked = names + (("mean",) if "std" in names and "mean" not in names else ())
+        r = _L.backend().forward_stats(Z, row_pointers, column_index, aggregators=asked, eps=eps)
+        ctx.graph, ctx.names = (row_pointers, column_index), names
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(Z, *(r.get(k) if k in ("argmax", "argmin") or "std" in names else None for k in ("mean", "std", "argmax", "argmin")))
+        return tuple(r[a] for a in names)
+
+    @staticmethod
+    def backward(ctx, *d):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 5
+        Z, mean, std, argmax, argmin = ctx.saved_tensors
+        grads = {a: g.contiguous() for a, g in zip(ctx.names, d) if g is not None}
+        saved = {"Z": Z, "mean": mean, "std": std, "argmax": argmax, "argmin": argmin}
+        return (_L.backend().backward_stats(grads, saved, *ctx.graph),) + (None,) * 4
+
+
+def aggregate_stats(Z, row_pointers, column_index, aggregators=("mean", "std", "max", "min"), eps=1e-5):
+    """PNA's aggregators over the edges of every CSR row (a node's incoming edges) from one gather of the neighbour rows: a tuple of
+    [N, D] tensors in the order of `aggregators` (among 'mean', 'std', 'max', 'min'; std = sqrt(max(var, 0) + eps), population
+    variance).  A row without edges gives 0 in every one.  max and min are exact and send their gradient to the first edge that
+    holds the value; the backward is one fixed-order walk over A^T for all of them (the backend's backward_stats), no atomics."""
+    names = (aggregators,) if isinstance(aggregators, str) else tuple(aggregators)
+    if not names or len(set(names)) != len(names) or any(a not in ("mean", "std", "max", "min") for a in names):
+        raise ValueError("aggregators must be distinct names among mean, std, max, min, got %r" % (aggregators,))
+    return _AggregateStats.apply(Z, row_pointers, column_index, names, float(eps))
 
 
 def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):

@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -142,7 +142,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     attention (AGNN only, not in the reference): AGNNConv(attention=...); 'softmax' prepares A^T's plan and the edge operators' buffers.
     heads (GAT, GATv2 and transformer only, not in the reference): the hidden layers are GATConv / GATv2Conv / TransformerConv(., hidden / heads, heads=heads) -
     concatenated back to `hidden` - and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths.
-    aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks."""
+    aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks.
+    model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max."""
     import tcgnn_layers as L
     heads = int(heads)
     multi_head = model_name in ("gat", "gatv2", "transformer")
@@ -169,7 +170,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     else:
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
-        conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv}[model_name]
+        conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv}[model_name]
     torch.manual_seed(seed)
     if model_name != "gcn" and (norm != "none" or bias):
         raise ValueError("norm / bias apply to the GCN model only")
@@ -180,8 +181,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if model_name != "agnn":
             raise ValueError("attention applies to the AGNN model only")
         conv_kwargs["attention"] = attention
-    if multi_head:
-        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv and TransformerConv back-propagate through A^T on every graph)
+    if multi_head or model_name == "pna":
+        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv and PNAConv back-propagate through A^T on every graph)
     model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
@@ -199,6 +200,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
         prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
              **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
+    elif prep is not None and meta[0].is_cuda and model_name == "pna":
+        prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats are planless: the transposed CSR is all they need)
     elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
         prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
              **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if multi_head else

@@ -10,7 +10,7 @@ gnn_conv.py:26-247, so a model written against the reference runs against this f
                         bwd: G = A_att dY; dX = G W^T; dW = X^T G;
                              da = (sddmm(dY)[None,:] @ col[:,None].float())^T
     SAG / GCNConv / GINConv / AGNNConv modules, n_heads = 1                                    (:10, :167-247)
-    GATConv, GATv2Conv, SAGEConv (not in the reference: DGL's layers of those names)
+    GATConv, GATv2Conv, SAGEConv, PNAConv (not in the reference: DGL's / PyG's layers of those names)
 
 The reference's backward uses A, not A^T (it assumes a symmetric graph) and does not propagate
 through ef into H; both are reproduced because the golden fixtures captured from gnn_conv.py
@@ -819,3 +819,80 @@ class SAGEConv(torch.nn.Module):
                 X = torch.relu(dense_update(X, self.weights_pool) + self.bias_pool)
             out = out + dense_update(E.aggregate_max(X, row_pointers, column_index), self.weights)
         return out + self.bias if self.bias is not None else out
+
+
+PNA_AGGREGATORS = ("mean", "std", "max", "min")
+PNA_SCALERS = ("identity", "amplification", "attenuation")
+
+
+def pna_delta(row_pointers):
+    """PNA's delta of a graph: the mean of log(deg + 1) over its nodes, deg the in-degree (a row's edge count) - a 0-dim fp32 tensor on
+    row_pointers' device (no synchronisation)."""
+    deg = (row_pointers[1:] - row_pointers[:-1]).clamp(min=0).to(torch.float32)
+    return torch.log(deg + 1).mean()
+
+
+class PNAConv(torch.nn.Module):
+    """Not in the reference: Principal Neighbourhood Aggregation after PyG's PNAConv - one tower, no edge features, linear pre- and
+    post-transformations.  The message of edge (i <- j) is X[j] W_src + X[i] W_dst + b_pre; it never exists per edge:
+        Z = X W_src  [N, message_dim],   c = X W_dst + b_pre,   M_a = agg_a(Z) (+ c for mean / max / min on rows that have edges; std
+        is unchanged by the shift)   with agg = tcgnn_edge_ops.aggregate_stats: every aggregator from one gather of the neighbour rows;
+        out = [X | S_s M_a for every scaler s and aggregator a] W_post + b_post,
+    the scalers being S = 1 ('identity'), log(deg + 1) / delta ('amplification') and delta / log(deg + 1) ('attenuation') with deg the
+    in-degree clamped to >= 1.  The product with W_post is one GEMM per scaler on the [N, |A| message_dim] block, its rows scaled
+    afterwards.  A node without incoming edges gets X W_post[:input_dim] + b_post.  message_dim defaults to min(input_dim, output_dim).
+    delta: a float fixes it; None takes pna_delta of the first graph the layer sees (kept in the buffer `delta`).  bias=False drops
+    b_pre and b_post.  Glorot initialisation with the ReLU gain, biases zero.  Gradients are exact on any graph (through A^T)."""
+
+    def __init__(self, input_dim, output_dim, aggregators=PNA_AGGREGATORS, scalers=PNA_SCALERS, delta=None, message_dim=None, bias=True):
+        super().__init__()
+        aggregators = (aggregators,) if isinstance(aggregators, str) else tuple(aggregators)
+        scalers = (scalers,) if isinstance(scalers, str) else tuple(scalers)
+        if not aggregators or len(set(aggregators)) != len(aggregators) or any(a not in PNA_AGGREGATORS for a in aggregators):
+            raise ValueError("aggregators must be distinct names among %s, got %r" % (", ".join(PNA_AGGREGATORS), aggregators))
+        if not scalers or len(set(scalers)) != len(scalers) or any(s not in PNA_SCALERS for s in scalers):
+            raise ValueError("scalers must be distinct names among %s, got %r" % (", ".join(PNA_SCALERS), scalers))
+        self.aggregators, self.scalers = aggregators, scalers
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        self.message_dim = int(message_dim) if message_dim is not None else min(self.input_dim, self.output_dim)
+        self.weights_src = torch.nn.Parameter(torch.empty(self.input_dim, self.message_dim))
+        self.weights_dst = torch.nn.Parameter(torch.empty(self.input_dim, self.message_dim))
+        self.weights_post = torch.nn.Parameter(torch.empty(self.input_dim + len(scalers) * len(aggregators) * self.message_dim, self.output_dim))
+        if bias:
+            self.bias_pre = torch.nn.Parameter(torch.zeros(self.message_dim))
+            self.bias_post = torch.nn.Parameter(torch.zeros(self.output_dim))
+        else:
+            self.register_parameter("bias_pre", None)
+            self.register_parameter("bias_post", None)
+        self.register_buffer("delta", None if delta is None else torch.tensor(float(delta), dtype=torch.float32))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        for w in (self.weights_src, self.weights_dst, self.weights_post):
+            torch.nn.init.xavier_uniform_(w, gain=gain)
+        for b in (self.bias_pre, self.bias_post):
+            if b is not None:
+                b.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        if self.delta is None:
+            self.delta = pna_delta(row_pointers).to(X.device)
+        deg = row_pointers[1:] - row_pointers[:-1]
+        has = (deg > 0).to(X.dtype).unsqueeze(1)
+        log_deg = torch.log(deg.clamp(min=1).to(X.dtype) + 1).unsqueeze(1)
+        scale = {"amplification": log_deg / self.delta, "attenuation": self.delta / log_deg}
+        Z = dense_update(X, self.weights_src)
+        c = dense_update(X, self.weights_dst)
+        if self.bias_pre is not None:
+            c = c + self.bias_pre
+        c = c * has
+        M = E.aggregate_stats(Z, row_pointers, column_index, self.aggregators)
+        block = torch.cat([m if a == "std" else m + c for a, m in zip(self.aggregators, M)], dim=1)
+        out = dense_update(X, self.weights_post[:self.input_dim])
+        wide = block.shape[1]
+        for k, s in enumerate(self.scalers):
+            part = dense_update(block, self.weights_post[self.input_dim + k * wide:self.input_dim + (k + 1) * wide])
+            out = out + (part if s == "identity" else part * scale[s])
+        return out + self.bias_post if self.bias_post is not None else out
