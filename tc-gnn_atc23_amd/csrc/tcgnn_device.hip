@@ -69,6 +69,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -187,7 +188,10 @@ struct tcgnn_plan {
         uint16_t* d_eidx16 = nullptr;      // the same as offsets from the window's first CSR edge, 0xffff: none (what val_permute_kernel reads)
         uint16_t* d_cold_eidx16 = nullptr;
     };
-    CellStream lds[7];   // (kLdsStreams; slot 6: the single-edge stream of the edge-valued LDS-resident SpMM, tcgnn_lds_val.inc)
+    CellStream lds[8];   // (kLdsStreams; slot 6: the single-edge stream of the edge-valued LDS-resident SpMM, tcgnn_lds_val.inc; slot 7: slot 4's layout on 952-row ranges)
+    // whole 64-column chunks run on slot 4 (760-row ranges) or slot 7 (952-row ranges): decided by build_lds_cells the first time either is
+    // asked for (-1: not yet), then only that one is ever built
+    mutable std::atomic<int8_t> lds_long{-1};
     // single-edge tile stream (built with slot 6, on the first edge-valued call that would use it): every condensed column repeated
     // once per edge, so a K slot of a tile carries exactly ONE edge and a per-call value array can sit beside the slots
     int64_t* d_xwb_ptr = nullptr;   // [nw_eff + 1]

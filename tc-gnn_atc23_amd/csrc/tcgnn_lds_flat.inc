@@ -242,11 +242,18 @@ struct FlatRangeFiller {
 };
 
 static constexpr bool flat_dense_ok(int nt, int maxw, int tpc) { return tpc == 1 && nt <= 2 && maxw * tpc <= 15; }
-static constexpr int flat_lds_main(int nt, int maxw, int tpc) { return 2 * nt * lds_buf_rows(nt, maxw) * 32 + kLdsWaves * 2 * (maxw * tpc * 128); }
+// (lng: the long walk - 960-row buffers, lds_stream_of's slot 7 - whose cold remainder shares kLongPoolTiles gather tiles)
+static constexpr int kLongPoolTiles = 4;
+static constexpr int kLongTurn = 8;       // a wavefront of the long walk may issue a cold gather in one entry of eight (tcgnn_lds_flat_kernel.inc)
+static constexpr int flat_cold_tiles(bool lng) { return lng ? kLongPoolTiles : kLdsWaves; }
+static constexpr int flat_lds_main(int nt, int maxw, int tpc, bool lng = false) { return 2 * nt * lds_buf_rows(nt, maxw, lng) * 32 + kLdsWaves * 2 * (maxw * tpc * 128); }
 // the in-kernel cold remainder needs one gathered tile (32 rows x NT planes x 32 bytes) per wavefront
-static constexpr bool flat_cold_fits(int nt, int maxw, int tpc) { return flat_lds_main(nt, maxw, tpc) + kLdsWaves * nt * 1024 <= 160 * 1024; }
+static constexpr bool flat_cold_fits(int nt, int maxw, int tpc, bool lng = false) { return flat_lds_main(nt, maxw, tpc, lng) + flat_cold_tiles(lng) * nt * 1024 <= 160 * 1024; }
 // (+ 128 bytes: the walk of a dense entry reads the id word / mask byte of "the next tile" behind its last one)
-static constexpr int flat_lds_bytes(int nt, int maxw, int tpc) { return flat_lds_main(nt, maxw, tpc) + (flat_cold_fits(nt, maxw, tpc) ? kLdsWaves * nt * 1024 : (flat_dense_ok(nt, maxw, tpc) ? 128 : 0)); }
+static constexpr int flat_lds_bytes(int nt, int maxw, int tpc, bool lng = false) { return flat_lds_main(nt, maxw, tpc, lng) + (flat_cold_fits(nt, maxw, tpc, lng) ? flat_cold_tiles(lng) * nt * 1024 : (flat_dense_ok(nt, maxw, tpc) ? 128 : 0)); }
+static_assert(flat_lds_bytes(2, 8, 1, true) == 160 * 1024 && flat_cold_fits(2, 8, 1, true), "the long walk: 2 x 2 planes x 960 rows, 32 KB of pads, four 2 KB gather tiles");
+static_assert(flat_lds_bytes(2, 8, 1) == 160 * 1024 && flat_lds_bytes(1, 8, 1) == 80 * 1024, "the shipped 8-window layouts keep their LDS");
+static_assert(lds_buf_rows(2, 8, true) * 32 < 32768 && kLongPoolTiles * 4 == kLdsWaves && kLongTurn == 2 * 4, "plane offsets as immediates, 16-bit row offsets; four wavefronts per pool tile, a turn every two entries");
 // (measured and not kept, r03: an L2 warm-up - one 4-byte-per-lane LDS-DMA per workgroup and range touching every 16th line of
 //  the range after next, shared between the workgroups of an XCD: with the multiply switched off a range lasts ~2 900 cycles, but
 //  that is not an L2 miss the warm-up could take - 0.602 ms with it, 0.607 without)
@@ -254,6 +261,7 @@ static constexpr int flat_lds_bytes(int nt, int maxw, int tpc) { return flat_lds
 // WITH_DENSE = false: the instantiation for streams WITHOUT dense entries (the launcher knows: CellStream::dense_entries).  The dense
 // walk is dead code there, and merely having it in the kernel costs the normal entries 5.5 % (r05, uniform Reddit shape, same box:
 // 0.477 ms with it, 0.451 without - r04's kernel 0.457): the second loop's live ranges push the first one's registers around.
+#define TCGNN_KERNEL_LONG false
 #define TCGNN_KERNEL_NAME spmm_lds_flat_kernel
 #define TCGNN_KERNEL_PARAM const SpmmFlatArgs a
 #define TCGNN_KERNEL_PROLOGUE
@@ -275,6 +283,28 @@ struct SpmmFlatEpiArgs { SpmmFlatArgs a; Epi epi; };
 #undef TCGNN_KERNEL_PARAM
 #undef TCGNN_KERNEL_PROLOGUE
 #undef TCGNN_KERNEL_STORE
+#undef TCGNN_KERNEL_LONG
+// the LONG walk (952-row ranges, cell stream slot kLdsLongSlot) and its twin: <2, 8, 1> only
+#define TCGNN_KERNEL_LONG true
+#define TCGNN_KERNEL_NAME spmm_lds_flat_long_kernel
+#define TCGNN_KERNEL_PARAM const SpmmFlatArgs a
+#define TCGNN_KERNEL_PROLOGUE
+#define TCGNN_KERNEL_STORE(relu, row, col, v) relu_if(relu, v)
+#include "tcgnn_lds_flat_kernel.inc"
+#undef TCGNN_KERNEL_NAME
+#undef TCGNN_KERNEL_PARAM
+#undef TCGNN_KERNEL_PROLOGUE
+#undef TCGNN_KERNEL_STORE
+#define TCGNN_KERNEL_NAME spmm_lds_flat_long_epi_kernel
+#define TCGNN_KERNEL_PARAM const SpmmFlatEpiArgs e
+#define TCGNN_KERNEL_PROLOGUE const SpmmFlatArgs& a = e.a;
+#define TCGNN_KERNEL_STORE(relu, row, col, v) epi_apply(relu, e.epi, row, col, v)
+#include "tcgnn_lds_flat_kernel.inc"
+#undef TCGNN_KERNEL_NAME
+#undef TCGNN_KERNEL_PARAM
+#undef TCGNN_KERNEL_PROLOGUE
+#undef TCGNN_KERNEL_STORE
+#undef TCGNN_KERNEL_LONG
 
 // (explicit instantiations: with implicit ones hipcc 7.2 leaves some host stubs undefined)
 template __global__ void spmm_lds_flat_kernel<1, 4, 1, false, false>(const SpmmFlatArgs);
@@ -293,7 +323,11 @@ template __global__ void spmm_lds_flat_kernel<3, 4, 2, false, false>(const SpmmF
 template __global__ void spmm_lds_flat_kernel<4, 4, 2, false, false>(const SpmmFlatArgs);
 template __global__ void spmm_lds_flat_kernel<1, 8, 2, false, false>(const SpmmFlatArgs);
 template __global__ void spmm_lds_flat_kernel<2, 8, 2, false, false>(const SpmmFlatArgs);
+template __global__ void spmm_lds_flat_long_kernel<2, 8, 1, false, false>(const SpmmFlatArgs);
+template __global__ void spmm_lds_flat_long_kernel<2, 8, 1, false, true>(const SpmmFlatArgs);
 #ifdef TCGNN_DEBUG_TIMERS
+template __global__ void spmm_lds_flat_long_kernel<2, 8, 1, true, false>(const SpmmFlatArgs);
+template __global__ void spmm_lds_flat_long_kernel<2, 8, 1, true, true>(const SpmmFlatArgs);
 template __global__ void spmm_lds_flat_kernel<1, 4, 1, true, false>(const SpmmFlatArgs);
 template __global__ void spmm_lds_flat_kernel<1, 4, 1, true, true>(const SpmmFlatArgs);
 template __global__ void spmm_lds_flat_kernel<2, 4, 1, true, false>(const SpmmFlatArgs);
@@ -329,8 +363,10 @@ template __global__ void spmm_lds_flat_epi_kernel<3, 4, 2, false, false>(const S
 template __global__ void spmm_lds_flat_epi_kernel<4, 4, 2, false, false>(const SpmmFlatEpiArgs);
 template __global__ void spmm_lds_flat_epi_kernel<1, 8, 2, false, false>(const SpmmFlatEpiArgs);
 template __global__ void spmm_lds_flat_epi_kernel<2, 8, 2, false, false>(const SpmmFlatEpiArgs);
+template __global__ void spmm_lds_flat_long_epi_kernel<2, 8, 1, false, false>(const SpmmFlatEpiArgs);
+template __global__ void spmm_lds_flat_long_epi_kernel<2, 8, 1, false, true>(const SpmmFlatEpiArgs);
 
-static constexpr LaunchGeom flat_geom(int nt, int maxw, int tpc) { return {kLdsWaves * 64, flat_lds_bytes(nt, maxw, tpc), kLdsWaves / 4, maxw}; }   // (as lds_geom)
+static constexpr LaunchGeom flat_geom(int nt, int maxw, int tpc, bool lng = false) { return {kLdsWaves * 64, flat_lds_bytes(nt, maxw, tpc, lng), kLdsWaves / 4, maxw}; }   // (as lds_geom)
 
 template <int NT, int MAXW, int TPC, bool DBG, bool WITH_DENSE>
 static hipError_t launch_flat_dbg(const SpmmFlatArgs& args, int nchunks, hipStream_t stream, const Epi& epi) {
@@ -360,8 +396,23 @@ static hipError_t launch_flat_tpc(int maxw, int nt, const SpmmFlatArgs& args, in
     return with_width<4>(nt, [&](auto NT) { return launch_flat_one<NT, kLdsMaxW, TPC>(args, nchunks, stream, dense, epi); });
 }
 // dense: the stream has dense entries (CellStream::dense_entries > 0) - the instantiation that walks them
+// the long walk: one layout, with / without dense entries, plain or twin (+ the phase-timer pair)
+template <bool DBG, bool WITH_DENSE>
+static hipError_t launch_flat_long_dbg(const SpmmFlatArgs& args, int nchunks, hipStream_t stream, const Epi& epi) {
+    constexpr LaunchGeom g = flat_geom(2, kLdsMaxW2, 1, true);
+    const dim3 grid((unsigned)args.nwg, (unsigned)nchunks);
+    if constexpr (DBG) return launch_kernel<spmm_lds_flat_long_kernel<2, kLdsMaxW2, 1, true, WITH_DENSE>, g.lds_bytes>(grid, g, stream, args);
+    else return launch_plain_or_twin<spmm_lds_flat_long_kernel<2, kLdsMaxW2, 1, false, WITH_DENSE>, spmm_lds_flat_long_epi_kernel<2, kLdsMaxW2, 1, false, WITH_DENSE>, g.lds_bytes>(grid, g, stream, args, epi);
+}
+static hipError_t launch_flat_long(const SpmmFlatArgs& args, int nchunks, hipStream_t stream, bool dense, const Epi& epi) {
+#ifdef TCGNN_DEBUG_TIMERS
+    if (args.dbg) return dense ? launch_flat_long_dbg<true, true>(args, nchunks, stream, epi) : launch_flat_long_dbg<true, false>(args, nchunks, stream, epi);
+#endif
+    return dense ? launch_flat_long_dbg<false, true>(args, nchunks, stream, epi) : launch_flat_long_dbg<false, false>(args, nchunks, stream, epi);
+}
 static hipError_t launch_flat_any(int maxw, int nt, int tpc, const SpmmFlatArgs& args, int nchunks, hipStream_t stream, bool dense,
-                                  const Epi& epi = Epi{nullptr, nullptr}) {
+                                  const Epi& epi = Epi{nullptr, nullptr}, bool long_ranges = false) {
+    if (long_ranges) return (maxw == kLdsMaxW2 && nt == 2 && tpc == 1) ? launch_flat_long(args, nchunks, stream, dense, epi) : hipErrorInvalidValue;
     return tpc == 2 ? launch_flat_tpc<2>(maxw, nt, args, nchunks, stream, dense, epi) : launch_flat_tpc<1>(maxw, nt, args, nchunks, stream, dense, epi);
 }
 

@@ -1,12 +1,17 @@
 // tcgnn_lds_flat_kernel.inc - the body of spmm_lds_flat_kernel (tcgnn_lds_flat.inc), included twice: as the plain kernel and as
 // spmm_lds_flat_epi_kernel, the same walk with tcgnn_spmm_scaled's row scale / bias in the final store.  The macros expand, for the
 // plain kernel, to exactly the tokens it was written with, so its code does not change.
+// TCGNN_KERNEL_LONG = true: the same walk over 952-row ranges (960-row buffers, cell stream slot kLdsLongSlot) - a kernel of its own name
+// rather than one more template parameter, which would rename every existing instantiation.  Everything it does differently stands
+// under `if constexpr (LONG)`: the buffer rows, and the cold remainder's gather tiles, of which the 160 KB then hold four, shared.
 template <int NT, int MAXW, int TPC, bool DBG, bool WITH_DENSE>
 __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL_PARAM) {
     TCGNN_KERNEL_PROLOGUE
     if (range_is_wide(a.hdr, 0)) { lds_own_fallback(a.fb); return; }   // (range guard: the fp32 walk does the work - here, or in a launch behind this one)
     const int dbg = DBG ? a.dbg : 0;
-    constexpr int kLdsBufRows = lds_buf_rows(NT, MAXW), kLdsRows = kLdsBufRows - 8;
+    constexpr bool LONG = TCGNN_KERNEL_LONG;
+    static_assert(!LONG || (NT == 2 && MAXW == 8 && TPC == 1), "the long ranges exist for whole 64-column chunks only");
+    constexpr int kLdsBufRows = lds_buf_rows(NT, MAXW, LONG), kLdsRows = kLdsBufRows - 8;
     constexpr int T = MAXW * TPC, PADB = T * 128, kLdsChunkDims = lds_chunk_dims(MAXW);
     static_assert(NT * MAXW <= 16, "accumulators: NT * MAXW * 4 VGPRs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -84,8 +89,15 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
     // it waits for its loads anyway: the record (column ids, mask words, window slot) is requested two ranges ahead with ordinary
     // loads, the 32 rows are gathered one range ahead by NT LDS-DMA instructions into a private 32 x NT x 32-byte tile in the same
     // planar format as the range buffers, and the tile step runs behind the wait that retires them - nothing new is waited for.
-    constexpr bool CAN_COLD = flat_cold_fits(NT, MAXW, TPC);
-    const uint32_t cbuf = lds0 + (uint32_t)flat_lds_main(NT, MAXW, TPC) + (uint32_t)wave * (NT * 1024u);
+    // LONG: the LDS behind the pads holds kLongPoolTiles = 4 gather tiles, not sixteen.  Wavefront v uses tile v >> 2 and may ISSUE a
+    // gather only at the end of an entry r with (r & 7) == 2 (v & 3); it multiplies the tile at the end of entry r + 1, as ever, and the
+    // tile's next user issues at the end of entry r + 2 - behind the barrier that ends entry r + 1.  No two wavefronts ever have the
+    // same tile in flight and nothing new is waited for; the test is wave-uniform scalar code.  A wavefront so retires at most one cold
+    // tile per eight entries (a private tile was in use in 1 - 2 % of the entries); what it cannot place in the walk is left to the
+    // loop behind it, where every wavefront has a private tile again: the range buffers are free by then.
+    constexpr bool CAN_COLD = flat_cold_fits(NT, MAXW, TPC, LONG);
+    uint32_t cbuf = lds0 + (uint32_t)flat_lds_main(NT, MAXW, TPC, LONG) + (uint32_t)(LONG ? wave >> 2 : wave) * (NT * 1024u);
+    const int cold_turn = 2 * (wave & 3);   // (LONG)
     int cold_c = 0, cold_n = 0, j_cur = 0;
     bool have_g = false, have_n = false;
     uint32_t cid_n = 0u, mw_n = 0u, mw_cur = 0u;   // (cid_n: row id | window slot << 28)
@@ -98,7 +110,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
             ++cold_c;
         }
     };
-    auto cold_step = [&]() {      // (behind a wait_vm0)
+    auto cold_step = [&](bool issue_ok) {      // (behind a wait_vm0; issue_ok: always, but for LONG outside this wavefront's turn)
         if (have_g) {             // the tile gathered during the range that just ended
             // (the lane id is re-derived here - mbcnt - so that this address is recomputed at its rare uses instead of living
             //  through the main loop: the kernel has exactly the 128 registers sixteen wavefronts per CU leave, and hipcc spilled it)
@@ -124,8 +136,9 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
                 }
             }
         }
-        have_g = have_n;
-        if (have_n) {             // gather the rows of the record requested a range ago: lane l fetches half l % 2 of row l / 2, one plane per instruction
+        const bool go = have_n && issue_ok;
+        have_g = go;
+        if (go) {                 // gather the rows of the record requested a range ago: lane l fetches half l % 2 of row l / 2, one plane per instruction
             const int plane0 = chunk_id * (kLdsChunkDims / 16);
 #pragma unroll
             for (int s = 0; s < NT; ++s) {
@@ -137,7 +150,7 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
             mw_cur = mw_n;
             j_cur = __builtin_amdgcn_readfirstlane((int)(cid_n >> 28));
         }
-        cold_request();
+        if (issue_ok) cold_request();   // (a record that has to wait for its turn stays where it is)
     };
     if constexpr (CAN_COLD) {
         if (a.wcold_ptr) {
@@ -190,7 +203,8 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
         ew2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)einfo[1]);
         if (dense_phase) ew1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)dnext);
         if (ew0 & 0x40000000u) buf ^= 1u;                                   // (another range: it sits in the other buffer)
-        if constexpr (CAN_COLD) { if (have_g || have_n) cold_step(); }
+        if constexpr (CAN_COLD && LONG) { const bool turn = (r & 7) == cold_turn; if (have_g || (have_n && turn)) cold_step(turn); }
+        else if constexpr (CAN_COLD) { if (have_g || have_n) cold_step(true); }
         if (more) {
             einfo = load_info(r + 2);
             if (dense_phase) dnext = load_desc(r + 2);
@@ -298,7 +312,11 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
     }
     if (!(dbg & 32)) __builtin_amdgcn_s_setprio(0);
     if constexpr (CAN_COLD) {   // what is left of the list (its last two tiles; all of it beyond the workgroup's ranges)
-        while (have_g || have_n) { wait_vm0(); cold_step(); }
+        if constexpr (LONG) {   // the tile still in flight in the pool first; then private tiles, in the range buffers (every wavefront is past the walk's last barrier: nobody reads or fills them any more)
+            if (have_g) { wait_vm0(); cold_step(false); }
+            cbuf = lds0 + (uint32_t)wave * (NT * 1024u);
+        }
+        while (have_g || have_n) { wait_vm0(); cold_step(true); }
     }
     if (dbg & 16) {   // measurement run: no results, the wavefronts of workgroup 0 report their phase totals
         if (wg == 0 && blockIdx.y == 0 && lane == 0) {

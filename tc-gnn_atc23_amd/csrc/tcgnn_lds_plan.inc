@@ -10,6 +10,13 @@ static int g_lds_maxw = [] { const char* e = test_knob("TCGNN_LDS_MAXW"); const 
 // what is left over (1-3 planes) as one pass of the 4-window layout.  TCGNN_LDS_MAXW = 4 / 8 forces one layout for every
 // pass (tests, timing).
 struct LdsPass { int maxw, nt, chunk0, nchunks; };
+// Whole 64-column chunks (8 windows x 2 planes) have two range lengths: 760 rows (slot 4) and 952 (slot kLdsLongSlot).  build_lds_cells
+// prices both the first time either is asked for and builds the cheaper one; plan->lds_long remembers which.  TCGNN_LDS_LONG=0 / 1
+// (tests, timing): never / wherever the long stream can be built (a flat stream with one tile per cell).
+static int lds_long_knob() { const char* e = test_knob("TCGNN_LDS_LONG"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }   // -1: by price (read when the stream is built)
+static int lds_pass_slot(const tcgnn_plan* p, const LdsPass& pass) {
+    return lds_stream_of(pass.nt, pass.maxw, pass.maxw == kLdsMaxW2 && pass.nt == 2 && p->lds_long.load(std::memory_order_acquire) == 1);
+}
 static int lds_passes(int dpad, LdsPass (&passes)[2]) {
     int n = 0;
     if (g_lds_maxw) {
@@ -400,7 +407,8 @@ struct CellBuild {
     CellPlacement best;
     std::vector<int32_t> kmap, rbase, rlist;        // hot pairs: compact number of pair (wg, range) or -1; per workgroup; their ranges
     int64_t npairs = 0, ncell_hot = 0, hot_cols = 0, cold_cols = 0;
-    std::vector<uint32_t> cnt;                      // tiles of every hot cell (ordinary count); an ordinary stream's cell table once summed
+    std::vector<uint32_t> cnt;                      // tiles of every hot cell (ordinary count; on the host from cells_entries on); an ordinary stream's cell table once summed
+    std::vector<uint32_t> pair_extra, pair_cellmx;  // per hot pair: extra tiles of its busiest wavefront, tiles of its fullest cell (cell_dense_stats_kernel)
     std::vector<uint32_t> dense_mx;                 // extra tiles of the pair's busiest wavefront (0: not a dense pair)
     int64_t over_dense = 0, dense_steps = 0, ndense_pairs = 0, ndense_entries = 0;
     int flat_tpc = 0;
@@ -414,6 +422,12 @@ struct CellBuild {
     DevBuf<int32_t> d_kmap, d_rbase, d_rlist, d_ent, d_ccols, d_eidx, d_cold_eidx, d_wcold_ptr;
     DevBuf<uint32_t> d_cnt, d_tiles, d_flat, d_rl2, d_xbase, d_cmask, d_wcold;
     DevBuf<int64_t> d_cold_ptr;
+    // what the choice between the two range lengths of whole 64-column chunks reads (cells_price): the ordinary stream's steps, the
+    // cold tiles the flat cap leaves (trial_tiles; worst_tail: those of the worst wavefront BEYOND what its walk admits - one per entry,
+    // the long walk one per kLongTurn entries - i.e. its serial loop behind the walk)
+    int64_t classic_steps = 0, trial_tiles = 0, worst_tail = 0;
+    double price = 0;
+    bool long_ranges() const { return slot == kLdsLongSlot; }
     bool with_dense() const { return flat_tpc == 1 && ndense_pairs > 0; }
 };
 
@@ -551,9 +565,20 @@ static int cells_hot_pairs(CellBuild& b) {
     if (e == hipSuccess) e = hipMemcpyAsync(b.d_rlist, rlist.data(), rlist.size() * sizeof(int32_t), hipMemcpyHostToDevice, b.stream);
     if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
     if (b.ncell > 0) hipLaunchKernelGGL(cell_compact_kernel, dim3((unsigned)((b.ncell + 255) / 256)), dim3(256), 0, b.stream, b.best.d_cellcols.ptr, b.d_kmap.ptr, b.npairs_all, b.per_wg, b.d_cnt.ptr);
-    b.cnt.resize((size_t)b.ncell_hot + 1);
     e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(b.cnt.data(), b.d_cnt, b.cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    // (the table itself - 4 bytes per hot cell, 20 MB on the Reddit shape - goes to the host in cells_entries, for the stream that is
+    //  built; what is decided before that reads two words per pair)
+    DevBuf<uint32_t> d_stats;
+    b.pair_extra.assign((size_t)b.npairs, 0u); b.pair_cellmx.assign((size_t)b.npairs, 0u);
+    if (e == hipSuccess && b.npairs > 0) {
+        e = d_stats.alloc((size_t)b.npairs * 2);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(cell_dense_stats_kernel, dim3((unsigned)((b.npairs + 255) / 256)), dim3(256), 0, b.stream, b.d_cnt.ptr, b.npairs, b.maxw, d_stats.ptr, d_stats.ptr + b.npairs);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(b.pair_extra.data(), d_stats, (size_t)b.npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.pair_cellmx.data(), d_stats.ptr + b.npairs, (size_t)b.npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
     if (e != hipSuccess) return fail(TCGNN_ERR_HIP, "cell count: %s", hipGetErrorString(e));
     return TCGNN_OK;
@@ -576,12 +601,7 @@ static void cells_dense_pairs(CellBuild& b) {
     b.dense_mx.assign((size_t)b.npairs, 0u);
     for (int64_t k = 0; k < b.npairs; ++k) {
         if (dense_min == 0xffffffffu && dense_cell_tiles == 0xffffffffu) break;
-        uint32_t mx = 0, cell_mx = 0;
-        for (int v = 0; v < kLdsWaves; ++v) {
-            uint32_t ex = 0;
-            for (int j = 0; j < maxw; ++j) { const uint32_t c = b.cnt[(size_t)((k * kLdsWaves + v) * maxw + j)]; ex += c > 1u ? c - 1u : 0u; cell_mx = std::max(cell_mx, c); }
-            mx = std::max(mx, ex);
-        }
+        const uint32_t mx = b.pair_extra[(size_t)k], cell_mx = b.pair_cellmx[(size_t)k];
         if (!mx || (b.best.pairover[(size_t)kall_of[(size_t)k]] < dense_min && cell_mx < dense_cell_tiles)) continue;
         b.dense_mx[(size_t)k] = mx;
         b.over_dense += b.best.pairover[(size_t)kall_of[(size_t)k]];
@@ -603,6 +623,7 @@ static void cells_flat_or_ordinary(CellBuild& b) {
     for (int64_t k = 0; k < npairs_all; ++k)
         if (b.kmap[(size_t)k] >= 0) { classic_tiles += best.pairtiles[(size_t)k]; classic_steps += best.pairmax[(size_t)k];
                                       over[0] += best.pairover[(size_t)k]; over[1] += best.pairover[(size_t)(npairs_all + k)]; }
+    b.classic_steps = classic_steps;
     const char* fenv = test_knob("TCGNN_LDS_FLAT");
     const int forced_flat = fenv ? atoi(fenv) : -1;
     if (best.nsplit == 0 && npairs > 0 && forced_flat != 0) {
@@ -658,8 +679,24 @@ static int cells_hub_row_trial(CellBuild& b) {
     if (e != hipSuccess) return fail(hip_rc(e), "cell table: %s", hipGetErrorString(e));
     uint32_t worst = 0;
     for (uint32_t c : trial) worst = std::max(worst, (c + 31u) / 32u);
-    if (worst > 16u) {
-        if (b.verbose) fprintf(stderr, "[tcgnn] cell stream %d: ordinary after all - one window would leave %u cold tiles behind\n", b.slot, worst);
+    // ... counted against what the walk ADMITS: a wavefront multiplies one cold tile per entry - the long walk, whose four gather tiles
+    // are shared, one per kLongTurn entries - and the rest of its list in a serial loop behind the walk: the same 16-tile bound
+    const int turn = b.long_ranges() ? kLongTurn : 1;
+    for (int g2 = 0; g2 < b.nwg; ++g2) {
+        const int64_t entries = b.with_dense() ? b.ent.wg_first[(size_t)g2 + 1] - b.ent.wg_first[(size_t)g2] : b.rbase[(size_t)g2 + 1] - b.rbase[(size_t)g2];
+        for (int v = 0; v < kLdsWaves; ++v) {
+            int64_t tiles = 0;
+            for (int j = 0; j < b.maxw; ++j) {
+                const int w = b.best.sorder[(size_t)cell_position(g2, v, j, b.maxw)];
+                if (w >= 0) tiles += (trial[(size_t)w] + 31u) / 32u;
+            }
+            b.trial_tiles += tiles;
+            b.worst_tail = std::max(b.worst_tail, tiles - entries / turn);
+        }
+    }
+    if (worst > 16u || (b.long_ranges() && b.worst_tail > 16)) {
+        if (b.verbose) fprintf(stderr, "[tcgnn] cell stream %d: ordinary after all - one window would leave %u cold tiles behind, one wavefront %lld beyond its walk\n", b.slot, worst,
+                               (long long)b.worst_tail);
         b.flat_tpc = 0; b.over_cols = 0;
     }
     return TCGNN_OK;
@@ -667,6 +704,12 @@ static int cells_hub_row_trial(CellBuild& b) {
 // step 7: the entries of the stream as it will be built (flat_entries) and, flat streams, their records on the device
 static int cells_entries(CellBuild& b) {
     if (!b.with_dense()) { (void)hipStreamSynchronize(b.stream); b.d_ent.reset(); }   // (the trial may have sent the stream back to ordinary)
+    b.cnt.resize((size_t)b.ncell_hot + 1);   // the hot cells' tile counts: the dense entries' records, an ordinary stream's cell table
+    {
+        hipError_t ec = hipMemcpyAsync(b.cnt.data(), b.d_cnt, b.cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream);
+        if (ec == hipSuccess) ec = hipStreamSynchronize(b.stream);
+        if (ec != hipSuccess) return fail(TCGNN_ERR_HIP, "cell count: %s", hipGetErrorString(ec));
+    }
     FlatEntries ent = flat_entries(b.nwg, b.maxw, b.rbase, b.rlist, b.cnt, b.dense_mx, b.with_dense(), b.flat_tpc != 0);
     hipError_t e = hipSuccess;
     if (b.flat_tpc) {
@@ -769,7 +812,7 @@ static int cells_cold_remainder(CellBuild& b) {
 // synchronisation every host table of the build waits for.
 static int cells_wavefront_cold_lists(CellBuild& b) {
     hipError_t e = hipSuccess;
-    if (!b.val && b.flat_tpc && b.cold_tiles > 0 && b.cold_tiles < (1ll << 28) && flat_cold_fits(lds_stream_nt(b.slot), b.maxw, b.flat_tpc)) {
+    if (!b.val && b.flat_tpc && b.cold_tiles > 0 && b.cold_tiles < (1ll << 28) && flat_cold_fits(lds_stream_nt(b.slot), b.maxw, b.flat_tpc, b.long_ranges())) {
         std::vector<int32_t>& wptr = b.wptr;
         std::vector<uint32_t>& wlist = b.wlist;
         wptr.assign((size_t)b.nwg * kLdsWaves + 1, 0);
@@ -860,15 +903,12 @@ static void release_cell_stream(tcgnn_plan::CellStream& cs) {
                     (void*)cs.d_cold_eidx16}) (void)hipFree(q);
 }
 
-static int build_lds_cells(tcgnn_plan* p, hipStream_t stream, int slot, size_t* build_only_bytes = nullptr) {
-    static std::mutex mu;
-    std::lock_guard<std::mutex> lock(mu);
-    if (p->lds[slot].nranges > 0) return TCGNN_OK;
-    if (p->nw_eff <= 0 || p->Nc <= 0) return fail(TCGNN_ERR_INVALID_ARG, "LDS-range SpMM: empty graph");
-    CellBuild b;
+// (a walk of fewer entries per workgroup is over before the per-entry fixed cost adds up: not worth planning a second stream)
+static constexpr int kLongMinEntries = 32;
+// the geometry of slot `slot`'s stream and what it is cut from
+static void cells_begin(CellBuild& b, tcgnn_plan* p, hipStream_t stream, int slot) {
     b.p = p; b.stream = stream; b.slot = slot;
     b.val = slot == kLdsValSlot;
-    if (b.val && !p->d_xwb_ptr) return fail(TCGNN_ERR_INVALID_ARG, "edge-valued LDS-resident SpMM: the single-edge stream has not been built");
     b.s_wb = b.val ? p->d_xwb_ptr : p->d_wb_ptr;
     b.s_cols = b.val ? p->d_xcols : p->d_cols;
     b.s_mask = b.val ? p->d_xmask : p->d_mask;
@@ -882,12 +922,72 @@ static int build_lds_cells(tcgnn_plan* p, hipStream_t stream, int slot, size_t* 
     b.ncell = (int64_t)b.nwg * b.nranges * b.per_wg;
     b.npairs_all = (int64_t)b.nwg * b.nranges;
     b.verbose = verbose_level() > 0;
+}
+// What a stream will cost a workgroup on average, in flat tile steps, from the counts made before anything is built: a flat step is
+// 1, an ordinary stream's step 1 / 0.75, a dense entry's step 1.6 + 4 per dense entry (cells_flat_or_ordinary's weights); every entry
+// costs the fixed ~1500 cycles tcgnn_lds_spmm.inc quotes on top - metadata latency, end-of-entry wait, barrier: 6 steps of ~260 cycles;
+// a cold tile inside the walk ~2 steps, one in the serial loop behind the walk a memory round trip, ~10.
+static double cells_price(const CellBuild& b) {
+    const double entries = (double)b.npairs + (b.flat_tpc == 1 ? (double)b.ndense_entries : 0.0);
+    double steps;
+    if (b.flat_tpc == 1) steps = (double)(b.npairs * b.maxw) + 1.6 * (double)b.dense_steps + 4.0 * (double)b.ndense_entries;
+    else if (b.flat_tpc == 2) steps = 2.0 * (double)(b.npairs * b.maxw);
+    else steps = (double)b.classic_steps / 0.75;
+    const double per_wg = (6.0 * entries + steps) / std::max(b.nwg, 1);
+    return per_wg + 2.0 * (double)b.trial_tiles / ((double)std::max(b.nwg, 1) * kLdsWaves) + 10.0 * (double)std::max<int64_t>(b.worst_tail, 0);
+}
+// steps 1 - 6: everything that is decided before anything is built, and the stream's price
+static int cells_plan(CellBuild& b) {
     if (const int rc = cells_window_weights(b)) return rc;
     if (const int rc = cells_choose_placement(b)) return rc;
     if (const int rc = cells_hot_pairs(b)) return rc;
     cells_dense_pairs(b);
     cells_flat_or_ordinary(b);
     if (const int rc = cells_hub_row_trial(b)) return rc;
+    b.price = cells_price(b);
+    return TCGNN_OK;
+}
+static int build_lds_cells(tcgnn_plan* p, hipStream_t stream, int slot, size_t* build_only_bytes = nullptr) {
+    static std::mutex mu;
+    std::lock_guard<std::mutex> lock(mu);
+    const bool two_lengths = slot == lds_stream_of(2, kLdsMaxW2) || slot == kLdsLongSlot;
+    int8_t decided = two_lengths ? p->lds_long.load(std::memory_order_acquire) : (int8_t)0;
+    if (two_lengths) slot = lds_stream_of(2, kLdsMaxW2, decided == 1);
+    if (p->lds[slot].nranges > 0) return TCGNN_OK;
+    if (p->nw_eff <= 0 || p->Nc <= 0) return fail(TCGNN_ERR_INVALID_ARG, "LDS-range SpMM: empty graph");
+    if (slot == kLdsValSlot && !p->d_xwb_ptr) return fail(TCGNN_ERR_INVALID_ARG, "edge-valued LDS-resident SpMM: the single-edge stream has not been built");
+    std::unique_ptr<CellBuild> bp(new CellBuild);
+    cells_begin(*bp, p, stream, slot);
+    if (const int rc = cells_plan(*bp)) return rc;
+    if (two_lengths && decided < 0) {
+        // 760- or 952-row ranges: the long stream is priced too - unless its cells would plainly overflow their one tile (the uniform
+        // Reddit shape: 25.7 columns per 760-row cell are 32 per 952-row cell) - and the cheaper one is built; the other's tables go
+        // before anything is (plan_bytes carries one stream)
+        CellBuild& s = *bp;
+        const double cells = (double)std::max<int64_t>(s.npairs, 1) * std::min<double>(s.per_wg, std::ceil((double)p->nw_eff / std::max(s.nwg, 1)));
+        const double fill_long = (double)(s.hot_cols - s.over_dense) / cells * (double)(lds_stream_buf_rows(kLdsLongSlot) - 8) / (double)s.rows;
+        bool take_long = false;
+        const int knob = lds_long_knob();
+        if (knob == 0) { if (s.verbose) fprintf(stderr, "[tcgnn] range length: 760 rows (TCGNN_LDS_LONG=0)\n"); }
+        else if (knob < 0 && s.npairs < (int64_t)kLongMinEntries * s.nwg) {
+            if (s.verbose) fprintf(stderr, "[tcgnn] range length: 760 rows; 952-row ranges not priced: %lld entries in %d workgroups\n", (long long)s.npairs, s.nwg);
+        } else if (knob < 0 && fill_long > 30.0) {
+            if (s.verbose) fprintf(stderr, "[tcgnn] range length: 760 rows, price %.0f steps per workgroup; 952-row ranges not priced: their ordinary cells would hold %.1f columns of 32\n", s.price, fill_long);
+        } else {
+            std::unique_ptr<CellBuild> bl(new CellBuild);
+            cells_begin(*bl, p, stream, kLdsLongSlot);
+            if (const int rc = cells_plan(*bl)) return rc;
+            const bool buildable = bl->flat_tpc == 1;
+            take_long = buildable && (knob == 1 || bl->price < s.price);
+            if (s.verbose) fprintf(stderr, "[tcgnn] range length: 760 rows: %lld entries, price %.0f steps per workgroup; 952 rows: %lld entries, price %.0f%s: %d-row ranges%s\n",
+                                   (long long)(s.npairs + (s.flat_tpc == 1 ? s.ndense_entries : 0)), s.price, (long long)(bl->npairs + (bl->flat_tpc == 1 ? bl->ndense_entries : 0)), bl->price,
+                                   buildable ? "" : " (not a flat stream with one tile per cell: cannot be built)", take_long ? 952 : 760, knob == 1 ? " (TCGNN_LDS_LONG=1)" : "");
+            (void)hipStreamSynchronize(stream);
+            if (take_long) { bp = std::move(bl); slot = kLdsLongSlot; }
+        }
+        p->lds_long.store(take_long ? 1 : 0, std::memory_order_release);
+    }
+    CellBuild& b = *bp;
     if (const int rc = cells_entries(b)) return rc;
     if (b.val && b.flat_tpc != 1)   // (spmm_lds_val_kernel walks flat streams with one tile per cell only; the caller keeps the gather walks)
         return fail(TCGNN_ERR_UNSUPPORTED, "edge-valued LDS-resident SpMM: the single-edge cells of this graph are not uniform enough for a flat stream");

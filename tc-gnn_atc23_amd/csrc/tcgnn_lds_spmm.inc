@@ -27,19 +27,23 @@ static constexpr int kLdsMaxW = 4;        // windows owned by a wavefront, 64 fe
 static constexpr int kLdsMaxW2 = 8;       // ... or twice the windows at 32 columns per pass: half as many workgroups stream each plane
 // Rows of one LDS range buffer (the range + eight all-zero rows, one per bank group).  Every range costs a fixed ~1500 cycles
 // (metadata latency, barrier) on top of its bytes, so narrow passes get longer ranges: 1 / 2 planes of 16 columns stream
-// 1528 / 760-row ranges (48 KB buffers), 3 planes 632-row ranges (60 KB), 4 planes 504-row ranges (64 KB).  The cell stream depends on the range length:
+// 1528 / 760-row ranges (48 KB buffers), 3 planes 632-row ranges (60 KB), 4 planes 504-row ranges (64 KB); the long flat walk streams
+// two planes of 952 rows (60 KB buffers, slot 7).  The cell stream depends on the range length:
 // a plan carries one stream per length in use (kLdsStreams slots).
 // Two layouts: 4 windows per wavefront with up to 4 planes per pass, or 8 windows with 2 planes per pass (half as many
 // workgroups stream each plane, 760-row ranges; measured better whenever the width is a multiple of 32 columns >= 64:
 // Reddit D = 64 0.69 vs 0.77 ms, D = 128 1.36 vs 1.50 ms).  Stream slots: 0-3 = 4 windows x {4, 2, 1, 3} planes,
-// 4-5 = 8 windows x {2, 1} planes.
-static constexpr int kLdsStreams = 7;
+// 4-5 = 8 windows x {2, 1} planes, 7 = slot 4's layout with 952-row ranges (960-row buffers: the LONG flat walk, spmm_lds_flat_long_kernel,
+// which pays for them with a shared pool of four cold tiles instead of one per wavefront).  A plan builds slot 4 OR slot 7, whichever
+// build_lds_cells prices lower: graphs whose 760-row cells are under-filled (communities) take the long ranges - a fifth fewer entries.
+static constexpr int kLdsStreams = 8;
 static constexpr int kLdsValSlot = 6;     // 8 windows x 2 planes like slot 4, cut from the SINGLE-EDGE tile stream (tcgnn_lds_val.inc)
-__host__ __device__ constexpr int lds_stream_of(int nt, int maxw) { return maxw == 8 ? (nt == 2 ? 4 : 5) : (nt >= 4 ? 0 : (nt == 2 ? 1 : (nt == 1 ? 2 : 3))); }
-__host__ __device__ constexpr int lds_stream_buf_rows(int slot) { return slot == 0 ? 512 : (slot == 1 ? 768 : (slot == 2 ? 1536 : (slot == 3 ? 640 : (slot == 4 || slot == 6 ? 768 : 512)))); }
+static constexpr int kLdsLongSlot = 7;    // 8 windows x 2 planes, 960-row buffers
+__host__ __device__ constexpr int lds_stream_of(int nt, int maxw, bool long_ranges = false) { return maxw == 8 ? (nt == 2 ? (long_ranges ? 7 : 4) : 5) : (nt >= 4 ? 0 : (nt == 2 ? 1 : (nt == 1 ? 2 : 3))); }
+__host__ __device__ constexpr int lds_stream_buf_rows(int slot) { return slot == 7 ? 960 : (slot == 0 ? 512 : (slot == 1 ? 768 : (slot == 2 ? 1536 : (slot == 3 ? 640 : (slot == 4 || slot == 6 ? 768 : 512))))); }
 __host__ __device__ constexpr int lds_stream_maxw(int slot) { return slot >= 4 ? 8 : 4; }
-__host__ __device__ constexpr int lds_stream_nt(int slot) { return slot == 0 ? 4 : (slot == 1 ? 2 : (slot == 2 ? 1 : (slot == 3 ? 3 : (slot == 4 || slot == 6 ? 2 : 1)))); }
-__host__ __device__ constexpr int lds_buf_rows(int nt, int maxw) { return lds_stream_buf_rows(lds_stream_of(nt, maxw)); }
+__host__ __device__ constexpr int lds_stream_nt(int slot) { return slot == 0 ? 4 : (slot == 1 ? 2 : (slot == 2 ? 1 : (slot == 3 ? 3 : (slot == 4 || slot == 6 || slot == 7 ? 2 : 1)))); }
+__host__ __device__ constexpr int lds_buf_rows(int nt, int maxw, bool long_ranges = false) { return lds_stream_buf_rows(lds_stream_of(nt, maxw, long_ranges)); }
 static constexpr int lds_pad_tiles(int maxw, int buf_rows) { return maxw != 4 ? (buf_rows == 768 ? 12 : 16) : (buf_rows == 512 ? 6 : (buf_rows == 1536 ? 12 : 8)); }   // tiles of metadata prefetched per wavefront and range (8 per DMA instruction)
 static constexpr int kCellWords = 32;     // one tile: 16 words holding 32 u16 row ids, then 16 mask words
 static constexpr int lds_chunk_dims(int maxw) { return 256 / maxw; }     // feature columns per pass
@@ -175,6 +179,19 @@ __global__ __launch_bounds__(256) void cell_compact_kernel(const uint32_t* __res
     const int64_t pair = idx / per_wg;
     const int k = kmap[pair];
     if (k >= 0) cnt[(int64_t)k * per_wg + (idx - pair * per_wg)] = (cellcols[idx] + 31u) / 32u;
+}
+// what cells_dense_pairs asks of every hot pair, from the compact tile counts: the extra tiles (beyond each cell's first) of its busiest
+// wavefront and the tiles of its fullest cell - so that the 4-bytes-per-cell table itself goes to the host only for the stream that is built
+__global__ __launch_bounds__(256) void cell_dense_stats_kernel(const uint32_t* __restrict__ cnt, int64_t npairs, int32_t maxw, uint32_t* __restrict__ extra_mx, uint32_t* __restrict__ cell_mx) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= npairs) return;
+    uint32_t mx = 0, cmx = 0;
+    for (int v = 0; v < kLdsWaves; ++v) {
+        uint32_t ex = 0;
+        for (int j = 0; j < maxw; ++j) { const uint32_t c = cnt[(k * kLdsWaves + v) * maxw + j]; ex += c > 1u ? c - 1u : 0u; cmx = c > cmx ? c : cmx; }
+        mx = ex > mx ? ex : mx;
+    }
+    extra_mx[k] = mx; cell_mx[k] = cmx;
 }
 // cold remainder: condensed columns of window slot p that fall into cold pairs -> coldcols[window]
 // (cap: columns a hot cell keeps - a flat stream's cells hold cap = 32 x tiles-per-cell, what lies beyond is cold too; 0: no cap)

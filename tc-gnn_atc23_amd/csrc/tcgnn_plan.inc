@@ -271,7 +271,7 @@ static int plan_first_cell_streams(tcgnn_plan* p, hipStream_t stream) {
     LdsPass passes[2];
     const int np = lds_passes(64, passes);
     for (int i = 0; i < np; ++i) {
-        const int rc = build_lds_cells(p, stream, lds_stream_of(passes[i].nt, passes[i].maxw));
+        const int rc = build_lds_cells(p, stream, lds_stream_of(passes[i].nt, passes[i].maxw));   // (slot 4: or the 952-row slot 7, if the build prices that lower)
         if (rc == TCGNN_ERR_OOM) { p->lds_choice[4] = 0; break; }   // (the gather walks need no stream)
         if (rc) return rc;
     }

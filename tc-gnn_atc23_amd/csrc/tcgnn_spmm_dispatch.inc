@@ -65,7 +65,7 @@ struct LdsStreamFacts { bool all_built, rows_cold, flat_cold, thin; };
 static LdsStreamFacts lds_stream_facts(const tcgnn_plan* plan, const LdsPass* passes, int npass) {
     LdsStreamFacts f{npass > 0, false, false, false};
     for (int i = 0; i < npass; ++i) {
-        const tcgnn_plan::CellStream& ci = plan->lds[lds_stream_of(passes[i].nt, passes[i].maxw)];
+        const tcgnn_plan::CellStream& ci = plan->lds[lds_pass_slot(plan, passes[i])];
         if (ci.nranges == 0) { f.all_built = false; continue; }
         // (a flat stream's remainder is added per pass from the planar image by spmm_cold_planar_kernel: no second image, any
         //  number of passes - but not under the fused dense update, which needs the whole sum before it multiplies)
@@ -91,7 +91,7 @@ static bool lds_streams_serve(const tcgnn_plan* plan, int mode, const LdsPass* p
     }
     if (f.thin && mode != 3) { *settle = true; return false; }
     if (f.rows_cold && planar_staged) return false;   // (the remainder's gather walk wants a row-major image of the same matrix: not in a planar staged call)
-    if (f.rows_cold) *cold = &plan->lds[lds_stream_of(passes[0].nt, passes[0].maxw)];
+    if (f.rows_cold) *cold = &plan->lds[lds_pass_slot(plan, passes[0])];
     return true;
 }
 // ---- lazy stream builds (allocate and synchronise the stream once)
@@ -112,8 +112,9 @@ enum class LdsBuild {
 static int ensure_lds_streams(const tcgnn_plan* plan, hipStream_t stream, int mode, int dpad, const LdsPass* passes, int npass, LdsBuild who, bool* ok) {
     *ok = true;
     for (int i = 0; i < npass; ++i) {
+        if (plan->lds[lds_pass_slot(plan, passes[i])].nranges > 0) continue;
+        // (whole 64-column chunks: the build decides between the 760- and the 952-row stream the first time and builds that one - lds_pass_slot follows)
         const int slot = lds_stream_of(passes[i].nt, passes[i].maxw);
-        if (plan->lds[slot].nranges > 0) continue;
         if (who == LdsBuild::kInCall && stream_is_capturing(stream)) {
             *ok = false;
             return mode == 3 ? fail(TCGNN_ERR_INVALID_ARG, "LDS-resident SpMM: the cell stream of this width has to be built before the call is captured into a graph") : TCGNN_OK;
@@ -170,7 +171,7 @@ static int route_spmm(const SpmmCall& c, SpmmRoute* r) {
         for (int i = 0; i < r->npass; ++i) total_chunks += r->passes[i].nchunks;
         r->accumulate = (c.d_W && total_chunks > 1) ? 1 : 0;
         // one launch, binary A, whole rows, nothing added behind it: the kernel is its own range-guard fallback (lds_own_fallback)
-        r->own_fb = r->npass == 1 && !r->cold && !c.d_W && !staged && c.stride() == D && !flat_cold_behind(plan->lds[lds_stream_of(r->passes[0].nt, r->passes[0].maxw)]) &&
+        r->own_fb = r->npass == 1 && !r->cold && !c.d_W && !staged && c.stride() == D && !flat_cold_behind(plan->lds[lds_pass_slot(plan, r->passes[0])]) &&
                     !c.scaled();   // (a scaled call's fallback is the scaled fp32 kernel behind the launch)
         r->walk = Walk::kLds;
         return TCGNN_OK;
@@ -340,13 +341,14 @@ static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& 
         if (const int rc = stage_features(plan, c.d_X, nullptr, D, static_cast<char*>(c.ws) + image, c.ws_bytes - image, stream, o, &rows)) return rc;
         x16_rows = rows.x16;
     }
-    const tcgnn_plan::CellStream& cs0 = plan->lds[lds_stream_of(r.passes[0].nt, r.passes[0].maxw)];
+    const tcgnn_plan::CellStream& cs0 = plan->lds[lds_pass_slot(plan, r.passes[0])];
     const SpmmSmallArgs fb = small_args(c, r.own_fb ? im.hdr : nullptr);
     KernelTimer timer(plan, stream, r.cold ? "spmm_lds_kernel + spmm_kernel (cold remainder)" :
-                                    (cs0.flat_tpc ? (flat_cold_behind(cs0) ? "spmm_lds_flat_kernel + spmm_cold_planar_kernel (cold remainder)" : "spmm_lds_flat_kernel") : "spmm_lds_kernel"));
+                                    (cs0.flat_tpc ? (flat_cold_behind(cs0) ? "spmm_lds_flat_kernel + spmm_cold_planar_kernel (cold remainder)" : "spmm_lds_flat_kernel") : "spmm_lds_kernel"));   // (the long walk, 952-row ranges, reports the family's name too)
     for (int i = 0; i < r.npass; ++i) {
         const LdsPass& p = r.passes[i];
-        const tcgnn_plan::CellStream& cs = plan->lds[lds_stream_of(p.nt, p.maxw)];
+        const int slot = lds_pass_slot(plan, p);
+        const tcgnn_plan::CellStream& cs = plan->lds[slot];
         if (cs.flat_tpc) {
             const bool has_cold = flat_cold_behind(cs);
             // (tcgnn_spmm_scaled: with a remainder behind it this kernel stores raw sums and spmm_cold_planar_kernel, the final writer,
@@ -356,7 +358,7 @@ static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& 
             f.N = plan->N; f.D = D; f.stride = im.dpad / 16; f.chunk0 = p.chunk0; f.xrows = plan->Nc + 1; f.nw = plan->nw_eff; f.nwg = cs.nwg;
             f.dbg = g_lds_dbg; f.relu = has_cold ? 0 : c.relu; f.rbase = cs.d_rbase; f.rl2 = cs.d_rl2; f.nent = std::max(cs.npairs, 1);
             f.w = c.d_W; f.dout = c.D_out; f.accumulate = r.accumulate; f.fill_quota = g_lds_fill_quota; f.wcold_ptr = cs.d_wcold_ptr; f.wcold = cs.d_wcold; f.fb = fb;
-            HIP_TRY(launch_flat_any(p.maxw, p.nt, cs.flat_tpc, f, p.nchunks, stream, cs.dense_entries > 0, has_cold ? no_epi : epi));
+            HIP_TRY(launch_flat_any(p.maxw, p.nt, cs.flat_tpc, f, p.nchunks, stream, cs.dense_entries > 0, has_cold ? no_epi : epi, slot == kLdsLongSlot));
             if (has_cold && !(g_lds_dbg & 16)) {
                 const int cd = lds_chunk_dims(p.maxw);
                 const int col0 = p.chunk0 * cd, ncols = std::min(p.nchunks * cd, im.dpad - col0);

@@ -29,7 +29,7 @@ def audit(path, filt=""):
         # the timing-only instantiations of the flat-stream kernel (template argument DBG = true: TCGNN_LDS_DBG switches as scalar
         # branches around every step) are not straight-line code: the approximation below does not apply, and they never run in the
         # product path
-        if re.match(r"_Z20spmm_lds_flat_kernelILi\dELi\dELi\dELb1E", kernel): continue
+        if re.match(r"_Z2[05]spmm_lds_flat(_long)?_kernelILi\dELi\dELi\dELb1E", kernel): continue
         if s.startswith(";;#ASMSTART"): in_asm = True; skip_to = None; continue
         if s.startswith(";;#ASMEND"): in_asm = False; skip_to = None; continue
         # an asm statement with its own branch (lds_flat_step_if: "s_cbranch 1f ... s_branch 2f / 1: wait for everything / 2:"): the

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time the LDS-resident range SpMM (mode 3) on the Reddit shape under the TCGNN_LDS_DBG switches (set in the environment; the
-phase-timer kernels exist only in a library built with `make -C tc-gnn_atc23_amd/csrc DEBUG_TIMERS=1`)."""
+phase-timer kernels exist only in a library built with `make -C tc-gnn_atc23_amd/csrc DEBUG_TIMERS=1`).
+TCGNN_LDS_LONG=0 / 1 picks the 760-row / the 952-row instantiation of the flat walk at D = 64 (spmm_lds_flat_long_kernel; unset:
+the plan's own choice); the line printed at the end says which ran (RANGE_ROWS)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tc-gnn_atc23_amd")): sys.path.insert(0, p)
@@ -29,4 +31,6 @@ if int(os.environ.get("TCGNN_LDS_DBG", "0")) & 16:
     print("cycles per range (%d ranges), rows = wavefronts of workgroup 0, columns = fill issue / multiply / wait / barrier (mean cycles), pad refills (total), longest multiply, longest wait, tiles (total)" % nr)
     y = y.reshape(16, 8); y[:, :4] /= nr
     print(np.round(y).astype(int))
-print("dbg=%s D=%d: %.3f ms (min %.3f)  %s  %s" % (os.environ.get("TCGNN_LDS_DBG", "0"), D, np.median(t), np.min(t), TCGNN.last_kernel(*meta), TCGNN.plan_info(*meta)))
+info = TCGNN.plan_info(*meta)
+rows = {(n + r - 1) // r: r for r in (504, 632, 760, 952, 1528)}.get(info["lds_ranges"], 0)   # (the finest stream built: at D = 64 the only one)
+print("dbg=%s D=%d RANGE_ROWS=%d: %.3f ms (min %.3f)  %s  %s" % (os.environ.get("TCGNN_LDS_DBG", "0"), D, rows, np.median(t), np.min(t), TCGNN.last_kernel(*meta), info))
