@@ -590,6 +590,42 @@ int tcgnn_gatv2_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edg
                             int64_t num_edges, int32_t H, int32_t F, const float* d_xl, const float* d_xr, const float* d_attn,
                             float negative_slope, const float* d_g, float* d_dxl, void* stream);
 
+/* ---- message passing with a feature vector per edge (DGL's u_add_e / sum and copy_e / sum, the message of PyG's GINEConv; no
+ * counterpart in the reference) ----
+ *
+ * CSR row = destination node, column = source node.  X, Y and dY are fp32 [num_nodes, D] row-major; Ef, dM and M are fp32
+ * [num_edges, D] row-major in CSR POSITION order, the order of every other per-edge array of this header.  act: TCGNN_ACT_IDENTITY or
+ * TCGNN_ACT_RELU.  Planless like tcgnn_segment_max: device pointers, the caller's stream, no allocation, no synchronisation
+ * (capturable in a HIP graph); no atomics and every order fixed: bit-identical on repetition.  Everything is read as fp32 - no fp16
+ * image, no range guard.
+ *   tcgnn_edge_message           z = fl32(X[col(e), d] + Ef[e, d]);  m = act(z);  Y[i, d] = fl32(sum over e in row i of (double)m), an
+ *                                fp64 sum in a fixed order, rounded once; an empty row: 0.  ReLU as torch.relu: a NaN z stays NaN.
+ *   tcgnn_edge_message_backward  dM[e, d] = dY[row(e), d] where act is the identity or !(z <= 0) - torch's threshold_backward: a NaN z
+ *                                passes the gradient, -0.0 and +0.0 block it - and +0.0 otherwise.  EXACT: the bits of dY or zero.
+ *                                dM is the gradient with respect to Ef and the per-edge gradient of the message: the gradient with
+ *                                respect to X is tcgnn_edge_sum over A^T through perm.  With TCGNN_ACT_IDENTITY d_edgeList, d_X and
+ *                                d_Ef are not read and may be NULL.  A position in front of nodePointer[0] or behind
+ *                                nodePointer[num_nodes] (a canonical CSR has none) belongs to no row: its row of dM is zeroed.
+ *   tcgnn_edge_sum               Y[r, d] = fl32(sum over the positions t of row r of (double)M[perm ? perm[t] : t, d]), an fp64 sum in a
+ *                                fixed order, rounded once; an empty row: 0.  With d_nodePointer_t and d_perm of tcgnn_transpose_ws:
+ *                                the sum of M's rows by SOURCE node; with d_perm = NULL: by destination node (copy_e / sum).
+ * Rows are read and written with 16-byte accesses when D % 4 == 0 and every [., D] array the call touches is 16-byte aligned, with
+ * 4-byte accesses otherwise: the same bits either way.  Row pointers are clamped to [0, num_edges] and a descending pair is an empty
+ * row.  For every read they index, a column id is clamped to the nearer end of [0, num_nodes) and a perm entry outside [0, num_edges)
+ * reads position 0: safe reads either way, values of no meaning for an array that holds such entries.  Every element of Y / dM is
+ * written and nothing outside it.  A size of 0 returns TCGNN_OK with the output, where it has elements, zeroed; a negative size,
+ * num_edges >= 2^31, an unknown act or a null array otherwise: TCGNN_ERR_INVALID_ARG before anything is written.  A hub row stays on
+ * one workgroup, as in tcgnn_segment_max. */
+#define TCGNN_ACT_IDENTITY 0
+#define TCGNN_ACT_RELU 1
+int tcgnn_edge_message(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                       const float* d_X, const float* d_Ef, int32_t D, int32_t act, float* d_Y, void* stream);
+int tcgnn_edge_message_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                                const float* d_X, const float* d_Ef, const float* d_dY, int32_t D, int32_t act, float* d_dM,
+                                void* stream);
+int tcgnn_edge_sum(const int32_t* d_nodePointer, const int32_t* d_perm /* may be NULL */, int32_t num_nodes, int64_t num_edges,
+                   const float* d_M, int32_t D, float* d_Y, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

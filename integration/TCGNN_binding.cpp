@@ -680,6 +680,111 @@ torch::Tensor backward_stats(TensorMap grads, TensorMap saved, torch::Tensor nod
   return dZ;
 }
 
+// ---- not in the reference: a feature vector per edge (tcgnn_edge_message / _backward, tcgnn_edge_sum; the ctypes module's forward_ue,
+// backward_ue and edge_sum) and the cached transpose their autograd Function asks for (the ctypes module's transpose_graph) ---------
+namespace {
+int ue_act(const c10::optional<std::string>& act) {
+  if (!act.has_value() || *act == "identity") return TCGNN_ACT_IDENTITY;
+  if (*act == "relu") return TCGNN_ACT_RELU;
+  throw py::value_error("act must be 'relu', 'identity' or None, got '" + *act + "'");
+}
+void check_edge_rows(const torch::Tensor& t, const char* name, int64_t E, int64_t D, const torch::Tensor& like) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a CUDA tensor");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == E && t.size(1) == D && t.device() == like.device(), name,
+              " must be a contiguous fp32 [num_edges, embedding_dim] = [", E, ", ", D, "] tensor on the device of nodePointer");
+}
+void check_out_apart(const c10::optional<torch::Tensor>& out, std::initializer_list<const torch::Tensor*> inputs) {
+  if (!out.has_value() || !out->numel()) return;
+  const char* lo = static_cast<const char*>(out->data_ptr());
+  const char* hi = lo + out->numel() * out->element_size();
+  for (const torch::Tensor* t : inputs)
+    if (t && t->defined() && t->numel()) {
+      const char* a = static_cast<const char*>(t->data_ptr());
+      TORCH_CHECK(!(a < hi && lo < a + t->numel() * t->element_size()), "out must not share memory with an input");
+    }
+}
+}  // namespace
+
+torch::Tensor forward_ue(torch::Tensor X, torch::Tensor Ef, torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<std::string> act,
+                         c10::optional<torch::Tensor> out) {
+  auto [N, E, D] = max_args(X, "X", nodePointer, edgeList);
+  const int code = ue_act(act);
+  check_edge_rows(Ef, "Ef", E, D, nodePointer);
+  torch::Tensor Y = out_like(out, X, "X");
+  check_out_apart(out, {&X, &Ef});
+  DeviceGuard guard(X.device());
+  tcgnn_check(tcgnn_edge_message(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, X.data_ptr<float>(), Ef.data_ptr<float>(), D, code,
+                                 Y.data_ptr<float>(), current_stream(X)), "tcgnn_edge_message");
+  return Y;
+}
+
+torch::Tensor backward_ue(torch::Tensor dY, c10::optional<torch::Tensor> X, c10::optional<torch::Tensor> Ef, torch::Tensor nodePointer,
+                          torch::Tensor edgeList, c10::optional<std::string> act, c10::optional<torch::Tensor> out) {
+  auto [N, E, D] = max_args(dY, "dY", nodePointer, edgeList);
+  const int code = ue_act(act);
+  if (code != TCGNN_ACT_IDENTITY) {
+    TORCH_CHECK(X.has_value() && Ef.has_value(), "X and Ef are needed to recompute the activation's mask");
+    CHECK_INPUT((*X));
+    TORCH_CHECK(X->scalar_type() == torch::kFloat32, "expected scalar type Float");
+    TORCH_CHECK(X->sizes() == dY.sizes() && X->device() == dY.device(), "X must have the shape and device of dY");
+    check_edge_rows(*Ef, "Ef", E, D, nodePointer);
+  }
+  torch::Tensor dM;
+  if (out.has_value()) {
+    check_edge_rows(*out, "out", E, D, nodePointer);
+    dM = *out;
+  } else {
+    dM = torch::empty({E, (int64_t)D}, dY.options());
+  }
+  const bool masked = code != TCGNN_ACT_IDENTITY;
+  check_out_apart(out, {&dY, masked ? &*X : nullptr, masked ? &*Ef : nullptr});
+  DeviceGuard guard(dY.device());
+  tcgnn_check(tcgnn_edge_message_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, masked ? X->data_ptr<float>() : nullptr,
+                                          masked ? Ef->data_ptr<float>() : nullptr, dY.data_ptr<float>(), D, code, dM.data_ptr<float>(),
+                                          current_stream(dY)), "tcgnn_edge_message_backward");
+  return dM;
+}
+
+torch::Tensor edge_sum(torch::Tensor M, torch::Tensor nodePointer, c10::optional<torch::Tensor> perm, c10::optional<torch::Tensor> out) {
+  CHECK_INPUT(nodePointer);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  CHECK_INPUT(M);
+  TORCH_CHECK(M.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(M.dim() == 2 && M.device() == nodePointer.device(), "M must be [num_edges, embedding_dim] on nodePointer's device");
+  const int64_t N = nodePointer.numel() - 1, E = M.size(0), D = M.size(1);
+  if (perm.has_value()) {
+    CHECK_INPUT((*perm));
+    TORCH_CHECK(perm->scalar_type() == torch::kInt32, "expected scalar type Int");
+    TORCH_CHECK(perm->dim() == 1 && perm->numel() == E && perm->device() == M.device(), "perm must hold num_edges entries on M's device");
+  }
+  torch::Tensor Y;
+  if (out.has_value()) {
+    TORCH_CHECK(out->is_cuda() && out->is_contiguous() && out->scalar_type() == torch::kFloat32 && out->dim() == 2 && out->size(0) == N &&
+                out->size(1) == D && out->device() == M.device(), "out must be a contiguous fp32 [num_nodes, embedding_dim] tensor on M's device");
+    Y = *out;
+  } else {
+    Y = torch::empty({N, D}, M.options());
+  }
+  check_out_apart(out, {&M});
+  DeviceGuard guard(M.device());
+  tcgnn_check(tcgnn_edge_sum(nodePointer.data_ptr<int>(), perm.has_value() ? perm->data_ptr<int>() : nullptr, (int32_t)N, E, M.data_ptr<float>(),
+                             (int32_t)D, Y.data_ptr<float>(), current_stream(M)), "tcgnn_edge_sum");
+  return Y;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
+  CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  TORCH_CHECK(edgeList.device() == nodePointer.device(), "nodePointer and edgeList must be on one device");
+  DeviceGuard guard(nodePointer.device());
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  return {t.rp_t, t.col_t, t.perm, t.symmetric};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -817,4 +922,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none());
   m.def("gatv2_source_grad", &gatv2_source_grad, "source side of gatv2_softmax's backward: d_xl (not in the reference)", py::arg("g"), py::arg("xl"),
         py::arg("xr"), py::arg("attn"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("negative_slope") = 0.2);
+  m.def("forward_ue", &forward_ue, "sum over a node's incoming edges of act(X[col e] + Ef[e]), Ef [E, D] (not in the reference)", py::arg("X"), py::arg("Ef"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu", py::arg("out") = py::none());
+  m.def("backward_ue", &backward_ue, "per-edge gradient of forward_ue: dM [E, D] (not in the reference)", py::arg("dY"), py::arg("X"), py::arg("Ef"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu", py::arg("out") = py::none());
+  m.def("edge_sum", &edge_sum, "per-edge rows summed into nodes, optionally through perm (not in the reference)", py::arg("M"), py::arg("nodePointer"),
+        py::arg("perm") = py::none(), py::arg("out") = py::none());
+  m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"));
 }

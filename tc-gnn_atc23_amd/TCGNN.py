@@ -36,7 +36,8 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "plan_info", "kernel_timing", "last_kernel", "clear_plan_cache", "set_plan_cache_size", "agnn_fused_supported", "agnn_fused_forward", "agnn_fused_backward",
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
-           "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad"]
+           "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
+           "forward_ue", "backward_ue", "edge_sum"]
 
 
 def _stream(device):
@@ -1091,6 +1092,105 @@ def backward_stats(grads, saved, nodePointer, edgeList, out=None):
           _ptr(a), _ptr(b), saved["argmax"].data_ptr() if "max" in g else None, _ptr(g.get("max")), saved["argmin"].data_ptr() if "min" in g else None,
           _ptr(g.get("min")), D, out.data_ptr())
     return out
+
+
+# ---- additions (not in the reference module): a feature vector per edge (u_add_e / sum, copy_e / sum; GINEConv) -------------
+
+UE_ACTS = {None: 0, "identity": 0, "relu": 1}   # (TCGNN_ACT_IDENTITY, TCGNN_ACT_RELU)
+
+
+def _ue_act(act):
+    if act not in UE_ACTS:
+        raise ValueError("act must be 'relu', 'identity' or None, got %r" % (act,))
+    return UE_ACTS[act]
+
+
+def _edge_rows(t, name, E, D, like):
+    _check_input(t, name)
+    _check_float(t, name)
+    if t.dim() != 2 or t.size(0) != E or (D is not None and t.size(1) != D) or t.device != like.device:
+        raise RuntimeError("%s must be a contiguous fp32 [num_edges, embedding_dim] = [%d, %s] tensor on the device of nodePointer, got %s"
+                           % (name, E, "D" if D is None else D, tuple(t.shape)))
+
+
+def _out_apart(out, given, *inputs):
+    """_out_like's result may not share memory with an operand the kernel still reads while it writes"""
+    if given is None or not out.numel():
+        return
+    lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
+    for t in inputs:
+        if t is not None and t.numel() and t.data_ptr() < hi and lo < t.data_ptr() + t.numel() * t.element_size():
+            raise RuntimeError("out must not share memory with an input")
+
+
+def forward_ue(X, Ef, nodePointer, edgeList, act="relu", out=None):
+    """Not in the reference module: message passing with a feature vector per edge (tcgnn_edge_message; DGL's u_add_e / sum),
+        Y[i, d] = the sum over the edges e of row i of act(X[col(e), d] + Ef[e, d]),   act: 'relu', or 'identity' / None.
+    X: fp32 [N, D]; Ef: fp32 [E, D] in CSR position order.  The message is formed in fp32 and summed in fp64 in a fixed order, rounded
+    once; no [E, D] tensor is made.  A row without edges gives 0.  ReLU as torch.relu (a NaN stays NaN).  Deterministic, no atomics."""
+    N, E, D = _max_args(X, "X", nodePointer, edgeList)
+    code = _ue_act(act)
+    _edge_rows(Ef, "Ef", E, D, nodePointer)
+    res = _out_like(out, X, "X")
+    _out_apart(res, out, X, Ef)
+    _call(_c.lib.tcgnn_edge_message, X.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, X.data_ptr(), Ef.data_ptr(), D, code, res.data_ptr())
+    return res
+
+
+def backward_ue(dY, X, Ef, nodePointer, edgeList, act="relu", out=None):
+    """Not in the reference module: the per-edge gradient of forward_ue (tcgnn_edge_message_backward), fp32 [E, D],
+        dM[e, d] = dY[row(e), d] where act is the identity or X[col(e), d] + Ef[e, d] is positive or a NaN (torch's ReLU backward), else 0
+    - exact: the bits of dY or zero.  dM is the gradient with respect to Ef; the gradient with respect to X is
+    edge_sum(dM, nodePointer_t, perm) over the transposed graph.  With act 'identity' / None X and Ef are not read and may be None."""
+    N, E, D = _max_args(dY, "dY", nodePointer, edgeList)
+    code = _ue_act(act)
+    if code:
+        _check_input(X, "X")
+        _check_float(X, "X")
+        if X.shape != dY.shape or X.device != dY.device:
+            raise RuntimeError("X must have the shape and device of dY")
+        _edge_rows(Ef, "Ef", E, D, nodePointer)
+    if out is None:
+        res = torch.empty(E, D, dtype=torch.float32, device=dY.device)
+    else:
+        _edge_rows(out, "out", E, D, nodePointer)
+        res = out
+    _out_apart(res, out, dY, X if code else None, Ef if code else None)
+    _call(_c.lib.tcgnn_edge_message_backward, dY.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, _ptr(X) if code else None,
+          _ptr(Ef) if code else None, dY.data_ptr(), D, code, res.data_ptr())
+    return res
+
+
+def edge_sum(M, nodePointer, perm=None, out=None):
+    """Not in the reference module: per-edge rows summed into nodes (tcgnn_edge_sum), fp32 [N, D],
+        Y[r, d] = the sum over the positions t of row r of M[perm[t], d]   (perm=None: M[t, d] - DGL's copy_e / sum),
+    fp64 sums in a fixed order, rounded once; a row without edges gives 0.  M: fp32 [E, D] in A's CSR position order.  With
+    (nodePointer_t, _, perm, _) = transpose_graph(nodePointer, edgeList) it sums by SOURCE node: the gradient of forward_ue with respect
+    to X from backward_ue's dM.  Deterministic, no atomics."""
+    _check_input(nodePointer, "nodePointer")
+    _check_int(nodePointer, "nodePointer")
+    N = nodePointer.numel() - 1
+    if N < 0:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    _check_input(M, "M")
+    _check_float(M, "M")
+    if M.dim() != 2 or M.device != nodePointer.device:
+        raise RuntimeError("M must be [num_edges, embedding_dim] on nodePointer's device, got %s" % (tuple(M.shape),))
+    E, D = M.shape
+    if perm is not None:
+        _check_input(perm, "perm")
+        _check_int(perm, "perm")
+        if perm.dim() != 1 or perm.numel() != E or perm.device != M.device:
+            raise RuntimeError("perm must hold num_edges = %d entries on M's device, got %s" % (E, tuple(perm.shape)))
+    if out is None:
+        res = torch.empty(N, D, dtype=torch.float32, device=M.device)
+    else:
+        if tuple(out.shape) != (N, D) or out.dtype != torch.float32 or out.device != M.device or not out.is_contiguous():
+            raise RuntimeError("out must be a contiguous fp32 [num_nodes, embedding_dim] = [%d, %d] tensor on M's device" % (N, D))
+        res = out
+    _out_apart(res, out, M)
+    _call(_c.lib.tcgnn_edge_sum, M.device, nodePointer.data_ptr(), _ptr(perm), N, E, M.data_ptr(), D, res.data_ptr())
+    return res
 
 
 # ---- additions (not in the reference module): the two products of an AGNN layer in one pass ------------

@@ -54,6 +54,8 @@
 //   tcgnn_segment_max.inc     element-wise maximum over a row's edges and its backward over A^T (the wide-row gather: a lane group per neighbour row)
 //   tcgnn_segment_stats.inc   mean / std / max / min over a row's edges in one walk and the backward of all four over A^T (PNA; segment_max's scheduling)
 //   tcgnn_gatv2.inc           GATv2 attention: fused score + softmax, the row-side backward (g, d_xr, d_attn), the source-side backward (d_xl)
+//   tcgnn_edge_message.inc    a feature vector per edge: sum of act(X[col] + Ef) over a row's edges, its backward (the per-edge gradient dM),
+//                             the sum of per-edge rows into nodes, optionally through perm over A^T (segment_max's scheduling)
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells (a cell stream in named steps over a
 //                             CellBuild; flat_entries, the entry records, is a pure host function; cells_publish cannot fail), build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
@@ -321,6 +323,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_segment_max.inc"
 #include "tcgnn_segment_stats.inc"
 #include "tcgnn_gatv2.inc"
+#include "tcgnn_edge_message.inc"
 
 // ---- run-time switches.  Product: TCGNN_SPMM_MODE / TCGNN_RANGE_GUARD (initial values of tcgnn_set_spmm_mode / tcgnn_set_range_guard,
 // include/tcgnn.h) and TCGNN_VERBOSE (plan statistics on stderr).  TEST AIDS, read through test_knob() only - tests/ forces every walk

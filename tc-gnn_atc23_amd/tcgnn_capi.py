@@ -98,6 +98,9 @@ SIGNATURES = {
     "tcgnn_gatv2_softmax_backward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _i32, _i32, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp,
                                                     _vp, _sz, _vp]),
     "tcgnn_gatv2_source_grad": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i64, _i32, _i32, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp]),
+    "tcgnn_edge_message": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "tcgnn_edge_message_backward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "tcgnn_edge_sum": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _i32, _vp, _vp]),
     "tcgnn_agnn_supported": (ctypes.c_int, [_vp, _i32]),
     "tcgnn_agnn_pair_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp]),
     "tcgnn_agnn_pair_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _sz, _vp]),

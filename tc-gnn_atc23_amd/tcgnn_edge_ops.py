@@ -14,13 +14,15 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     edge_softmax_heads(S, rowptr, beta)  edge_softmax of every row of S [H, E] (head by head on the one-head operator, one [H, E] result)
     aggregate_max(X, rowptr, col) Y[i, d] = max over row i of X[col e, d] (0 for an empty row)     bwd: dX[j, d] = sum of dY[i, d] over the edges that won (i, d)
     aggregate_stats(Z, rowptr, col, aggregators)  mean / std / max / min over row i of Z[col e, d], one gather for all (PNA)     bwd: one walk over A^T for all of them
+    aggregate_ue(X, Ef, rowptr, col, act)  Y[i, d] = sum over row i of act(X[col e, d] + Ef[e, d]), Ef [E, D] (u_add_e; GINE)   bwd: dM = dY[row e] masked, once; dEf = dM, dX = sum of dM by source over A^T
+    edge_sum(M, rowptr, col)      Y[i, d] = sum over row i of M[e, d], M [E, D] (copy_e)                        bwd: dM[e] = dY[row e]
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -279,6 +281,66 @@ def aggregate_stats(Z, row_pointers, column_index, aggregators=("mean", "std", "
     if not names or len(set(names)) != len(names) or any(a not in ("mean", "std", "max", "min") for a in names):
         raise ValueError("aggregators must be distinct names among mean, std, max, min, got %r" % (aggregators,))
     return _AggregateStats.apply(Z, row_pointers, column_index, names, float(eps))
+
+
+class _AggregateUE(torch.autograd.Function):
+    """Y = forward_ue(X, Ef); backward: dM = backward_ue(dY) ONCE - it is dEf, and dX = edge_sum(dM) over A^T through perm.  Saved: X
+    and Ef under ReLU (the mask is recomputed from them); nothing under the identity."""
+
+    @staticmethod
+    def forward(ctx, X, Ef, row_pointers, column_index, act):
+        X, Ef = X.contiguous(), Ef.contiguous()
+        ctx.graph, ctx.act = (row_pointers, column_index), act
+        if act == "relu":
+            ctx.save_for_backward(X, Ef)
+        return _L.backend().forward_ue(X, Ef, row_pointers, column_index, act=act)
+
+    @staticmethod
+    def backward(ctx, d_y):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return (None,) * 5
+        X, Ef = ctx.saved_tensors if ctx.act == "relu" else (None, None)
+        b = _L.backend()
+        d_m = b.backward_ue(d_y.contiguous(), X, Ef, *ctx.graph, act=ctx.act)
+        d_x = None
+        if ctx.needs_input_grad[0]:
+            rp_t, _, perm, _ = b.transpose_graph(*ctx.graph)
+            d_x = b.edge_sum(d_m, rp_t, perm)
+        return d_x, (d_m if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def aggregate_ue(X, Ef, row_pointers, column_index, act="relu"):
+    """Y[i, d] = the sum over the edges e of CSR row i of act(X[col e, d] + Ef[e, d]): message passing with a feature vector per edge
+    (DGL's u_add_e / sum; act 'relu': GINEConv's message, 'identity' or None: the plain sum).  X: [N, D], Ef: [E, D] in CSR position
+    order.  One fused walk, no [E, D] tensor going forward; going back the per-edge gradient dM [E, D] is made once - it IS dEf - and
+    dX is its sum by source node, one row-granular read of dM over A^T.  fp64 sums in a fixed order, no atomics; exact on any graph."""
+    if act not in ("relu", "identity", None):
+        raise ValueError("act must be 'relu', 'identity' or None, got %r" % (act,))
+    if X.dim() != 2 or Ef.dim() != 2 or Ef.shape[0] != column_index.numel() or Ef.shape[1] != X.shape[1]:
+        raise RuntimeError("X must be [N, D] and Ef [E, D] = [%d, %d], got %s and %s" % (column_index.numel(), X.shape[-1], tuple(X.shape), tuple(Ef.shape)))
+    return _AggregateUE.apply(X, Ef, row_pointers, column_index, "relu" if act == "relu" else "identity")
+
+
+class _EdgeSum(torch.autograd.Function):
+    """Y = edge_sum(M) by destination node; dM[e] = dY[row e]: backward_ue without an activation."""
+
+    @staticmethod
+    def forward(ctx, M, row_pointers, column_index):
+        ctx.graph = (row_pointers, column_index)
+        return _L.backend().edge_sum(M.contiguous(), row_pointers)
+
+    @staticmethod
+    def backward(ctx, d_y):
+        d_m = _L.backend().backward_ue(d_y.contiguous(), None, None, *ctx.graph, act=None) if ctx.needs_input_grad[0] else None
+        return d_m, None, None
+
+
+def edge_sum(M, row_pointers, column_index):
+    """Y[i, d] = the sum of M[e, d] over the edges e of CSR row i (DGL's copy_e / sum): per-edge rows [E, D] in CSR position order summed
+    into their destination nodes, fp64 in a fixed order; a row without edges gives 0.  bwd: dM[e] = dY[row e]."""
+    if M.dim() != 2 or M.shape[0] != column_index.numel():
+        raise RuntimeError("M must be [E, D] with E = %d, got %s" % (column_index.numel(), tuple(M.shape)))
+    return _EdgeSum.apply(M, row_pointers, column_index)
 
 
 def gat_attention(el, er, row_pointers, column_index, negative_slope=0.2):

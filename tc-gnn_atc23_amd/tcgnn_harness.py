@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna", "gine"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -57,6 +57,8 @@ def build_parser():
     p.add_argument("--aggregator", type=str, default="mean", choices=["mean", "max", "pool"],
                    help="SAGE only: GraphSAGE's neighbour aggregation - 'mean', or the element-wise maximum over a node's incoming edges of the "
                    "features ('max') or of a learned projection of them ('pool') (not in the reference)")
+    p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
+                   help="GINE only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
     return p
 
 
@@ -131,7 +133,7 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean"):
+                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -143,7 +145,9 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     heads (GAT, GATv2 and transformer only, not in the reference): the hidden layers are GATConv / GATv2Conv / TransformerConv(., hidden / heads, heads=heads) -
     concatenated back to `hidden` - and the output layer is one head of `classes`; A^T's plan and the edge operators' buffers are prepared at the per-head widths.
     aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks.
-    model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max."""
+    model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max.
+    model 'gine' (not in the reference): GINEConv layers with edge_dim=edge_dim; no dataset here has edge features, so edge_attr [E, edge_dim] is drawn
+    ONCE, standard normal, from a generator on the device seeded with `seed`, and every layer reads it; the transposed CSR is prepared as for SAGE's max."""
     import tcgnn_layers as L
     heads = int(heads)
     multi_head = model_name in ("gat", "gatv2", "transformer")
@@ -167,6 +171,15 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     elif model_name == "sage":
         def conv_cls(a, b, **kw):
             return L.SAGEConv(a, b, aggregator=aggregator, **kw)
+    elif model_name == "gine":
+        edge_attr = torch.randn(meta[1].numel(), int(edge_dim), device=x.device, generator=torch.Generator(device=x.device).manual_seed(seed))
+
+        class conv_cls(L.GINEConv):
+            def __init__(self, a, b, **kw):
+                super().__init__(a, b, edge_dim=int(edge_dim), **kw)
+
+            def forward(self, X, *graph):
+                return super().forward(X, *graph, edge_attr=edge_attr)
     else:
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
@@ -181,8 +194,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if model_name != "agnn":
             raise ValueError("attention applies to the AGNN model only")
         conv_kwargs["attention"] = attention
-    if multi_head or model_name == "pna":
-        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv and PNAConv back-propagate through A^T on every graph)
+    if multi_head or model_name in ("pna", "gine"):
+        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv, PNAConv and GINEConv back-propagate through A^T on every graph)
     model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
@@ -200,8 +213,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
         prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
              **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
-    elif prep is not None and meta[0].is_cuda and model_name == "pna":
-        prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats are planless: the transposed CSR is all they need)
+    elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
+        prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
     elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
         prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
              **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if multi_head else
@@ -289,11 +302,14 @@ def run(args, quiet=False):
         result["sag_ms"] = L.SAG(*meta).profile(x)
         return result
 
+    if args.model == "gine":
+        say("edge_attr:\t[%d, %d] standard normal, drawn once on the device from seed %d (the dataset carries no edge features)"
+            % (meta[1].numel(), getattr(args, "edge_dim", 16), args.seed))
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
-                      aggregator=getattr(args, "aggregator", "mean"))
+                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

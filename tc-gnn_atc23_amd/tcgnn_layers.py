@@ -10,7 +10,7 @@ gnn_conv.py:26-247, so a model written against the reference runs against this f
                         bwd: G = A_att dY; dX = G W^T; dW = X^T G;
                              da = (sddmm(dY)[None,:] @ col[:,None].float())^T
     SAG / GCNConv / GINConv / AGNNConv modules, n_heads = 1                                    (:10, :167-247)
-    GATConv, GATv2Conv, SAGEConv, PNAConv (not in the reference: DGL's / PyG's layers of those names)
+    GATConv, GATv2Conv, SAGEConv, PNAConv, GINEConv (not in the reference: DGL's / PyG's layers of those names)
 
 The reference's backward uses A, not A^T (it assumes a symmetric graph) and does not propagate
 through ef into H; both are reproduced because the golden fixtures captured from gnn_conv.py
@@ -818,6 +818,65 @@ class SAGEConv(torch.nn.Module):
             if self.aggregator == "pool":
                 X = torch.relu(dense_update(X, self.weights_pool) + self.bias_pool)
             out = out + dense_update(E.aggregate_max(X, row_pointers, column_index), self.weights)
+        return out + self.bias if self.bias is not None else out
+
+
+class GINEConv(torch.nn.Module):
+    """Not in the reference: GIN with edge features after PyG's GINEConv (Hu et al., "Strategies for Pre-training Graph Neural Networks"),
+        h = (1 + eps) X + sum over a node's incoming edges e of relu(X[col e] + Ef'[e]);   out = h W + b,
+    with Ef' = edge_attr W_e + b_e when edge_dim is given (required when the edge features are not input_dim wide) and Ef' = edge_attr
+    [E, input_dim] otherwise; edge_attr rows are in CSR position order.  The sum is tcgnn_edge_ops.aggregate_ue: one fused walk, exact
+    gradients for X and edge_attr on any graph.  One linear map where PyG takes any `nn`, as this file's GINConv does.  eps is a
+    Parameter with train_eps, a buffer otherwise.  Glorot-uniform weights, zero biases."""
+
+    def __init__(self, input_dim, output_dim, edge_dim=None, eps=0.0, train_eps=False, bias=True):
+        super().__init__()
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
+        self.weights = torch.nn.Parameter(torch.empty(self.input_dim, self.output_dim))
+        if self.edge_dim is not None:
+            self.weights_edge = torch.nn.Parameter(torch.empty(self.edge_dim, self.input_dim))
+            self.bias_edge = torch.nn.Parameter(torch.zeros(self.input_dim))
+        else:
+            self.register_parameter("weights_edge", None)
+            self.register_parameter("bias_edge", None)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(self.output_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.initial_eps = float(eps)
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.tensor(self.initial_eps, dtype=torch.float32))
+        else:
+            self.register_buffer("eps", torch.tensor(self.initial_eps, dtype=torch.float32))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.weights)
+        if self.weights_edge is not None:
+            torch.nn.init.xavier_uniform_(self.weights_edge)
+            self.bias_edge.data.zero_()
+        if self.bias is not None:
+            self.bias.data.zero_()
+        self.eps.data.fill_(self.initial_eps)
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, edge_attr=None):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        if edge_attr is None:
+            raise ValueError("GINEConv needs edge_attr: one feature row per edge, in CSR position order")
+        if edge_attr.dim() != 2 or edge_attr.shape[0] != column_index.numel():
+            raise ValueError("edge_attr must be [num_edges, features] = [%d, .], got %s" % (column_index.numel(), tuple(edge_attr.shape)))
+        if self.edge_dim is None:
+            if edge_attr.shape[1] != self.input_dim:
+                raise ValueError("edge_attr is %d wide and the node features %d: construct the layer with edge_dim=%d" %
+                                 (edge_attr.shape[1], self.input_dim, edge_attr.shape[1]))
+            Ef = edge_attr
+        else:
+            if edge_attr.shape[1] != self.edge_dim:
+                raise ValueError("edge_attr is %d wide, the layer was built with edge_dim=%d" % (edge_attr.shape[1], self.edge_dim))
+            Ef = dense_update(edge_attr, self.weights_edge) + self.bias_edge
+        h = (1.0 + self.eps) * X + E.aggregate_ue(X, Ef, row_pointers, column_index, "relu")
+        out = dense_update(h, self.weights)
         return out + self.bias if self.bias is not None else out
 
 
