@@ -172,6 +172,35 @@ int tcgnn_transpose_ws(const int32_t* d_nodePointer, const int32_t* d_edgeList, 
                        size_t workspace_bytes, int32_t* symmetric, void* stream);
 int tcgnn_permute_edge_values(const float* d_val, const int32_t* d_perm, int64_t num_edges, float* d_out, void* stream);
 
+/* Seeded neighbour sampling (no counterpart in the reference): the graph over the SAME num_nodes nodes that keeps at most `fanout`
+ * in-edges per row - what fan-out training (GraphSAGE; DGL's sample_neighbors) aggregates over.  Every operator of this header takes
+ * the result as it takes any square CSR.  Every CSR position e gets a 64-bit word that depends on (seed, e) alone, all arithmetic
+ * modulo 2^64:
+ *     G = 0x9E3779B97F4A7C15
+ *     mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *     h32(seed, e)  = mix(mix(seed + G) + (e + 1) * G) >> 32
+ *     word(seed, e) = (h32(seed, e) << 32) | e                       (unique: no tie rule)
+ * A row of degree d <= fanout keeps all its edges, a longer one the fanout positions with the smallest words; a row whose d_row_mask
+ * byte (uint8 [num_nodes], may be NULL: all ones) is 0 keeps none.  Kept edges stay in CSR order.  Outputs:
+ *   d_nodePointer_s [num_nodes + 1], d_edgeList_s [E'], d_eid [E']: eid = the CSR position in the input of every kept edge.
+ * A pure function of its inputs (no global atomics): bit-identical on repetition; without replacement, uniform over the
+ * fanout-subsets of a row up to collisions of h32.  DEVICE pointers.
+ * tcgnn_sample_neighbors_count: writes d_nodePointer_s (an exclusive scan of min(d, fanout) * mask) and *num_sampled = E', on CALLER
+ *   scratch (tcgnn_sample_workspace_bytes, 256-byte aligned; allocates nothing), and synchronises `stream` ONCE to read back E' and the
+ *   validation words: nodePointer[0] = 0, monotone, nodePointer[num_nodes] = num_edges, else TCGNN_ERR_BAD_GRAPH.  Until that check
+ *   every index derived from nodePointer is clamped to [0, num_edges].
+ * tcgnn_sample_neighbors: with the d_nodePointer_s the count call wrote for the same (nodePointer, row_mask, fanout), writes exactly E'
+ *   entries of d_edgeList_s and of d_eid.  Stream-ordered, no allocation, no synchronisation; reads the column id of kept edges only.
+ * Both return TCGNN_ERR_INVALID_ARG before any launch for num_edges > 2^31 - 1, a negative fanout or a null required pointer, the count
+ * call TCGNN_ERR_WORKSPACE for scratch that is too small or not 256-byte aligned. */
+int tcgnn_sample_workspace_bytes(int32_t num_nodes, size_t* bytes);
+int tcgnn_sample_neighbors_count(const int32_t* d_nodePointer, const uint8_t* d_row_mask, int32_t num_nodes, int64_t num_edges,
+                                 int32_t fanout, int32_t* d_nodePointer_s, void* d_workspace, size_t workspace_bytes,
+                                 int64_t* num_sampled, void* stream);
+int tcgnn_sample_neighbors(const int32_t* d_nodePointer, const int32_t* d_edgeList, const uint8_t* d_row_mask,
+                           const int32_t* d_nodePointer_s, int32_t num_nodes, int64_t num_edges, int32_t fanout, uint64_t seed,
+                           int32_t* d_edgeList_s, int32_t* d_eid, void* stream);
+
 /* Tile statistics of the translation - what the reference's counting scripts report
  * (3_cnt_TC_blk_SpMM.py:38-94 with 16x8 tiles, 3_cnt_TC_blk_SDDMM.py with 16x16; logs/16x8_reduction.csv,
  * logs/reduce_blocks.csv): per window of tile_h rows, U = sorted unique neighbour ids;

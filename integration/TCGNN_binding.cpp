@@ -785,6 +785,45 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(to
   return {t.rp_t, t.col_t, t.perm, t.symmetric};
 }
 
+// Not in the reference: seeded neighbour sampling (tcgnn_sample_neighbors_count + tcgnn_sample_neighbors; TCGNN.sample_neighbors of the
+// ctypes module).  The graph over the same nodes with at most `fanout` in-edges per row: (nodePointer_s, edgeList_s, eid).  fanout = None
+// keeps every edge.  seed: any Python int, taken modulo 2^64.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_neighbors(torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<int64_t> fanout,
+                                                                         py::int_ seed, c10::optional<torch::Tensor> row_mask) {
+  CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  TORCH_CHECK(edgeList.device() == nodePointer.device(), "nodePointer and edgeList must be on one device");
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel();
+  const uint8_t* mask = nullptr;
+  torch::Tensor mask_keep;
+  if (row_mask.has_value()) {
+    CHECK_INPUT((*row_mask));
+    TORCH_CHECK(row_mask->scalar_type() == torch::kUInt8 || row_mask->scalar_type() == torch::kBool, "row_mask must be uint8 or bool");
+    TORCH_CHECK(row_mask->numel() == N && row_mask->device() == nodePointer.device(), "row_mask must hold one entry per node on nodePointer's device");
+    mask_keep = *row_mask;
+    mask = static_cast<const uint8_t*>(mask_keep.data_ptr());
+  }
+  TORCH_CHECK(!fanout.has_value() || *fanout >= 0, "fanout must be None or >= 0");
+  const int32_t k = (int32_t)std::min<int64_t>(fanout.value_or(0x7fffffff), 0x7fffffff);
+  const uint64_t seed64 = py::cast<uint64_t>(seed.attr("__and__")(py::int_(0xFFFFFFFFFFFFFFFFull)));
+  DeviceGuard guard(nodePointer.device());
+  size_t need = 0;
+  tcgnn_check(tcgnn_sample_workspace_bytes((int32_t)N, &need), "tcgnn_sample_workspace_bytes");
+  torch::Tensor ws = torch::empty({(int64_t)need + 256}, nodePointer.options().dtype(torch::kUInt8));
+  char* wsp = static_cast<char*>(ws.data_ptr());
+  wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
+  torch::Tensor rp_s = torch::empty({N + 1}, nodePointer.options());
+  int64_t kept = 0;
+  tcgnn_check(tcgnn_sample_neighbors_count(nodePointer.data_ptr<int>(), mask, (int32_t)N, E, k, rp_s.data_ptr<int>(), wsp, need, &kept,
+                                           current_stream(nodePointer)), "tcgnn_sample_neighbors_count");
+  torch::Tensor col_s = torch::empty({kept}, edgeList.options()), eid = torch::empty({kept}, edgeList.options());
+  if (kept > 0)
+    tcgnn_check(tcgnn_sample_neighbors(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), mask, rp_s.data_ptr<int>(), (int32_t)N, E, k, seed64,
+                                       col_s.data_ptr<int>(), eid.data_ptr<int>(), current_stream(nodePointer)), "tcgnn_sample_neighbors");
+  return {rp_s, col_s, eid};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -928,6 +967,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu", py::arg("out") = py::none());
   m.def("edge_sum", &edge_sum, "per-edge rows summed into nodes, optionally through perm (not in the reference)", py::arg("M"), py::arg("nodePointer"),
         py::arg("perm") = py::none(), py::arg("out") = py::none());
+  m.def("sample_neighbors", &sample_neighbors, "seeded fan-out sampling over the same nodes: (nodePointer_s, edgeList_s, eid) (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("fanout"), py::arg("seed"), py::arg("row_mask") = py::none());
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

@@ -37,7 +37,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum"]
+           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors"]
 
 
 def _stream(device):
@@ -61,7 +61,8 @@ _cache = GraphCache(os.environ.get("TCGNN_PLAN_CACHE_SIZE", "8"), _c.lib.tcgnn_p
 _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
-          "softmax": (1, 256)}        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
+          "softmax": (1, 256),        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
+          "sample": (1, 256)}         # sample_neighbors' row counts and scan scratch (its count call synchronises: nothing reads it afterwards)
 
 
 def _buffer(kind, need, device, stream=None):
@@ -211,6 +212,50 @@ def transpose_graph(nodePointer, edgeList):
     if c.transposed is None:
         c.transposed = _transpose(nodePointer, edgeList)
     return c.transposed
+
+
+# ---------------------------------------------------------------- neighbour sampling
+
+def sample_neighbors(nodePointer, edgeList, fanout, seed, row_mask=None):
+    """Not in the reference module: seeded fan-out sampling, (nodePointer_s, edgeList_s, eid).  The sampled graph keeps the node set
+    (DGL's sample_neighbors): a square CSR over the same nodes in which a row of degree d keeps all its in-edges when d <= fanout and
+    else the fanout positions with the smallest words (h32(seed, e) << 32) | e (include/tcgnn.h states h32), in CSR order; a row whose
+    row_mask entry (uint8 or bool [num_nodes]) is 0 keeps none.  eid (int32 [E']) = the CSR position in edgeList of every kept edge:
+    edge values or features of the sampled graph are val[eid].  A pure function of its arguments.  fanout=None keeps every edge of the
+    unmasked rows; seed is any int, taken modulo 2**64.  One stream synchronisation (to size the outputs)."""
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    dev = nodePointer.device
+    if edgeList.device != dev:
+        raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, dev))
+    if nodePointer.numel() < 1:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+    N, E = nodePointer.numel() - 1, edgeList.numel()
+    if row_mask is not None:
+        _check_input(row_mask, "row_mask")
+        if row_mask.dtype not in (torch.uint8, torch.bool):
+            raise RuntimeError("row_mask must be uint8 or bool, not %s" % row_mask.dtype)
+        if row_mask.numel() != N or row_mask.device != dev:
+            raise RuntimeError("row_mask must hold one entry per node (%d) on %s" % (N, dev))
+    if fanout is not None and int(fanout) < 0:
+        raise ValueError("fanout must be None or >= 0, not %r" % (fanout,))
+    k = 0x7fffffff if fanout is None else min(int(fanout), 0x7fffffff)
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_sample_workspace_bytes(N, _c.ctypes.byref(need)), "tcgnn_sample_workspace_bytes")
+        ws, ws_bytes = _buffer("sample", need.value, dev, stream)
+        rp_s = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        kept = _c._i64(0)
+        _c.check(_c.lib.tcgnn_sample_neighbors_count(nodePointer.data_ptr(), _ptr(row_mask), N, E, k, rp_s.data_ptr(), ws, ws_bytes,
+                                                     _c.ctypes.byref(kept), stream), "tcgnn_sample_neighbors_count")
+        col_s = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        eid = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        if kept.value:
+            _c.check(_c.lib.tcgnn_sample_neighbors(nodePointer.data_ptr(), edgeList.data_ptr(), _ptr(row_mask), rp_s.data_ptr(), N, E, k,
+                                                   int(seed) & 0xFFFFFFFFFFFFFFFF, col_s.data_ptr(), eid.data_ptr(), stream), "tcgnn_sample_neighbors")
+    return rp_s, col_s, eid
 
 
 def _transposed_plan(e):

@@ -49,6 +49,7 @@
 //   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction; launch_agnn*
 //   tcgnn_small_fallback.inc  CSR kernels of non-canonical plans, the range guard's fallbacks, symmetry_kernel, wide_patch_kernel
 //   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
+//   tcgnn_sample.inc          seeded neighbour sampling: row counts + validation, the per-row select (host side: tcgnn_sample.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
 //   tcgnn_segment_max.inc     element-wise maximum over a row's edges and its backward over A^T (the wide-row gather: a lane group per neighbour row)
@@ -317,6 +318,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_heads.inc"   // (behind the fallbacks: its range-guard kernel is spmm_wide_fallback_body per head)
 
 #include "tcgnn_transpose.inc"
+#include "tcgnn_sample.inc"
 
 #include "tcgnn_edge_softmax.inc"
 #include "tcgnn_gat.inc"

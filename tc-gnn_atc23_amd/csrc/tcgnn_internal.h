@@ -25,5 +25,13 @@ int transpose_check(const int32_t* rowptr, const int32_t* col, const int32_t* ro
                     uint32_t* res, void* stream);
 int permute_edge_values(const float* val, const int32_t* perm, int64_t E, float* out, void* stream);
 
+// Launchers of the neighbour sampler's kernels (tcgnn_sample.inc, compiled into tcgnn_device.hip; the entry points are in
+// tcgnn_sample.hip).  Stream-ordered; each returns the hipError_t of its launch as an int.
+int64_t sample_scan_blocks(int32_t N);   // words of scratch sample_count needs
+int sample_count(const int32_t* rowptr, const uint8_t* mask, int32_t N, int64_t E, int32_t fanout, uint32_t* sums, uint32_t* res, int32_t* rowptr_s,
+                 void* stream);
+int sample_select(const int32_t* rowptr, const int32_t* col, const uint8_t* mask, const int32_t* rowptr_s, int32_t N, int64_t E, int32_t fanout,
+                  uint64_t seed, int32_t* col_s, int32_t* eid, void* stream);
+
 } // namespace tcgnn
 #endif

@@ -59,7 +59,22 @@ def build_parser():
                    "features ('max') or of a learned projection of them ('pool') (not in the reference)")
     p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
                    help="GINE only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
+    p.add_argument("--fanout", type=str, default=None,
+                   help="K[,K...]: train every epoch on a freshly sampled graph that keeps at most K in-edges per node (TCGNN.sample_neighbors, seed + epoch); "
+                   "several values give one fan-out per layer, input layer first; the final loss is evaluated on the full graph (not in the reference)")
     return p
+
+
+def parse_fanout(text, num_layers):
+    """--fanout's value as one fan-out per layer (None: no sampling)"""
+    if text is None:
+        return None
+    ks = [int(t) for t in str(text).split(",")] if not isinstance(text, (list, tuple)) else [int(t) for t in text]
+    if len(ks) == 1:
+        ks = ks * num_layers
+    if len(ks) != num_layers or min(ks) < 0:
+        raise ValueError("--fanout takes one value >= 0, or one per layer (%d), got %r" % (num_layers, text))
+    return ks
 
 
 class Net(nn.Module):
@@ -81,10 +96,13 @@ class Net(nn.Module):
         return self.relu(conv(x, *meta))
 
     def forward(self, x, meta):
-        x = self._act(self.conv1, x, meta)
+        """meta: the graph's five tensors, or a sequence of such groups with one graph per layer (fan-out sampling)"""
+        per_layer = list(meta) if isinstance(meta[0], (list, tuple)) else [meta] * (len(self.hidden_layers) + 2)
+        meta = per_layer[-1]
+        x = self._act(self.conv1, x, per_layer[0])
         x = F.dropout(x, training=self.training)
-        for conv in self.hidden_layers:
-            x = self._act(conv, x, meta)
+        for conv, m in zip(self.hidden_layers, per_layer[1:-1]):
+            x = self._act(conv, x, m)
         import tcgnn_layers as L
         din, dout = self.conv2.weights.shape if isinstance(self.conv2, L.GCNConv) else (0, 0)   # (only GCNConv has the aggregate-first form)
         want = AGGREGATE_FIRST in (True, "1") or (AGGREGATE_FIRST == "auto" and din < dout)
@@ -133,7 +151,7 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16):
+                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -147,8 +165,19 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     aggregator (SAGE only, not in the reference): SAGEConv(aggregator=...); 'max' and 'pool' prepare the transposed CSR their backward walks.
     model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max.
     model 'gine' (not in the reference): GINEConv layers with edge_dim=edge_dim; no dataset here has edge features, so edge_attr [E, edge_dim] is drawn
-    ONCE, standard normal, from a generator on the device seeded with `seed`, and every layer reads it; the transposed CSR is prepared as for SAGE's max."""
+    ONCE, standard normal, from a generator on the device seeded with `seed`, and every layer reads it; the transposed CSR is prepared as for SAGE's max.
+    fanout (not in the reference; None: the path above, unchanged): a list of one fan-out per layer.  Every epoch, dry ones included, draws
+    tcgnn_layers.sample_meta(meta, k, seed + epoch) per distinct k, builds what the model's operators need on it (the plan at every width and,
+    for the layers with a `directed` switch, A^T's - a sampled graph is not symmetric, so those layers are built with directed=True - or, for
+    the planless models, only the transposed CSR) and trains on it; GINE gathers edge_attr[eid].  The three parts are timed apart, each
+    behind a device synchronisation: the result holds sample_ms, plan_ms and train_ms per epoch and their sum epoch_ms.  Plans are created
+    every epoch: that cost is plan_ms, not hidden.  final_loss is the loss on the FULL graph after the last step (model.eval()).  Refused
+    together with hip_graph: a captured epoch replays one graph."""
     import tcgnn_layers as L
+    if fanout is not None and hip_graph:
+        raise ValueError("--fanout samples a new graph every epoch and can not be combined with --hip_graph, which replays one captured epoch")
+    fanout = parse_fanout(fanout, num_layers)
+    directed = bool(directed) or fanout is not None
     heads = int(heads)
     multi_head = model_name in ("gat", "gatv2", "transformer")
     if heads != 1 and not multi_head:
@@ -178,12 +207,13 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
             def __init__(self, a, b, **kw):
                 super().__init__(a, b, edge_dim=int(edge_dim), **kw)
 
-            def forward(self, X, *graph):
-                return super().forward(X, *graph, edge_attr=edge_attr)
+            def forward(self, X, *graph):   # (a sampled graph's rows of edge_attr: sampled_attr, keyed by its column_index)
+                return super().forward(X, *graph, edge_attr=sampled_attr.get(graph[1].data_ptr(), edge_attr))
     else:
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
         conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv}[model_name]
+    sampled_attr = {}
     torch.manual_seed(seed)
     if model_name != "gcn" and (norm != "none" or bias):
         raise ValueError("norm / bias apply to the GCN model only")
@@ -208,20 +238,62 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         return loss
 
     prep = getattr(L.backend(), "prepare", None)
-    if prep is not None and meta[0].is_cuda and model_name == "sage":
-        # a mean layer aggregates at min(in, out), the max layers take no plan-based aggregation at all
-        dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
-        prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
-             **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
-    elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
-        prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
-    elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at: nothing is built (or synchronised) inside an epoch
-        prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
-             **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if multi_head else
-                {"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
-                ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
+    planless = model_name in ("pna", "gine") or (model_name == "sage" and aggregator != "mean")
+
+    def prepare(meta):
+        """what this model's operators need on the graph `meta`, built now: nothing is built (or synchronised) inside a step"""
+        if planless and prep is not None and meta[2].numel() == 0:
+            L.backend().transpose_graph(meta[0], meta[1])   # (a sampled graph without metadata: the transposed CSR is all the planless operators need)
+        elif prep is not None and meta[0].is_cuda and model_name == "sage":
+            # a mean layer aggregates at min(in, out), the max layers take no plan-based aggregation at all
+            dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
+            prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
+                 **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
+        elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
+            prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
+        elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at
+            prep(([in_dim] if model_name == "gin" else []) + [hidden // heads] * max(1, num_layers - 1) + [classes], *meta,
+                 **({"transpose": True, "edge_valued": True, "attention": True, "heads": heads} if multi_head else
+                    {"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
+                    ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
+
+    if fanout is None:
+        prepare(meta)
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)
+    if fanout is not None:
+        full, spent = meta, {"sample_ms": 0.0, "plan_ms": 0.0, "train_ms": 0.0}
+
+        def lap(key, since):
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            spent[key] += (now - since) * 1e3
+            return now
+
+        for epoch in range(warmup + epochs):
+            if epoch == warmup:
+                spent = dict.fromkeys(spent, 0.0)
+            t = time.perf_counter()
+            drawn = {k: L.sample_meta(full, k, seed + epoch, plan=False) for k in set(fanout)}
+            t = lap("sample_ms", t)
+            sampled_attr.clear()
+            for k, (m, eid) in drawn.items():
+                if not planless:
+                    m = L.csr_meta(m[0], m[1])
+                    drawn[k] = (m, eid)
+                prepare(m)
+                if model_name == "gine":
+                    sampled_attr[m[1].data_ptr()] = edge_attr[eid.long()]
+            t = lap("plan_ms", t)
+            meta = [drawn[k][0] for k in fanout]
+            loss = train()
+            lap("train_ms", t)
+        model.eval()
+        with torch.no_grad():
+            final = float(node_nll_loss(model(x, full), y))
+        r = {k: v / max(epochs, 1) for k, v in spent.items()}
+        r.update(epoch_ms=sum(r.values()), final_loss=final, sampled_loss=float(loss.detach()), fanout=fanout)
+        return r
     for _ in range(warmup):
         train()
     torch.cuda.synchronize()
@@ -309,7 +381,9 @@ def run(args, quiet=False):
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
-                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16))
+                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None))
+    if "sample_ms" in r:
+        say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

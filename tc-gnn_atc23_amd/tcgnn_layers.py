@@ -955,3 +955,51 @@ class PNAConv(torch.nn.Module):
             part = dense_update(block, self.weights_post[self.input_dim + k * wide:self.input_dim + (k + 1) * wide])
             out = out + (part if s == "identity" else part * scale[s])
         return out + self.bias_post if self.bias_post is not None else out
+
+
+# ---------------------------------------------------------------- fan-out sampling (not in the reference)
+
+def csr_meta(row_pointers, column_index):
+    """The five metadata tensors of a CSR on the device: the device sparse-graph translation at the 16 x 8 tile every layer here uses"""
+    import contextlib
+    import io
+    N, E, dev = row_pointers.numel() - 1, column_index.numel(), row_pointers.device
+    bp = torch.zeros((N + 15) // 16, dtype=torch.int32, device=dev)
+    e2c = torch.zeros(E, dtype=torch.int32, device=dev)
+    e2r = torch.zeros(E, dtype=torch.int32, device=dev)
+    with contextlib.redirect_stdout(io.StringIO()):   # (the translation's two TC_Blocks lines belong to the full graph's run)
+        backend().preprocess_gpu(column_index, row_pointers, N, 16, 8, bp, e2c, e2r)
+    return (row_pointers, column_index, bp, e2c, e2r)
+
+
+def sample_meta(meta_or_csr, fanout, seed, row_mask=None, plan=True):
+    """(meta_s, eid): the graph over the same nodes that keeps at most `fanout` in-edges per row (the backend's sample_neighbors: a pure
+    function of the CSR, fanout, seed and row_mask), as the five tensors every layer here takes, and the CSR position in the full graph
+    of every kept edge - edge features or weights of the sampled graph are edge_attr[eid.long()].  meta_or_csr: the full graph's five
+    metadata tensors, or just (row_pointers, column_index).
+    plan=True runs the device sparse-graph translation on the sampled CSR: any layer takes the result.  plan=False pads the CSR pair with
+    empty metadata, for layers that call planless operators only (SAGEConv max / pool, PNAConv, GINEConv).
+    A sampled graph has NEW tensors: a layer that aggregates through a plan builds one for it at first use, and every new sampled graph
+    takes one slot of the backend's plan / CSR cache (TCGNN.set_plan_cache_size; least recently used first, so resampling every epoch
+    stays bounded).  A sampled graph is not symmetric even when the full one is: layers with a `directed` switch want directed=True."""
+    rp_s, col_s, eid = backend().sample_neighbors(meta_or_csr[0], meta_or_csr[1], fanout, seed, row_mask)
+    if plan:
+        return csr_meta(rp_s, col_s), eid
+    empty = tuple(torch.empty(0, dtype=torch.int32, device=rp_s.device) for _ in range(3))
+    return (rp_s, col_s) + empty, eid
+
+
+def sample_layers(csr, seeds, fanouts, seed):
+    """Layered fan-out sampling (DGL's MultiLayerNeighborSampler, e.g. fanouts [25, 10]) without relabelling: one sampled graph per
+    layer, input layer first, each (row_pointers_s, column_index_s, eid) over the SAME node set.  The last layer's graph keeps up to
+    fanouts[-1] in-edges of the seed nodes only; the layer before it those of the seeds and of that hop's sources, and so on
+    (row_mask = the frontier).  Hop h from the seeds draws with seed + h."""
+    rp, col = csr[0], csr[1]
+    frontier = torch.zeros(rp.numel() - 1, dtype=torch.uint8, device=rp.device)
+    frontier.index_fill_(0, seeds.long(), 1)
+    graphs = []
+    for hop, k in enumerate(reversed(list(fanouts))):
+        g = backend().sample_neighbors(rp, col, k, int(seed) + hop, frontier)
+        graphs.insert(0, g)
+        frontier = frontier.clone().index_fill_(0, g[1].long(), 1)
+    return graphs
