@@ -201,6 +201,46 @@ int tcgnn_sample_neighbors(const int32_t* d_nodePointer, const int32_t* d_edgeLi
                            const int32_t* d_nodePointer_s, int32_t num_nodes, int64_t num_edges, int32_t fanout, uint64_t seed,
                            int32_t* d_edgeList_s, int32_t* d_eid, void* stream);
 
+/* Relabelled mini-batch blocks (no counterpart in the reference): the sampled layer graphs of one mini-batch keep all num_nodes rows;
+ * these calls find the M nodes they touch and emit the same graphs over those M nodes.  Inputs: one or more CSRs over the same
+ * num_nodes nodes and a byte mask d_keep [num_nodes] that the caller has cleared or filled with the seeds.  The node set is every v for
+ * which, in any of the graphs, keep[v] != 0 held beforehand, v has at least one edge, or v is a column id.  Outputs:
+ *   d_nodes  int32 [M], strictly increasing: the kept original ids;
+ *   d_new_id int32 [num_nodes]: the rank of v in nodes, or -1;
+ *   per graph d_nodePointer_b [M + 1], d_edgeList_b [num_edges]:
+ *     nodePointer_b[i] = nodePointer[nodes[i]], nodePointer_b[M] = num_edges, edgeList_b[e] = new_id[edgeList[e]].
+ * The relabelling is monotone, so the result is a SQUARE CSR over M nodes in which every row keeps its edges in their order: sorted
+ * rows stay sorted, the number and order of edges do not change (a sampled graph's eid serves its compact form as it is), and every
+ * operator of this header takes it.  A pure function of the inputs, bit-identical on repetition; no global atomics (the mask and the
+ * validation word only ever receive concurrent stores of the same value).  DEVICE pointers; caller scratch
+ * (tcgnn_compact_workspace_bytes, 256-byte aligned, answered without a device); nothing allocates; everything is stream-ordered.
+ * One mini-batch is begin, mark per graph, count, nodes, graph per graph - ONE stream synchronisation in all:
+ * tcgnn_compact_begin  clears the workspace's validation word.  Needed before the first mark call on a workspace; the count call leaves
+ *                      the word clear again.
+ * tcgnn_compact_mark   sets d_keep[v] = 1 for every row with edges and every column id in [0, num_nodes) of the num_edges entries of
+ *                      d_edgeList.  A column id outside that range, nodePointer[0] != 0, a descending pair, a pointer outside
+ *                      [0, num_edges] or nodePointer[num_nodes] != num_edges sets the validation word; none of them is followed.
+ * tcgnn_compact_count  writes all num_nodes entries of d_new_id (the exclusive scan of keep != 0) and *num_kept = M, and synchronises
+ *                      `stream` ONCE to read back M and the validation word: TCGNN_ERR_BAD_GRAPH when a mark call on this workspace
+ *                      since the last begin / count set it (*num_kept is then left alone).
+ * tcgnn_compact_nodes  writes exactly num_kept entries of d_nodes from the d_new_id and M of the count call.
+ * tcgnn_compact_graph  writes exactly num_kept + 1 entries of d_nodePointer_b and num_edges of d_edgeList_b.  Contract: d_new_id comes
+ *                      from a mask the mark call saw THIS graph with.  For any other input the call stays memory-safe - every index is
+ *                      checked or clamped, a column without a new id is written as 0 - and the result is unspecified.
+ * All before any launch: a null required pointer, a negative size, num_kept > num_nodes or num_edges > 2^31 - 1 is
+ * TCGNN_ERR_INVALID_ARG; a workspace that is null, short or not 256-byte aligned TCGNN_ERR_WORKSPACE; num_nodes = 0 and
+ * num_edges = 0 give TCGNN_OK (arrays of no entries may be NULL). */
+int tcgnn_compact_workspace_bytes(int32_t num_nodes, size_t* bytes);
+int tcgnn_compact_begin(int32_t num_nodes, void* d_workspace, size_t workspace_bytes, void* stream);
+int tcgnn_compact_mark(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges, uint8_t* d_keep,
+                       void* d_workspace, size_t workspace_bytes, void* stream);
+int tcgnn_compact_count(const uint8_t* d_keep, int32_t num_nodes, int32_t* d_new_id, void* d_workspace, size_t workspace_bytes,
+                        int32_t* num_kept, void* stream);
+int tcgnn_compact_nodes(const int32_t* d_new_id, int32_t num_nodes, int32_t num_kept, int32_t* d_nodes, void* stream);
+int tcgnn_compact_graph(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_new_id, const int32_t* d_nodes,
+                        int32_t num_nodes, int32_t num_kept, int64_t num_edges, int32_t* d_nodePointer_b, int32_t* d_edgeList_b,
+                        void* stream);
+
 /* Tile statistics of the translation - what the reference's counting scripts report
  * (3_cnt_TC_blk_SpMM.py:38-94 with 16x8 tiles, 3_cnt_TC_blk_SDDMM.py with 16x16; logs/16x8_reduction.csv,
  * logs/reduce_blocks.csv): per window of tile_h rows, U = sorted unique neighbour ids;

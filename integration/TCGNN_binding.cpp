@@ -824,6 +824,68 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_neighbors(torch::
   return {rp_s, col_s, eid};
 }
 
+// Not in the reference: relabelled mini-batch blocks (tcgnn_compact_*; TCGNN.compact_nodes / compact_graph of the ctypes module).
+// compact_nodes: the node set of the layer graphs of one mini-batch, (nodes, new_id) - one stream synchronisation however many graphs.
+static void check_csr_pair(const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
+  TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodePointer.numel() >= 1, "nodePointer must hold num_nodes + 1 entries");
+  TORCH_CHECK(edgeList.device() == nodePointer.device(), "nodePointer and edgeList must be on one device");
+}
+
+std::tuple<torch::Tensor, torch::Tensor> compact_nodes(std::vector<std::vector<torch::Tensor>> graphs, c10::optional<torch::Tensor> keep) {
+  TORCH_CHECK(!graphs.empty(), "compact_nodes needs at least one (nodePointer, edgeList) pair");
+  for (const auto& g : graphs) {
+    TORCH_CHECK(g.size() >= 2, "every graph is a (nodePointer, edgeList) pair");
+    check_csr_pair(g[0], g[1]);
+    TORCH_CHECK(g[0].device() == graphs[0][0].device(), "every graph must be on one device");
+    TORCH_CHECK(g[0].numel() == graphs[0][0].numel(), "every graph must have the same number of nodes");
+  }
+  const torch::Tensor& first = graphs[0][0];
+  const int64_t N = first.numel() - 1;
+  if (keep.has_value()) {
+    CHECK_INPUT((*keep));
+    TORCH_CHECK(keep->scalar_type() == torch::kUInt8 || keep->scalar_type() == torch::kBool, "keep must be uint8 or bool");
+    TORCH_CHECK(keep->numel() == N && keep->device() == first.device(), "keep must hold one entry per node on nodePointer's device");
+  }
+  DeviceGuard guard(first.device());
+  void* stream = current_stream(first);
+  torch::Tensor mask = keep.has_value() ? keep->reshape({-1}).to(torch::kUInt8, /*non_blocking=*/false, /*copy=*/true)
+                                        : torch::zeros({N}, first.options().dtype(torch::kUInt8));
+  size_t need = 0;
+  tcgnn_check(tcgnn_compact_workspace_bytes((int32_t)N, &need), "tcgnn_compact_workspace_bytes");
+  torch::Tensor ws = torch::empty({(int64_t)need + 256}, first.options().dtype(torch::kUInt8));
+  char* wsp = static_cast<char*>(ws.data_ptr());
+  wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
+  tcgnn_check(tcgnn_compact_begin((int32_t)N, wsp, need, stream), "tcgnn_compact_begin");
+  for (const auto& g : graphs)
+    tcgnn_check(tcgnn_compact_mark(g[0].data_ptr<int>(), g[1].data_ptr<int>(), (int32_t)N, g[1].numel(), static_cast<uint8_t*>(mask.data_ptr()), wsp, need,
+                                   stream), "tcgnn_compact_mark");
+  torch::Tensor new_id = torch::empty({N}, first.options());
+  int32_t kept = 0;
+  tcgnn_check(tcgnn_compact_count(static_cast<const uint8_t*>(mask.data_ptr()), (int32_t)N, new_id.data_ptr<int>(), wsp, need, &kept, stream),
+              "tcgnn_compact_count");
+  torch::Tensor nodes = torch::empty({(int64_t)kept}, first.options());
+  tcgnn_check(tcgnn_compact_nodes(new_id.data_ptr<int>(), (int32_t)N, kept, nodes.data_ptr<int>(), stream), "tcgnn_compact_nodes");
+  return {nodes, new_id};
+}
+
+// compact_graph: (nodePointer_b [M + 1], edgeList_b [E]) of a graph that compact_nodes was given.  No synchronisation.
+std::tuple<torch::Tensor, torch::Tensor> compact_graph(torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor nodes, torch::Tensor new_id) {
+  check_csr_pair(nodePointer, edgeList);
+  CHECK_INPUT(nodes); CHECK_INPUT(new_id);
+  TORCH_CHECK(nodes.scalar_type() == torch::kInt32 && new_id.scalar_type() == torch::kInt32, "expected scalar type Int");
+  TORCH_CHECK(nodes.device() == nodePointer.device() && new_id.device() == nodePointer.device(), "nodes and new_id must be on nodePointer's device");
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), M = nodes.numel();
+  TORCH_CHECK(new_id.numel() == N, "new_id must hold one entry per node");
+  TORCH_CHECK(M <= N, "nodes holds more entries than the graph has nodes");
+  DeviceGuard guard(nodePointer.device());
+  torch::Tensor rp_b = torch::empty({M + 1}, nodePointer.options()), col_b = torch::empty({E}, edgeList.options());
+  tcgnn_check(tcgnn_compact_graph(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), new_id.data_ptr<int>(), nodes.data_ptr<int>(), (int32_t)N,
+                                  (int32_t)M, E, rp_b.data_ptr<int>(), col_b.data_ptr<int>(), current_stream(nodePointer)), "tcgnn_compact_graph");
+  return {rp_b, col_b};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -969,6 +1031,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("perm") = py::none(), py::arg("out") = py::none());
   m.def("sample_neighbors", &sample_neighbors, "seeded fan-out sampling over the same nodes: (nodePointer_s, edgeList_s, eid) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("fanout"), py::arg("seed"), py::arg("row_mask") = py::none());
+  m.def("compact_nodes", &compact_nodes, "the node set of one mini-batch's layer graphs: (nodes, new_id) (not in the reference)", py::arg("graphs"),
+        py::arg("keep") = py::none());
+  m.def("compact_graph", &compact_graph, "a graph over the nodes of compact_nodes: (nodePointer_b, edgeList_b) (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("nodes"), py::arg("new_id"));
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

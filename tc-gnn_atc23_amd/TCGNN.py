@@ -37,7 +37,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors"]
+           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors", "compact_nodes", "compact_graph"]
 
 
 def _stream(device):
@@ -62,7 +62,8 @@ _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
           "softmax": (1, 256),        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
-          "sample": (1, 256)}         # sample_neighbors' row counts and scan scratch (its count call synchronises: nothing reads it afterwards)
+          "sample": (1, 256),         # sample_neighbors' row counts and scan scratch (its count call synchronises: nothing reads it afterwards)
+          "compact": (1, 256)}        # compact_nodes' validation words and scan scratch (likewise: its count call synchronises)
 
 
 def _buffer(kind, need, device, stream=None):
@@ -256,6 +257,86 @@ def sample_neighbors(nodePointer, edgeList, fanout, seed, row_mask=None):
             _c.check(_c.lib.tcgnn_sample_neighbors(nodePointer.data_ptr(), edgeList.data_ptr(), _ptr(row_mask), rp_s.data_ptr(), N, E, k,
                                                    int(seed) & 0xFFFFFFFFFFFFFFFF, col_s.data_ptr(), eid.data_ptr(), stream), "tcgnn_sample_neighbors")
     return rp_s, col_s, eid
+
+
+# ---------------------------------------------------------------- relabelled mini-batch blocks
+
+def _check_csr_pair(nodePointer, edgeList, dev=None):
+    for t, n in ((nodePointer, "nodePointer"), (edgeList, "edgeList")):
+        _check_input(t, n)
+        _check_int(t, n)
+    if edgeList.device != (dev or nodePointer.device):
+        raise RuntimeError("edgeList is on %s but nodePointer is on %s" % (edgeList.device, dev or nodePointer.device))
+    if dev is not None and nodePointer.device != dev:
+        raise RuntimeError("nodePointer is on %s but the first graph's is on %s" % (nodePointer.device, dev))
+    if nodePointer.numel() < 1:
+        raise RuntimeError("nodePointer must hold num_nodes + 1 entries")
+
+
+def compact_nodes(graphs, keep=None):
+    """Not in the reference module: the node set of one mini-batch, (nodes, new_id).  graphs: a sequence of (nodePointer, edgeList)
+    pairs over the same N nodes (the layer graphs of sample_layers); keep: uint8 or bool [N], e.g. the seeds (None: nothing beyond the
+    graphs; it is not written).  A node is kept when keep says so, when it has an edge or when it is a column id in any of the graphs.
+    nodes (int32 [M]) = the kept ids in increasing order, new_id (int32 [N]) = the rank of a node in nodes, or -1.  A pure function of
+    its arguments; column ids must lie in [0, N) and the row pointers be well-formed.  One stream synchronisation (to size nodes),
+    however many graphs."""
+    graphs = [tuple(g[:2]) for g in graphs]
+    if not graphs:
+        raise ValueError("compact_nodes needs at least one (nodePointer, edgeList) pair")
+    dev = graphs[0][0].device if isinstance(graphs[0][0], torch.Tensor) else None
+    for rp, col in graphs:
+        _check_csr_pair(rp, col, dev)
+    N = graphs[0][0].numel() - 1
+    if any(rp.numel() - 1 != N for rp, _ in graphs):
+        raise RuntimeError("every graph must have the same number of nodes (%d)" % N)
+    if keep is not None:
+        _check_input(keep, "keep")
+        if keep.dtype not in (torch.uint8, torch.bool):
+            raise RuntimeError("keep must be uint8 or bool, not %s" % keep.dtype)
+        if keep.numel() != N or keep.device != dev:
+            raise RuntimeError("keep must hold one entry per node (%d) on %s" % (N, dev))
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        mask = torch.zeros(N, dtype=torch.uint8, device=dev) if keep is None else keep.view(-1).to(torch.uint8, copy=True)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_compact_workspace_bytes(N, _c.ctypes.byref(need)), "tcgnn_compact_workspace_bytes")
+        ws, ws_bytes = _buffer("compact", need.value, dev, stream)
+        _c.check(_c.lib.tcgnn_compact_begin(N, ws, ws_bytes, stream), "tcgnn_compact_begin")
+        for rp, col in graphs:
+            _c.check(_c.lib.tcgnn_compact_mark(rp.data_ptr(), col.data_ptr(), N, col.numel(), mask.data_ptr(), ws, ws_bytes, stream), "tcgnn_compact_mark")
+        new_id = torch.empty(N, dtype=torch.int32, device=dev)
+        kept = _c._i32(0)
+        _c.check(_c.lib.tcgnn_compact_count(mask.data_ptr(), N, new_id.data_ptr(), ws, ws_bytes, _c.ctypes.byref(kept), stream), "tcgnn_compact_count")
+        nodes = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        _c.check(_c.lib.tcgnn_compact_nodes(new_id.data_ptr(), N, kept.value, nodes.data_ptr(), stream), "tcgnn_compact_nodes")
+    return nodes, new_id
+
+
+def compact_graph(nodePointer, edgeList, nodes, new_id):
+    """Not in the reference module: (nodePointer_b [M + 1], edgeList_b [E]) - the graph over the M nodes of compact_nodes, which must have
+    been given this graph: nodePointer_b[i] = nodePointer[nodes[i]], edgeList_b[e] = new_id[edgeList[e]].  The relabelling is monotone: a
+    square CSR whose rows keep their edges in their order, so every operator here takes it and per-edge data of the uncompacted graph
+    (a sampled graph's eid) serves it unchanged.  No synchronisation.  With a (nodes, new_id) that did not see this graph the call is
+    memory-safe and its result unspecified."""
+    _check_csr_pair(nodePointer, edgeList)
+    dev = nodePointer.device
+    N, E = nodePointer.numel() - 1, edgeList.numel()
+    for t, n in ((nodes, "nodes"), (new_id, "new_id")):
+        _check_input(t, n)
+        _check_int(t, n)
+        if t.device != dev:
+            raise RuntimeError("%s is on %s but nodePointer is on %s" % (n, t.device, dev))
+    if new_id.numel() != N:
+        raise RuntimeError("new_id must hold one entry per node (%d), not %d" % (N, new_id.numel()))
+    M = nodes.numel()
+    if M > N:
+        raise RuntimeError("nodes holds %d entries, more than the graph's %d nodes" % (M, N))
+    with torch.cuda.device(dev):
+        rp_b = torch.empty(M + 1, dtype=torch.int32, device=dev)
+        col_b = torch.empty(E, dtype=torch.int32, device=dev)
+        _c.check(_c.lib.tcgnn_compact_graph(nodePointer.data_ptr(), edgeList.data_ptr(), new_id.data_ptr(), nodes.data_ptr(), N, M, E,
+                                            rp_b.data_ptr(), col_b.data_ptr(), _stream(dev)), "tcgnn_compact_graph")
+    return rp_b, col_b
 
 
 def _transposed_plan(e):

@@ -49,7 +49,13 @@ SIGNATURES = {
     "tcgnn_sample_workspace_bytes": (ctypes.c_int, [_i32, ctypes.POINTER(_sz)]),
     "tcgnn_sample_neighbors_count": (ctypes.c_int, [_i32p, _vp, _i32, _i64, _i32, _i32p, _vp, _sz, ctypes.POINTER(_i64), _vp]),
     "tcgnn_sample_neighbors": (ctypes.c_int, [_i32p, _i32p, _vp, _i32p, _i32, _i64, _i32, ctypes.c_uint64, _i32p, _i32p, _vp]),
-    "tcgnn_tile_stats": (ctypes.c_int, [_i32p, _i32p, _i32, _i32, _i32, ctypes.POINTER(TileStats), _i32]),
+    "tcgnn_compact_workspace_bytes": (ctypes.c_int, [_i32, ctypes.POINTER(_sz)]),
+    "tcgnn_compact_begin": (ctypes.c_int, [_i32, _vp, _sz, _vp]),
+    "tcgnn_compact_mark": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "tcgnn_compact_count": (ctypes.c_int, [_vp, _i32, _i32p, _vp, _sz, ctypes.POINTER(_i32), _vp]),
+    "tcgnn_compact_nodes": (ctypes.c_int, [_i32p, _i32, _i32, _i32p, _vp]),
+    "tcgnn_compact_graph": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32, _i32, _i64, _i32p, _i32p, _vp]),
+    "tcgnn_tile_stats":(ctypes.c_int, [_i32p, _i32p, _i32, _i32, _i32, ctypes.POINTER(TileStats), _i32]),
     "tcgnn_plan_create": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, _i32, _i64, _i32, _vp, ctypes.POINTER(_vp)]),
     "tcgnn_plan_create_sharded": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, _i32, _i32, _i32, _i64, _i32, _vp, ctypes.POINTER(_vp)]),
     "tcgnn_plan_prepare": (ctypes.c_int, [_vp, _i32, _vp]),

@@ -62,6 +62,10 @@ def build_parser():
     p.add_argument("--fanout", type=str, default=None,
                    help="K[,K...]: train every epoch on a freshly sampled graph that keeps at most K in-edges per node (TCGNN.sample_neighbors, seed + epoch); "
                    "several values give one fan-out per layer, input layer first; the final loss is evaluated on the full graph (not in the reference)")
+    p.add_argument("--batch-size", dest="batch_size", type=int, default=None,
+                   help="B: with --fanout, mini-batch training - every epoch cuts a seeded permutation of the nodes into batches of B seeds, samples each "
+                   "batch's layer graphs, relabels them to the nodes they touch (tcgnn_layers.sample_batch) and takes one optimiser step per batch on the "
+                   "seeds' loss; the final loss is evaluated on the full graph (not in the reference)")
     return p
 
 
@@ -75,6 +79,29 @@ def parse_fanout(text, num_layers):
     if len(ks) != num_layers or min(ks) < 0:
         raise ValueError("--fanout takes one value >= 0, or one per layer (%d), got %r" % (num_layers, text))
     return ks
+
+
+def parse_batch_size(batch_size, fanout, hip_graph=False):
+    """--batch-size's value checked against the flags it depends on (None: no mini-batches)"""
+    if batch_size is None:
+        return None
+    if fanout is None:
+        raise ValueError("--batch-size trains on sampled mini-batches and needs --fanout")
+    if hip_graph:
+        raise ValueError("--batch-size samples a new graph every step and can not be combined with --hip_graph, which replays one captured epoch")
+    if int(batch_size) < 1:
+        raise ValueError("--batch-size takes a value >= 1, got %r" % (batch_size,))
+    return int(batch_size)
+
+
+def epoch_order(num_nodes, seed, epoch):
+    """the permutation of the nodes that epoch `epoch` cuts into batches: a function of (num_nodes, seed + epoch) alone, drawn on the host"""
+    return torch.randperm(num_nodes, generator=torch.Generator().manual_seed((int(seed) + int(epoch)) % (1 << 63)))
+
+
+def batch_seed(seed, epoch, index):
+    """the sampling seed of batch `index` of epoch `epoch` (sample_layers draws hop h with this + h: the stride keeps batches apart)"""
+    return ((int(seed) * 1000003 + int(epoch)) * 1000003 + int(index)) * 64
 
 
 class Net(nn.Module):
@@ -151,7 +178,8 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None):
+                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None,
+                  batch_size=None, batch_hook=None):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -172,8 +200,17 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     the planless models, only the transposed CSR) and trains on it; GINE gathers edge_attr[eid].  The three parts are timed apart, each
     behind a device synchronisation: the result holds sample_ms, plan_ms and train_ms per epoch and their sum epoch_ms.  Plans are created
     every epoch: that cost is plan_ms, not hidden.  final_loss is the loss on the FULL graph after the last step (model.eval()).  Refused
-    together with hip_graph: a captured epoch replays one graph."""
+    together with hip_graph: a captured epoch replays one graph.
+    batch_size (not in the reference; None: the paths above, unchanged; needs fanout): mini-batch training.  Every timed epoch draws
+    epoch_order(N, seed, epoch) and cuts it into batches of batch_size seeds - every node is a seed exactly once per epoch.  Per batch:
+    tcgnn_layers.sample_layers with batch_seed(seed, epoch, index), compact_layers (the two halves of sample_batch, timed apart), x[nodes]
+    (and, for GINE, edge_attr[eid]), what the model's operators need on the compact graphs, and ONE optimiser step on
+    node_nll_loss(out[seed_pos], y[seeds]).  `warmup` counts dry STEPS here (batches of a permutation no timed epoch uses), not epochs.
+    The result holds sample_ms, compact_ms, plan_ms and train_ms per epoch (each behind a device synchronisation), their sum epoch_ms,
+    batches (per epoch), mean_block_nodes (the mean M) and final_loss on the FULL graph.  batch_hook(epoch, index, seeds), when given, is
+    called before every timed step.  Refused together with hip_graph."""
     import tcgnn_layers as L
+    batch_size = parse_batch_size(batch_size, fanout, hip_graph)
     if fanout is not None and hip_graph:
         raise ValueError("--fanout samples a new graph every epoch and can not be combined with --hip_graph, which replays one captured epoch")
     fanout = parse_fanout(fanout, num_layers)
@@ -261,6 +298,63 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         prepare(meta)
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)
+    if batch_size is not None:
+        full, n = meta, x.shape[0]
+        spent = {"sample_ms": 0.0, "compact_ms": 0.0, "plan_ms": 0.0, "train_ms": 0.0}
+        block_nodes, loss = 0, None
+
+        def lap(key, since):
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            spent[key] += (now - since) * 1e3
+            return now
+
+        def step(epoch, index, seeds):
+            """one optimiser step on the compact batch of `seeds`; -> (loss, M)"""
+            t = time.perf_counter()
+            graphs = L.sample_layers(full, seeds, fanout, batch_seed(seed, epoch, index))
+            t = lap("sample_ms", t)
+            batch = L.compact_layers(graphs, seeds, plan=False)   # (with the line above: tcgnn_layers.sample_batch, timed in its two parts)
+            xb, yb = x[batch.nodes.long()], y[seeds]
+            t = lap("compact_ms", t)
+            sampled_attr.clear()
+            for i, (m, eid) in enumerate(zip(batch.metas, batch.eids)):
+                if not planless:
+                    m = batch.metas[i] = L.csr_meta(m[0], m[1])
+                prepare(m)
+                if model_name == "gine":
+                    sampled_attr[m[1].data_ptr()] = edge_attr[eid.long()]
+            t = lap("plan_ms", t)
+            model.train()
+            optimizer.zero_grad()
+            loss = node_nll_loss(model(xb, batch.metas)[batch.seed_pos], yb)
+            loss.backward()
+            optimizer.step()
+            lap("train_ms", t)
+            return loss, batch.nodes.numel()
+
+        order = epoch_order(n, seed, epochs).to(x.device)   # the dry steps: a permutation no timed epoch uses
+        for index in range(min(warmup, (n + batch_size - 1) // batch_size)):
+            loss, _ = step(epochs, index, order[index * batch_size:(index + 1) * batch_size])
+        spent = dict.fromkeys(spent, 0.0)
+        batches = 0
+        for epoch in range(epochs):
+            order = epoch_order(n, seed, epoch).to(x.device)
+            batches = 0
+            for index, lo in enumerate(range(0, n, batch_size)):
+                seeds = order[lo:lo + batch_size]
+                if batch_hook is not None:
+                    batch_hook(epoch, index, seeds)
+                loss, m = step(epoch, index, seeds)
+                block_nodes += m
+                batches += 1
+        model.eval()
+        with torch.no_grad():
+            final = float(node_nll_loss(model(x, full), y))
+        r = {k: v / max(epochs, 1) for k, v in spent.items()}
+        r.update(epoch_ms=sum(r.values()), final_loss=final, sampled_loss=float(loss.detach()) if loss is not None else float("nan"), fanout=fanout, batch_size=batch_size,
+                 batches=batches, mean_block_nodes=block_nodes / max(batches * epochs, 1))
+        return r
     if fanout is not None:
         full, spent = meta, {"sample_ms": 0.0, "plan_ms": 0.0, "train_ms": 0.0}
 
@@ -381,9 +475,12 @@ def run(args, quiet=False):
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
-                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None))
+                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None),
+                      batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None))
     if "sample_ms" in r:
         say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
+    if "compact_ms" in r:
+        say("Compact (ms):\t{:6.3f}\nBatches:\t{:d}\tmean block nodes {:.1f}".format(r["compact_ms"], r["batches"], r["mean_block_nodes"]))
     say("Train (ms):\t{:6.3f}".format(r["train_ms"]))
     result.update(r)
     return result

@@ -1003,3 +1003,50 @@ def sample_layers(csr, seeds, fanouts, seed):
         graphs.insert(0, g)
         frontier = frontier.clone().index_fill_(0, g[1].long(), 1)
     return graphs
+
+
+# ---------------------------------------------------------------- relabelled mini-batch blocks (not in the reference)
+
+class CompactBatch:
+    """What compact_layers returns: the layer graphs of one mini-batch over the M nodes they touch.
+    nodes [M] int32: the kept original ids, increasing - the batch's features are x[nodes.long()];
+    seed_pos [S] int64: new_id[seeds], where the seeds' rows are in the batch - the loss reads out[seed_pos];
+    metas: one five-tensor group per layer, input layer first, as every layer here takes it;
+    eids: per layer, the sampled graph's eid, unchanged - compaction keeps the number and order of edges;
+    new_id [N] int32: the rank of every original id in nodes, or -1."""
+    __slots__ = ("nodes", "seed_pos", "metas", "eids", "new_id")
+
+    def __init__(self, nodes, seed_pos, metas, eids, new_id):
+        self.nodes, self.seed_pos, self.metas, self.eids, self.new_id = nodes, seed_pos, metas, eids, new_id
+
+
+def compact_layers(graphs, seeds, plan=True):
+    """The layer graphs of sample_layers - (row_pointers_s, column_index_s, eid) each, over all N nodes - as a CompactBatch over the M
+    nodes they touch: the seeds, every row with an edge and every source (the backend's compact_nodes / compact_graph; one stream
+    synchronisation for the whole batch).  The relabelling is monotone, so each result is a square CSR whose rows keep their edges in
+    their order: every layer and operator takes it unchanged, and eid still names the full graph's edges.
+    plan=True runs the device sparse-graph translation (csr_meta) on every compact CSR; plan=False pads with empty metadata as
+    sample_meta does, for layers that call planless operators only.
+    A compact graph is directed even when the full graph is symmetric: layers with a `directed` switch want directed=True.  Its tensors
+    are NEW: as for a sampled graph, a layer that aggregates through a plan builds one at first use, and every batch takes plan / CSR
+    cache slots of the backend (TCGNN.set_plan_cache_size; least recently used first, so a loop over batches stays bounded)."""
+    graphs = list(graphs)
+    rp0 = graphs[0][0]
+    keep = torch.zeros(rp0.numel() - 1, dtype=torch.uint8, device=rp0.device)
+    keep.index_fill_(0, seeds.long(), 1)
+    nodes, new_id = backend().compact_nodes([(g[0], g[1]) for g in graphs], keep)
+    metas = []
+    for g in graphs:
+        rp_b, col_b = backend().compact_graph(g[0], g[1], nodes, new_id)
+        if plan:
+            metas.append(csr_meta(rp_b, col_b))
+        else:
+            metas.append((rp_b, col_b) + tuple(torch.empty(0, dtype=torch.int32, device=rp_b.device) for _ in range(3)))
+    return CompactBatch(nodes, new_id[seeds.long()].long(), metas, [g[2] if len(g) > 2 else None for g in graphs], new_id)
+
+
+def sample_batch(csr, seeds, fanouts, seed, plan=True):
+    """One mini-batch: sample_layers(csr, seeds, fanouts, seed) followed by compact_layers - a CompactBatch whose graphs have M rows,
+    M = the nodes within len(fanouts) sampled hops of the seeds, instead of the full graph's N.  What compact_layers says of directed
+    graphs and of the plan / CSR cache slots every batch takes holds here."""
+    return compact_layers(sample_layers(csr, seeds, fanouts, seed), seeds, plan=plan)
