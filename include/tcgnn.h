@@ -241,6 +241,52 @@ int tcgnn_compact_graph(const int32_t* d_nodePointer, const int32_t* d_edgeList,
                         int32_t num_nodes, int32_t num_kept, int64_t num_edges, int32_t* d_nodePointer_b, int32_t* d_edgeList_b,
                         void* stream);
 
+/* Seed-list sampling (no counterpart in the reference): the two sections above from LISTS of row ids, so that one mini-batch costs the
+ * rows it touches and not num_nodes (DGL's and PyG's loaders sample from a list of seed nodes).  A row-list graph has one row per
+ * entry of d_rows (int32 [num_rows], any order, an id may repeat: every occurrence has its own slot):
+ *   d_rowPointer_s [num_rows + 1]: rowPointer_s[i] = the sum over j < i of min(deg(rows[j]), fanout);
+ *   d_edgeList_s [E'], d_eid [E']: slot i holds what row rows[i] of tcgnn_sample_neighbors(..., fanout, seed) holds - the same words
+ *     h32(seed, e), the same rule (the fanout smallest words of the row, kept in CSR order), eid = the position in the FULL CSR.
+ * nodePointer[r] and nodePointer[r + 1] are read for listed r ONLY: the pointers of unlisted rows are neither read nor validated.
+ * Pure functions of their inputs (no global atomics), bit-identical on repetition.  DEVICE pointers.
+ * tcgnn_sample_rows_workspace_bytes: answered without a device - the result words plus one partial sum per 1 024 of the list's
+ *   num_rows + 1 slots (256-byte aligned parts).
+ * tcgnn_sample_rows_count: writes d_rowPointer_s and *num_sampled = E' on CALLER scratch and synchronises `stream` ONCE to read back E'
+ *   and the validation words.  A listed id outside [0, num_nodes), a descending pointer pair at a listed row or a pointer of a listed
+ *   row outside [0, num_edges] is TCGNN_ERR_BAD_GRAPH, reported behind the read-back; until then such an id is an empty row and every
+ *   index derived from nodePointer is clamped to [0, num_edges].  A list whose rows keep more than 2^31 - 1 edges (possible with
+ *   repeats) is TCGNN_ERR_INVALID_ARG, also behind the read-back: the sums saturate, nothing wraps.
+ * tcgnn_sample_rows: with the d_rowPointer_s the count call wrote for the same (nodePointer, rows, fanout), writes exactly E' entries
+ *   of d_edgeList_s and of d_eid; a row never writes beyond the slot rowPointer_s gives it.  Stream-ordered, no allocation, no
+ *   synchronisation; one workgroup per four list slots.
+ * Both return TCGNN_ERR_INVALID_ARG before any launch for num_edges > 2^31 - 1, a negative size or fanout or a null required pointer
+ * (d_rows may be NULL when num_rows = 0), the count call TCGNN_ERR_WORKSPACE for scratch that is too small or not 256-byte aligned.
+ *
+ * The node set and the blocks of row-list graphs, with tcgnn_compact_begin / _count / _nodes and their workspace as above:
+ * tcgnn_compact_mark_ids    sets d_keep[id] = 1 for `count` ids (the seeds; the d_edgeList_s of a row-list graph).  An id outside
+ *                           [0, num_nodes) sets the workspace's validation word and is not followed, as tcgnn_compact_mark treats a
+ *                           bad column; tcgnn_compact_count reports it.  Concurrent stores only ever write the same value.
+ * tcgnn_compact_rows_graph  the square block over the num_kept = M nodes of a row-list graph whose d_rows are STRICTLY INCREASING (as
+ *                           tcgnn_compact_nodes emits them): writes exactly M + 1 entries of d_nodePointer_b and num_sampled of
+ *                           d_edgeList_b, nodePointer_b[j] = rowPointer_s[#{i : new_id[rows[i]] < j}] (a node of the batch that is
+ *                           not listed gets an empty row), nodePointer_b[M] = num_sampled, edgeList_b[e] = new_id[edgeList_s[e]].
+ *                           One writer per slot, no synchronisation.  Under rows that are not increasing or a d_new_id that never saw
+ *                           the graph the call stays memory-safe - every index is checked or clamped, a column without a new id is
+ *                           written as 0 - and the result is unspecified.
+ * Null pointers, negative sizes and workspaces are refused as in the section above. */
+int tcgnn_sample_rows_workspace_bytes(int32_t num_rows, size_t* bytes);
+int tcgnn_sample_rows_count(const int32_t* d_nodePointer, const int32_t* d_rows, int32_t num_rows, int32_t num_nodes, int64_t num_edges,
+                            int32_t fanout, int32_t* d_rowPointer_s, void* d_workspace, size_t workspace_bytes, int64_t* num_sampled,
+                            void* stream);
+int tcgnn_sample_rows(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_rows, const int32_t* d_rowPointer_s,
+                      int32_t num_rows, int32_t num_nodes, int64_t num_edges, int32_t fanout, uint64_t seed, int32_t* d_edgeList_s,
+                      int32_t* d_eid, void* stream);
+int tcgnn_compact_mark_ids(const int32_t* d_ids, int64_t count, int32_t num_nodes, uint8_t* d_keep, void* d_workspace,
+                           size_t workspace_bytes, void* stream);
+int tcgnn_compact_rows_graph(const int32_t* d_rows, int32_t num_rows, const int32_t* d_rowPointer_s, const int32_t* d_edgeList_s,
+                             int64_t num_sampled, const int32_t* d_new_id, int32_t num_nodes, int32_t num_kept, int32_t* d_nodePointer_b,
+                             int32_t* d_edgeList_b, void* stream);
+
 /* Tile statistics of the translation - what the reference's counting scripts report
  * (3_cnt_TC_blk_SpMM.py:38-94 with 16x8 tiles, 3_cnt_TC_blk_SDDMM.py with 16x16; logs/16x8_reduction.csv,
  * logs/reduce_blocks.csv): per window of tile_h rows, U = sorted unique neighbour ids;

@@ -886,6 +886,87 @@ std::tuple<torch::Tensor, torch::Tensor> compact_graph(torch::Tensor nodePointer
   return {rp_b, col_b};
 }
 
+// Not in the reference: seed-list sampling (tcgnn_sample_rows*, tcgnn_compact_mark_ids, tcgnn_compact_rows_graph; TCGNN.sample_rows /
+// extend_nodes / compact_rows_graph of the ctypes module).  A mini-batch costs the rows it touches, not the graph's.
+static void check_ids(const torch::Tensor& t, const torch::Device& dev, const char* name) {
+  CHECK_INPUT(t);
+  TORCH_CHECK(t.scalar_type() == torch::kInt32, "expected scalar type Int (", name, ")");
+  TORCH_CHECK(t.device() == dev, name, " must be on the other tensors' device");
+}
+
+// sample_rows: sample_neighbors from a list of row ids - (rowPointer_s [R + 1], edgeList_s, eid), slot i = row rows[i].
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> sample_rows(torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor rows,
+                                                                    c10::optional<int64_t> fanout, py::int_ seed) {
+  check_csr_pair(nodePointer, edgeList);
+  check_ids(rows, nodePointer.device(), "rows");
+  TORCH_CHECK(!fanout.has_value() || *fanout >= 0, "fanout must be None or >= 0");
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), R = rows.numel();
+  const int32_t k = (int32_t)std::min<int64_t>(fanout.value_or(0x7fffffff), 0x7fffffff);
+  const uint64_t seed64 = py::cast<uint64_t>(seed.attr("__and__")(py::int_(0xFFFFFFFFFFFFFFFFull)));
+  DeviceGuard guard(nodePointer.device());
+  size_t need = 0;
+  tcgnn_check(tcgnn_sample_rows_workspace_bytes((int32_t)R, &need), "tcgnn_sample_rows_workspace_bytes");
+  torch::Tensor ws = torch::empty({(int64_t)need + 256}, nodePointer.options().dtype(torch::kUInt8));
+  char* wsp = static_cast<char*>(ws.data_ptr());
+  wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
+  torch::Tensor rp_s = torch::empty({R + 1}, nodePointer.options());
+  int64_t kept = 0;
+  tcgnn_check(tcgnn_sample_rows_count(nodePointer.data_ptr<int>(), rows.data_ptr<int>(), (int32_t)R, (int32_t)N, E, k, rp_s.data_ptr<int>(), wsp, need,
+                                      &kept, current_stream(nodePointer)), "tcgnn_sample_rows_count");
+  torch::Tensor col_s = torch::empty({kept}, edgeList.options()), eid = torch::empty({kept}, edgeList.options());
+  if (kept > 0)
+    tcgnn_check(tcgnn_sample_rows(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), rows.data_ptr<int>(), rp_s.data_ptr<int>(), (int32_t)R,
+                                  (int32_t)N, E, k, seed64, col_s.data_ptr<int>(), eid.data_ptr<int>(), current_stream(nodePointer)),
+                "tcgnn_sample_rows");
+  return {rp_s, col_s, eid};
+}
+
+// extend_nodes: marks lists of ids into the caller's uint8 mask IN PLACE; (nodes, new_id) of the mask afterwards.  One synchronisation.
+std::tuple<torch::Tensor, torch::Tensor> extend_nodes(torch::Tensor keep, py::object ids) {
+  CHECK_INPUT(keep);
+  TORCH_CHECK(keep.scalar_type() == torch::kUInt8, "keep must be uint8 (it is written in place)");
+  std::vector<torch::Tensor> lists;
+  if (THPVariable_Check(ids.ptr())) lists.push_back(py::cast<torch::Tensor>(ids));
+  else lists = py::cast<std::vector<torch::Tensor>>(ids);
+  for (const auto& t : lists) check_ids(t, keep.device(), "ids");
+  const int64_t N = keep.numel();
+  DeviceGuard guard(keep.device());
+  void* stream = current_stream(keep);
+  size_t need = 0;
+  tcgnn_check(tcgnn_compact_workspace_bytes((int32_t)N, &need), "tcgnn_compact_workspace_bytes");
+  torch::Tensor ws = torch::empty({(int64_t)need + 256}, keep.options());
+  char* wsp = static_cast<char*>(ws.data_ptr());
+  wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
+  uint8_t* const mask = static_cast<uint8_t*>(keep.data_ptr());
+  tcgnn_check(tcgnn_compact_begin((int32_t)N, wsp, need, stream), "tcgnn_compact_begin");
+  for (const auto& t : lists)
+    tcgnn_check(tcgnn_compact_mark_ids(t.data_ptr<int>(), t.numel(), (int32_t)N, mask, wsp, need, stream), "tcgnn_compact_mark_ids");
+  torch::Tensor new_id = torch::empty({N}, keep.options().dtype(torch::kInt32));
+  int32_t kept = 0;
+  tcgnn_check(tcgnn_compact_count(mask, (int32_t)N, new_id.data_ptr<int>(), wsp, need, &kept, stream), "tcgnn_compact_count");
+  torch::Tensor nodes = torch::empty({(int64_t)kept}, new_id.options());
+  tcgnn_check(tcgnn_compact_nodes(new_id.data_ptr<int>(), (int32_t)N, kept, nodes.data_ptr<int>(), stream), "tcgnn_compact_nodes");
+  return {nodes, new_id};
+}
+
+// compact_rows_graph: (nodePointer_b [M + 1], edgeList_b [E']) of a sample_rows graph whose rows are strictly increasing.  No synchronisation.
+std::tuple<torch::Tensor, torch::Tensor> compact_rows_graph(torch::Tensor rows, torch::Tensor rowPointer_s, torch::Tensor edgeList_s,
+                                                            torch::Tensor nodes, torch::Tensor new_id) {
+  CHECK_INPUT(rows);
+  const torch::Device dev = rows.device();
+  check_ids(rows, dev, "rows"); check_ids(rowPointer_s, dev, "rowPointer_s"); check_ids(edgeList_s, dev, "edgeList_s");
+  check_ids(nodes, dev, "nodes"); check_ids(new_id, dev, "new_id");
+  const int64_t R = rows.numel(), E = edgeList_s.numel(), M = nodes.numel(), N = new_id.numel();
+  TORCH_CHECK(rowPointer_s.numel() == R + 1, "rowPointer_s must hold one entry per listed row and one more");
+  TORCH_CHECK(M <= N, "nodes holds more entries than new_id has nodes");
+  DeviceGuard guard(dev);
+  torch::Tensor rp_b = torch::empty({M + 1}, rows.options()), col_b = torch::empty({E}, rows.options());
+  tcgnn_check(tcgnn_compact_rows_graph(rows.data_ptr<int>(), (int32_t)R, rowPointer_s.data_ptr<int>(), edgeList_s.data_ptr<int>(), E,
+                                       new_id.data_ptr<int>(), (int32_t)N, (int32_t)M, rp_b.data_ptr<int>(), col_b.data_ptr<int>(),
+                                       current_stream(rows)), "tcgnn_compact_rows_graph");
+  return {rp_b, col_b};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -1035,6 +1116,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keep") = py::none());
   m.def("compact_graph", &compact_graph, "a graph over the nodes of compact_nodes: (nodePointer_b, edgeList_b) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("nodes"), py::arg("new_id"));
+  m.def("sample_rows", &sample_rows, "sample_neighbors from a list of row ids: (rowPointer_s, edgeList_s, eid) (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("rows"), py::arg("fanout"), py::arg("seed"));
+  m.def("extend_nodes", &extend_nodes, "marks ids into the uint8 mask in place: (nodes, new_id) of the mask afterwards (not in the reference)",
+        py::arg("keep"), py::arg("ids"));
+  m.def("compact_rows_graph", &compact_rows_graph, "the block of a sample_rows graph over the nodes of extend_nodes: (nodePointer_b, edgeList_b) "
+        "(not in the reference)", py::arg("rows"), py::arg("rowPointer_s"), py::arg("edgeList_s"), py::arg("nodes"), py::arg("new_id"));
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

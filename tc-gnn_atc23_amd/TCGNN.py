@@ -37,7 +37,8 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors", "compact_nodes", "compact_graph"]
+           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors", "compact_nodes", "compact_graph",
+           "sample_rows", "extend_nodes", "compact_rows_graph"]
 
 
 def _stream(device):
@@ -62,8 +63,8 @@ _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
           "softmax": (1, 256),        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
-          "sample": (1, 256),         # sample_neighbors' row counts and scan scratch (its count call synchronises: nothing reads it afterwards)
-          "compact": (1, 256)}        # compact_nodes' validation words and scan scratch (likewise: its count call synchronises)
+          "sample": (1, 256),         # sample_neighbors' / sample_rows' row counts and scan scratch (the count call synchronises: nothing reads it afterwards)
+          "compact": (1, 256)}        # compact_nodes' / extend_nodes' validation words and scan scratch (likewise: the count call synchronises)
 
 
 def _buffer(kind, need, device, stream=None):
@@ -336,6 +337,111 @@ def compact_graph(nodePointer, edgeList, nodes, new_id):
         col_b = torch.empty(E, dtype=torch.int32, device=dev)
         _c.check(_c.lib.tcgnn_compact_graph(nodePointer.data_ptr(), edgeList.data_ptr(), new_id.data_ptr(), nodes.data_ptr(), N, M, E,
                                             rp_b.data_ptr(), col_b.data_ptr(), _stream(dev)), "tcgnn_compact_graph")
+    return rp_b, col_b
+
+
+# ---------------------------------------------------------------- seed-list sampling: a mini-batch costs its frontier
+
+def _check_id_types(*named):
+    """every (tensor, name) is an int32 tensor - the type before the place: a wrong dtype is named wherever the tensor lives"""
+    for t, name in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s must be a torch.Tensor" % name)
+        _check_int(t, name)
+
+
+def _check_ids(t, name, dev):
+    _check_input(t, name)
+    if t.device != dev:
+        raise RuntimeError("%s is on %s, expected %s" % (name, t.device, dev))
+
+
+def sample_rows(nodePointer, edgeList, rows, fanout, seed):
+    """Not in the reference module: sample_neighbors from a LIST of row ids, (rowPointer_s, edgeList_s, eid).  rows: int32 [R], any
+    order, ids may repeat (every occurrence gets its own slot).  The result has one row per list entry - rowPointer_s int32 [R + 1] -
+    and slot i holds exactly what row rows[i] of sample_neighbors(nodePointer, edgeList, fanout, seed) holds: the same edges in CSR
+    order and the same eid (positions in the FULL edgeList).  The work follows R, not the number of nodes; nodePointer is read, and
+    validated, at the listed rows only.  fanout=None keeps every edge of the listed rows; seed is any int, taken modulo 2**64.  One
+    stream synchronisation (to size the outputs)."""
+    _check_id_types((nodePointer, "nodePointer"), (edgeList, "edgeList"), (rows, "rows"))
+    if fanout is not None and int(fanout) < 0:
+        raise ValueError("fanout must be None or >= 0, not %r" % (fanout,))
+    _check_csr_pair(nodePointer, edgeList)
+    dev = nodePointer.device
+    _check_ids(rows, "rows", dev)
+    N, E, R = nodePointer.numel() - 1, edgeList.numel(), rows.numel()
+    k = 0x7fffffff if fanout is None else min(int(fanout), 0x7fffffff)
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_sample_rows_workspace_bytes(R, _c.ctypes.byref(need)), "tcgnn_sample_rows_workspace_bytes")
+        ws, ws_bytes = _buffer("sample", need.value, dev, stream)
+        rp_s = torch.empty(R + 1, dtype=torch.int32, device=dev)
+        kept = _c._i64(0)
+        _c.check(_c.lib.tcgnn_sample_rows_count(nodePointer.data_ptr(), _ptr(rows), R, N, E, k, rp_s.data_ptr(), ws, ws_bytes, _c.ctypes.byref(kept),
+                                                stream), "tcgnn_sample_rows_count")
+        col_s = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        eid = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        if kept.value:
+            _c.check(_c.lib.tcgnn_sample_rows(nodePointer.data_ptr(), edgeList.data_ptr(), rows.data_ptr(), rp_s.data_ptr(), R, N, E, k,
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, col_s.data_ptr(), eid.data_ptr(), stream), "tcgnn_sample_rows")
+    return rp_s, col_s, eid
+
+
+def extend_nodes(keep, ids):
+    """Not in the reference module: marks ids into the caller's mask IN PLACE and returns (nodes, new_id) of the mask afterwards.
+    keep: uint8 [N], contiguous - the node set so far (zeros to start one); ids: an int32 tensor or a sequence of them (seeds, the
+    edgeList_s of sample_rows), in any order, repeats allowed, every id in [0, N).  nodes (int32 [M]) = the kept ids in increasing order -
+    the next hop's row list - and new_id (int32 [N]) = the rank of a node in nodes, or -1.  One stream synchronisation (to size nodes),
+    however many tensors."""
+    if not isinstance(keep, torch.Tensor):
+        raise TypeError("keep must be a torch.Tensor")
+    if keep.dtype != torch.uint8:
+        raise RuntimeError("keep must be uint8 (it is written in place), not %s" % keep.dtype)
+    ids = [ids] if isinstance(ids, torch.Tensor) else list(ids)
+    _check_id_types(*((t, "ids") for t in ids))
+    _check_input(keep, "keep")
+    dev = keep.device
+    for t in ids:
+        _check_ids(t, "ids", dev)
+    N = keep.numel()
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_compact_workspace_bytes(N, _c.ctypes.byref(need)), "tcgnn_compact_workspace_bytes")
+        ws, ws_bytes = _buffer("compact", need.value, dev, stream)
+        _c.check(_c.lib.tcgnn_compact_begin(N, ws, ws_bytes, stream), "tcgnn_compact_begin")
+        for t in ids:
+            _c.check(_c.lib.tcgnn_compact_mark_ids(_ptr(t), t.numel(), N, _ptr(keep), ws, ws_bytes, stream), "tcgnn_compact_mark_ids")
+        new_id = torch.empty(N, dtype=torch.int32, device=dev)
+        kept = _c._i32(0)
+        _c.check(_c.lib.tcgnn_compact_count(_ptr(keep), N, _ptr(new_id), ws, ws_bytes, _c.ctypes.byref(kept), stream), "tcgnn_compact_count")
+        nodes = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        _c.check(_c.lib.tcgnn_compact_nodes(_ptr(new_id), N, kept.value, _ptr(nodes), stream), "tcgnn_compact_nodes")
+    return nodes, new_id
+
+
+def compact_rows_graph(rows, rowPointer_s, edgeList_s, nodes, new_id):
+    """Not in the reference module: (nodePointer_b [M + 1], edgeList_b [E']) - the square block over the M nodes of extend_nodes of a
+    sample_rows graph whose rows are STRICTLY INCREASING (a `nodes` of extend_nodes) and whose rows and columns the mask has seen.  A
+    node of the batch that is not listed gets an empty row; edgeList_b[e] = new_id[edgeList_s[e]].  The result equals compact_graph of
+    the same sampled graph written over all N rows: eid serves it unchanged.  No synchronisation.  With other rows or another new_id
+    the call is memory-safe and its result unspecified."""
+    named = ((rows, "rows"), (rowPointer_s, "rowPointer_s"), (edgeList_s, "edgeList_s"), (nodes, "nodes"), (new_id, "new_id"))
+    _check_id_types(*named)
+    dev = rows.device
+    for t, n in named:
+        _check_ids(t, n, dev)
+    R, E, M, N = rows.numel(), edgeList_s.numel(), nodes.numel(), new_id.numel()
+    if rowPointer_s.numel() != R + 1:
+        raise RuntimeError("rowPointer_s must hold one entry per listed row and one more (%d), not %d" % (R + 1, rowPointer_s.numel()))
+    if M > N:
+        raise RuntimeError("nodes holds %d entries, more than new_id's %d nodes" % (M, N))
+    with torch.cuda.device(dev):
+        rp_b = torch.empty(M + 1, dtype=torch.int32, device=dev)
+        col_b = torch.empty(E, dtype=torch.int32, device=dev)
+        _c.check(_c.lib.tcgnn_compact_rows_graph(_ptr(rows), R, rowPointer_s.data_ptr(), _ptr(edgeList_s), E, _ptr(new_id), N, M, rp_b.data_ptr(),
+                                                 _ptr(col_b), _stream(dev)), "tcgnn_compact_rows_graph")
     return rp_b, col_b
 
 

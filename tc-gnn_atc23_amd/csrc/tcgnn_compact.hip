@@ -121,3 +121,28 @@ extern "C" int tcgnn_compact_graph(const int32_t* d_nodePointer, const int32_t* 
                           static_cast<hipStream_t>(stream)));
     return TCGNN_OK;
 }
+
+// ---- row-list graphs: mark from lists of ids, and the block of a graph that has one row per listed id instead of num_nodes rows
+
+extern "C" int tcgnn_compact_mark_ids(const int32_t* d_ids, int64_t count, int32_t num_nodes, uint8_t* d_keep, void* d_workspace,
+                                      size_t workspace_bytes, void* stream) {
+    if (count < 0 || num_nodes < 0 || (count > 0 && !d_ids) || (count > 0 && num_nodes > 0 && !d_keep))
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_compact_mark_ids: null pointer or bad size");
+    uint32_t* const d_res = compact_res(d_workspace, workspace_bytes, num_nodes, nullptr);
+    WORKSPACE_TRY(d_res, "tcgnn_compact_mark_ids", num_nodes);
+    HIP_TRY(compact_mark_ids(d_ids, count, num_nodes, d_keep, d_res, static_cast<hipStream_t>(stream)));
+    return TCGNN_OK;
+}
+
+extern "C" int tcgnn_compact_rows_graph(const int32_t* d_rows, int32_t num_rows, const int32_t* d_rowPointer_s, const int32_t* d_edgeList_s,
+                                        int64_t num_sampled, const int32_t* d_new_id, int32_t num_nodes, int32_t num_kept,
+                                        int32_t* d_nodePointer_b, int32_t* d_edgeList_b, void* stream) {
+    if (!d_rowPointer_s || !d_nodePointer_b || num_rows < 0 || num_nodes < 0 || num_kept < 0 || num_kept > num_nodes || num_sampled < 0 ||
+        (num_rows > 0 && !d_rows) || (num_nodes > 0 && !d_new_id) || (num_sampled > 0 && (!d_edgeList_s || !d_edgeList_b)))
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_compact_rows_graph: null pointer or bad size");
+    if (num_sampled > 0x7fffffffLL)
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_compact_rows_graph: int32 CSR positions only (E' = %lld)", (long long)num_sampled);
+    HIP_TRY(compact_rows_graph(d_rows, num_rows, d_rowPointer_s, d_edgeList_s, num_sampled, d_new_id, num_nodes, num_kept, d_nodePointer_b,
+                               d_edgeList_b, static_cast<hipStream_t>(stream)));
+    return TCGNN_OK;
+}

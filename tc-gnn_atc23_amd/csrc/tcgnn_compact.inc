@@ -13,6 +13,8 @@
 //   compact_offsets_kernel  the mask again, scanned inside the workgroup on top of sums[b]: new_id[v], v = 0 .. N - 1
 //   compact_nodes_kernel    thread t: nodes[new_id[v]] = v for v = 4 t .. 4 t + 3
 //   compact_graph_kernel    thread t: nodePointer_b[4 t .. 4 t + 3] through nodes, edgeList_b[4 t .. 4 t + 3] through new_id
+//   compact_mark_ids_kernel   thread t: ids 4 t .. 4 t + 3 of a list (an id in range is kept)
+//   compact_rows_graph_kernel thread t: nodePointer_b[4 t .. 4 t + 3] by a search over the row list, edgeList_b[4 t .. 4 t + 3] through new_id
 // No global atomics: every output slot has one writer; the mask and the validation word only ever receive the same value (1) from
 // whoever stores to them.  The scan is this file's own (block sums, one workgroup over the sums, offsets), for the reason
 // tcgnn_sample.hip gives; it shares no code with tcgnn_sample.inc, whose kernels stay as they are.
@@ -219,6 +221,93 @@ __global__ __launch_bounds__(kCompactThreads) void compact_graph_kernel(const in
     }
 }
 
+// ---- row-list graphs (tcgnn_sample_rows' results): the same node set and blocks without the N-row CSRs in between.
+
+// keep[id] = 1 for a list of ids (seeds, the columns of a row-list graph); thread t: ids 4 t .. 4 t + 3.  VEC: ids is 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(kCompactThreads) void compact_mark_ids_kernel(const int32_t* __restrict__ ids, int64_t count, int32_t N, uint8_t* keep,
+                                                                           uint32_t* res) {
+    const int64_t first = ((int64_t)blockIdx.x * kCompactThreads + threadIdx.x) * kCompactItems;
+    if (first >= count) return;
+    const bool whole = first + kCompactItems <= count;
+    const int n = whole ? kCompactItems : (int)(count - first);
+    int32_t c[kCompactItems];
+    if (VEC && whole) {
+        const int4 q = *reinterpret_cast<const int4*>(ids + first);
+        c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kCompactItems; ++j) c[j] = j < n ? ids[first + j] : 0;
+    }
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j) {
+        if (j < n) {
+            if ((uint32_t)c[j] < (uint32_t)N) keep[c[j]] = 1;   // (a negative id is a large unsigned one)
+            else bad = true;
+        }
+    }
+    if (bad) res[kCompactResBad] = 1u;   // never followed; every thread that finds one stores the same 1
+}
+
+// the block position of list slot i: new_id[rows[i]], or -1 where either index fails its check
+__device__ __forceinline__ int32_t compact_list_pos(const int32_t* __restrict__ rows, const int32_t* __restrict__ new_id, int32_t i, int32_t N) {
+    const int32_t v = rows[i];
+    return (uint32_t)v < (uint32_t)N ? new_id[v] : -1;
+}
+
+// The square M-node block of a row-list graph whose R rows are strictly increasing.  Thread t owns row-pointer slots 4 t .. 4 t + 3 and
+// edges 4 t .. 4 t + 3.  Slot j <= M: new_id is monotone over increasing rows, so #{i : new_id[rows[i]] < j} is the lower bound of j in
+// the list's block positions - a binary search over [0, R], whose result indexes rowptr_s [R + 1] whatever the arrays hold.
+// VEC: edgeList_s and edgeList_b are 16-byte aligned
+template <bool VEC>
+__global__ __launch_bounds__(kCompactThreads) void compact_rows_graph_kernel(const int32_t* __restrict__ rows, int32_t R,
+                                                                             const int32_t* __restrict__ rowptr_s, const int32_t* __restrict__ col,
+                                                                             int64_t E, const int32_t* __restrict__ new_id, int32_t N, int32_t M,
+                                                                             int32_t* __restrict__ rowptr_b, int32_t* __restrict__ col_b) {
+    const int64_t first = ((int64_t)blockIdx.x * kCompactThreads + threadIdx.x) * kCompactItems;
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j) {
+        const int64_t slot = first + j;
+        if (slot < M) {
+            int32_t lo = 0, hi = R;   // the first list slot whose block position is >= slot
+            while (lo < hi) {
+                const int32_t mid = lo + ((hi - lo) >> 1);
+                if (compact_list_pos(rows, new_id, mid, N) < (int32_t)slot) lo = mid + 1;
+                else hi = mid;
+            }
+            int64_t p = rowptr_s[lo];
+            p = p < 0 ? 0 : (p > E ? E : p);
+            rowptr_b[slot] = (int32_t)p;
+        } else if (slot == M) {
+            rowptr_b[slot] = (int32_t)E;
+        }
+    }
+    if (first >= E) return;
+    const bool whole = first + kCompactItems <= E;
+    const int n = whole ? kCompactItems : (int)(E - first);
+    int32_t c[kCompactItems];
+    if (VEC && whole) {
+        const int4 q = *reinterpret_cast<const int4*>(col + first);
+        c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < kCompactItems; ++j) c[j] = j < n ? col[first + j] : -1;
+    }
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j) {   // the gather through new_id: a column without a new id becomes 0
+        const int32_t id = (uint32_t)c[j] < (uint32_t)N ? new_id[c[j]] : -1;
+        c[j] = (uint32_t)id < (uint32_t)M ? id : 0;
+    }
+    if (VEC && whole) {
+        *reinterpret_cast<int4*>(col_b + first) = make_int4(c[0], c[1], c[2], c[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < kCompactItems; ++j)
+            if (j < n) col_b[first + j] = c[j];
+    }
+}
+
 inline bool compact_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // workgroups whose threads own `items` items, four a thread
@@ -267,6 +356,25 @@ int compact_graph(const int32_t* rowptr, const int32_t* col, const int32_t* new_
         hipLaunchKernelGGL(compact_graph_kernel<true>, grid, block, 0, stream, rowptr, col, new_id, nodes, N, M, E, rowptr_b, col_b);
     else
         hipLaunchKernelGGL(compact_graph_kernel<false>, grid, block, 0, stream, rowptr, col, new_id, nodes, N, M, E, rowptr_b, col_b);
+    return (int)hipGetLastError();
+}
+
+int compact_mark_ids(const int32_t* ids, int64_t count, int32_t N, uint8_t* keep, uint32_t* res, hipStream_t stream) {
+    const dim3 grid(compact_grid(count)), block(kCompactThreads);
+    if (grid.x == 0) return (int)hipSuccess;
+    if (compact_aligned(ids, 16)) hipLaunchKernelGGL(compact_mark_ids_kernel<true>, grid, block, 0, stream, ids, count, N, keep, res);
+    else hipLaunchKernelGGL(compact_mark_ids_kernel<false>, grid, block, 0, stream, ids, count, N, keep, res);
+    return (int)hipGetLastError();
+}
+
+int compact_rows_graph(const int32_t* rows, int32_t R, const int32_t* rowptr_s, const int32_t* col, int64_t E, const int32_t* new_id, int32_t N,
+                       int32_t M, int32_t* rowptr_b, int32_t* col_b, hipStream_t stream) {
+    const int64_t slots = (int64_t)M + 1;
+    const dim3 grid(compact_grid(slots > E ? slots : E)), block(kCompactThreads);
+    if (compact_aligned(col, 16) && compact_aligned(col_b, 16))
+        hipLaunchKernelGGL(compact_rows_graph_kernel<true>, grid, block, 0, stream, rows, R, rowptr_s, col, E, new_id, N, M, rowptr_b, col_b);
+    else
+        hipLaunchKernelGGL(compact_rows_graph_kernel<false>, grid, block, 0, stream, rows, R, rowptr_s, col, E, new_id, N, M, rowptr_b, col_b);
     return (int)hipGetLastError();
 }
 

@@ -49,7 +49,7 @@
 //   tcgnn_agnn.inc            agnn_kernel (fused pair, forward / backward), slice sum, d_w reduction; launch_agnn*
 //   tcgnn_small_fallback.inc  CSR kernels of non-canonical plans, the range guard's fallbacks, symmetry_kernel, wide_patch_kernel
 //   tcgnn_transpose.inc       hand-written kernels of the CSR transpose (host side: tcgnn_transpose.hip)
-//   tcgnn_sample.inc          seeded neighbour sampling: row counts + validation, the per-row select (host side: tcgnn_sample.hip)
+//   tcgnn_sample.inc          seeded neighbour sampling: row counts + validation, the per-row select, both also from a list of rows (host side: tcgnn_sample.hip)
 //   tcgnn_edge_softmax.inc    softmax over a row's edges, forward / backward, and its C ABI
 //   tcgnn_gat.inc             multi-head GAT attention: fused score + softmax, its backward with d_er, per-source-node edge sums
 //   tcgnn_segment_max.inc     element-wise maximum over a row's edges and its backward over A^T (the wide-row gather: a lane group per neighbour row)

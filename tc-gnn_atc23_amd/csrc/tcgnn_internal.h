@@ -32,6 +32,12 @@ int sample_count(const int32_t* rowptr, const uint8_t* mask, int32_t N, int64_t 
                  void* stream);
 int sample_select(const int32_t* rowptr, const int32_t* col, const uint8_t* mask, const int32_t* rowptr_s, int32_t N, int64_t E, int32_t fanout,
                   uint64_t seed, int32_t* col_s, int32_t* eid, void* stream);
+// the same over a list of R row ids (tcgnn_sample_rows*): the scan runs over the list, the select launches one workgroup per four slots
+int64_t sample_rows_scan_blocks(int32_t R);   // words of scratch sample_rows_count needs
+int sample_rows_count(const int32_t* rowptr, const int32_t* rows, int32_t R, int32_t N, int64_t E, int32_t fanout, uint32_t* sums, uint32_t* res,
+                      int32_t* rowptr_s, void* stream);
+int sample_rows_select(const int32_t* rowptr, const int32_t* col, const int32_t* rows, const int32_t* rowptr_s, int32_t R, int32_t N, int64_t E,
+                       int32_t fanout, uint64_t seed, int32_t* col_s, int32_t* eid, void* stream);
 
 } // namespace tcgnn
 #endif

@@ -87,3 +87,72 @@ extern "C" int tcgnn_sample_neighbors(const int32_t* d_nodePointer, const int32_
     HIP_TRY(sample_select(d_nodePointer, d_edgeList, d_row_mask, d_nodePointer_s, num_nodes, num_edges, fanout, seed, d_edgeList_s, d_eid, stream));
     return TCGNN_OK;
 }
+
+// ---- seed-list sampling: the same two calls over a list of row ids.  The scan covers the list's num_rows + 1 slots and the select
+// launches one workgroup per four slots, so a mini-batch costs its frontier and not num_nodes.
+
+namespace {
+
+// read-back words of the rows count: a listed id out of range, a listed pointer out of range, a descending listed pair, E' (saturating)
+struct SampleRowsResult { uint32_t bad_id, bad_ptr, descending, total, pad[4]; };
+
+SampleLayout sample_rows_layout(int32_t num_rows) {
+    SampleLayout L;
+    L.off_res = 0;
+    L.off_sums = up256(sizeof(SampleRowsResult));
+    L.total = L.off_sums + up256((size_t)sample_rows_scan_blocks(num_rows) * 4);
+    return L;
+}
+
+} // namespace
+
+extern "C" int tcgnn_sample_rows_workspace_bytes(int32_t num_rows, size_t* bytes) {
+    if (!bytes || num_rows < 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows_workspace_bytes: null pointer or bad size");
+    *bytes = sample_rows_layout(num_rows).total;
+    return TCGNN_OK;
+}
+
+extern "C" int tcgnn_sample_rows_count(const int32_t* d_nodePointer, const int32_t* d_rows, int32_t num_rows, int32_t num_nodes, int64_t num_edges,
+                                       int32_t fanout, int32_t* d_rowPointer_s, void* d_workspace, size_t workspace_bytes, int64_t* num_sampled,
+                                       void* stream_v) {
+    if (!d_nodePointer || !d_rowPointer_s || !num_sampled || num_rows < 0 || num_nodes < 0 || num_edges < 0 || (num_rows > 0 && !d_rows))
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows_count: null pointer or bad size");
+    if (fanout < 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows_count: fanout = %d is negative", fanout);
+    if (num_edges > 0x7fffffffLL) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows_count: int32 CSR positions only (E = %lld)", (long long)num_edges);
+    const SampleLayout L = sample_rows_layout(num_rows);
+    if (!d_workspace || workspace_bytes < L.total || (reinterpret_cast<uintptr_t>(d_workspace) & 255))
+        return fail(TCGNN_ERR_WORKSPACE, "tcgnn_sample_rows_count: workspace needs %zu bytes 256-aligned (tcgnn_sample_rows_workspace_bytes), got %zu at %p",
+                    L.total, workspace_bytes, d_workspace);
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    char* const ws = static_cast<char*>(d_workspace);
+    uint32_t* const d_res = reinterpret_cast<uint32_t*>(ws + L.off_res);
+    uint32_t* const sums = reinterpret_cast<uint32_t*>(ws + L.off_sums);
+
+    HIP_TRY(hipMemsetAsync(d_res, 0, sizeof(SampleRowsResult), stream));
+    HIP_TRY(sample_rows_count(d_nodePointer, d_rows, num_rows, num_nodes, num_edges, fanout, sums, d_res, d_rowPointer_s, stream));
+    SampleRowsResult res;
+    HIP_TRY(hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (res.bad_id) return fail(TCGNN_ERR_BAD_GRAPH, "tcgnn_sample_rows_count: a listed row id lies outside [0, %d)", num_nodes);
+    if (res.bad_ptr)
+        return fail(TCGNN_ERR_BAD_GRAPH, "tcgnn_sample_rows_count: nodePointer of a listed row lies outside [0, %lld]", (long long)num_edges);
+    if (res.descending) return fail(TCGNN_ERR_BAD_GRAPH, "tcgnn_sample_rows_count: nodePointer descends at a listed row");
+    if (res.total > 0x7fffffffu)
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows_count: the listed rows keep more than 2^31 - 1 edges (int32 positions only)");
+    *num_sampled = (int64_t)res.total;
+    return TCGNN_OK;
+}
+
+extern "C" int tcgnn_sample_rows(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_rows, const int32_t* d_rowPointer_s,
+                                 int32_t num_rows, int32_t num_nodes, int64_t num_edges, int32_t fanout, uint64_t seed, int32_t* d_edgeList_s,
+                                 int32_t* d_eid, void* stream) {
+    if (!d_nodePointer || !d_rowPointer_s || num_rows < 0 || num_nodes < 0 || num_edges < 0 || (num_rows > 0 && !d_rows))
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows: null pointer or bad size");
+    if (fanout < 0) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows: fanout = %d is negative", fanout);
+    if (num_edges > 0x7fffffffLL) return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows: int32 CSR positions only (E = %lld)", (long long)num_edges);
+    if (num_rows > 0 && num_edges > 0 && fanout > 0 && (!d_edgeList || !d_edgeList_s || !d_eid))   // (nothing is kept otherwise: nothing is written)
+        return fail(TCGNN_ERR_INVALID_ARG, "tcgnn_sample_rows: null edge array");
+    HIP_TRY(sample_rows_select(d_nodePointer, d_edgeList, d_rows, d_rowPointer_s, num_rows, num_nodes, num_edges, fanout, seed, d_edgeList_s, d_eid,
+                               stream));
+    return TCGNN_OK;
+}

@@ -18,6 +18,8 @@
 // No global atomics: every output slot has one writer, fixed by the row pointers the count call wrote.  The LDS histogram's integer
 // adds commute, so the result is a pure function of the inputs.  A column id is read only for an edge that is kept.
 // Every index derived from the caller's row pointers is clamped to [0, E]; a row writes no more than its slot of nodePointer_s holds.
+// The second half of the file is the same selection from a LIST of row ids (sample_rows_select_kernel and its count): the grid follows the
+// list, not N, and the device functions below are shared.
 
 namespace {
 
@@ -311,6 +313,162 @@ __global__ __launch_bounds__(kSampleThreads) void sample_offsets_kernel(const in
     }
 }
 
+// ---- seed-list sampling (tcgnn_sample_rows*): the same selection over a LIST of row ids, so that the grid follows the list and not N.
+// List slot i names row rows[i] (any order, repeats allowed: every occurrence has its own slot) and owns positions
+// rowptr_s[i] .. rowptr_s[i + 1] of the outputs.  Workgroup b owns slots 4 b .. 4 b + 3 exactly as sample_select_kernel owns rows;
+// the device functions above are shared, only the SampleRow comes through rows[].  nodePointer is read at listed rows alone.
+
+// SampleRow of list slot `slot`; an id outside [0, N) is an empty row
+__device__ __forceinline__ SampleRow sample_list_row(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rows,
+                                                     const int32_t* __restrict__ rowptr_s, int64_t slot, int32_t N, int64_t E, int32_t fanout) {
+    const int32_t row = rows[slot];
+    int64_t lo = 0, hi = 0;
+    if ((uint32_t)row < (uint32_t)N) {   // (a negative id is a large unsigned one)
+        lo = rowptr[row];
+        hi = rowptr[row + 1];
+    }
+    lo = lo < 0 ? 0 : (lo > E ? E : lo);
+    hi = hi < 0 ? 0 : (hi > E ? E : hi);
+    SampleRow r;
+    r.lo = lo;
+    r.d = hi > lo ? (int32_t)(hi - lo) : 0;
+    r.keep = r.d < fanout ? r.d : fanout;
+    const int64_t o = rowptr_s[slot], size = (int64_t)rowptr_s[slot + 1] - o;
+    r.out = o;
+    if (o < 0 || size < r.keep) r.keep = 0;   // (not what the count call wrote: write nothing rather than beyond the slot)
+    return r;
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_select_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                            const int32_t* __restrict__ rows, const int32_t* __restrict__ rowptr_s,
+                                                                            int32_t R, int32_t N, int64_t E, int32_t fanout, uint64_t S,
+                                                                            int32_t* __restrict__ col_s, int32_t* __restrict__ eid) {
+    __shared__ SampleShared sh;
+    const int lane = threadIdx.x & 63;
+    const int64_t first = (int64_t)blockIdx.x * kSampleRowsPerGroup;
+    const int64_t mine = first + (threadIdx.x >> 6);
+    if (mine < R) {
+        const SampleRow r = sample_list_row(rowptr, rows, rowptr_s, mine, N, E, fanout);
+        if (r.keep > 0 && r.d <= kSampleWaveRow) {
+            if (r.keep == r.d) sample_copy_row(col, r, lane, 64, col_s, eid);
+            else sample_wave_select(col, r, S, lane, col_s, eid);
+        }
+    }
+    for (int q = 0; q < kSampleRowsPerGroup; ++q) {   // the same slots for every thread: the barriers inside are uniform
+        if (first + q >= R) break;
+        const SampleRow r = sample_list_row(rowptr, rows, rowptr_s, first + q, N, E, fanout);
+        if (r.keep == 0 || r.d <= kSampleWaveRow) continue;
+        if (r.keep == r.d) sample_copy_row(col, r, (int)threadIdx.x, kSampleThreads, col_s, eid);
+        else sample_group_select(col, r, S, sh, col_s, eid);
+    }
+}
+
+// ---- the rows count call: rowPointer_s[i] = the exclusive sum of min(d(rows[j]), fanout) over j < i, i = 0 .. R, in the three launches
+// of sample_count over R + 1 slots (slot R: the total), with the validation of the LISTED rows in the first:
+//   res[kRowsResBadId] = 1 a listed id outside [0, N);  res[kRowsResBadPtr] = 1 a listed row's pointer outside [0, E];
+//   res[kRowsResDescending] = 1 a listed row's pointers descend;  res[kRowsResTotal] = E'
+// Every thread that finds a fault stores the same 1.  A list may repeat long rows, so unlike the sums above these can pass 2^31 - 1:
+// every add saturates at kRowsSumCap, which as an int32 row pointer is negative - sample_list_row keeps nothing behind it - and the
+// entry point reports a total that reached the cap.
+constexpr int kRowsResBadId = 0, kRowsResBadPtr = 1, kRowsResDescending = 2, kRowsResTotal = 3;
+constexpr uint32_t kRowsSumCap = 0x80000000u;
+
+__device__ __forceinline__ uint32_t sample_sat_add(uint32_t a, uint32_t b) {   // a, b <= kRowsSumCap
+    const uint64_t s = (uint64_t)a + b;
+    return s > kRowsSumCap ? kRowsSumCap : (uint32_t)s;
+}
+
+// bit 0: id out of range, bit 1: pointer out of range, bit 2: descending pair
+__device__ __forceinline__ uint32_t sample_list_count(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rows, int64_t i, int32_t R,
+                                                      int32_t N, int64_t E, int32_t fanout, uint32_t& faults) {
+    if (i >= R) return 0;   // (slot R: the total)
+    const int32_t row = rows[i];
+    if ((uint32_t)row >= (uint32_t)N) {
+        faults |= 1u;
+        return 0;
+    }
+    int64_t lo = rowptr[row], hi = rowptr[row + 1];
+    if (lo < 0 || lo > E || hi < 0 || hi > E) faults |= 2u;
+    if (lo > hi) faults |= 4u;
+    lo = lo < 0 ? 0 : (lo > E ? E : lo);
+    hi = hi < 0 ? 0 : (hi > E ? E : hi);
+    int64_t c = hi > lo ? hi - lo : 0;
+    if (c > fanout) c = fanout;
+    return (uint32_t)c;
+}
+
+// sample_group_scan with saturating adds: exclusive sum of v over the workgroup's threads in thread order, *total over all of them
+__device__ __forceinline__ uint32_t sample_group_scan_sat(uint32_t v, uint32_t* part, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t up = __shfl_up(incl, s);
+        if (lane >= s) incl = sample_sat_add(incl, up);
+    }
+    const uint32_t below = __shfl_up(incl, 1);
+    const uint32_t excl = lane ? below : 0u;
+    __syncthreads();   // (part may still be read from the call before)
+    if (lane == 63) part[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+    for (int w = 0; w < kSampleRowsPerGroup; ++w) {
+        const uint32_t p = part[w];
+        if (w < wave) before = sample_sat_add(before, p);
+        all = sample_sat_add(all, p);
+    }
+    *total = all;
+    return sample_sat_add(before, excl);
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_count_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rows,
+                                                                           int32_t R, int32_t N, int64_t E, int32_t fanout,
+                                                                           uint32_t* __restrict__ sums, uint32_t* res) {
+    __shared__ uint32_t part[kSampleRowsPerGroup];
+    const int64_t first = (int64_t)blockIdx.x * kSampleScanRows + 4 * (int64_t)threadIdx.x;
+    uint32_t faults = 0, c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c = sample_sat_add(c, sample_list_count(rowptr, rows, first + j, R, N, E, fanout, faults));
+    if (faults & 1u) res[kRowsResBadId] = 1u;
+    if (faults & 2u) res[kRowsResBadPtr] = 1u;
+    if (faults & 4u) res[kRowsResDescending] = 1u;
+    uint32_t total;
+    sample_group_scan_sat(c, part, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_scan_sums_kernel(uint32_t* __restrict__ sums, int64_t blocks, uint32_t* res) {
+    __shared__ uint32_t part[kSampleRowsPerGroup];
+    uint32_t carry = 0;
+    for (int64_t b0 = 0; b0 < blocks; b0 += kSampleThreads) {
+        const int64_t b = b0 + threadIdx.x;
+        const uint32_t v = b < blocks ? sums[b] : 0u;
+        uint32_t total;
+        const uint32_t before = sample_group_scan_sat(v, part, &total);
+        if (b < blocks) sums[b] = sample_sat_add(carry, before);
+        carry = sample_sat_add(carry, total);
+    }
+    if (threadIdx.x == 0) res[kRowsResTotal] = carry;
+}
+
+__global__ __launch_bounds__(kSampleThreads) void sample_rows_offsets_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ rows,
+                                                                             int32_t R, int32_t N, int64_t E, int32_t fanout,
+                                                                             const uint32_t* __restrict__ sums, int32_t* __restrict__ rowptr_s) {
+    __shared__ uint32_t part[kSampleRowsPerGroup];
+    const int64_t first = (int64_t)blockIdx.x * kSampleScanRows + 4 * (int64_t)threadIdx.x;
+    uint32_t faults = 0;
+    uint32_t c[4], mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) mine = sample_sat_add(mine, c[j] = sample_list_count(rowptr, rows, first + j, R, N, E, fanout, faults));
+    uint32_t total;
+    uint32_t at = sample_sat_add(sums[blockIdx.x], sample_group_scan_sat(mine, part, &total));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (first + j <= R) rowptr_s[first + j] = (int32_t)at;
+        at = sample_sat_add(at, c[j]);
+    }
+}
+
 } // namespace
 
 namespace tcgnn {
@@ -340,6 +498,27 @@ int sample_select(const int32_t* rowptr, const int32_t* col, const uint8_t* mask
     if (N > 0 && E > 0 && fanout > 0)
         hipLaunchKernelGGL(sample_select_kernel, dim3((unsigned)(((int64_t)N + kSampleRowsPerGroup - 1) / kSampleRowsPerGroup)), dim3(kSampleThreads), 0,
                            static_cast<hipStream_t>(stream), rowptr, col, mask, rowptr_s, N, E, fanout, sample_seed_word(seed), col_s, eid);
+    return (int)hipGetLastError();
+}
+
+int64_t sample_rows_scan_blocks(int32_t R) { return ((int64_t)R + 1 + kSampleScanRows - 1) / kSampleScanRows; }
+
+// rowPointer_s [R + 1] and the four result words (see sample_rows_count_kernel); sums: sample_rows_scan_blocks(R) words of scratch
+int sample_rows_count(const int32_t* rowptr, const int32_t* rows, int32_t R, int32_t N, int64_t E, int32_t fanout, uint32_t* sums, uint32_t* res,
+                      int32_t* rowptr_s, void* stream_v) {
+    hipStream_t stream = static_cast<hipStream_t>(stream_v);
+    const int64_t blocks = sample_rows_scan_blocks(R);
+    hipLaunchKernelGGL(sample_rows_count_kernel, dim3((unsigned)blocks), dim3(kSampleThreads), 0, stream, rowptr, rows, R, N, E, fanout, sums, res);
+    hipLaunchKernelGGL(sample_rows_scan_sums_kernel, dim3(1), dim3(kSampleThreads), 0, stream, sums, blocks, res);
+    hipLaunchKernelGGL(sample_rows_offsets_kernel, dim3((unsigned)blocks), dim3(kSampleThreads), 0, stream, rowptr, rows, R, N, E, fanout, sums, rowptr_s);
+    return (int)hipGetLastError();
+}
+
+int sample_rows_select(const int32_t* rowptr, const int32_t* col, const int32_t* rows, const int32_t* rowptr_s, int32_t R, int32_t N, int64_t E,
+                       int32_t fanout, uint64_t seed, int32_t* col_s, int32_t* eid, void* stream) {
+    if (R > 0 && E > 0 && fanout > 0)
+        hipLaunchKernelGGL(sample_rows_select_kernel, dim3((unsigned)(((int64_t)R + kSampleRowsPerGroup - 1) / kSampleRowsPerGroup)), dim3(kSampleThreads),
+                           0, static_cast<hipStream_t>(stream), rowptr, col, rows, rowptr_s, R, N, E, fanout, sample_seed_word(seed), col_s, eid);
     return (int)hipGetLastError();
 }
 

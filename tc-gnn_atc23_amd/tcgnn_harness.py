@@ -66,6 +66,9 @@ def build_parser():
                    help="B: with --fanout, mini-batch training - every epoch cuts a seeded permutation of the nodes into batches of B seeds, samples each "
                    "batch's layer graphs, relabels them to the nodes they touch (tcgnn_layers.sample_batch) and takes one optimiser step per batch on the "
                    "seeds' loss; the final loss is evaluated on the full graph (not in the reference)")
+    p.add_argument("--sampler", type=str, default="dense", choices=["dense", "rows"],
+                   help="with --batch-size: 'dense' samples every hop over all rows of the graph behind a frontier mask; 'rows' samples from the list of "
+                   "frontier rows (tcgnn_layers.sample_batch_rows), so a step costs its batch - the same batches, bit for bit (not in the reference)")
     return p
 
 
@@ -92,6 +95,15 @@ def parse_batch_size(batch_size, fanout, hip_graph=False):
     if int(batch_size) < 1:
         raise ValueError("--batch-size takes a value >= 1, got %r" % (batch_size,))
     return int(batch_size)
+
+
+def parse_sampler(sampler, batch_size):
+    """--sampler's value checked against the flag it depends on"""
+    if sampler not in ("dense", "rows"):
+        raise ValueError("--sampler takes 'dense' or 'rows', got %r" % (sampler,))
+    if sampler == "rows" and batch_size is None:
+        raise ValueError("--sampler rows samples a mini-batch from its list of rows and needs --batch-size")
+    return sampler
 
 
 def epoch_order(num_nodes, seed, epoch):
@@ -179,7 +191,7 @@ def make_adam(params, lr=0.01):
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
                   norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None,
-                  batch_size=None, batch_hook=None):
+                  batch_size=None, batch_hook=None, sampler="dense"):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -208,9 +220,13 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     node_nll_loss(out[seed_pos], y[seeds]).  `warmup` counts dry STEPS here (batches of a permutation no timed epoch uses), not epochs.
     The result holds sample_ms, compact_ms, plan_ms and train_ms per epoch (each behind a device synchronisation), their sum epoch_ms,
     batches (per epoch), mean_block_nodes (the mean M) and final_loss on the FULL graph.  batch_hook(epoch, index, seeds), when given, is
-    called before every timed step.  Refused together with hip_graph."""
+    called before every timed step.  Refused together with hip_graph.
+    sampler (not in the reference; needs batch_size for 'rows'): 'dense' is the step above; 'rows' draws the same batch through
+    tcgnn_layers.sample_layers_rows and compact_layers_rows (the two halves of sample_batch_rows, timed apart as sample_ms and compact_ms):
+    the sampler runs over the batch's rows, not over all N.  The batches, and with them every loss, are bit-equal."""
     import tcgnn_layers as L
     batch_size = parse_batch_size(batch_size, fanout, hip_graph)
+    sampler = parse_sampler(sampler, batch_size)
     if fanout is not None and hip_graph:
         raise ValueError("--fanout samples a new graph every epoch and can not be combined with --hip_graph, which replays one captured epoch")
     fanout = parse_fanout(fanout, num_layers)
@@ -312,9 +328,14 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         def step(epoch, index, seeds):
             """one optimiser step on the compact batch of `seeds`; -> (loss, M)"""
             t = time.perf_counter()
-            graphs = L.sample_layers(full, seeds, fanout, batch_seed(seed, epoch, index))
-            t = lap("sample_ms", t)
-            batch = L.compact_layers(graphs, seeds, plan=False)   # (with the line above: tcgnn_layers.sample_batch, timed in its two parts)
+            if sampler == "rows":   # tcgnn_layers.sample_batch_rows, timed in its two parts
+                drawn = L.sample_layers_rows(full, seeds, fanout, batch_seed(seed, epoch, index))
+                t = lap("sample_ms", t)
+                batch = L.compact_layers_rows(*drawn, seeds, plan=False)
+            else:
+                graphs = L.sample_layers(full, seeds, fanout, batch_seed(seed, epoch, index))
+                t = lap("sample_ms", t)
+                batch = L.compact_layers(graphs, seeds, plan=False)   # (with the line above: tcgnn_layers.sample_batch, timed in its two parts)
             xb, yb = x[batch.nodes.long()], y[seeds]
             t = lap("compact_ms", t)
             sampled_attr.clear()
@@ -476,7 +497,8 @@ def run(args, quiet=False):
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
                       aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None),
-                      batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None))
+                      batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None),
+                      sampler=getattr(args, "sampler", "dense"))
     if "sample_ms" in r:
         say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
     if "compact_ms" in r:

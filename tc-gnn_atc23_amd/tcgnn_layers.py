@@ -1050,3 +1050,48 @@ def sample_batch(csr, seeds, fanouts, seed, plan=True):
     M = the nodes within len(fanouts) sampled hops of the seeds, instead of the full graph's N.  What compact_layers says of directed
     graphs and of the plan / CSR cache slots every batch takes holds here."""
     return compact_layers(sample_layers(csr, seeds, fanouts, seed), seeds, plan=plan)
+
+
+# ---------------------------------------------------------------- seed-list mini-batches: the same CompactBatch at the frontier's cost
+
+def sample_layers_rows(csr, seeds, fanouts, seed):
+    """The sampling half of sample_batch_rows: (hops, nodes, new_id).  hops: per layer, input layer first, (rows, row_pointers_s,
+    column_index_s, eid) - the backend's sample_rows of that hop's row list; nodes / new_id: the batch's node set, as extend_nodes returns
+    it after the last hop.  The mask starts as the seeds (any order, repeats allowed); extend_nodes turns it into the first, increasing
+    row list; hop h from the seeds draws with seed + h and fanouts taken from the last layer backwards, as sample_layers does, and its
+    columns are marked into the same mask - the new nodes are the next hop's row list.  Nothing here walks all N rows of the graph but
+    the mask's scan.  Stream synchronisations: one per sample_rows and one per extend_nodes, 2 len(fanouts) + 1 in all."""
+    rp, col = csr[0], csr[1]
+    keep = torch.zeros(rp.numel() - 1, dtype=torch.uint8, device=rp.device)
+    nodes, new_id = backend().extend_nodes(keep, seeds.to(torch.int32))
+    hops = []
+    for hop, k in enumerate(reversed(list(fanouts))):
+        rows = nodes
+        rp_s, col_s, eid = backend().sample_rows(rp, col, rows, k, int(seed) + hop)
+        nodes, new_id = backend().extend_nodes(keep, col_s)
+        hops.insert(0, (rows, rp_s, col_s, eid))
+    return hops, nodes, new_id
+
+
+def compact_layers_rows(hops, nodes, new_id, seeds, plan=True):
+    """The relabelling half of sample_batch_rows: what sample_layers_rows returned as a CompactBatch (the backend's compact_rows_graph
+    per hop; no stream synchronisation).  plan as in compact_layers."""
+    metas = []
+    for rows, rp_s, col_s, _ in hops:
+        rp_b, col_b = backend().compact_rows_graph(rows, rp_s, col_s, nodes, new_id)
+        if plan:
+            metas.append(csr_meta(rp_b, col_b))
+        else:
+            metas.append((rp_b, col_b) + tuple(torch.empty(0, dtype=torch.int32, device=rp_b.device) for _ in range(3)))
+    return CompactBatch(nodes, new_id[seeds.long()].long(), metas, [h[3] for h in hops], new_id)
+
+
+def sample_batch_rows(csr, seeds, fanouts, seed, plan=True):
+    """sample_batch from lists of row ids: the same CompactBatch - every field equals sample_batch(csr, seeds, fanouts, seed, plan)'s,
+    element for element - without a pass over the graph's N rows per hop: the sampler runs over the seeds and, hop by hop, over the
+    nodes reached so far (sample_layers_rows), and every hop's row-list graph becomes its block directly (compact_layers_rows).  What
+    is left at O(N) is the byte mask and its scan.  Stream synchronisations per batch: 2 len(fanouts) + 1 - one per sample_rows (to size
+    its outputs) and one per extend_nodes (to size nodes), against sample_batch's len(fanouts) + 1.  What compact_layers says of directed
+    graphs and of the plan / CSR cache slots every batch takes holds here."""
+    hops, nodes, new_id = sample_layers_rows(csr, seeds, fanouts, seed)
+    return compact_layers_rows(hops, nodes, new_id, seeds, plan=plan)
