@@ -287,6 +287,57 @@ int tcgnn_compact_rows_graph(const int32_t* d_rows, int32_t num_rows, const int3
                              int64_t num_sampled, const int32_t* d_new_id, int32_t num_nodes, int32_t num_kept, int32_t* d_nodePointer_b,
                              int32_t* d_edgeList_b, void* stream);
 
+/* Subgraph sampling (no counterpart in the reference): the other family of mini-batches - a node set drawn by random walks (GraphSAINT)
+ * or taken as a range of ids (Cluster-GCN) and the subgraph the full graph INDUCES on it (DGL's random_walk / node_subgraph, PyG's
+ * subgraph).  The induced subgraph is a square CSR over its M nodes in which every row is used: one block serves every layer.
+ * Both operations take DEVICE pointers, are pure functions of their inputs (no global atomics), bit-identical on repetition, run on
+ * caller scratch, allocate nothing and are stream-ordered.
+ *
+ * tcgnn_random_walk: d_walks int32 [num_walks, length + 1], row-major.  walks[w][0] = starts[w]; for t = 0 .. length - 1, with
+ *   v = walks[w][t]:  v outside [0, num_nodes): the walk stays on it, walks[w][t + 1] = v, and nothing is read through it;
+ *   otherwise lo, hi = nodePointer[v], nodePointer[v + 1], each clamped to [0, num_edges], d = hi - lo;  d <= 0: the walk stays on v
+ *   (torch_cluster's rule for a node without edges, so every entry of walks is an id and needs no filtering);  otherwise
+ *     walks[w][t + 1] = edgeList[lo + ((h32(seed, w * length + t) * d) >> 32)]
+ *   with h32 of the sampling section above, its second argument a 64-bit integer (arithmetic modulo 2^64); the product is a 64-bit one,
+ *   below 2^63 because d <= 2^31 - 1.  A column id outside [0, num_nodes) is written and then not followed.  Rows hold IN-edges, so a
+ *   walk moves from a node to one of its SOURCES - the direction neighbour sampling expands in.  One lane per walk; no workspace, no
+ *   synchronisation and no report: an id out of range reaches tcgnn_compact_mark_ids, which sets the validation word that
+ *   tcgnn_compact_count reports.  TCGNN_ERR_INVALID_ARG before any launch: a null required pointer (d_starts and d_walks may be NULL
+ *   when num_walks = 0, d_edgeList when num_edges = 0), a negative size or length, num_edges > 2^31 - 1,
+ *   num_walks * (length + 1) > 2^31 - 1.
+ *
+ * tcgnn_induce_*: the node-induced subgraph of a CSR over a node list.  Inputs: d_nodePointer, d_edgeList; d_nodes int32 [num_kept = M],
+ *   STRICTLY INCREASING, as tcgnn_compact_nodes emits it; d_new_id int32 [num_nodes], from the tcgnn_compact_count of the same mask.
+ *   Outputs: d_nodePointer_b [M + 1], d_edgeList_b [E_b], d_eid [E_b].  Row i of the result holds, in CSR order, the positions e in
+ *   [nodePointer[nodes[i]], nodePointer[nodes[i] + 1]) with new_id[edgeList[e]] >= 0; for each of them edgeList_b = new_id[edgeList[e]]
+ *   and eid = e, the position in the FULL CSR (edge values of the block are val[eid]).  The relabelling is monotone: sorted rows stay
+ *   sorted, the block is square over M nodes and every operator of this header takes it.
+ * tcgnn_induce_workspace_bytes: answered without a device - 256 bytes for the result words plus, rounded up to 256 bytes, one 4-byte
+ *   partial sum per 1 024 of the list's num_kept + 1 slots.
+ * tcgnn_induce_count: writes d_nodePointer_b and *num_induced = E_b on CALLER scratch and synchronises `stream` ONCE to read back E_b
+ *   and the validation words.  nodePointer is read, and validated, at LISTED rows only.  A listed id outside [0, num_nodes), a
+ *   descending pointer pair at a listed row, a pointer of a listed row outside [0, num_edges] or a column id outside [0, num_nodes) in
+ *   a listed row is TCGNN_ERR_BAD_GRAPH, reported behind the read-back; until then such a row is empty or such an edge dropped, and
+ *   every index is clamped.  The sums saturate: a list with repeats (outside the contract) whose rows keep more than 2^31 - 1 edges is
+ *   TCGNN_ERR_INVALID_ARG behind the read-back, nothing wraps.
+ * tcgnn_induce: with the d_nodePointer_b and num_induced = E_b of the count call for the same inputs, writes exactly E_b entries of
+ *   d_edgeList_b and of d_eid.  No allocation, no synchronisation; a row never writes beyond the slot nodePointer_b gives it, nor
+ *   beyond E_b.  One wavefront per listed row of up to 1 024 edges, four rows per workgroup; the whole workgroup takes a longer row.
+ * Outside the contract - nodes not increasing, a new_id of another mask, values >= M in it - both calls stay memory-safe: every index
+ * is checked or clamped, a new id outside [0, M) is written as 0; the result is then unspecified.
+ * Before any launch both refuse a null required pointer (arrays of no entries may be NULL), a negative size, num_kept > num_nodes and
+ * num_edges > 2^31 - 1 with TCGNN_ERR_INVALID_ARG; the count call refuses a workspace that is null, short or not 256-byte aligned with
+ * TCGNN_ERR_WORKSPACE.  num_kept = 0 gives TCGNN_OK (nodePointer_b[0] = 0, E_b = 0). */
+int tcgnn_random_walk(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_starts, int32_t num_walks,
+                      int32_t num_nodes, int64_t num_edges, int32_t length, uint64_t seed, int32_t* d_walks, void* stream);
+int tcgnn_induce_workspace_bytes(int32_t num_kept, size_t* bytes);
+int tcgnn_induce_count(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_nodes, const int32_t* d_new_id,
+                       int32_t num_kept, int32_t num_nodes, int64_t num_edges, int32_t* d_nodePointer_b, void* d_workspace,
+                       size_t workspace_bytes, int64_t* num_induced, void* stream);
+int tcgnn_induce(const int32_t* d_nodePointer, const int32_t* d_edgeList, const int32_t* d_nodes, const int32_t* d_new_id,
+                 const int32_t* d_nodePointer_b, int32_t num_kept, int32_t num_nodes, int64_t num_edges, int64_t num_induced,
+                 int32_t* d_edgeList_b, int32_t* d_eid, void* stream);
+
 /* Tile statistics of the translation - what the reference's counting scripts report
  * (3_cnt_TC_blk_SpMM.py:38-94 with 16x8 tiles, 3_cnt_TC_blk_SDDMM.py with 16x16; logs/16x8_reduction.csv,
  * logs/reduce_blocks.csv): per window of tile_h rows, U = sorted unique neighbour ids;

@@ -967,6 +967,51 @@ std::tuple<torch::Tensor, torch::Tensor> compact_rows_graph(torch::Tensor rows, 
   return {rp_b, col_b};
 }
 
+// Not in the reference: subgraph sampling (tcgnn_random_walk, tcgnn_induce_*; TCGNN.random_walk / induce_subgraph of the ctypes module).
+// random_walk: walks int32 [W, length + 1], one seeded walk per entry of starts, towards a row's sources.  No synchronisation.
+torch::Tensor random_walk(torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor starts, int64_t length, py::int_ seed) {
+  check_csr_pair(nodePointer, edgeList);
+  check_ids(starts, nodePointer.device(), "starts");
+  TORCH_CHECK(length >= 0 && length < 0x7fffffff, "length must be >= 0");
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), W = starts.numel();
+  const uint64_t seed64 = py::cast<uint64_t>(seed.attr("__and__")(py::int_(0xFFFFFFFFFFFFFFFFull)));
+  DeviceGuard guard(nodePointer.device());
+  torch::Tensor walks = torch::empty({W, length + 1}, nodePointer.options());
+  tcgnn_check(tcgnn_random_walk(nodePointer.data_ptr<int>(), E ? edgeList.data_ptr<int>() : nullptr, W ? starts.data_ptr<int>() : nullptr, (int32_t)W,
+                                (int32_t)N, E, (int32_t)length, seed64, W ? walks.data_ptr<int>() : nullptr, current_stream(nodePointer)),
+              "tcgnn_random_walk");
+  return walks;
+}
+
+// induce_subgraph: (nodePointer_b [M + 1], edgeList_b [E_b], eid [E_b]) - what the graph induces on the nodes of extend_nodes.  One synchronisation.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> induce_subgraph(torch::Tensor nodePointer, torch::Tensor edgeList, torch::Tensor nodes,
+                                                                        torch::Tensor new_id) {
+  check_csr_pair(nodePointer, edgeList);
+  check_ids(nodes, nodePointer.device(), "nodes"); check_ids(new_id, nodePointer.device(), "new_id");
+  const int64_t N = nodePointer.numel() - 1, E = edgeList.numel(), M = nodes.numel();
+  TORCH_CHECK(new_id.numel() == N, "new_id must hold one entry per node");
+  TORCH_CHECK(M <= N, "nodes holds more entries than the graph has nodes");
+  DeviceGuard guard(nodePointer.device());
+  void* stream = current_stream(nodePointer);
+  size_t need = 0;
+  tcgnn_check(tcgnn_induce_workspace_bytes((int32_t)M, &need), "tcgnn_induce_workspace_bytes");
+  torch::Tensor ws = torch::empty({(int64_t)need + 256}, nodePointer.options().dtype(torch::kUInt8));
+  char* wsp = static_cast<char*>(ws.data_ptr());
+  wsp += (256 - reinterpret_cast<uintptr_t>(wsp) % 256) % 256;
+  const int* col = E ? edgeList.data_ptr<int>() : nullptr;
+  const int* list = M ? nodes.data_ptr<int>() : nullptr;
+  const int* ids = N ? new_id.data_ptr<int>() : nullptr;
+  torch::Tensor rp_b = torch::empty({M + 1}, nodePointer.options());
+  int64_t kept = 0;
+  tcgnn_check(tcgnn_induce_count(nodePointer.data_ptr<int>(), col, list, ids, (int32_t)M, (int32_t)N, E, rp_b.data_ptr<int>(), wsp, need, &kept, stream),
+              "tcgnn_induce_count");
+  torch::Tensor col_b = torch::empty({kept}, edgeList.options()), eid = torch::empty({kept}, edgeList.options());
+  if (kept > 0)
+    tcgnn_check(tcgnn_induce(nodePointer.data_ptr<int>(), col, list, ids, rp_b.data_ptr<int>(), (int32_t)M, (int32_t)N, E, kept, col_b.data_ptr<int>(),
+                             eid.data_ptr<int>(), stream), "tcgnn_induce");
+  return {rp_b, col_b, eid};
+}
+
 // Not in the reference: the normalised GCN aggregation, Y = act(row_scale * (A @ (col_scale * X')) + bias) (tcgnn_spmm_scaled;
 // TCGNN.forward_scaled of the ctypes module).  Every optional tensor is fp32, contiguous and on input's device; the error names it.
 std::vector<torch::Tensor> spmm_forward_scaled(torch::Tensor input, torch::Tensor nodePointer, torch::Tensor edgeList,
@@ -1122,6 +1167,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("keep"), py::arg("ids"));
   m.def("compact_rows_graph", &compact_rows_graph, "the block of a sample_rows graph over the nodes of extend_nodes: (nodePointer_b, edgeList_b) "
         "(not in the reference)", py::arg("rows"), py::arg("rowPointer_s"), py::arg("edgeList_s"), py::arg("nodes"), py::arg("new_id"));
+  m.def("random_walk", &random_walk, "one seeded random walk per start, towards a row's sources: walks [W, length + 1] (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("starts"), py::arg("length"), py::arg("seed"));
+  m.def("induce_subgraph", &induce_subgraph, "the subgraph induced on the nodes of extend_nodes: (nodePointer_b, edgeList_b, eid) (not in the reference)",
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("nodes"), py::arg("new_id"));
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

@@ -38,7 +38,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
            "forward_ue", "backward_ue", "edge_sum", "sample_neighbors", "compact_nodes", "compact_graph",
-           "sample_rows", "extend_nodes", "compact_rows_graph"]
+           "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
 def _stream(device):
@@ -63,7 +63,7 @@ _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
           "softmax": (1, 256),        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
-          "sample": (1, 256),         # sample_neighbors' / sample_rows' row counts and scan scratch (the count call synchronises: nothing reads it afterwards)
+          "sample": (1, 256),         # sample_neighbors' / sample_rows' / induce_subgraph's row counts and scan scratch (the count call synchronises: nothing reads it afterwards)
           "compact": (1, 256)}        # compact_nodes' / extend_nodes' validation words and scan scratch (likewise: the count call synchronises)
 
 
@@ -443,6 +443,63 @@ def compact_rows_graph(rows, rowPointer_s, edgeList_s, nodes, new_id):
         _c.check(_c.lib.tcgnn_compact_rows_graph(_ptr(rows), R, rowPointer_s.data_ptr(), _ptr(edgeList_s), E, _ptr(new_id), N, M, rp_b.data_ptr(),
                                                  _ptr(col_b), _stream(dev)), "tcgnn_compact_rows_graph")
     return rp_b, col_b
+
+
+# ---------------------------------------------------------------- subgraph sampling: random walks and induced subgraphs
+
+def random_walk(nodePointer, edgeList, starts, length, seed):
+    """Not in the reference module: walks, int32 [W, length + 1] - one seeded random walk of `length` steps from every entry of starts
+    (int32 [W], ids may repeat: every occurrence walks on its own).  walks[w][0] = starts[w]; step t of walk w moves from v to
+    edgeList[nodePointer[v] + ((h32(seed, w * length + t) * degree(v)) >> 32)] - rows hold in-edges, so to one of v's SOURCES, the
+    direction neighbour sampling expands in.  A node without edges keeps the walk where it is (torch_cluster's rule); an id outside
+    [0, N) is carried through unfollowed.  A pure function of its arguments; seed is any int, taken modulo 2**64.  No synchronisation."""
+    _check_id_types((nodePointer, "nodePointer"), (edgeList, "edgeList"), (starts, "starts"))
+    if int(length) < 0:
+        raise ValueError("length must be >= 0, not %r" % (length,))
+    _check_csr_pair(nodePointer, edgeList)
+    dev = nodePointer.device
+    _check_ids(starts, "starts", dev)
+    N, E, W, length = nodePointer.numel() - 1, edgeList.numel(), starts.numel(), int(length)
+    with torch.cuda.device(dev):
+        walks = torch.empty((W, length + 1), dtype=torch.int32, device=dev)
+        _c.check(_c.lib.tcgnn_random_walk(nodePointer.data_ptr(), _ptr(edgeList), _ptr(starts), W, N, E, length, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          _ptr(walks), _stream(dev)), "tcgnn_random_walk")
+    return walks
+
+
+def induce_subgraph(nodePointer, edgeList, nodes, new_id):
+    """Not in the reference module: (nodePointer_b [M + 1], edgeList_b [E_b], eid [E_b]) - the subgraph the graph induces on the M nodes
+    of extend_nodes / compact_nodes (nodes strictly increasing, new_id of the same mask).  Row i keeps, in CSR order, the edges of row
+    nodes[i] whose column is in the set; edgeList_b = new_id[edgeList[e]], eid = e, the position in the FULL edgeList (edge values of
+    the block are val[eid.long()]).  A square CSR over M nodes in which every row is used: one block serves every layer.  The work
+    follows the edges of the listed rows; nodePointer is read, and validated, at the listed rows only.  One stream synchronisation (to
+    size the outputs).  With other nodes or another new_id the call is memory-safe and its result unspecified."""
+    named = ((nodePointer, "nodePointer"), (edgeList, "edgeList"), (nodes, "nodes"), (new_id, "new_id"))
+    _check_id_types(*named)
+    _check_csr_pair(nodePointer, edgeList)
+    dev = nodePointer.device
+    _check_ids(nodes, "nodes", dev)
+    _check_ids(new_id, "new_id", dev)
+    N, E, M = nodePointer.numel() - 1, edgeList.numel(), nodes.numel()
+    if new_id.numel() != N:
+        raise RuntimeError("new_id must hold one entry per node (%d), not %d" % (N, new_id.numel()))
+    if M > N:
+        raise RuntimeError("nodes holds %d entries, more than the graph's %d nodes" % (M, N))
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        need = _c._sz(0)
+        _c.check(_c.lib.tcgnn_induce_workspace_bytes(M, _c.ctypes.byref(need)), "tcgnn_induce_workspace_bytes")
+        ws, ws_bytes = _buffer("sample", need.value, dev, stream)
+        rp_b = torch.empty(M + 1, dtype=torch.int32, device=dev)
+        kept = _c._i64(0)
+        _c.check(_c.lib.tcgnn_induce_count(nodePointer.data_ptr(), _ptr(edgeList), _ptr(nodes), _ptr(new_id), M, N, E, rp_b.data_ptr(), ws, ws_bytes,
+                                           _c.ctypes.byref(kept), stream), "tcgnn_induce_count")
+        col_b = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        eid = torch.empty(kept.value, dtype=torch.int32, device=dev)
+        if kept.value:
+            _c.check(_c.lib.tcgnn_induce(nodePointer.data_ptr(), _ptr(edgeList), _ptr(nodes), _ptr(new_id), rp_b.data_ptr(), M, N, E, kept.value,
+                                         col_b.data_ptr(), eid.data_ptr(), stream), "tcgnn_induce")
+    return rp_b, col_b, eid
 
 
 def _transposed_plan(e):

@@ -60,6 +60,10 @@ SIGNATURES = {
     "tcgnn_sample_rows": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32, _i32, _i64, _i32, ctypes.c_uint64, _i32p, _i32p, _vp]),
     "tcgnn_compact_mark_ids": (ctypes.c_int, [_i32p, _i64, _i32, _vp, _vp, _sz, _vp]),
     "tcgnn_compact_rows_graph": (ctypes.c_int, [_i32p, _i32, _i32p, _i32p, _i64, _i32p, _i32, _i32, _i32p, _i32p, _vp]),
+    "tcgnn_random_walk": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i32, _i64, _i32, ctypes.c_uint64, _i32p, _vp]),
+    "tcgnn_induce_workspace_bytes": (ctypes.c_int, [_i32, ctypes.POINTER(_sz)]),
+    "tcgnn_induce_count": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32, _i32, _i64, _i32p, _vp, _sz, ctypes.POINTER(_i64), _vp]),
+    "tcgnn_induce": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, _i32, _i32, _i64, _i64, _i32p, _i32p, _vp]),
     "tcgnn_tile_stats":(ctypes.c_int, [_i32p, _i32p, _i32, _i32, _i32, ctypes.POINTER(TileStats), _i32]),
     "tcgnn_plan_create": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, _i32, _i64, _i32, _vp, ctypes.POINTER(_vp)]),
     "tcgnn_plan_create_sharded": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32p, _i32p, _i32, _i32, _i32, _i64, _i32, _vp, ctypes.POINTER(_vp)]),

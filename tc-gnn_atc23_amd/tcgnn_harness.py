@@ -66,9 +66,16 @@ def build_parser():
                    help="B: with --fanout, mini-batch training - every epoch cuts a seeded permutation of the nodes into batches of B seeds, samples each "
                    "batch's layer graphs, relabels them to the nodes they touch (tcgnn_layers.sample_batch) and takes one optimiser step per batch on the "
                    "seeds' loss; the final loss is evaluated on the full graph (not in the reference)")
-    p.add_argument("--sampler", type=str, default="dense", choices=["dense", "rows"],
+    p.add_argument("--sampler", type=str, default="dense", choices=["dense", "rows", "saint", "cluster"],
                    help="with --batch-size: 'dense' samples every hop over all rows of the graph behind a frontier mask; 'rows' samples from the list of "
-                   "frontier rows (tcgnn_layers.sample_batch_rows), so a step costs its batch - the same batches, bit for bit (not in the reference)")
+                   "frontier rows (tcgnn_layers.sample_batch_rows), so a step costs its batch - the same batches, bit for bit; 'saint' (GraphSAINT) trains "
+                   "on the subgraph induced on the nodes that one random walk from each of B roots visits, 'cluster' (Cluster-GCN) on the one induced on B "
+                   "consecutive node ids - both without --fanout, the loss over every node of the batch (not in the reference)")
+    p.add_argument("--walk-length", dest="walk_length", type=int, default=2,
+                   help="--sampler saint only: steps of every root's random walk (not in the reference)")
+    p.add_argument("--saint-norm", dest="saint_norm", type=int, default=0,
+                   help="S: --sampler saint / cluster only - weight every node's loss by GraphSAINT's node normalisation, estimated from S batches drawn "
+                   "before training (0: off; not in the reference)")
     return p
 
 
@@ -84,11 +91,19 @@ def parse_fanout(text, num_layers):
     return ks
 
 
-def parse_batch_size(batch_size, fanout, hip_graph=False):
+SUBGRAPH_SAMPLERS = ("saint", "cluster")
+
+
+def parse_batch_size(batch_size, fanout, hip_graph=False, sampler="dense"):
     """--batch-size's value checked against the flags it depends on (None: no mini-batches)"""
+    if sampler in SUBGRAPH_SAMPLERS:
+        if batch_size is None:
+            raise ValueError("--sampler %s trains on induced subgraphs of --batch-size roots or node ids and needs --batch-size" % sampler)
+        if fanout is not None:
+            raise ValueError("--sampler %s trains on the whole induced subgraph and takes no --fanout" % sampler)
     if batch_size is None:
         return None
-    if fanout is None:
+    if fanout is None and sampler not in SUBGRAPH_SAMPLERS:
         raise ValueError("--batch-size trains on sampled mini-batches and needs --fanout")
     if hip_graph:
         raise ValueError("--batch-size samples a new graph every step and can not be combined with --hip_graph, which replays one captured epoch")
@@ -99,11 +114,24 @@ def parse_batch_size(batch_size, fanout, hip_graph=False):
 
 def parse_sampler(sampler, batch_size):
     """--sampler's value checked against the flag it depends on"""
-    if sampler not in ("dense", "rows"):
-        raise ValueError("--sampler takes 'dense' or 'rows', got %r" % (sampler,))
+    if sampler not in ("dense", "rows") + SUBGRAPH_SAMPLERS:
+        raise ValueError("--sampler takes 'dense', 'rows', 'saint' or 'cluster', got %r" % (sampler,))
     if sampler == "rows" and batch_size is None:
         raise ValueError("--sampler rows samples a mini-batch from its list of rows and needs --batch-size")
+    if sampler in SUBGRAPH_SAMPLERS and batch_size is None:
+        raise ValueError("--sampler %s trains on induced subgraphs of --batch-size roots or node ids and needs --batch-size" % sampler)
     return sampler
+
+
+def parse_walk_length(walk_length):
+    """--walk-length's value"""
+    if int(walk_length) < 0:
+        raise ValueError("--walk-length takes a value >= 0, got %r" % (walk_length,))
+    return int(walk_length)
+
+
+# the seed stride of --saint-norm's dry batches: batch_seed's epoch argument, which no dry step (epoch = epochs) or timed epoch reaches
+SAINT_NORM_EPOCH = 1 << 40
 
 
 def epoch_order(num_nodes, seed, epoch):
@@ -191,7 +219,7 @@ def make_adam(params, lr=0.01):
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
                   norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None,
-                  batch_size=None, batch_hook=None, sampler="dense"):
+                  batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -223,14 +251,29 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     called before every timed step.  Refused together with hip_graph.
     sampler (not in the reference; needs batch_size for 'rows'): 'dense' is the step above; 'rows' draws the same batch through
     tcgnn_layers.sample_layers_rows and compact_layers_rows (the two halves of sample_batch_rows, timed apart as sample_ms and compact_ms):
-    the sampler runs over the batch's rows, not over all N.  The batches, and with them every loss, are bit-equal."""
+    the sampler runs over the batch's rows, not over all N.  The batches, and with them every loss, are bit-equal.
+    sampler 'saint' / 'cluster' (not in the reference; need batch_size, refuse fanout and hip_graph): subgraph sampling.  A batch is the
+    subgraph the full graph induces on a node set (tcgnn_layers.subgraph_batch: ONE square block that every layer runs on, built and
+    prepared once per batch), and the loss runs over ALL M rows of it, against y[batch.nodes].  'saint': every timed epoch cuts
+    epoch_order(N, seed, epoch) into batches of batch_size ROOTS; the node set is what one walk of walk_length steps from every root
+    visits (the backend's random_walk with batch_seed(seed, epoch, index)).  'cluster': the node ids are cut into ceil(N / batch_size)
+    ranges of batch_size consecutive ids - communities under --reorder or the sbm generators - and batch i of an epoch is range number
+    epoch_order(ceil(N / batch_size), seed, epoch)[i].  saint_norm = S > 0: S dry batches are drawn first, with batch_seed's epoch at
+    SAINT_NORM_EPOCH (a stride no epoch uses; for 'cluster', the first S ranges of that epoch's order), the nodes' appearances counted
+    with index_add_, and every node's NLL weighted by tcgnn_layers.saint_node_norm(counts, S) - summed, as PyG's example does, not
+    averaged.  The result holds the keys of the mini-batch path - sample_ms covers the walk (or the range), compact_ms extend_nodes,
+    induce_subgraph and the feature and label gathers - plus mean_block_edges.  batch_hook gets the epoch's order in place of the seeds."""
     import tcgnn_layers as L
-    batch_size = parse_batch_size(batch_size, fanout, hip_graph)
+    batch_size = parse_batch_size(batch_size, fanout, hip_graph, sampler=sampler)
     sampler = parse_sampler(sampler, batch_size)
+    subgraph = sampler in SUBGRAPH_SAMPLERS
+    walk_length = parse_walk_length(walk_length)
+    if int(saint_norm) < 0 or (int(saint_norm) and not subgraph):
+        raise ValueError("--saint-norm takes a value >= 0 and applies to --sampler saint / cluster only, got %r" % (saint_norm,))
     if fanout is not None and hip_graph:
         raise ValueError("--fanout samples a new graph every epoch and can not be combined with --hip_graph, which replays one captured epoch")
     fanout = parse_fanout(fanout, num_layers)
-    directed = bool(directed) or fanout is not None
+    directed = bool(directed) or fanout is not None or subgraph
     heads = int(heads)
     multi_head = model_name in ("gat", "gatv2", "transformer")
     if heads != 1 and not multi_head:
@@ -310,10 +353,93 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
                     {"transpose": True, "edge_valued": True, "attention": True} if attention == "softmax" else
                     ({"transpose": True, "edge_valued": model_name == "agnn"} if directed else {})))
 
-    if fanout is None:
+    if fanout is None and not subgraph:
         prepare(meta)
     if tune:   # the tall dense products of this model: library / layout / slab count measured once, here, not inside autograd
         L.tune(L.tune_layers(x.shape[0], [in_dim] + [hidden] * (num_layers - 1) + [classes]), device=x.device)
+    if subgraph:
+        full, n = meta, x.shape[0]
+        spent = {"sample_ms": 0.0, "compact_ms": 0.0, "plan_ms": 0.0, "train_ms": 0.0}
+        block_nodes, block_edges, loss = 0, 0, None
+        per_epoch = (n + batch_size - 1) // batch_size
+
+        def lap(key, since):
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            spent[key] += (now - since) * 1e3
+            return now
+
+        def draw(epoch, index, order):
+            """the node ids of batch `index` of an epoch whose order is `order` (roots for 'saint', range numbers for 'cluster')"""
+            if sampler == "saint":
+                roots = order[index * batch_size:(index + 1) * batch_size].to(torch.int32)
+                return L.backend().random_walk(full[0], full[1], roots, walk_length, batch_seed(seed, epoch, index)).reshape(-1)
+            lo = int(order[index]) * batch_size
+            return torch.arange(lo, min(lo + batch_size, n), dtype=torch.int32, device=x.device)
+
+        def orders(epoch):
+            order = epoch_order(n if sampler == "saint" else per_epoch, seed, epoch)
+            return order.to(x.device) if sampler == "saint" else order   # (range numbers are read on the host)
+
+        node_norm = None
+        if int(saint_norm):
+            counts = torch.zeros(n, dtype=torch.float32, device=x.device)
+            order = orders(SAINT_NORM_EPOCH)
+            for index in range(int(saint_norm)):
+                nodes = L.subgraph_batch(full, draw(SAINT_NORM_EPOCH, index % per_epoch, order), plan=False).nodes
+                counts.index_add_(0, nodes.long(), torch.ones(nodes.numel(), dtype=torch.float32, device=x.device))
+            node_norm = L.saint_node_norm(counts, int(saint_norm))
+
+        def step(epoch, index, order):
+            """one optimiser step on the induced subgraph of batch `index`; -> (loss, M, E_b)"""
+            t = time.perf_counter()
+            ids = draw(epoch, index, order)
+            t = lap("sample_ms", t)
+            batch = L.subgraph_batch(full, ids, plan=False, layers=num_layers)
+            at = batch.nodes.long()
+            xb, yb = x[at], y[at]
+            t = lap("compact_ms", t)
+            sampled_attr.clear()
+            m = batch.metas[0]
+            if not planless:
+                m = L.csr_meta(m[0], m[1])
+                batch.metas = [m] * num_layers   # (one tuple object: a layer's plan is looked up, not rebuilt)
+            prepare(m)
+            if model_name == "gine":
+                sampled_attr[m[1].data_ptr()] = edge_attr[batch.eids[0].long()]
+            t = lap("plan_ms", t)
+            model.train()
+            optimizer.zero_grad()
+            out = model(xb, batch.metas)
+            if node_norm is None:
+                loss = node_nll_loss(out, yb)
+            else:
+                loss = -(out.gather(1, yb.view(-1, 1)).view(-1) * node_norm[at]).sum()
+            loss.backward()
+            optimizer.step()
+            lap("train_ms", t)
+            return loss, batch.nodes.numel(), m[1].numel()
+
+        order = orders(epochs)   # the dry steps: an order no timed epoch uses
+        for index in range(min(warmup, per_epoch)):
+            loss, _, _ = step(epochs, index, order)
+        spent = dict.fromkeys(spent, 0.0)
+        for epoch in range(epochs):
+            order = orders(epoch)
+            for index in range(per_epoch):
+                if batch_hook is not None:
+                    batch_hook(epoch, index, order)
+                loss, m, e = step(epoch, index, order)
+                block_nodes += m
+                block_edges += e
+        model.eval()
+        with torch.no_grad():
+            final = float(node_nll_loss(model(x, full), y))
+        r = {k: v / max(epochs, 1) for k, v in spent.items()}
+        r.update(epoch_ms=sum(r.values()), final_loss=final, sampled_loss=float(loss.detach()) if loss is not None else float("nan"), fanout=None,
+                 batch_size=batch_size, batches=per_epoch, mean_block_nodes=block_nodes / max(per_epoch * epochs, 1),
+                 mean_block_edges=block_edges / max(per_epoch * epochs, 1), sampler=sampler, walk_length=walk_length, saint_norm=int(saint_norm))
+        return r
     if batch_size is not None:
         full, n = meta, x.shape[0]
         spent = {"sample_ms": 0.0, "compact_ms": 0.0, "plan_ms": 0.0, "train_ms": 0.0}
@@ -498,7 +624,7 @@ def run(args, quiet=False):
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
                       aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None),
                       batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None),
-                      sampler=getattr(args, "sampler", "dense"))
+                      sampler=getattr(args, "sampler", "dense"), walk_length=getattr(args, "walk_length", 2), saint_norm=getattr(args, "saint_norm", 0))
     if "sample_ms" in r:
         say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
     if "compact_ms" in r:

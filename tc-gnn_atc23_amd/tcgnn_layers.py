@@ -1095,3 +1095,41 @@ def sample_batch_rows(csr, seeds, fanouts, seed, plan=True):
     graphs and of the plan / CSR cache slots every batch takes holds here."""
     hops, nodes, new_id = sample_layers_rows(csr, seeds, fanouts, seed)
     return compact_layers_rows(hops, nodes, new_id, seeds, plan=plan)
+
+
+# ---------------------------------------------------------------- subgraph mini-batches: GraphSAINT walks and Cluster-GCN ranges
+
+def subgraph_batch(csr, ids, plan=True, layers=1):
+    """One mini-batch of subgraph sampling: the subgraph the graph induces on the node set `ids` (any order, ids may repeat), as a
+    CompactBatch.  A mask is cleared, the backend's extend_nodes(keep, ids) gives (nodes, new_id) and induce_subgraph the block: a square
+    CSR over the M distinct ids in which EVERY row is used - the loss runs over all M rows, against y[batch.nodes.long()] - and the one
+    graph serves every layer: metas is the same five-tensor tuple object `layers` times, so a layer's plan is built once per batch, and
+    eids the block's eid (positions in the full graph's edge list) as often.  seed_pos = new_id[ids], where every entry of ids sits in
+    the batch.  plan as in compact_layers.  Two stream synchronisations: one in extend_nodes (to size nodes), one in induce_subgraph
+    (to size the edge arrays).  What compact_layers says of directed graphs and of plan / CSR cache slots holds here."""
+    rp, col = csr[0], csr[1]
+    ids = ids.reshape(-1).to(torch.int32)
+    keep = torch.zeros(rp.numel() - 1, dtype=torch.uint8, device=rp.device)
+    nodes, new_id = backend().extend_nodes(keep, ids)
+    rp_b, col_b, eid = backend().induce_subgraph(rp, col, nodes, new_id)
+    if plan:
+        meta = csr_meta(rp_b, col_b)
+    else:
+        meta = (rp_b, col_b) + tuple(torch.empty(0, dtype=torch.int32, device=rp_b.device) for _ in range(3))
+    return CompactBatch(nodes, new_id[ids.long()].long(), [meta] * int(layers), [eid] * int(layers), new_id)
+
+
+def saint_batch(csr, roots, walk_length, seed, plan=True, layers=1):
+    """GraphSAINT's random-walk sampler: one walk of walk_length steps from every root (the backend's random_walk: towards a row's
+    sources, a pure function of the graph, roots, walk_length and seed), then subgraph_batch of every node the walks visited.  seed_pos
+    has one entry per walk entry, [len(roots) * (walk_length + 1)], roots' at stride walk_length + 1.  Two stream synchronisations."""
+    walks = backend().random_walk(csr[0], csr[1], roots.to(torch.int32), walk_length, seed)
+    return subgraph_batch(csr, walks.reshape(-1), plan=plan, layers=layers)
+
+
+def saint_node_norm(counts, num_samples):
+    """GraphSAINT's loss normalisation as PyG's GraphSAINTSampler computes it: for counts [N] (how often each node appeared in
+    num_samples sampled subgraphs), num_samples / max(counts, 0.1) / N, float32 - the weight of a node's loss term.  Pure torch.  The
+    aggregator (edge) normalisation of GraphSAINT is not built."""
+    c = counts.to(torch.float32).clamp_min(0.1)
+    return float(num_samples) / c / float(counts.numel())
