@@ -22,6 +22,7 @@ import numpy as np
 OWN_SUM = 2.0 ** -40
 SETS = ("integer", "normal", "large", "boundary")
 ACTS = {None: 0, "identity": 0, "relu": 1}
+TOL_Y, TOL_G = 1e-5, 1e-4   # the operator and GINEConv against dense fp64, of the largest entry (tests/test_gpu_edge_message.py says why)
 
 
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------

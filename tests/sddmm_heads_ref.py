@@ -3,6 +3,7 @@ multi-head SDDMM (tcgnn_sddmm_heads / TCGNN.forward_ef_heads), ef[h, e] = <X[row
 goes head by head through edge_ops_ref.sddmm2_tf32 and sddmm2_f64, stacked to [H, E]; test_gpu_parity.assert_parity judges against it
 with the project's three bounds, unchanged.  (Its 10-bit operand rounding is scale-free, so one power-of-two scale per operand
 instead of one per head does not move it.)  No GPU needed to import."""
+import math
 import zlib
 
 import numpy as np
@@ -129,3 +130,30 @@ def fp32_way(rp, col, X, Z, H):
             off >>= 1
         out[h] = lanes[:, 0]
     return out
+
+
+# ---- the dense fp64 model of TransformerConv ---------------------------------------------------------------------------------------------
+
+def dense_transformer_model(A, X, layer, heads):
+    """TransformerConv on a dense 0/1 adjacency matrix A [n, n] (rows = destination nodes) in torch, differentiable in X and in the
+    layer's parameters: per head softmax over each row's edges of Q_h K_h^T / sqrt(F), Y_h = P_h V_h, heads concatenated or averaged,
+    the root term and the bias added.  Rows without edges give root term and bias only."""
+    import torch
+
+    def lin(W, b):
+        Y = X @ W
+        return Y + b if b is not None else Y
+    Q, K, V = lin(layer.weights_q, layer.bias_q), lin(layer.weights_k, layer.bias_k), lin(layer.weights_v, layer.bias_v)
+    F = Q.shape[1] // heads
+    none = A.sum(1, keepdim=True) == 0
+    outs = []
+    for h in range(heads):
+        c = slice(h * F, (h + 1) * F)
+        S = (Q[:, c] @ K[:, c].t()) / math.sqrt(F)
+        S = S.masked_fill(A == 0, float("-inf")).masked_fill(none, 0.0)
+        P = torch.where(A != 0, torch.softmax(S, dim=1), torch.zeros_like(S))
+        outs.append(P @ V[:, c])
+    Y = torch.cat(outs, dim=1) if layer.concat else torch.stack(outs, dim=1).mean(1)
+    if layer.weights_root is not None:
+        Y = Y + X @ layer.weights_root
+    return Y + layer.bias if layer.bias is not None else Y

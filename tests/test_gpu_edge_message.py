@@ -452,7 +452,7 @@ def _layer_graph(name):
 # largest entry is of the order of that sum).  An output is a chain of two or three such steps, a gradient of up to five, and the
 # longest row multiplies a gradient's terms by a few hundred: 1e-5 of the largest entry for an output, 1e-4 for a gradient - the bounds
 # of the max aggregation's layer tests (tests/test_gpu_segmax.py), which rest on the same arithmetic.
-TOL_Y, TOL_G = 1e-5, 1e-4
+TOL_Y, TOL_G = R.TOL_Y, R.TOL_G
 
 
 @pytest.mark.parametrize("name", ["layers_n200", "powerlaw_n3000_directed"])

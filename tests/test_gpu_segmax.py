@@ -488,7 +488,7 @@ def test_sage_layer_against_the_dense_fp64_model_on_a_directed_graph(dev, T, agg
     Xg = X.to(dev).requires_grad_(True)
     Y = conv(Xg, *meta)
     want = S.dense_sage(A, leaves[0], leaves[1], leaves[2], leaves[3], aggregator, *leaves[4:])
-    tol_y, tol_g = (2e-3, 2e-3) if aggregator == "mean" else (1e-5, 1e-4)
+    tol_y, tol_g = S.SAGE_TOL[aggregator]
     got = torch.autograd.grad((Y * dY.float().to(dev)).sum(), [Xg] + params)
     ref = torch.autograd.grad((want * dY).sum(), leaves)
     figs = [("Y", _rel(Y, want), tol_y)] + [(w, _rel(g, r), tol_g) for g, r, w in zip(got, ref, ("dX", "dW_self", "dW_neigh", "dbias", "dW_pool", "dbias_pool"))]

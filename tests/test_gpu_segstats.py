@@ -487,7 +487,7 @@ def test_pna_layer_against_the_dense_fp64_model_on_a_directed_graph(dev, T, dims
     want = R.dense_pna(A, *leaves)
     got = torch.autograd.grad((Y * dY.float().to(dev)).sum(), [Xg] + params)
     ref = torch.autograd.grad((want * dY).sum(), leaves)
-    figs = [("Y", M._rel(Y, want), 1e-5)] + [(w, M._rel(g, r), 1e-4) for g, r, w in zip(got, ref, ["dX"] + ["d" + k for k in names])]
+    figs = [("Y", M._rel(Y, want), R.LAYER_TOL_Y)] + [(w, M._rel(g, r), R.LAYER_TOL_G) for g, r, w in zip(got, ref, ["dX"] + ["d" + k for k in names])]
     for w, f, t in figs:
         print("FIG pna %-9s %-13s %.3e of the largest entry (bound %.0e)" % ("%d->%d" % dims, w, f, t))
     assert all(f <= t for _, f, t in figs), figs

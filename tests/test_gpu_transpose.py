@@ -14,6 +14,7 @@ import scipy.sparse as sp
 import torch
 
 import graphs
+from minibatch_ref import AGNN_DW_TOL, DIRECTED_GRAD_TOL, GCN_DX_NORM_TOL
 from oracle import oracle as O
 from test_gpu_parity import CASES, ROOT, _sampled_oracle_checks, assert_parity, meta_for, to_dev
 
@@ -341,7 +342,7 @@ def test_directed_normalised_gcn_matches_the_dgl_port(dev, T):
     for i, (conv, layer) in enumerate(zip(convs, cpu.layers)):
         errs["layer %d weight grad" % i] = _rel_err(conv.weights.grad, layer.weight.grad)
         errs["layer %d bias grad" % i] = _rel_err(conv.bias.grad, layer.bias.grad)
-    bounds = {"input grad vs fp64": 3e-3, "input grad vs port": 5e-2}
+    bounds = {"input grad vs fp64": GCN_DX_NORM_TOL, "input grad vs port": 5e-2}
     for k, e in errs.items():
         if k.startswith("undirected"):
             assert e > 0.2, errs
@@ -391,7 +392,7 @@ def test_directed_sag_gin_agnn_match_a_dense_fp64_evaluation(dev, T):
         (dense_out * dy).sum().backward()
         for pg, pd in zip(params_g, params_d):
             scale = pd.grad.abs().max().item()
-            assert ((pg.grad.detach().cpu().double() - pd.grad).abs().max().item()) <= 5e-3 * max(1.0, scale)   # (10-bit operands)
+            assert ((pg.grad.detach().cpu().double() - pd.grad).abs().max().item()) <= DIRECTED_GRAD_TOL * max(1.0, scale)   # (10-bit operands)
 
     xg, xd = x.float().to(dev).requires_grad_(True), x.clone().requires_grad_(True)
     sag = L.SAG(*meta, directed=True)
@@ -420,7 +421,7 @@ def test_directed_sag_gin_agnn_match_a_dense_fp64_evaluation(dev, T):
     dyh = dy
     d_w = ((dyh[rows] * dyh[colt]).sum(1) * colt.double()).sum().item()
     bound = ((dyh[rows] * dyh[colt]).sum(1).abs() * colt.double()).sum().item()
-    assert abs(float(agnn.attention_w.grad) - d_w) <= 2e-3 * bound
+    assert abs(float(agnn.attention_w.grad) - d_w) <= AGNN_DW_TOL * bound
     T.clear_plan_cache()
 
 

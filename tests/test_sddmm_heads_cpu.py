@@ -15,6 +15,7 @@ import gat_ref as G
 import graphs
 import sddmm_heads_ref as HR
 import walks
+from sddmm_heads_ref import dense_transformer_model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = {"tcgnn_sddmm_heads_workspace_bytes": 3, "tcgnn_sddmm_heads": 9}
@@ -208,31 +209,6 @@ def test_a_backend_without_the_call_gets_the_per_head_definition(backend):
     assert float((dP - want).abs().max()) <= 1e-12 * float(want.abs().max())
     import TCGNN
     assert "forward_ef_heads" in vars(TCGNN)          # (the product's own module never takes the fallback: it has the name)
-
-
-def dense_transformer_model(A, X, layer, heads):
-    """TransformerConv on a dense 0/1 adjacency matrix A [n, n] (rows = destination nodes) in torch, differentiable in X and in the
-    layer's parameters: per head softmax over each row's edges of Q_h K_h^T / sqrt(F), Y_h = P_h V_h, heads concatenated or averaged,
-    the root term and the bias added.  Rows without edges give root term and bias only."""
-    n = A.shape[0]
-
-    def lin(W, b):
-        Y = X @ W
-        return Y + b if b is not None else Y
-    Q, K, V = lin(layer.weights_q, layer.bias_q), lin(layer.weights_k, layer.bias_k), lin(layer.weights_v, layer.bias_v)
-    F = Q.shape[1] // heads
-    none = A.sum(1, keepdim=True) == 0
-    outs = []
-    for h in range(heads):
-        c = slice(h * F, (h + 1) * F)
-        S = (Q[:, c] @ K[:, c].t()) / math.sqrt(F)
-        S = S.masked_fill(A == 0, float("-inf")).masked_fill(none, 0.0)
-        P = torch.where(A != 0, torch.softmax(S, dim=1), torch.zeros_like(S))
-        outs.append(P @ V[:, c])
-    Y = torch.cat(outs, dim=1) if layer.concat else torch.stack(outs, dim=1).mean(1)
-    if layer.weights_root is not None:
-        Y = Y + X @ layer.weights_root
-    return Y + layer.bias if layer.bias is not None else Y
 
 
 def _close(got, want, what, tol=1e-9, floor=0.0):
