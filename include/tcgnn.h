@@ -792,6 +792,44 @@ int tcgnn_edge_message_backward(const int32_t* d_nodePointer, const int32_t* d_e
 int tcgnn_edge_sum(const int32_t* d_nodePointer, const int32_t* d_perm /* may be NULL */, int32_t num_nodes, int64_t num_edges,
                    const float* d_M, int32_t D, float* d_Y, void* stream);
 
+/* ---- the same message with the edge projection fused in (PyG's GINEConv with edge_dim; no counterpart in the reference) ----
+ *
+ * The per-edge operand is A = edge_attr, fp32 [num_edges, K] row-major in CSR position order, with We fp32 [K, D] and be fp32 [D]:
+ *   p[e, d] = be[d] + sum_k A[e, k] We[k, d]   fp32 on the matrix pipe (v_mfma_f32_16x16x4_f32) in a fixed order, the bias as one more
+ *                                              term of the product;   z = fl32(X[col(e), d] + p[e, d]);  m = act(z)
+ *   tcgnn_edge_project_message      Y[i, d] = fl32(sum over e in row i of (double)m), an fp64 sum in a fixed order; an empty row: 0.
+ *   tcgnn_edge_project_backward     with g[e, d] = dY[row(e), d] where act is the identity or !(z <= 0) (tcgnn_edge_message_backward's
+ *                                   rule), else 0:  dA[e, k] = sum_d g[e, d] We[k, d] (fp32);  dWe[k, d] = sum_e A[e, k] g[e, d] and
+ *                                   dbe[d] = sum_e g[e, d]: fp32 sums per wavefront, the workgroups' partials ([K + 1, D] fp32 each, in
+ *                                   d_scratch) added in fp64 in workgroup order and rounded once.  d_scratch: at least
+ *                                   tcgnn_edge_project_workspace_bytes(num_nodes, K, D) bytes (under 64 MB up to D = 256), 4-byte
+ *                                   aligned, else TCGNN_ERR_WORKSPACE; its contents mean nothing afterwards.  A position in front of
+ *                                   nodePointer[0] or behind nodePointer[num_nodes] belongs to no row: its row of dA is zeroed.
+ *   tcgnn_edge_project_source_grad  dX[j, d] = fl32(sum over the positions t of row j of A^T of (double)g[perm[t], d]) with z recomputed
+ *                                   as X[j, d] + p[perm[t], d] and dY's row col_t[t]; d_nodePointer_t, d_edgeList_t and d_perm of
+ *                                   tcgnn_transpose_ws.  A node nobody reads gets 0.
+ * p and the pass mask are recomputed wherever they are needed: NO array of [num_edges, D] is read, written or allocated.  1 <= K <= 63;
+ * any D >= 1.  Planless: device pointers, the caller's stream, no allocation, no synchronisation (capturable in a HIP graph); no
+ * atomics and every order fixed: bit-identical on repetition.  [., D] rows go by 16-byte accesses when D % 4 == 0 and X, dY and the
+ * [num_nodes, D] output are 16-byte aligned, A and dA when K % 4 == 0 and both are aligned, by 4-byte accesses otherwise: the same
+ * bits either way.  Row pointers, column ids and perm entries are clamped as for tcgnn_edge_message.  Every element of Y / dA / dWe /
+ * dbe / dX is written and nothing outside them.  A size of 0 returns TCGNN_OK with the outputs, where they have elements, zeroed; a
+ * negative size, num_edges >= 2^31, K outside [1, 63], an unknown act or a null array otherwise: TCGNN_ERR_INVALID_ARG before
+ * anything is written.  A hub row stays on one workgroup; a row shorter than 16 edges fills part of a tile (no tile is shared
+ * between rows). */
+size_t tcgnn_edge_project_workspace_bytes(int32_t num_nodes, int32_t K, int32_t D);
+int tcgnn_edge_project_message(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                               const float* d_X, const float* d_A, const float* d_We, const float* d_be, int32_t K, int32_t D,
+                               int32_t act, float* d_Y, void* stream);
+int tcgnn_edge_project_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                                const float* d_X, const float* d_A, const float* d_We, const float* d_be, const float* d_dY,
+                                int32_t K, int32_t D, int32_t act, float* d_dA, float* d_dWe, float* d_dbe, void* d_scratch,
+                                size_t scratch_bytes, void* stream);
+int tcgnn_edge_project_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm,
+                                   int32_t num_nodes, int64_t num_edges, const float* d_X, const float* d_A, const float* d_We,
+                                   const float* d_be, const float* d_dY, int32_t K, int32_t D, int32_t act, float* d_dX,
+                                   void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

@@ -775,6 +775,77 @@ torch::Tensor edge_sum(torch::Tensor M, torch::Tensor nodePointer, c10::optional
   return Y;
 }
 
+// ---- not in the reference: forward_ue with the edge projection edge_attr We + be fused in (tcgnn_edge_project_*; the ctypes module's
+// forward_uep, backward_uep and source_grad_uep) --------------------------------------------------------------------------------------
+namespace {
+std::tuple<int32_t, int64_t, int32_t, int32_t> uep_args(const torch::Tensor& X, const torch::Tensor& edge_attr, const torch::Tensor& We,
+                                                        const torch::Tensor& be, const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  auto [N, E, D] = max_args(X, "X", nodePointer, edgeList);
+  TORCH_CHECK(edge_attr.dim() == 2, "edge_attr must be [num_edges, K]");
+  const int64_t K = edge_attr.size(1);
+  check_edge_rows(edge_attr, "edge_attr", E, K, nodePointer);
+  if (K < 1 || K > 63) throw py::value_error("edge_attr must be 1 to 63 wide, got " + std::to_string(K));
+  CHECK_INPUT(We); CHECK_INPUT(be);
+  TORCH_CHECK(We.scalar_type() == torch::kFloat32 && be.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(We.dim() == 2 && We.size(0) == K && We.size(1) == D && We.device() == X.device(), "We must be a contiguous fp32 [K, D] tensor on X's device");
+  TORCH_CHECK(be.dim() == 1 && be.size(0) == D && be.device() == X.device(), "be must be a contiguous fp32 [D] tensor on X's device");
+  return {N, E, D, (int32_t)K};
+}
+void uep_dy(const torch::Tensor& dY, const torch::Tensor& X) {
+  CHECK_INPUT(dY);
+  TORCH_CHECK(dY.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(dY.sizes() == X.sizes() && dY.device() == X.device(), "dY must have the shape and device of X");
+}
+}  // namespace
+
+torch::Tensor forward_uep(torch::Tensor X, torch::Tensor edge_attr, torch::Tensor We, torch::Tensor be, torch::Tensor nodePointer, torch::Tensor edgeList,
+                          c10::optional<std::string> act, c10::optional<torch::Tensor> out) {
+  auto [N, E, D, K] = uep_args(X, edge_attr, We, be, nodePointer, edgeList);
+  const int code = ue_act(act);
+  torch::Tensor Y = out_like(out, X, "X");
+  check_out_apart(out, {&X, &edge_attr, &We, &be});
+  DeviceGuard guard(X.device());
+  tcgnn_check(tcgnn_edge_project_message(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, X.data_ptr<float>(), edge_attr.data_ptr<float>(),
+                                         We.data_ptr<float>(), be.data_ptr<float>(), K, D, code, Y.data_ptr<float>(), current_stream(X)),
+              "tcgnn_edge_project_message");
+  return Y;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> backward_uep(torch::Tensor dY, torch::Tensor X, torch::Tensor edge_attr, torch::Tensor We,
+                                                                     torch::Tensor be, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                                     c10::optional<std::string> act) {
+  auto [N, E, D, K] = uep_args(X, edge_attr, We, be, nodePointer, edgeList);
+  uep_dy(dY, X);
+  const int code = ue_act(act);
+  DeviceGuard guard(X.device());
+  torch::Tensor dA = torch::empty({E, (int64_t)K}, X.options()), dWe = torch::empty({(int64_t)K, (int64_t)D}, X.options()),
+                dbe = torch::empty({(int64_t)D}, X.options());
+  void* scratch = nullptr;
+  const size_t need = tcgnn_edge_project_workspace_bytes(N, K, D);
+  torch::Tensor buf = aligned_scratch(need, X, &scratch);
+  tcgnn_check(tcgnn_edge_project_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, X.data_ptr<float>(), edge_attr.data_ptr<float>(),
+                                          We.data_ptr<float>(), be.data_ptr<float>(), dY.data_ptr<float>(), K, D, code, dA.data_ptr<float>(),
+                                          dWe.data_ptr<float>(), dbe.data_ptr<float>(), scratch, need, current_stream(X)),
+              "tcgnn_edge_project_backward");
+  return {dA, dWe, dbe};
+}
+
+torch::Tensor source_grad_uep(torch::Tensor dY, torch::Tensor X, torch::Tensor edge_attr, torch::Tensor We, torch::Tensor be, torch::Tensor nodePointer,
+                              torch::Tensor edgeList, c10::optional<std::string> act, c10::optional<torch::Tensor> out) {
+  auto [N, E, D, K] = uep_args(X, edge_attr, We, be, nodePointer, edgeList);
+  uep_dy(dY, X);
+  const int code = ue_act(act);
+  torch::Tensor dX = out_like(out, X, "X");
+  check_out_apart(out, {&dY, &X, &edge_attr, &We, &be});
+  DeviceGuard guard(X.device());
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_edge_project_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E, X.data_ptr<float>(),
+                                             edge_attr.data_ptr<float>(), We.data_ptr<float>(), be.data_ptr<float>(), dY.data_ptr<float>(), K, D, code,
+                                             dX.data_ptr<float>(), current_stream(X)),
+              "tcgnn_edge_project_source_grad");
+  return dX;
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
   CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
@@ -1171,6 +1242,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("starts"), py::arg("length"), py::arg("seed"));
   m.def("induce_subgraph", &induce_subgraph, "the subgraph induced on the nodes of extend_nodes: (nodePointer_b, edgeList_b, eid) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"), py::arg("nodes"), py::arg("new_id"));
+  m.def("forward_uep", &forward_uep, "forward_ue with the edge projection edge_attr We + be fused into the walk, edge_attr [E, K] (not in the reference)",
+        py::arg("X"), py::arg("edge_attr"), py::arg("We"), py::arg("be"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu",
+        py::arg("out") = py::none());
+  m.def("backward_uep", &backward_uep, "row side of forward_uep's backward: (dA, dWe, dbe) (not in the reference)", py::arg("dY"), py::arg("X"),
+        py::arg("edge_attr"), py::arg("We"), py::arg("be"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu");
+  m.def("source_grad_uep", &source_grad_uep, "source side of forward_uep's backward: dX (not in the reference)", py::arg("dY"), py::arg("X"),
+        py::arg("edge_attr"), py::arg("We"), py::arg("be"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu",
+        py::arg("out") = py::none());
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

@@ -37,7 +37,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum", "sample_neighbors", "compact_nodes", "compact_graph",
+           "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "sample_neighbors", "compact_nodes", "compact_graph",
            "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
@@ -63,6 +63,7 @@ _buffers = {}
 _KINDS = {"workspace": (1.25, 256),   # what the plan-based calls stage into (and leave the range guard's header in)
           "values": (1, 0),           # fp32 [max(H E, 1)]: A's edge values in A^T's order, forward_AGNN / forward_heads(transpose=True)
           "softmax": (1, 256),        # the fp64 partials of edge_softmax_backward's d_beta and of gatv2_softmax_backward's d_attn
+          "project": (1, 256),        # the workgroups' fp32 partials of backward_uep's dWe / dbe
           "sample": (1, 256),         # sample_neighbors' / sample_rows' / induce_subgraph's row counts and scan scratch (the count call synchronises: nothing reads it afterwards)
           "compact": (1, 256)}        # compact_nodes' / extend_nodes' validation words and scan scratch (likewise: the count call synchronises)
 
@@ -551,7 +552,7 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
 
 
 def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1,
-            max_aggregation=False):
+            max_aggregation=False, edge_project=None):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
@@ -569,9 +570,15 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     `widths` (more than a width the model aggregates with one head needs) on both plans and the [H, E] buffer forward_heads(transpose=True) permutes the values into, on the current stream.
     max_aggregation=True (a model with forward_max / backward_max: SAGEConv's max and pool aggregators - or with forward_stats /
     backward_stats: PNAConv): the transposed CSR backward_max and backward_stats walk, built now (transpose_graph: the graph's one
-    transpose) - the calls are planless and need nothing else."""
-    if max_aggregation:
+    transpose) - the calls are planless and need nothing else.
+    edge_project=K (a model with GINEConv(fuse_edge=True) layers of edge_dim K: forward_uep / backward_uep / source_grad_uep): the
+    transposed CSR source_grad_uep walks and the scratch of backward_uep's dWe / dbe partials at every width, on the current stream."""
+    if max_aggregation or edge_project is not None:
         transpose_graph(nodePointer, edgeList)
+    if edge_project is not None:
+        with torch.cuda.device(nodePointer.device):
+            for d in {int(w) for w in widths if int(w) >= 1}:
+                _buffer("project", _c.lib.tcgnn_edge_project_workspace_bytes(max(nodePointer.numel() - 1, 0), int(edge_project), d), nodePointer.device)
     e = _plan_entry((nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow))
     plans = [e.handle]
     dev = nodePointer.device
@@ -1479,6 +1486,80 @@ def edge_sum(M, nodePointer, perm=None, out=None):
         res = out
     _out_apart(res, out, M)
     _call(_c.lib.tcgnn_edge_sum, M.device, nodePointer.data_ptr(), _ptr(perm), N, E, M.data_ptr(), D, res.data_ptr())
+    return res
+
+
+# ---- additions (not in the reference module): forward_ue with the edge projection edge_attr We + be fused in (GINEConv, edge_dim) ----
+
+def _uep_args(X, edge_attr, We, be, nodePointer, edgeList):
+    N, E, D = _max_args(X, "X", nodePointer, edgeList)
+    _edge_rows(edge_attr, "edge_attr", E, None, nodePointer)
+    K = edge_attr.size(1)
+    if not 1 <= K <= 63:
+        raise ValueError("edge_attr must be 1 to 63 wide, got %d" % K)
+    for t, n, shape in ((We, "We", (K, D)), (be, "be", (D,))):
+        _check_input(t, n)
+        _check_float(t, n)
+        if tuple(t.shape) != shape or t.device != X.device:
+            raise RuntimeError("%s must be a contiguous fp32 %s tensor on X's device, got %s" % (n, list(shape), tuple(t.shape)))
+    return N, E, D, K
+
+
+def _uep_dy(dY, X):
+    _check_input(dY, "dY")
+    _check_float(dY, "dY")
+    if dY.shape != X.shape or dY.device != X.device:
+        raise RuntimeError("dY must have the shape and device of X")
+
+
+def forward_uep(X, edge_attr, We, be, nodePointer, edgeList, act="relu", out=None):
+    """Not in the reference module: forward_ue with the edge projection fused into the walk (tcgnn_edge_project_message),
+        Y[i, d] = the sum over the edges e of row i of act(X[col(e), d] + (edge_attr[e] @ We + be)[d]),   act: 'relu', or 'identity' / None.
+    X: fp32 [N, D]; edge_attr: fp32 [E, K] in CSR position order, 1 <= K <= 63; We: fp32 [K, D]; be: fp32 [D].  The projection is an
+    fp32 matrix-pipe product per tile of 16 edges (the bias one more term of it), the message fp32, the sum fp64 in a fixed order,
+    rounded once; no [E, D] tensor exists.  A row without edges gives 0.  Deterministic, no atomics."""
+    N, E, D, K = _uep_args(X, edge_attr, We, be, nodePointer, edgeList)
+    code = _ue_act(act)
+    res = _out_like(out, X, "X")
+    _out_apart(res, out, X, edge_attr, We, be)
+    _call(_c.lib.tcgnn_edge_project_message, X.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, X.data_ptr(), edge_attr.data_ptr(), We.data_ptr(),
+          be.data_ptr(), K, D, code, res.data_ptr())
+    return res
+
+
+def backward_uep(dY, X, edge_attr, We, be, nodePointer, edgeList, act="relu"):
+    """Not in the reference module: the row side of forward_uep's backward (tcgnn_edge_project_backward), (dA, dWe, dbe) with
+        g[e, d] = dY[row(e), d] where act is the identity or X[col(e), d] + p[e, d] is positive or a NaN, else 0   (p recomputed)
+        dA = g @ We^T  (fp32 [E, K]: the gradient of edge_attr),   dWe = edge_attr^T @ g  (fp32 [K, D]),   dbe = column sums of g  (fp32 [D])
+    from ONE walk: no [E, D] tensor exists.  dWe / dbe: fp32 sums per wavefront, the workgroups' partials added in fp64 in a fixed
+    order.  The partials live in the stream's buffer pool (prepare(..., edge_project=K) sizes it ahead).  Deterministic, no atomics."""
+    N, E, D, K = _uep_args(X, edge_attr, We, be, nodePointer, edgeList)
+    _uep_dy(dY, X)
+    code = _ue_act(act)
+    dev = X.device
+    d_a = torch.empty(E, K, dtype=torch.float32, device=dev)
+    d_we = torch.empty(K, D, dtype=torch.float32, device=dev)
+    d_be = torch.empty(D, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        scratch = _buffer("project", _c.lib.tcgnn_edge_project_workspace_bytes(N, K, D), dev)
+    _call(_c.lib.tcgnn_edge_project_backward, dev, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, X.data_ptr(), edge_attr.data_ptr(), We.data_ptr(),
+          be.data_ptr(), dY.data_ptr(), K, D, code, d_a.data_ptr(), d_we.data_ptr(), d_be.data_ptr(), *scratch)
+    return d_a, d_we, d_be
+
+
+def source_grad_uep(dY, X, edge_attr, We, be, nodePointer, edgeList, act="relu", out=None):
+    """Not in the reference module: the source side of forward_uep's backward (tcgnn_edge_project_source_grad), fp32 [N, D],
+        dX[j, d] = the sum over the edges e with col(e) = j of g[e, d]   (g as in backward_uep, recomputed - no [E, D] tensor),
+    a walk over the rows of A^T in a fixed order (fp64 sums, no atomics); a node nobody reads gets 0.  The transposed CSR is the
+    module's cached one (transpose_graph): built at the first call for a graph, or by prepare(..., edge_project=K)."""
+    N, E, D, K = _uep_args(X, edge_attr, We, be, nodePointer, edgeList)
+    _uep_dy(dY, X)
+    code = _ue_act(act)
+    res = _out_like(out, X, "X")
+    _out_apart(res, out, dY, X, edge_attr, We, be)
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_edge_project_source_grad, X.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, X.data_ptr(), edge_attr.data_ptr(),
+          We.data_ptr(), be.data_ptr(), dY.data_ptr(), K, D, code, res.data_ptr())
     return res
 
 

@@ -15,6 +15,7 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate_max(X, rowptr, col) Y[i, d] = max over row i of X[col e, d] (0 for an empty row)     bwd: dX[j, d] = sum of dY[i, d] over the edges that won (i, d)
     aggregate_stats(Z, rowptr, col, aggregators)  mean / std / max / min over row i of Z[col e, d], one gather for all (PNA)     bwd: one walk over A^T for all of them
     aggregate_ue(X, Ef, rowptr, col, act)  Y[i, d] = sum over row i of act(X[col e, d] + Ef[e, d]), Ef [E, D] (u_add_e; GINE)   bwd: dM = dY[row e] masked, once; dEf = dM, dX = sum of dM by source over A^T
+    aggregate_uep(X, A, We, be, rowptr, col, act)  aggregate_ue with Ef = A We + be formed inside the walk, A [E, K] (GINE with edge_dim)   bwd: (dA, dWe, dbe) from one walk by row, dX from one over A^T; no [E, D] tensor either way
     edge_sum(M, rowptr, col)      Y[i, d] = sum over row i of M[e, d], M [E, D] (copy_e)                        bwd: dM[e] = dY[row e]
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
@@ -22,7 +23,7 @@ edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, als
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum, forward_uep, backward_uep, source_grad_uep (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -319,6 +320,46 @@ def aggregate_ue(X, Ef, row_pointers, column_index, act="relu"):
     if X.dim() != 2 or Ef.dim() != 2 or Ef.shape[0] != column_index.numel() or Ef.shape[1] != X.shape[1]:
         raise RuntimeError("X must be [N, D] and Ef [E, D] = [%d, %d], got %s and %s" % (column_index.numel(), X.shape[-1], tuple(X.shape), tuple(Ef.shape)))
     return _AggregateUE.apply(X, Ef, row_pointers, column_index, "relu" if act == "relu" else "identity")
+
+
+class _AggregateUEP(torch.autograd.Function):
+    """Y = forward_uep(X, A, We, be); backward: (dA, dWe, dbe) = backward_uep(dY), ONE walk by row, and dX = source_grad_uep(dY), one walk
+    over A^T (the backend's cached transpose_graph) where X needs a gradient.  Saved: the four operands - the projection and the mask are
+    recomputed from them."""
+
+    @staticmethod
+    def forward(ctx, X, A, We, be, row_pointers, column_index, act):
+        X, A, We, be = X.contiguous(), A.contiguous(), We.contiguous(), be.contiguous()
+        ctx.graph, ctx.act = (row_pointers, column_index), act
+        ctx.save_for_backward(X, A, We, be)
+        return _L.backend().forward_uep(X, A, We, be, row_pointers, column_index, act=act)
+
+    @staticmethod
+    def backward(ctx, d_y):
+        X, A, We, be = ctx.saved_tensors
+        b = _L.backend()
+        d_y = d_y.contiguous()
+        d_a = d_we = d_be = d_x = None
+        if any(ctx.needs_input_grad[1:4]):
+            d_a, d_we, d_be = b.backward_uep(d_y, X, A, We, be, *ctx.graph, act=ctx.act)
+        if ctx.needs_input_grad[0]:
+            d_x = b.source_grad_uep(d_y, X, A, We, be, *ctx.graph, act=ctx.act)
+        need = ctx.needs_input_grad
+        return d_x, (d_a if need[1] else None), (d_we if need[2] else None), (d_be if need[3] else None), None, None, None
+
+
+def aggregate_uep(X, edge_attr, We, be, row_pointers, column_index, act="relu"):
+    """Y[i, d] = the sum over the edges e of CSR row i of act(X[col e, d] + (edge_attr[e] @ We + be)[d]): aggregate_ue with the edge
+    projection formed inside the walk (GINEConv with edge_dim).  X: [N, D], edge_attr: [E, K] in CSR position order with 1 <= K <= 63,
+    We: [K, D], be: [D].  No [E, D] tensor exists going forward or back: the gradients of edge_attr, We and be come from one walk by row,
+    the gradient of X from one walk over A^T.  fp64 sums in a fixed order, no atomics; exact on any graph."""
+    if act not in ("relu", "identity", None):
+        raise ValueError("act must be 'relu', 'identity' or None, got %r" % (act,))
+    if X.dim() != 2 or edge_attr.dim() != 2 or edge_attr.shape[0] != column_index.numel():
+        raise RuntimeError("X must be [N, D] and edge_attr [E, K] with E = %d, got %s and %s" % (column_index.numel(), tuple(X.shape), tuple(edge_attr.shape)))
+    if tuple(We.shape) != (edge_attr.shape[1], X.shape[1]) or tuple(be.shape) != (X.shape[1],):
+        raise RuntimeError("We must be [K, D] = [%d, %d] and be [D], got %s and %s" % (edge_attr.shape[1], X.shape[1], tuple(We.shape), tuple(be.shape)))
+    return _AggregateUEP.apply(X, edge_attr, We, be, row_pointers, column_index, "relu" if act == "relu" else "identity")
 
 
 class _EdgeSum(torch.autograd.Function):

@@ -57,6 +57,8 @@ def build_parser():
     p.add_argument("--aggregator", type=str, default="mean", choices=["mean", "max", "pool"],
                    help="SAGE only: GraphSAGE's neighbour aggregation - 'mean', or the element-wise maximum over a node's incoming edges of the "
                    "features ('max') or of a learned projection of them ('pool') (not in the reference)")
+    p.add_argument("--fuse-edge", dest="fuse_edge", action="store_true",
+                   help="GINE only: form the edge projection inside the message walk (GINEConv(fuse_edge=True): no [E, hidden] tensor; not in the reference)")
     p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
                    help="GINE only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
     p.add_argument("--fanout", type=str, default=None,
@@ -218,7 +220,7 @@ def make_adam(params, lr=0.01):
 
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
-                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fanout=None,
+                  norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fuse_edge=False, fanout=None,
                   batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
@@ -234,6 +236,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max.
     model 'gine' (not in the reference): GINEConv layers with edge_dim=edge_dim; no dataset here has edge features, so edge_attr [E, edge_dim] is drawn
     ONCE, standard normal, from a generator on the device seeded with `seed`, and every layer reads it; the transposed CSR is prepared as for SAGE's max.
+    fuse_edge (GINE only): GINEConv(fuse_edge=True) - the edge projection formed inside the walk; the scratch of its backward is prepared with the transposed CSR.
     fanout (not in the reference; None: the path above, unchanged): a list of one fan-out per layer.  Every epoch, dry ones included, draws
     tcgnn_layers.sample_meta(meta, k, seed + epoch) per distinct k, builds what the model's operators need on it (the plan at every width and,
     for the layers with a `directed` switch, A^T's - a sampled graph is not symmetric, so those layers are built with directed=True - or, for
@@ -301,7 +304,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
 
         class conv_cls(L.GINEConv):
             def __init__(self, a, b, **kw):
-                super().__init__(a, b, edge_dim=int(edge_dim), **kw)
+                super().__init__(a, b, edge_dim=int(edge_dim), fuse_edge=bool(fuse_edge), **kw)
 
             def forward(self, X, *graph):   # (a sampled graph's rows of edge_attr: sampled_attr, keyed by its column_index)
                 return super().forward(X, *graph, edge_attr=sampled_attr.get(graph[1].data_ptr(), edge_attr))
@@ -309,6 +312,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
         conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv}[model_name]
+    if fuse_edge and model_name != "gine":
+        raise ValueError("fuse_edge applies to the GINE model only")
     sampled_attr = {}
     torch.manual_seed(seed)
     if model_name != "gcn" and (norm != "none" or bias):
@@ -345,6 +350,9 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
             dims = [in_dim] + [hidden] * max(1, num_layers - 1) + [classes]
             prep([min(a, b) for a, b in zip(dims[:-1], dims[1:])] if aggregator == "mean" else [], *meta,
                  **({"max_aggregation": True} if aggregator != "mean" else ({"transpose": True} if directed else {})))
+        elif prep is not None and meta[0].is_cuda and model_name == "gine" and fuse_edge:
+            # (the transposed CSR and, at every width a layer aggregates at, the scratch of backward_uep's partials)
+            prep([in_dim] + [hidden] * max(1, num_layers - 1), *meta, max_aggregation=True, edge_project=int(edge_dim))
         elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
             prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at
@@ -622,7 +630,7 @@ def run(args, quiet=False):
                       seed=args.seed, warmup=9, hip_graph=getattr(args, "hip_graph", False),  # 9 dry epochs, main_tcgnn.py:166-167
                       norm=getattr(args, "norm", "none"), bias=getattr(args, "bias", False), directed=getattr(args, "directed", False),
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
-                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fanout=getattr(args, "fanout", None),
+                      aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fuse_edge=getattr(args, "fuse_edge", False), fanout=getattr(args, "fanout", None),
                       batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None),
                       sampler=getattr(args, "sampler", "dense"), walk_length=getattr(args, "walk_length", 2), saint_norm=getattr(args, "saint_norm", 0))
     if "sample_ms" in r:

@@ -827,12 +827,17 @@ class GINEConv(torch.nn.Module):
     with Ef' = edge_attr W_e + b_e when edge_dim is given (required when the edge features are not input_dim wide) and Ef' = edge_attr
     [E, input_dim] otherwise; edge_attr rows are in CSR position order.  The sum is tcgnn_edge_ops.aggregate_ue: one fused walk, exact
     gradients for X and edge_attr on any graph.  One linear map where PyG takes any `nn`, as this file's GINConv does.  eps is a
-    Parameter with train_eps, a buffer otherwise.  Glorot-uniform weights, zero biases."""
+    Parameter with train_eps, a buffer otherwise.  Glorot-uniform weights, zero biases.
+    fuse_edge=True (needs edge_dim, at most 63): the projection is formed inside the walk (tcgnn_edge_ops.aggregate_uep) - Ef' and its
+    gradient, [E, input_dim] each, are never made.  The same parameters under the same names: a state dict moves between the two."""
 
-    def __init__(self, input_dim, output_dim, edge_dim=None, eps=0.0, train_eps=False, bias=True):
+    def __init__(self, input_dim, output_dim, edge_dim=None, eps=0.0, train_eps=False, bias=True, fuse_edge=False):
         super().__init__()
         self.input_dim, self.output_dim = int(input_dim), int(output_dim)
         self.edge_dim = None if edge_dim is None else int(edge_dim)
+        self.fuse_edge = bool(fuse_edge)
+        if self.fuse_edge and (self.edge_dim is None or not 1 <= self.edge_dim <= 63):
+            raise ValueError("fuse_edge=True needs edge_dim between 1 and 63, got %r" % (edge_dim,))
         self.weights = torch.nn.Parameter(torch.empty(self.input_dim, self.output_dim))
         if self.edge_dim is not None:
             self.weights_edge = torch.nn.Parameter(torch.empty(self.edge_dim, self.input_dim))
@@ -874,8 +879,13 @@ class GINEConv(torch.nn.Module):
         else:
             if edge_attr.shape[1] != self.edge_dim:
                 raise ValueError("edge_attr is %d wide, the layer was built with edge_dim=%d" % (edge_attr.shape[1], self.edge_dim))
-            Ef = dense_update(edge_attr, self.weights_edge) + self.bias_edge
-        h = (1.0 + self.eps) * X + E.aggregate_ue(X, Ef, row_pointers, column_index, "relu")
+            if not self.fuse_edge:
+                Ef = dense_update(edge_attr, self.weights_edge) + self.bias_edge
+        if self.fuse_edge:
+            agg = E.aggregate_uep(X, edge_attr, self.weights_edge, self.bias_edge, row_pointers, column_index, "relu")
+        else:
+            agg = E.aggregate_ue(X, Ef, row_pointers, column_index, "relu")
+        h = (1.0 + self.eps) * X + agg
         out = dense_update(h, self.weights)
         return out + self.bias if self.bias is not None else out
 

@@ -12,6 +12,12 @@ Per graph and width, HIP events, median of --reps calls after --warmup (the torc
                                      ids + 4 N D written; backward the same read plus 4 N D of dY and 4 E D of dM written
     GINE epoch                       tcgnn_harness.time_training("gine"): two layers D -> D -> classes on random D-wide inputs (a GINE
                                      layer aggregates at its INPUT width: the datasets' own widths would make Ef' hundreds of GB)
+    fused projection                 forward_uep / backward_uep / source_grad_uep (tcgnn_edge_project_*, edge_attr [E, edge_dim]) and the
+                                     layer's aggregation forward + backward, fused (aggregate_uep) against unfused (edge_attr We + be by torch,
+                                     then aggregate_ue) in ALTERNATING samples: median [min, max] of --reps each, and the peak bytes torch
+                                     allocated during one such step; likewise the GINE epoch with and without --fuse-edge, --epoch-samples
+                                     alternating samples a side; the last line names either as a miss where the fused interval is not
+                                     wholly below the unfused one
 GRAPHS: name:generator:D[,D...] separated by spaces; default the three of DESIGN.md 4.15."""
 import argparse
 import os
@@ -37,6 +43,33 @@ def median_ms(fn, reps, warmup):
     return float(np.median(times))
 
 
+def alternating_ms(fns, reps, warmup):
+    """[(median, min, max)] of each fn, sampled in turn: a, b, a, b, ..."""
+    import numpy as np
+    import torch
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    times = [[] for _ in fns]
+    for _ in range(reps):
+        for fn, ts in zip(fns, times):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); b.synchronize()
+            ts.append(a.elapsed_time(b))
+    return [(float(np.median(ts)), min(ts), max(ts)) for ts in times]
+
+
+def peak_gb(fn):
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 1e9
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("graphs", nargs="*", default=DEFAULT)
@@ -45,6 +78,7 @@ def main():
     ap.add_argument("--edge-dim", type=int, default=16)
     ap.add_argument("--skip-torch", action="store_true")
     ap.add_argument("--skip-epochs", action="store_true")
+    ap.add_argument("--epoch-samples", type=int, default=3, help="alternating GINE epoch samples per side")
     args = ap.parse_args()
     import torch
     import TCGNN
@@ -109,24 +143,56 @@ def main():
                     line = "         torch composition: %s" % str(e).splitlines()[0][:100]
                 torch.cuda.empty_cache()
                 print(line, flush=True)
-            del X, dY, Ef, Y, dX, Xg, Eg
+            del Ef, Eg
+            torch.cuda.empty_cache()
+            K = args.edge_dim
+            A = torch.randn(E, K, device=dev, generator=g).requires_grad_(True)
+            We = (torch.randn(K, D, device=dev, generator=g) / K ** 0.5).requires_grad_(True)
+            be = torch.randn(D, device=dev, generator=g).requires_grad_(True)
+            TCGNN.prepare([D], *meta, edge_project=K)
+            Ad, Wd, bd = A.detach(), We.detach(), be.detach()
+            t_pf = median_ms(lambda: TCGNN.forward_uep(X, Ad, Wd, bd, rp, col, out=Y), args.reps, args.warmup)
+            t_pb = median_ms(lambda: TCGNN.backward_uep(dY, X, Ad, Wd, bd, rp, col), args.reps, args.warmup)
+            t_ps = median_ms(lambda: TCGNN.source_grad_uep(dY, X, Ad, Wd, bd, rp, col, out=dX), args.reps, args.warmup)
+            print("         fused projection (edge_dim %d): forward_uep %.3f ms  backward_uep %.3f ms  source_grad_uep %.3f ms" % (K, t_pf, t_pb, t_ps), flush=True)
+            try:
+                def step_fused():
+                    return torch.autograd.grad(EO.aggregate_uep(Xg, A, We, be, rp, col, "relu"), [Xg, A, We, be], dY)
+
+                def step_unfused():
+                    return torch.autograd.grad(EO.aggregate_ue(Xg, A @ We + be, rp, col, "relu"), [Xg, A, We, be], dY)
+                (f_med, f_lo, f_hi), (u_med, u_lo, u_hi) = alternating_ms([step_fused, step_unfused], args.reps, args.warmup)
+                print("         aggregation fwd+bwd: fused %.3f ms [%.3f, %.3f]  unfused %.3f ms [%.3f, %.3f]  peak allocated: fused %.2f GB, unfused %.2f GB"
+                      % (f_med, f_lo, f_hi, u_med, u_lo, u_hi, peak_gb(step_fused), peak_gb(step_unfused)), flush=True)
+                if f_hi >= u_lo:   # (not faster with disjoint intervals)
+                    misses.append("%s aggregation fwd+bwd: fused [%.3f, %.3f] ms not below unfused [%.3f, %.3f] ms" % (tag, f_lo, f_hi, u_lo, u_hi))
+            except RuntimeError as e:
+                print("         aggregation fwd+bwd: %s" % str(e).splitlines()[0][:100], flush=True)
+            del X, dY, Y, dX, Xg, A, We, be, Ad, Wd, bd
             torch.cuda.empty_cache()
             if not args.skip_epochs:
                 gen_ = torch.Generator().manual_seed(0)
                 x = torch.randn(n, D, generator=gen_).to(dev)
                 y = torch.randint(0, classes, (n,), generator=gen_).to(dev)
-                try:
-                    r = H.time_training("gine", meta, x, y, D, D, classes, 2, 5, warmup=2, edge_dim=args.edge_dim)
-                    print("         GINE epoch (%d -> %d -> %d, edge_dim %d, edge_attr drawn on the device from seed 0): %.3f ms" % (D, D, classes, args.edge_dim, r["train_ms"]),
-                          flush=True)
-                except RuntimeError as e:
-                    print("         GINE epoch: %s" % str(e).splitlines()[0][:100], flush=True)
+                epochs = {False: [], True: []}
+                for fuse in (False, True) * args.epoch_samples:   # (alternating samples, each the mean of five epochs)
+                    try:
+                        r = H.time_training("gine", meta, x, y, D, D, classes, 2, 5, warmup=2, edge_dim=args.edge_dim, fuse_edge=fuse)
+                        epochs[fuse].append(r["train_ms"])
+                        print("         GINE epoch%s (%d -> %d -> %d, edge_dim %d, edge_attr drawn on the device from seed 0): %.3f ms"
+                              % (" --fuse-edge" if fuse else "", D, D, classes, args.edge_dim, r["train_ms"]), flush=True)
+                    except RuntimeError as e:
+                        print("         GINE epoch%s: %s" % (" --fuse-edge" if fuse else "", str(e).splitlines()[0][:100]), flush=True)
+                    torch.cuda.empty_cache()
+                if epochs[True] and epochs[False] and max(epochs[True]) >= min(epochs[False]):   # (not faster with disjoint intervals)
+                    misses.append("%s GINE epoch: fused [%.3f, %.3f] ms not below unfused [%.3f, %.3f] ms"
+                                  % (tag, min(epochs[True]), max(epochs[True]), min(epochs[False]), max(epochs[False])))
                 del x, y
                 torch.cuda.empty_cache()
         del rp_t, perm
         TCGNN.clear_plan_cache()
         torch.cuda.empty_cache()
-    print("misses against the torch composition: %s" % ("; ".join(misses) if misses else "none"))
+    print("misses (against the torch composition; fused against unfused): %s" % ("; ".join(misses) if misses else "none"))
 
 
 if __name__ == "__main__":
