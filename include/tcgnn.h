@@ -830,6 +830,40 @@ int tcgnn_edge_project_source_grad(const int32_t* d_nodePointer_t, const int32_t
                                    const float* d_be, const float* d_dY, int32_t K, int32_t D, int32_t act, float* d_dX,
                                    void* stream);
 
+/* ---- gated aggregation (Bresson & Laurent's residual gated graph convolution: PyG's ResGatedGraphConv, the core of DGL's GatedGCNConv;
+ * no counterpart in the reference) ----
+ *
+ * CSR row = destination node, column = source node.  k, q, v, dY and every output are fp32 [num_nodes, D] row-major; d_k, d_q and d_v
+ * may alias one another.  Planless like tcgnn_segment_max: device pointers, the caller's stream, no allocation, no synchronisation
+ * (capturable in a HIP graph); no atomics and every reduction order fixed: bit-identical on repetition.  Everything is read as fp32 -
+ * no fp16 image, no range guard.
+ *   the gate                 z = fl32(k[row e, d] + q[col e, d]);  t = exp2(fl32(-|z| * log2 e)) on the hardware exponential
+ *                            (tcgnn_edge_softmax's);  r = fl32(1 + t);  for z >= 0: eta = fl32(1 / r), c = fl32(t / r); for z < 0 the two
+ *                            are swapped.  True divisions; a NaN z gives NaN.  eta = sigmoid(z) and c = 1 - eta come from the SAME
+ *                            exponential, never from a subtraction: both carry a small relative error at any |z|, eta * c does not cancel.
+ *   tcgnn_gated_sum          m = fl32(eta * v[col e, d]);  Y[i, d] = fl32(sum over e in row i of (double)m), an fp64 sum in a fixed order,
+ *                            rounded once; an empty row: 0.  d_S (may be NULL) receives the row's gate sensitivity
+ *                            S[i, d] = fl32(sum over e in row i of (double)fl32(fl32(eta * c) * v[col e, d])): the gradient with respect to
+ *                            k is dk = dY (.) S, an element-wise product the caller forms - no row-side backward kernel, no second
+ *                            gather over A.  Y is bit-identical with and without d_S.
+ *   tcgnn_gated_source_grad  over the rows of A^T (d_nodePointer_t, d_edgeList_t, d_perm: what tcgnn_transpose_ws wrote; d_perm is taken
+ *                            for symmetry with the family, is not read and may be NULL).  For source row j and i = edgeList_t[eT],
+ *                            z = fl32(k[i, d] + q[j, d]) is the forward's number.  dv[j, d] = fl32(sum (double)fl32(eta * dY[i, d]));
+ *                            dq[j, d] = fl32((double)v[j, d] * sum (double)fl32(fl32(eta * c) * dY[i, d])).  One walk gathers k[i] and
+ *                            dY[i] once per edge for both sums.  A source nobody reads gets 0.
+ * Rows are read with 16-byte loads when D % 4 == 0 and k, q, v (and dY) are 16-byte aligned, with 4-byte loads otherwise: the same bits
+ * either way.  Row pointers are clamped to [0, num_edges] and a descending pair is an empty row; for every read it indexes a column id
+ * is clamped to the nearer end of [0, num_nodes): safe reads, values of no meaning for an array that holds such entries.  Every element
+ * of Y / S / dq / dv is written and nothing outside them.  num_nodes = 0 or D = 0 returns TCGNN_OK; num_edges = 0 returns TCGNN_OK with
+ * the outputs zeroed; a negative size, num_edges >= 2^31 or a null array otherwise: TCGNN_ERR_INVALID_ARG before anything is written.
+ * A hub row stays on one workgroup, as in tcgnn_segment_max. */
+int tcgnn_gated_sum(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                    const float* d_k, const float* d_q, const float* d_v, int32_t D, float* d_Y, float* d_S /* may be NULL */,
+                    void* stream);
+int tcgnn_gated_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm /* not read */,
+                            int32_t num_nodes, int64_t num_edges, const float* d_k, const float* d_q, const float* d_v,
+                            const float* d_dY, int32_t D, float* d_dq, float* d_dv, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

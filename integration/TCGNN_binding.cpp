@@ -846,6 +846,47 @@ torch::Tensor source_grad_uep(torch::Tensor dY, torch::Tensor X, torch::Tensor e
   return dX;
 }
 
+// ---- not in the reference: gated aggregation (tcgnn_gated_sum / tcgnn_gated_source_grad; the ctypes module's forward_gated and
+// source_grad_gated) -----------------------------------------------------------------------------------------------------------------
+namespace {
+std::tuple<int32_t, int64_t, int32_t> gated_args(const torch::Tensor& k, const torch::Tensor& q, const torch::Tensor& v, const torch::Tensor& nodePointer,
+                                                 const torch::Tensor& edgeList) {
+  auto [N, E, D] = max_args(k, "k", nodePointer, edgeList);
+  for (const torch::Tensor* t : {&q, &v}) {
+    CHECK_INPUT((*t));
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, "expected scalar type Float");
+    TORCH_CHECK(t->sizes() == k.sizes() && t->device() == k.device(), "q and v must have the shape and device of k");
+  }
+  return {N, E, D};
+}
+}  // namespace
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> forward_gated(torch::Tensor k, torch::Tensor q, torch::Tensor v, torch::Tensor nodePointer,
+                                                                      torch::Tensor edgeList, bool return_sens, c10::optional<torch::Tensor> out) {
+  auto [N, E, D] = gated_args(k, q, v, nodePointer, edgeList);
+  torch::Tensor Y = out_like(out, k, "k");
+  check_out_apart(out, {&k, &q, &v});
+  DeviceGuard guard(k.device());
+  c10::optional<torch::Tensor> S;
+  if (return_sens) S = torch::empty({(int64_t)N, (int64_t)D}, k.options());
+  tcgnn_check(tcgnn_gated_sum(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, k.data_ptr<float>(), q.data_ptr<float>(), v.data_ptr<float>(), D,
+                              Y.data_ptr<float>(), S.has_value() ? S->data_ptr<float>() : nullptr, current_stream(k)), "tcgnn_gated_sum");
+  return {Y, S};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> source_grad_gated(torch::Tensor k, torch::Tensor q, torch::Tensor v, torch::Tensor dY, torch::Tensor nodePointer,
+                                                           torch::Tensor edgeList) {
+  auto [N, E, D] = gated_args(k, q, v, nodePointer, edgeList);
+  uep_dy(dY, k);
+  DeviceGuard guard(k.device());
+  torch::Tensor dq = torch::empty_like(k), dv = torch::empty_like(k);
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_gated_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E, k.data_ptr<float>(),
+                                      q.data_ptr<float>(), v.data_ptr<float>(), dY.data_ptr<float>(), D, dq.data_ptr<float>(), dv.data_ptr<float>(),
+                                      current_stream(k)), "tcgnn_gated_source_grad");
+  return {dq, dv};
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
   CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
@@ -1250,6 +1291,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("source_grad_uep", &source_grad_uep, "source side of forward_uep's backward: dX (not in the reference)", py::arg("dY"), py::arg("X"),
         py::arg("edge_attr"), py::arg("We"), py::arg("be"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("act") = "relu",
         py::arg("out") = py::none());
+  m.def("forward_gated", &forward_gated, "gated aggregation sum of sigmoid(k[row] + q[col]) v[col] over every node's incoming edges: (Y, S) "
+        "(not in the reference)", py::arg("k"), py::arg("q"), py::arg("v"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("return_sens") = true,
+        py::arg("out") = py::none());
+  m.def("source_grad_gated", &source_grad_gated, "source side of forward_gated's backward: (dq, dv) (not in the reference)", py::arg("k"), py::arg("q"),
+        py::arg("v"), py::arg("dY"), py::arg("nodePointer"), py::arg("edgeList"));
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

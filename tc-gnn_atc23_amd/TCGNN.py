@@ -37,7 +37,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "sample_neighbors", "compact_nodes", "compact_graph",
+           "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "forward_gated", "source_grad_gated", "sample_neighbors", "compact_nodes", "compact_graph",
            "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
@@ -552,7 +552,7 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
 
 
 def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1,
-            max_aggregation=False, edge_project=None):
+            max_aggregation=False, edge_project=None, gated=False):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
@@ -572,8 +572,10 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     backward_stats: PNAConv): the transposed CSR backward_max and backward_stats walk, built now (transpose_graph: the graph's one
     transpose) - the calls are planless and need nothing else.
     edge_project=K (a model with GINEConv(fuse_edge=True) layers of edge_dim K: forward_uep / backward_uep / source_grad_uep): the
-    transposed CSR source_grad_uep walks and the scratch of backward_uep's dWe / dbe partials at every width, on the current stream."""
-    if max_aggregation or edge_project is not None:
+    transposed CSR source_grad_uep walks and the scratch of backward_uep's dWe / dbe partials at every width, on the current stream.
+    gated=True (a model with ResGatedGraphConv layers: forward_gated / source_grad_gated): the transposed CSR source_grad_gated walks,
+    built now - the calls are planless and need nothing else."""
+    if max_aggregation or gated or edge_project is not None:
         transpose_graph(nodePointer, edgeList)
     if edge_project is not None:
         with torch.cuda.device(nodePointer.device):
@@ -1561,6 +1563,54 @@ def source_grad_uep(dY, X, edge_attr, We, be, nodePointer, edgeList, act="relu",
     _call(_c.lib.tcgnn_edge_project_source_grad, X.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, X.data_ptr(), edge_attr.data_ptr(),
           We.data_ptr(), be.data_ptr(), dY.data_ptr(), K, D, code, res.data_ptr())
     return res
+
+
+# ---- additions (not in the reference module): gated aggregation (ResGatedGraphConv; the core of GatedGCN) -------------------
+
+def _gated_args(k, q, v, nodePointer, edgeList):
+    N, E, D = _max_args(k, "k", nodePointer, edgeList)
+    for t, n in ((q, "q"), (v, "v")):
+        _check_input(t, n)
+        _check_float(t, n)
+        if t.shape != k.shape or t.device != k.device:
+            raise RuntimeError("%s must have the shape and device of k, got %s" % (n, tuple(t.shape)))
+    return N, E, D
+
+
+def forward_gated(k, q, v, nodePointer, edgeList, return_sens=True, out=None):
+    """Not in the reference module: (Y, S) of the gated aggregation (tcgnn_gated_sum),
+        Y[i, d] = the sum over the edges e of row i of sigmoid(k[i, d] + q[col(e), d]) * v[col(e), d]
+        S[i, d] = the same sum of sigmoid' * v - the row's gate sensitivity: the gradient of k is dY * S, element by element.
+    k, q, v: fp32 [N, D]; they may be one tensor.  The gate and its complement come from one exponential (include/tcgnn.h states the
+    roundings); the sums are fp64 in a fixed order, rounded once; no [E, D] tensor is made.  A row without edges gives 0 in both.
+    return_sens=False: S is None (nothing is computed or written for it; Y has the same bits).  Deterministic, no atomics."""
+    N, E, D = _gated_args(k, q, v, nodePointer, edgeList)
+    res = _out_like(out, k, "k")
+    _out_apart(res, out, k, q, v)
+    sens = torch.empty(N, D, dtype=torch.float32, device=k.device) if return_sens else None
+    _call(_c.lib.tcgnn_gated_sum, k.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, k.data_ptr(), q.data_ptr(), v.data_ptr(), D, res.data_ptr(),
+          _ptr(sens))
+    return res, sens
+
+
+def source_grad_gated(k, q, v, dY, nodePointer, edgeList):
+    """Not in the reference module: (dq, dv), the source side of forward_gated's backward (tcgnn_gated_source_grad), fp32 [N, D] each,
+        dv[j, d] = the sum over the edges (i <- j) of sigmoid(k[i, d] + q[j, d]) * dY[i, d]
+        dq[j, d] = v[j, d] * the sum over the same edges of sigmoid'(k[i, d] + q[j, d]) * dY[i, d]
+    - ONE walk over the rows of A^T gathers k[i] and dY[i] once per edge for both (fp64 sums in a fixed order, no atomics); a node nobody
+    reads gets 0.  The gradient of k needs no call: it is dY * S with forward_gated's S.  The transposed CSR is the module's cached one
+    (transpose_graph): built at the first call for a graph, or by prepare(..., gated=True)."""
+    N, E, D = _gated_args(k, q, v, nodePointer, edgeList)
+    _check_input(dY, "dY")
+    _check_float(dY, "dY")
+    if dY.shape != k.shape or dY.device != k.device:
+        raise RuntimeError("dY must have the shape and device of k")
+    dq = torch.empty(N, D, dtype=torch.float32, device=k.device)
+    dv = torch.empty(N, D, dtype=torch.float32, device=k.device)
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_gated_source_grad, k.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, k.data_ptr(), q.data_ptr(), v.data_ptr(),
+          dY.data_ptr(), D, dq.data_ptr(), dv.data_ptr())
+    return dq, dv
 
 
 # ---- additions (not in the reference module): the two products of an AGNN layer in one pass ------------

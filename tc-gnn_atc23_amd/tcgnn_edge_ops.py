@@ -17,13 +17,14 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate_ue(X, Ef, rowptr, col, act)  Y[i, d] = sum over row i of act(X[col e, d] + Ef[e, d]), Ef [E, D] (u_add_e; GINE)   bwd: dM = dY[row e] masked, once; dEf = dM, dX = sum of dM by source over A^T
     aggregate_uep(X, A, We, be, rowptr, col, act)  aggregate_ue with Ef = A We + be formed inside the walk, A [E, K] (GINE with edge_dim)   bwd: (dA, dWe, dbe) from one walk by row, dX from one over A^T; no [E, D] tensor either way
     edge_sum(M, rowptr, col)      Y[i, d] = sum over row i of M[e, d], M [E, D] (copy_e)                        bwd: dM[e] = dY[row e]
+    aggregate_gated(k, q, v, rowptr, col)  Y[i, d] = sum over row i of sigmoid(k[i, d] + q[col e, d]) v[col e, d] (ResGatedGraphConv)   bwd: dk = dY * S (S: the forward's second output), (dq, dv) from one walk over A^T
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum, forward_uep, backward_uep, source_grad_uep (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum, forward_uep, backward_uep, source_grad_uep, forward_gated, source_grad_gated (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -360,6 +361,39 @@ def aggregate_uep(X, edge_attr, We, be, row_pointers, column_index, act="relu"):
     if tuple(We.shape) != (edge_attr.shape[1], X.shape[1]) or tuple(be.shape) != (X.shape[1],):
         raise RuntimeError("We must be [K, D] = [%d, %d] and be [D], got %s and %s" % (edge_attr.shape[1], X.shape[1], tuple(We.shape), tuple(be.shape)))
     return _AggregateUEP.apply(X, edge_attr, We, be, row_pointers, column_index, "relu" if act == "relu" else "identity")
+
+
+class _AggregateGated(torch.autograd.Function):
+    """(Y, S) = forward_gated(k, q, v); backward: dk = dY * S element by element, (dq, dv) = source_grad_gated(dY), ONE walk over A^T.
+    Saved: k, q, v and S - four [N, D] tensors, nothing of size E."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, row_pointers, column_index):
+        k, q, v = k.contiguous(), q.contiguous(), v.contiguous()
+        ctx.graph = (row_pointers, column_index)
+        Y, S = _L.backend().forward_gated(k, q, v, row_pointers, column_index)
+        ctx.save_for_backward(k, q, v, S)
+        return Y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        k, q, v, S = ctx.saved_tensors
+        d_y = d_y.contiguous()
+        d_k = d_y * S if ctx.needs_input_grad[0] else None
+        d_q = d_v = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            d_q, d_v = _L.backend().source_grad_gated(k, q, v, d_y, *ctx.graph)
+        return d_k, (d_q if ctx.needs_input_grad[1] else None), (d_v if ctx.needs_input_grad[2] else None), None, None
+
+
+def aggregate_gated(k, q, v, row_pointers, column_index):
+    """Y[i, d] = the sum over the edges e of CSR row i of sigmoid(k[i, d] + q[col e, d]) * v[col e, d]: a per-edge, per-channel gate of
+    both endpoints on the message (u_mul_e with a computed e; ResGatedGraphConv, the core of GatedGCN).  k, q, v: [N, D].  One fused
+    walk forward and one over A^T back; the gradient of k is an element-wise product with the forward's second output.  No [E, D]
+    tensor in either direction; fp64 sums in a fixed order, no atomics; exact on any graph."""
+    if k.dim() != 2 or q.shape != k.shape or v.shape != k.shape:
+        raise RuntimeError("k, q and v must be [N, D] tensors of one shape, got %s, %s and %s" % (tuple(k.shape), tuple(q.shape), tuple(v.shape)))
+    return _AggregateGated.apply(k, q, v, row_pointers, column_index)
 
 
 class _EdgeSum(torch.autograd.Function):

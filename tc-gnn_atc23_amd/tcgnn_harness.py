@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna", "gine"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna", "gine", "resgated"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -311,7 +311,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     else:
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
-        conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv}[model_name]
+        conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv, "resgated": L.ResGatedGraphConv}[model_name]
     if fuse_edge and model_name != "gine":
         raise ValueError("fuse_edge applies to the GINE model only")
     sampled_attr = {}
@@ -325,8 +325,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if model_name != "agnn":
             raise ValueError("attention applies to the AGNN model only")
         conv_kwargs["attention"] = attention
-    if multi_head or model_name in ("pna", "gine"):
-        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv, PNAConv and GINEConv back-propagate through A^T on every graph)
+    if multi_head or model_name in ("pna", "gine", "resgated"):
+        conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv, PNAConv, GINEConv and ResGatedGraphConv back-propagate through A^T on every graph)
     model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
@@ -339,7 +339,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         return loss
 
     prep = getattr(L.backend(), "prepare", None)
-    planless = model_name in ("pna", "gine") or (model_name == "sage" and aggregator != "mean")
+    planless = model_name in ("pna", "gine", "resgated") or (model_name == "sage" and aggregator != "mean")
 
     def prepare(meta):
         """what this model's operators need on the graph `meta`, built now: nothing is built (or synchronised) inside a step"""
@@ -353,6 +353,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         elif prep is not None and meta[0].is_cuda and model_name == "gine" and fuse_edge:
             # (the transposed CSR and, at every width a layer aggregates at, the scratch of backward_uep's partials)
             prep([in_dim] + [hidden] * max(1, num_layers - 1), *meta, max_aggregation=True, edge_project=int(edge_dim))
+        elif prep is not None and meta[0].is_cuda and model_name == "resgated":
+            prep([], *meta, gated=True)   # (forward_gated / source_grad_gated are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
             prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at

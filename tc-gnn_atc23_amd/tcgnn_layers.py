@@ -890,6 +890,46 @@ class GINEConv(torch.nn.Module):
         return out + self.bias if self.bias is not None else out
 
 
+class ResGatedGraphConv(torch.nn.Module):
+    """Not in the reference: the residual gated graph convolution (Bresson & Laurent, "Residual Gated Graph ConvNets") after PyG's
+    ResGatedGraphConv,
+        out[i] = X[i] W_skip + b + sum over a node's incoming edges (i <- j) of sigmoid(X[i] W_k + X[j] W_q) * (X[j] W_v),
+    the gate per edge AND per channel.  The three projections are ONE dense product with `weights` = [W_k | W_q | W_v]
+    ([input_dim, 3 output_dim]); the sum is tcgnn_edge_ops.aggregate_gated: one fused walk forward, one over A^T back, no [E, D] tensor
+    either way, exact gradients on any graph.  root_weight=False drops the skip term (`weights_skip` is None).  Glorot-uniform weights
+    (each projection on its own), zero bias; the projections carry no bias of their own."""
+
+    def __init__(self, input_dim, output_dim, bias=True, root_weight=True):
+        super().__init__()
+        self.input_dim, self.output_dim = int(input_dim), int(output_dim)
+        self.weights = torch.nn.Parameter(torch.empty(self.input_dim, 3 * self.output_dim))
+        if root_weight:
+            self.weights_skip = torch.nn.Parameter(torch.empty(self.input_dim, self.output_dim))
+        else:
+            self.register_parameter("weights_skip", None)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.zeros(self.output_dim))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for w in self.weights.data.split(self.output_dim, dim=1):
+            torch.nn.init.xavier_uniform_(w)
+        if self.weights_skip is not None:
+            torch.nn.init.xavier_uniform_(self.weights_skip)
+        if self.bias is not None:
+            self.bias.data.zero_()
+
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        k, q, v = dense_update(X, self.weights).split(self.output_dim, dim=1)
+        out = E.aggregate_gated(k, q, v, row_pointers, column_index)
+        if self.weights_skip is not None:
+            out = out + dense_update(X, self.weights_skip)
+        return out + self.bias if self.bias is not None else out
+
+
 PNA_AGGREGATORS = ("mean", "std", "max", "min")
 PNA_SCALERS = ("identity", "amplification", "attenuation")
 
