@@ -864,6 +864,48 @@ int tcgnn_gated_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edg
                             int32_t num_nodes, int64_t num_edges, const float* d_k, const float* d_q, const float* d_v,
                             const float* d_dY, int32_t D, float* d_dq, float* d_dv, void* stream);
 
+/* ---- GatedGCN with edge features (Bresson & Laurent's layer as "Benchmarking GNNs" trains it: DGL's GatedGCNConv, the local layer of
+ * GraphGPS; no counterpart in the reference) ----
+ *
+ * The gate above with a per-edge term, which is also the layer's NEW EDGE FEATURE, and the gated mean.  CSR row = destination i, column =
+ * source j, e = CSR position.  k, q, v, Y, Den, dY, dk, dq, dv are fp32 [num_nodes, D]; c, Z, dZ, G are fp32 [num_edges, D] in CSR
+ * position order; all row-major.  Inputs may alias one another, outputs may not alias anything.  eps >= 0 (DGL: 1e-6) is widened to
+ * double exactly.  Planless: device pointers, the caller's stream, no allocation, no synchronisation (capturable in a HIP graph); no
+ * atomics and every reduction order fixed: bit-identical on repetition.  Everything is read as fp32.
+ *   quot(x, den)                s = den + (double)eps in fp64;  s == 0 ? 0 : fl32(x / s), one fp64 division, rounded once
+ *   tcgnn_gatedgcn_forward      Z[e, d] = fl32(fl32(k[i, d] + q[j, d]) + c[e, d]) - numpy's ((k[row] + q[col]) + c) in fp32, bit for bit.
+ *                               (eta, cc) = the gate and its complement of tcgnn_gated_sum from z = Z[e, d]: one exponential, two true
+ *                               divisions.  num = sum over e in row i of (double)fl32(eta * v[j, d]), den = sum of (double)eta, fp64 in a
+ *                               fixed order;  Y[i, d] = quot(num, den);  Den[i, d] = fl32(den).  A row without edges: Y = Den = 0, also
+ *                               with eps = 0 (so does a row whose gates all underflowed to 0 under eps = 0).
+ *   tcgnn_gatedgcn_backward     by row.  u = quot((double)dY[i, d], (double)Den[i, d]), once per row; the gate recomputed from the STORED
+ *                               Z[e, d] - the forward's bits; k, q and c are not needed.
+ *                               G[e, d] = fl32(dz + fl32(fl32(eta * cc) * fl32(u * fl32(v[j, d] - Y[i, d])))), dz = dZ[e, d], or +0 when
+ *                               d_dZ is NULL (the edge output was not used): the same bits as a d_dZ of zeros.  G is the gradient of c
+ *                               (and of Z's sum k + q + c).  dk[i, d] = fl32(sum over e in row i of (double)G[e, d]).
+ *   tcgnn_gatedgcn_source_grad  over the rows of A^T (d_nodePointer_t, d_edgeList_t, d_perm: what tcgnn_transpose_ws wrote; d_perm IS
+ *                               read).  For position t of source row j: e = perm[t], i = edgeList_t[t].
+ *                               dq[j, d] = fl32(sum (double)G[e, d]);  dv[j, d] = fl32(sum (double)fl32(eta * u)) with the gate from
+ *                               Z[e, d] and u = quot(dY[i, d], Den[i, d]) - the row side's number.  One walk for both; a source nobody
+ *                               reads gets 0 in both.
+ * Rows are moved with 16-byte accesses when D % 4 == 0 and every array the call touches is 16-byte aligned, with 4-byte ones otherwise:
+ * the same bits either way.  The [E, D] arrays are touched once per call and move past the caches' retention (non-temporal).  Row
+ * pointers are clamped to [0, num_edges] and a descending pair is an empty row; a column id is clamped to the nearer end of
+ * [0, num_nodes), a perm entry outside [0, num_edges) reads position 0: safe accesses, values of no meaning for such arrays.  Every
+ * element of Y / Den / dk / dq / dv and of Z / G is written (positions of Z / G no row covers: 0) and nothing outside them.
+ * num_nodes = 0 or D = 0 returns TCGNN_OK and writes nothing; num_edges = 0 returns TCGNN_OK with Y / Den / dk / dq / dv zeroed; a
+ * negative size, num_edges >= 2^31, an eps that is negative, infinite or NaN, or a null array otherwise (d_dZ excepted):
+ * TCGNN_ERR_INVALID_ARG before anything is written.  A hub row stays on one workgroup, as in tcgnn_gated_sum. */
+int tcgnn_gatedgcn_forward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                           const float* d_k, const float* d_q, const float* d_v, const float* d_c, int32_t D, float eps,
+                           float* d_Y, float* d_Z, float* d_Den, void* stream);
+int tcgnn_gatedgcn_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                            const float* d_dY, const float* d_dZ /* may be NULL */, const float* d_Y, const float* d_Den,
+                            const float* d_Z, const float* d_v, int32_t D, float eps, float* d_G, float* d_dk, void* stream);
+int tcgnn_gatedgcn_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm,
+                               int32_t num_nodes, int64_t num_edges, const float* d_G, const float* d_Z, const float* d_dY,
+                               const float* d_Den, int32_t D, float eps, float* d_dq, float* d_dv, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

@@ -887,6 +887,62 @@ std::tuple<torch::Tensor, torch::Tensor> source_grad_gated(torch::Tensor k, torc
   return {dq, dv};
 }
 
+// ---- not in the reference: GatedGCN with edge features (tcgnn_gatedgcn_forward / _backward / _source_grad; the ctypes module's
+// forward_gatedgcn, backward_gatedgcn and source_grad_gatedgcn) ----------------------------------------------------------------------
+namespace {
+std::tuple<int32_t, int64_t, int32_t> gatedgcn_nodes(const torch::Tensor& first, const char* name, std::initializer_list<const torch::Tensor*> others,
+                                                     const torch::Tensor& nodePointer, const torch::Tensor& edgeList) {
+  auto [N, E, D] = max_args(first, name, nodePointer, edgeList);
+  for (const torch::Tensor* t : others) {
+    CHECK_INPUT((*t));
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, "expected scalar type Float");
+    TORCH_CHECK(t->sizes() == first.sizes() && t->device() == first.device(), "every [num_nodes, D] operand must have the shape and device of ", name);
+  }
+  return {N, E, D};
+}
+}  // namespace
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> forward_gatedgcn(torch::Tensor k, torch::Tensor q, torch::Tensor v, torch::Tensor c,
+                                                                         torch::Tensor nodePointer, torch::Tensor edgeList, double eps) {
+  auto [N, E, D] = gatedgcn_nodes(k, "k", {&q, &v}, nodePointer, edgeList);
+  check_edge_rows(c, "c", E, D, nodePointer);
+  DeviceGuard guard(k.device());
+  torch::Tensor Y = torch::empty_like(k), Den = torch::empty_like(k), Z = torch::empty_like(c);
+  tcgnn_check(tcgnn_gatedgcn_forward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, k.data_ptr<float>(), q.data_ptr<float>(),
+                                     v.data_ptr<float>(), c.data_ptr<float>(), D, (float)eps, Y.data_ptr<float>(), Z.data_ptr<float>(),
+                                     Den.data_ptr<float>(), current_stream(k)), "tcgnn_gatedgcn_forward");
+  return {Y, Z, Den};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> backward_gatedgcn(torch::Tensor dY, c10::optional<torch::Tensor> dZ, torch::Tensor Y, torch::Tensor Den,
+                                                           torch::Tensor Z, torch::Tensor v, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                           double eps) {
+  auto [N, E, D] = gatedgcn_nodes(dY, "dY", {&Y, &Den, &v}, nodePointer, edgeList);
+  check_edge_rows(Z, "Z", E, D, nodePointer);
+  if (dZ.has_value()) check_edge_rows(*dZ, "dZ", E, D, nodePointer);
+  DeviceGuard guard(dY.device());
+  torch::Tensor dc = torch::empty_like(Z), dk = torch::empty_like(dY);
+  tcgnn_check(tcgnn_gatedgcn_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), N, E, dY.data_ptr<float>(),
+                                      dZ.has_value() ? dZ->data_ptr<float>() : nullptr, Y.data_ptr<float>(), Den.data_ptr<float>(), Z.data_ptr<float>(),
+                                      v.data_ptr<float>(), D, (float)eps, dc.data_ptr<float>(), dk.data_ptr<float>(), current_stream(dY)),
+              "tcgnn_gatedgcn_backward");
+  return {dc, dk};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> source_grad_gatedgcn(torch::Tensor G, torch::Tensor Z, torch::Tensor dY, torch::Tensor Den,
+                                                              torch::Tensor nodePointer, torch::Tensor edgeList, double eps) {
+  auto [N, E, D] = gatedgcn_nodes(dY, "dY", {&Den}, nodePointer, edgeList);
+  check_edge_rows(G, "G", E, D, nodePointer);
+  check_edge_rows(Z, "Z", E, D, nodePointer);
+  DeviceGuard guard(dY.device());
+  torch::Tensor dq = torch::empty_like(dY), dv = torch::empty_like(dY);
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_gatedgcn_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), N, E, G.data_ptr<float>(),
+                                         Z.data_ptr<float>(), dY.data_ptr<float>(), Den.data_ptr<float>(), D, (float)eps, dq.data_ptr<float>(),
+                                         dv.data_ptr<float>(), current_stream(dY)), "tcgnn_gatedgcn_source_grad");
+  return {dq, dv};
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
   CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
@@ -1296,6 +1352,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = py::none());
   m.def("source_grad_gated", &source_grad_gated, "source side of forward_gated's backward: (dq, dv) (not in the reference)", py::arg("k"), py::arg("q"),
         py::arg("v"), py::arg("dY"), py::arg("nodePointer"), py::arg("edgeList"));
+  m.def("forward_gatedgcn", &forward_gatedgcn, "GatedGCN aggregation with edge features: (Y, Z, Den) with Z = k[row] + q[col] + c the new edge "
+        "feature and Y the sigmoid(Z)-gated mean of v[col] (not in the reference)", py::arg("k"), py::arg("q"), py::arg("v"), py::arg("c"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("eps") = 1e-6);
+  m.def("backward_gatedgcn", &backward_gatedgcn, "row side of forward_gatedgcn's backward: (dc, dk) (not in the reference)", py::arg("dY"), py::arg("dZ"),
+        py::arg("Y"), py::arg("Den"), py::arg("Z"), py::arg("v"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("eps") = 1e-6);
+  m.def("source_grad_gatedgcn", &source_grad_gatedgcn, "source side of forward_gatedgcn's backward: (dq, dv) (not in the reference)", py::arg("G"),
+        py::arg("Z"), py::arg("dY"), py::arg("Den"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("eps") = 1e-6);
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

@@ -37,7 +37,8 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_fused", "forward_gemm", "forward_scaled", "degree_scales", "transpose_graph",
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
-           "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "forward_gated", "source_grad_gated", "sample_neighbors", "compact_nodes", "compact_graph",
+           "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "forward_gated", "source_grad_gated",
+           "forward_gatedgcn", "backward_gatedgcn", "source_grad_gatedgcn", "sample_neighbors", "compact_nodes", "compact_graph",
            "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
@@ -573,8 +574,8 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     transpose) - the calls are planless and need nothing else.
     edge_project=K (a model with GINEConv(fuse_edge=True) layers of edge_dim K: forward_uep / backward_uep / source_grad_uep): the
     transposed CSR source_grad_uep walks and the scratch of backward_uep's dWe / dbe partials at every width, on the current stream.
-    gated=True (a model with ResGatedGraphConv layers: forward_gated / source_grad_gated): the transposed CSR source_grad_gated walks,
-    built now - the calls are planless and need nothing else."""
+    gated=True (a model with ResGatedGraphConv or GatedGCNConv layers: forward_gated / source_grad_gated, forward_gatedgcn /
+    backward_gatedgcn / source_grad_gatedgcn): the transposed CSR the source-side calls walk, built now - the calls are planless and need nothing else."""
     if max_aggregation or gated or edge_project is not None:
         transpose_graph(nodePointer, edgeList)
     if edge_project is not None:
@@ -1610,6 +1611,64 @@ def source_grad_gated(k, q, v, dY, nodePointer, edgeList):
     rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
     _call(_c.lib.tcgnn_gated_source_grad, k.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, k.data_ptr(), q.data_ptr(), v.data_ptr(),
           dY.data_ptr(), D, dq.data_ptr(), dv.data_ptr())
+    return dq, dv
+
+
+# ---- additions (not in the reference module): GatedGCN with edge features (DGL's GatedGCNConv; the local layer of GraphGPS) --
+
+def _gatedgcn_nodes(first, name, others, nodePointer, edgeList):
+    N, E, D = _max_args(first, name, nodePointer, edgeList)
+    for t, n in others:
+        _check_input(t, n)
+        _check_float(t, n)
+        if t.shape != first.shape or t.device != first.device:
+            raise RuntimeError("%s must have the shape and device of %s, got %s" % (n, name, tuple(t.shape)))
+    return N, E, D
+
+
+def forward_gatedgcn(k, q, v, c, nodePointer, edgeList, eps=1e-6):
+    """Not in the reference module: (Y, Z, Den) of the GatedGCN aggregation with edge features (tcgnn_gatedgcn_forward),
+        Z[e, d]   = k[row(e), d] + q[col(e), d] + c[e, d]          the new edge feature, fp32 [E, D] in CSR position order
+        Y[i, d]   = sum over the edges e of row i of sigmoid(Z[e, d]) * v[col(e), d]  /  (Den[i, d] + eps)
+        Den[i, d] = sum over the same edges of sigmoid(Z[e, d])                        (what the backward calls need)
+    k, q, v: fp32 [N, D]; c: fp32 [E, D].  One fused walk: nothing of size E but c and Z exists.  include/tcgnn.h states the roundings;
+    the sums are fp64 in a fixed order, rounded once.  A row without edges gives Y = Den = 0.  Deterministic, no atomics."""
+    N, E, D = _gatedgcn_nodes(k, "k", ((q, "q"), (v, "v")), nodePointer, edgeList)
+    _edge_rows(c, "c", E, D, nodePointer)
+    Y, Den = torch.empty_like(k), torch.empty_like(k)
+    Z = torch.empty_like(c)
+    _call(_c.lib.tcgnn_gatedgcn_forward, k.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, k.data_ptr(), q.data_ptr(), v.data_ptr(), c.data_ptr(),
+          D, float(eps), Y.data_ptr(), Z.data_ptr(), Den.data_ptr())
+    return Y, Z, Den
+
+
+def backward_gatedgcn(dY, dZ, Y, Den, Z, v, nodePointer, edgeList, eps=1e-6):
+    """Not in the reference module: (dc, dk), the row side of forward_gatedgcn's backward (tcgnn_gatedgcn_backward).  dc, fp32 [E, D], is
+    the gradient of c - and, summed by row, dk (fp32 [N, D]); summed by source it is dq: hand it to source_grad_gatedgcn as G.  dZ is
+    the gradient that reached the edge output, or None when nothing used it.  The gate is recomputed from the stored Z; k, q and c are
+    not needed.  eps must be the forward's."""
+    N, E, D = _gatedgcn_nodes(dY, "dY", ((Y, "Y"), (Den, "Den"), (v, "v")), nodePointer, edgeList)
+    _edge_rows(Z, "Z", E, D, nodePointer)
+    if dZ is not None:
+        _edge_rows(dZ, "dZ", E, D, nodePointer)
+    dc, dk = torch.empty_like(Z), torch.empty_like(dY)
+    _call(_c.lib.tcgnn_gatedgcn_backward, dY.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, dY.data_ptr(), _ptr(dZ), Y.data_ptr(),
+          Den.data_ptr(), Z.data_ptr(), v.data_ptr(), D, float(eps), dc.data_ptr(), dk.data_ptr())
+    return dc, dk
+
+
+def source_grad_gatedgcn(G, Z, dY, Den, nodePointer, edgeList, eps=1e-6):
+    """Not in the reference module: (dq, dv), the source side of forward_gatedgcn's backward (tcgnn_gatedgcn_source_grad), fp32 [N, D]
+    each: dq[j] = the sum of G[e] over the edges that read j (G: backward_gatedgcn's dc), dv[j] = the sum over the same edges of
+    sigmoid(Z[e]) * dY[row(e)] / (Den[row(e)] + eps) - ONE walk over the rows of A^T for both (fp64 sums in a fixed order, no atomics).
+    The transposed CSR is the module's cached one (transpose_graph): built at the first call for a graph, or by prepare(..., gated=True)."""
+    N, E, D = _gatedgcn_nodes(dY, "dY", ((Den, "Den"),), nodePointer, edgeList)
+    _edge_rows(G, "G", E, D, nodePointer)
+    _edge_rows(Z, "Z", E, D, nodePointer)
+    dq, dv = torch.empty_like(dY), torch.empty_like(dY)
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_gatedgcn_source_grad, dY.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, G.data_ptr(), Z.data_ptr(), dY.data_ptr(),
+          Den.data_ptr(), D, float(eps), dq.data_ptr(), dv.data_ptr())
     return dq, dv
 
 

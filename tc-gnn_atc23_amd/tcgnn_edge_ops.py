@@ -18,13 +18,14 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate_uep(X, A, We, be, rowptr, col, act)  aggregate_ue with Ef = A We + be formed inside the walk, A [E, K] (GINE with edge_dim)   bwd: (dA, dWe, dbe) from one walk by row, dX from one over A^T; no [E, D] tensor either way
     edge_sum(M, rowptr, col)      Y[i, d] = sum over row i of M[e, d], M [E, D] (copy_e)                        bwd: dM[e] = dY[row e]
     aggregate_gated(k, q, v, rowptr, col)  Y[i, d] = sum over row i of sigmoid(k[i, d] + q[col e, d]) v[col e, d] (ResGatedGraphConv)   bwd: dk = dY * S (S: the forward's second output), (dq, dv) from one walk over A^T
+    aggregate_gatedgcn(k, q, v, c, rowptr, col, eps)  Z[e] = k[row e] + q[col e] + c[e] and Y[i] = sum of sigmoid(Z[e]) v[col e] / (sum of sigmoid(Z[e]) + eps), c and Z [E, D] (GatedGCN)   bwd: (dc, dk) from one walk by row, (dq, dv) from one over A^T
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
 weights are not symmetric (the backend then permutes the values over A's own plan).
 
 The operators come from tcgnn_layers.backend(): forward_ef2, edge_softmax, edge_softmax_backward, forward_AGNN(transpose=),
-forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum, forward_uep, backward_uep, source_grad_uep, forward_gated, source_grad_gated (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
+forward_heads(transpose=), forward_ef_heads, forward_max, backward_max, forward_stats, backward_stats, forward_ue, backward_ue, edge_sum, forward_uep, backward_uep, source_grad_uep, forward_gated, source_grad_gated, forward_gatedgcn, backward_gatedgcn, source_grad_gatedgcn (with transpose_graph) and the gat_* / gatv2_* calls.  A backend without them is an error - there is no composed fallback in this module (a
 stand-in backend installed with tcgnn_layers.set_backend is given forward_heads and forward_ef_heads there, by their per-head definitions, if it has none).
 """
 import torch
@@ -394,6 +395,44 @@ def aggregate_gated(k, q, v, row_pointers, column_index):
     if k.dim() != 2 or q.shape != k.shape or v.shape != k.shape:
         raise RuntimeError("k, q and v must be [N, D] tensors of one shape, got %s, %s and %s" % (tuple(k.shape), tuple(q.shape), tuple(v.shape)))
     return _AggregateGated.apply(k, q, v, row_pointers, column_index)
+
+
+class _AggregateGatedGCN(torch.autograd.Function):
+    """(Y, Z) = forward_gatedgcn(k, q, v, c)[:2]; backward: (dc, dk) = backward_gatedgcn - one walk by row, which recomputes the gate
+    from the stored Z -, (dq, dv) = source_grad_gatedgcn(dc) - one walk over A^T.  Saved: v, Y, Den ([N, D]) and Z ([E, D], an output
+    that exists anyway); k, q and c are not.  A Z nobody used sends dZ = None down, and the row side reads no [E, D] gradient."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, c, row_pointers, column_index, eps):
+        k, q, v, c = k.contiguous(), q.contiguous(), v.contiguous(), c.contiguous()
+        ctx.graph, ctx.eps = (row_pointers, column_index), eps
+        Y, Z, Den = _L.backend().forward_gatedgcn(k, q, v, c, row_pointers, column_index, eps)
+        ctx.save_for_backward(v, Z, Y, Den)
+        ctx.set_materialize_grads(False)
+        return Y, Z
+
+    @staticmethod
+    def backward(ctx, d_y, d_z):
+        v, Z, Y, Den = ctx.saved_tensors
+        d_y = torch.zeros_like(Y) if d_y is None else d_y.contiguous()
+        d_c, d_k = _L.backend().backward_gatedgcn(d_y, None if d_z is None else d_z.contiguous(), Y, Den, Z, v, *ctx.graph, ctx.eps)
+        d_q = d_v = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            d_q, d_v = _L.backend().source_grad_gatedgcn(d_c, Z, d_y, Den, *ctx.graph, ctx.eps)
+        need = ctx.needs_input_grad
+        return (d_k if need[0] else None), (d_q if need[1] else None), (d_v if need[2] else None), (d_c if need[3] else None), None, None, None
+
+
+def aggregate_gatedgcn(k, q, v, c, row_pointers, column_index, eps=1e-6):
+    """(Y, Z): Z[e, d] = k[row e, d] + q[col e, d] + c[e, d], the new edge feature ([E, D], CSR position order), and
+    Y[i, d] = sum over the edges e of row i of sigmoid(Z[e, d]) v[col e, d] / (sum over the same edges of sigmoid(Z[e, d]) + eps): the
+    aggregation of GatedGCN with edge features (DGL's GatedGCNConv, the local layer of GraphGPS).  k, q, v: [N, D]; c: [E, D].  One fused
+    walk forward, one by row and one over A^T back; of size E only c, Z and their gradients exist.  fp64 sums in a fixed order, no
+    atomics; exact on any graph."""
+    if k.dim() != 2 or q.shape != k.shape or v.shape != k.shape or c.dim() != 2 or c.size(1) != k.size(1):
+        raise RuntimeError("k, q and v must be [N, D] tensors of one shape and c [E, D], got %s, %s, %s and %s"
+                           % (tuple(k.shape), tuple(q.shape), tuple(v.shape), tuple(c.shape)))
+    return _AggregateGatedGCN.apply(k, q, v, c, row_pointers, column_index, float(eps))
 
 
 class _EdgeSum(torch.autograd.Function):

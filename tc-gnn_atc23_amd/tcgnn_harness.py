@@ -34,7 +34,7 @@ def build_parser():
     p.add_argument("--hidden", type=int, default=16, help="hidden dimension")
     p.add_argument("--classes", type=int, default=22, help="number of output classes")
     p.add_argument("--epochs", type=int, default=200, help="number of epoches")
-    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna", "gine", "resgated"])
+    p.add_argument("--model", type=str, default="gcn", help="GNN model", choices=["gcn", "gin", "agnn", "gat", "gatv2", "sage", "transformer", "pna", "gine", "resgated", "gatedgcn"])
     p.add_argument("--single_kernel", action="store_true", help="whether to profile a single SAG kernel")
     p.add_argument("--synthetic", type=str, default=None, help="named synthetic shape instead of a dataset file")
     p.add_argument("--scale", type=float, default=1.0, help="shrink a synthetic shape (N*scale, nnz*scale^2)")
@@ -60,7 +60,7 @@ def build_parser():
     p.add_argument("--fuse-edge", dest="fuse_edge", action="store_true",
                    help="GINE only: form the edge projection inside the message walk (GINEConv(fuse_edge=True): no [E, hidden] tensor; not in the reference)")
     p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
-                   help="GINE only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
+                   help="GINE and GatedGCN only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
     p.add_argument("--fanout", type=str, default=None,
                    help="K[,K...]: train every epoch on a freshly sampled graph that keeps at most K in-edges per node (TCGNN.sample_neighbors, seed + epoch); "
                    "several values give one fan-out per layer, input layer first; the final loss is evaluated on the full graph (not in the reference)")
@@ -182,6 +182,29 @@ class Net(nn.Module):
         return F.log_softmax(x, dim=1)
 
 
+class GatedGCNNet(nn.Module):
+    """num_layers GatedGCNConv layers of width `hidden` (the ReLU is inside the layer) -> linear read-out -> log_softmax, with Net's
+    dropout behind the first layer.  attr(graph) gives a graph's edge features [E, edge_dim].  flow=True (every layer runs on ONE graph):
+    the first layer takes attr(graph) and every later one the e' of the layer before it, `hidden` wide.  flow=False (a graph per
+    layer: positions differ from layer to layer): every layer takes its own graph's attr."""
+
+    def __init__(self, in_dim, hidden, classes, num_layers, edge_dim, flow, attr):
+        import tcgnn_layers as L
+        super().__init__()
+        self.convs = nn.ModuleList(L.GatedGCNConv(hidden if i else in_dim, hidden if i and flow else edge_dim, hidden) for i in range(num_layers))
+        self.readout = nn.Linear(hidden, classes)
+        self.flow, self.attr = bool(flow), attr
+
+    def forward(self, x, meta):
+        per_layer = list(meta) if isinstance(meta[0], (list, tuple)) else [meta] * len(self.convs)
+        e = None
+        for i, (conv, m) in enumerate(zip(self.convs, per_layer)):
+            x, e = conv(x, e if i and self.flow else self.attr(m), *m)
+            if i == 0:
+                x = F.dropout(x, training=self.training)
+        return F.log_softmax(self.readout(x), dim=1)
+
+
 def load_graph(args):
     import tcgnn_graph as G
     if args.synthetic:
@@ -236,6 +259,9 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     model 'pna' (not in the reference): PNAConv layers with their default aggregators and scalers; the transposed CSR is prepared as for SAGE's max.
     model 'gine' (not in the reference): GINEConv layers with edge_dim=edge_dim; no dataset here has edge features, so edge_attr [E, edge_dim] is drawn
     ONCE, standard normal, from a generator on the device seeded with `seed`, and every layer reads it; the transposed CSR is prepared as for SAGE's max.
+    model 'gatedgcn' (not in the reference): GatedGCNNet - GatedGCNConv layers of width hidden and a linear read-out - on the same drawn edge_attr; on the full
+    graph the edge features flow from layer to layer, on sampled graphs (fanout, batch_size, the subgraph samplers) every layer takes its graph's edge_attr[eid];
+    the transposed CSR is prepared as for 'resgated'.
     fuse_edge (GINE only): GINEConv(fuse_edge=True) - the edge projection formed inside the walk; the scratch of its backward is prepared with the transposed CSR.
     fanout (not in the reference; None: the path above, unchanged): a list of one fan-out per layer.  Every epoch, dry ones included, draws
     tcgnn_layers.sample_meta(meta, k, seed + epoch) per distinct k, builds what the model's operators need on it (the plan at every width and,
@@ -299,6 +325,9 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     elif model_name == "sage":
         def conv_cls(a, b, **kw):
             return L.SAGEConv(a, b, aggregator=aggregator, **kw)
+    elif model_name == "gatedgcn":
+        edge_attr = torch.randn(meta[1].numel(), int(edge_dim), device=x.device, generator=torch.Generator(device=x.device).manual_seed(seed))
+        conv_cls = None   # (GatedGCNNet below: its layers take and return edge features)
     elif model_name == "gine":
         edge_attr = torch.randn(meta[1].numel(), int(edge_dim), device=x.device, generator=torch.Generator(device=x.device).manual_seed(seed))
 
@@ -327,7 +356,11 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         conv_kwargs["attention"] = attention
     if multi_head or model_name in ("pna", "gine", "resgated"):
         conv_kwargs.pop("directed", None)   # (GATConv, GATv2Conv, TransformerConv, PNAConv, GINEConv and ResGatedGraphConv back-propagate through A^T on every graph)
-    model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
+    if model_name == "gatedgcn":   # (on the full graph the edge features flow from layer to layer; sampled layers take their own edge_attr[eid])
+        model = GatedGCNNet(in_dim, hidden, classes, num_layers, int(edge_dim), fanout is None and not subgraph,
+                            lambda graph: sampled_attr.get(graph[1].data_ptr(), edge_attr)).to(x.device)
+    else:
+        model = Net(conv_cls, in_dim, hidden, classes, num_layers, out_cls=out_cls, **conv_kwargs).to(x.device)
     optimizer = make_adam(model.parameters())
 
     def train():
@@ -339,7 +372,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         return loss
 
     prep = getattr(L.backend(), "prepare", None)
-    planless = model_name in ("pna", "gine", "resgated") or (model_name == "sage" and aggregator != "mean")
+    planless = model_name in ("pna", "gine", "resgated", "gatedgcn") or (model_name == "sage" and aggregator != "mean")
 
     def prepare(meta):
         """what this model's operators need on the graph `meta`, built now: nothing is built (or synchronised) inside a step"""
@@ -353,8 +386,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         elif prep is not None and meta[0].is_cuda and model_name == "gine" and fuse_edge:
             # (the transposed CSR and, at every width a layer aggregates at, the scratch of backward_uep's partials)
             prep([in_dim] + [hidden] * max(1, num_layers - 1), *meta, max_aggregation=True, edge_project=int(edge_dim))
-        elif prep is not None and meta[0].is_cuda and model_name == "resgated":
-            prep([], *meta, gated=True)   # (forward_gated / source_grad_gated are planless: the transposed CSR is all they need)
+        elif prep is not None and meta[0].is_cuda and model_name in ("resgated", "gatedgcn"):
+            prep([], *meta, gated=True)   # (the gated calls are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
             prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at
@@ -415,7 +448,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
                 m = L.csr_meta(m[0], m[1])
                 batch.metas = [m] * num_layers   # (one tuple object: a layer's plan is looked up, not rebuilt)
             prepare(m)
-            if model_name == "gine":
+            if model_name in ("gine", "gatedgcn"):
                 sampled_attr[m[1].data_ptr()] = edge_attr[batch.eids[0].long()]
             t = lap("plan_ms", t)
             model.train()
@@ -479,7 +512,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
                 if not planless:
                     m = batch.metas[i] = L.csr_meta(m[0], m[1])
                 prepare(m)
-                if model_name == "gine":
+                if model_name in ("gine", "gatedgcn"):
                     sampled_attr[m[1].data_ptr()] = edge_attr[eid.long()]
             t = lap("plan_ms", t)
             model.train()
@@ -533,7 +566,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
                     m = L.csr_meta(m[0], m[1])
                     drawn[k] = (m, eid)
                 prepare(m)
-                if model_name == "gine":
+                if model_name in ("gine", "gatedgcn"):
                     sampled_attr[m[1].data_ptr()] = edge_attr[eid.long()]
             t = lap("plan_ms", t)
             meta = [drawn[k][0] for k in fanout]
@@ -625,7 +658,7 @@ def run(args, quiet=False):
         result["sag_ms"] = L.SAG(*meta).profile(x)
         return result
 
-    if args.model == "gine":
+    if args.model in ("gine", "gatedgcn"):
         say("edge_attr:\t[%d, %d] standard normal, drawn once on the device from seed %d (the dataset carries no edge features)"
             % (meta[1].numel(), getattr(args, "edge_dim", 16), args.seed))
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,

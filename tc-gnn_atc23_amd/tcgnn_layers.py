@@ -930,6 +930,75 @@ class ResGatedGraphConv(torch.nn.Module):
         return out + self.bias if self.bias is not None else out
 
 
+class _AddBias(torch.autograd.Function):
+    """X + b for a tall X [N, M] with db = 1^T g formed as a tall product (tall_tn_mm).  With torch's own column sum a captured
+    GatedGCNConv step replayed a bias gradient that differed from the eager one (supposed cause: the memset with which
+    its multi-block reduction clears its semaphores, a node that not every HIP runtime replays)."""
+
+    @staticmethod
+    def forward(ctx, X, b):
+        return X + b
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        d_b = tall_tn_mm(g.new_ones(g.shape[0], 1), g).view(-1) if ctx.needs_input_grad[1] else None
+        return g, d_b
+
+
+class GatedGCNConv(torch.nn.Module):
+    """Not in the reference: the GatedGCN layer with edge features (Bresson & Laurent's layer as "Benchmarking GNNs" trains it) after
+    DGL's GatedGCNConv, which it follows in its signature - (X, edge_attr, graph) -> (h', e'):
+        e_ij = X[i] W_E + X[j] W_D + edge_attr[ij] W_C                                      (each with its bias; i <- j)
+        h'   = [X +] relu(bn(X W_A + sum_j sigmoid(e_ij) * (X[j] W_B) / (sum_j sigmoid(e_ij) + eps)))
+        e'   = [edge_attr +] relu(bn(e_ij))
+    The layer UPDATES the edge features: e' ([E, out_feats], CSR position order) is what the next layer takes as edge_attr.  The four
+    node projections are ONE dense product with `weights` = [W_A | W_B | W_D | W_E] ([in_feats, 4 out_feats]) and `bias`; edge_attr W_C
+    + b_C is a dense product too (`weights_edge`, `bias_edge`); e_ij, the gates and the gated mean are tcgnn_edge_ops.aggregate_gatedgcn:
+    one fused walk forward, one by row and one over A^T back, exact gradients on any graph.  A residual applies only where its widths
+    match (in_feats == out_feats; edge_feats == out_feats).  batch_norm=False drops both normalisations.  Glorot-uniform weights (each
+    projection on its own), zero biases."""
+
+    def __init__(self, in_feats, edge_feats, out_feats, batch_norm=True, residual=True, eps=1e-6):
+        super().__init__()
+        self.in_feats, self.edge_feats, self.out_feats, self.eps = int(in_feats), int(edge_feats), int(out_feats), float(eps)
+        self.residual = bool(residual)
+        self.weights = torch.nn.Parameter(torch.empty(self.in_feats, 4 * self.out_feats))
+        self.bias = torch.nn.Parameter(torch.zeros(4 * self.out_feats))
+        self.weights_edge = torch.nn.Parameter(torch.empty(self.edge_feats, self.out_feats))
+        self.bias_edge = torch.nn.Parameter(torch.zeros(self.out_feats))
+        self.bn_nodes = torch.nn.BatchNorm1d(self.out_feats) if batch_norm else None
+        self.bn_edges = torch.nn.BatchNorm1d(self.out_feats) if batch_norm else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for w in self.weights.data.split(self.out_feats, dim=1):
+            torch.nn.init.xavier_uniform_(w)
+        torch.nn.init.xavier_uniform_(self.weights_edge)
+        self.bias.data.zero_()
+        self.bias_edge.data.zero_()
+        for bn in (self.bn_nodes, self.bn_edges):
+            if bn is not None:
+                bn.reset_parameters()
+
+    def forward(self, X, edge_attr, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+        import tcgnn_edge_ops as E   # (it imports this module)
+        if edge_attr.dim() != 2 or edge_attr.shape != (column_index.numel(), self.edge_feats):
+            raise ValueError("edge_attr must be [num_edges, edge_feats] = [%d, %d], got %s" % (column_index.numel(), self.edge_feats, tuple(edge_attr.shape)))
+        Ah, Bh, Dh, Eh = _AddBias.apply(dense_update(X, self.weights), self.bias).split(self.out_feats, dim=1)
+        c = _AddBias.apply(dense_update(edge_attr, self.weights_edge), self.bias_edge)
+        Y, e = E.aggregate_gatedgcn(Eh, Dh, Bh, c, row_pointers, column_index, self.eps)
+        h = Ah + Y
+        if self.bn_nodes is not None:
+            h, e = self.bn_nodes(h), self.bn_edges(e)
+        h, e = torch.relu(h), torch.relu(e)
+        if self.residual and self.in_feats == self.out_feats:
+            h = X + h
+        if self.residual and self.edge_feats == self.out_feats:
+            e = edge_attr + e
+        return h, e
+
+
 PNA_AGGREGATORS = ("mean", "std", "max", "min")
 PNA_SCALERS = ("identity", "amplification", "attenuation")
 
