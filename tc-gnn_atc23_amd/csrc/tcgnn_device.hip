@@ -354,6 +354,9 @@ static int g_lds_dbg = [] { const char* e = getenv("TCGNN_LDS_DBG"); return e ? 
 static constexpr int g_lds_dbg = 0;
 #endif
 static constexpr int g_lds_fill_quota = 1;     // (r03: the wavefronts with an empty last slot take the range fills, -0.5 %)
+// the long walk's fill_quota word: + bit 1, the spread schedule of its range fills (tcgnn_lds_flat_kernel.inc).  TCGNN_LDS_FILL_SPREAD=0
+// (test knob, read per launch: tests compare the two schedules on one plan) restores the burst at the top of every entry
+static int lds_long_fill_quota() { const char* e = test_knob("TCGNN_LDS_FILL_SPREAD"); const int v = e ? atoi(e) : 1; return g_lds_fill_quota | (v ? 2 : 0); }
 static int g_spmm_mode = [] { const char* e = getenv("TCGNN_SPMM_MODE"); return e ? atoi(e) : 0; }();
 static inline int spmm_mode_of(const tcgnn_plan* p) { const int m = p ? (int)p->spmm_mode.load(std::memory_order_relaxed) : -1; return m >= 0 ? m : g_spmm_mode; }
 static constexpr size_t kBlockedMinBytes = 6u << 20;   // below this X16 is (nearly) L2-resident anyway

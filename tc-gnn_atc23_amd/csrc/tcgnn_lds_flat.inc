@@ -50,7 +50,8 @@ struct SpmmFlatArgs {
     int32_t nent;               // entries of the stream (the descriptor words start at rl2 + 4 nent)
     const float* w;             // f3 (as SpmmLdsArgs::w)
     int32_t dout, accumulate;
-    int32_t fill_quota;         // 1: the wavefronts whose last window slot is empty do the range fills (TCGNN_LDS_FILL_QUOTA=0: everybody fills)
+    int32_t fill_quota;         // not 0: the wavefronts whose last window slot is empty do the range fills (0: everybody fills); bit 1 (the long walk
+                                // only): a normal entry's fill goes out one instruction at a time between its tile steps (TCGNN_LDS_FILL_SPREAD=0: in one burst at its top)
     // the cold remainder INSIDE the kernel (layouts with 16 x NT KB of LDS to spare): per wavefront a list of cold tiles in
     // 256-byte records - 32 column ids (window slot in the top four bits), 16 mask words - of which it multiplies one per range (see cold_step)
     const int32_t* wcold_ptr;   // [nwg * 16 + 1] first record of every (workgroup, wavefront); nullptr: no in-kernel remainder
@@ -217,6 +218,29 @@ struct FlatRangeFiller {
         (void)lane;
         rank = rank_; nfill = nfill_; plane0 = plane0_; nplanes = nplanes_; xrows = xrows_;
     }
+    // instruction q of this wavefront's share of a range: k = rank + nfill q of the TOTAL (none where k >= TOTAL); lrow, hoff: lane / 2,
+    // 16 (lane % 2)
+    __device__ __forceinline__ void issue(int q, int r0, uint32_t buf, uint32_t lrow, int hoff) const {
+        const int k = rank + nfill * q;                         // (wave-uniform)
+        if (k < TOTAL) {
+            const int plane = k / IPP, blk = k - plane * IPP;
+            const bool real_plane = plane0 + plane < nplanes;   // (a pass whose last plane lies beyond the matrix: all zeros)
+            const uint32_t row = (uint32_t)(blk * 32) + lrow;
+            const uint32_t want = (uint32_t)r0 + row;
+            const uint32_t srow = (row < (uint32_t)(BR - 8) && real_plane && want < zrow) ? want : zrow;
+            const int pbase = real_plane ? (plane0 + plane) * xrows : 0;
+            __builtin_amdgcn_struct_ptr_buffer_load_lds(xrsrc, (LDS_AS void*)(uintptr_t)(buf + (uint32_t)plane * (BR * 32u) + (uint32_t)blk * 1024u), 16,
+                                                        pbase + (int)srow, hoff, 0, 0, 0);
+        }
+    }
+    // ONE instruction of the share, for a walk that deals the fill out between its tile steps (the long walk): the lane id is
+    // re-derived at every call, so nothing of the fill lives from one slice to the next
+    __device__ __forceinline__ void fill_one(int q, int r0, uint32_t buf) const {
+        if (rank < 0) return;
+        const uint32_t l2 = lane_id_now();
+        issue(q, r0, buf, l2 >> 1, (int)(l2 & 1u) * 16);
+    }
+    // the whole share, back to back
     __device__ __forceinline__ void fill(int r0, uint32_t buf) const {
         if (rank < 0) return;
         // (lane / 2 and lane % 2 are re-derived per call - mbcnt - instead of kept: the kernel has no register to spare, and hipcc
@@ -225,19 +249,7 @@ struct FlatRangeFiller {
         const uint32_t lrow = l2 >> 1;
         const int hoff = (int)(l2 & 1u) * 16;
 #pragma unroll
-        for (int q = 0; q < MAXC; ++q) {
-            const int k = rank + nfill * q;                         // (wave-uniform)
-            if (k < TOTAL) {
-                const int plane = k / IPP, blk = k - plane * IPP;
-                const bool real_plane = plane0 + plane < nplanes;   // (a pass whose last plane lies beyond the matrix: all zeros)
-                const uint32_t row = (uint32_t)(blk * 32) + lrow;
-                const uint32_t want = (uint32_t)r0 + row;
-                const uint32_t srow = (row < (uint32_t)(BR - 8) && real_plane && want < zrow) ? want : zrow;
-                const int pbase = real_plane ? (plane0 + plane) * xrows : 0;
-                __builtin_amdgcn_struct_ptr_buffer_load_lds(xrsrc, (LDS_AS void*)(uintptr_t)(buf + (uint32_t)plane * (BR * 32u) + (uint32_t)blk * 1024u), 16,
-                                                            pbase + (int)srow, hoff, 0, 0, 0);
-            }
-        }
+        for (int q = 0; q < MAXC; ++q) issue(q, r0, buf, lrow, hoff);
     }
 };
 

@@ -183,10 +183,24 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
     uint32_t buf = 0u;               // range buffer of the current entry
     int r = 0;
     uint32_t t0 = 0u, t1 = 0u, t2 = 0u;
+    // LONG, the spread schedule (fill_quota bit 1): a normal entry's fill does not go out as one burst at its top - 60 LDS-DMA
+    // instructions, four or five back to back per filling wavefront, whose 61 KB of LDS writes all meet the entry's first tile steps -
+    // but one instruction per filling wavefront in front of tile step q * kSpreadStride, q = 0 .. MAXC - 1 (fill_one).  Every slice
+    // lies in front of a step that every wavefront takes (the empty last slot's `break` is behind them), between the asm statements of
+    // the walk, and the end-of-entry wait retires it as it retired the burst: the buffer protocol is the same.  Dense entries, the
+    // prologue's fill and the multiply-off timing switch (which has no tile steps) keep the burst.
+    using Filler = FlatRangeFiller<NT, kLdsBufRows>;
+    // (priced on sbm_reddit, D = 64, against the burst's 0.502 ms: this dealing - the light wavefronts' up to MAXC = 5 slices at steps
+    //  0 .. 4 - 0.493; all sixteen wavefronts with four slices at steps 0, 2, 4, 6: 0.495)
+    constexpr int kSpreadStride = 1, kSpreadSlices = Filler::MAXC;
+    static_assert(!LONG || (kSpreadSlices - 1) * kSpreadStride < T - 1, "every slice in front of a tile step that no wavefront skips");
+    bool spread = false;
+    if constexpr (LONG) spread = (a.fill_quota & 2) != 0 && !(dbg & 2);
+    uint32_t tfill = 0u;             // (phase timers: cycles of this entry's fill issue inside the walk)
     // top of an entry: the fill its w2 names goes out, into the buffer the entries before this one have finished with
-    auto entry_top = [&]() {
+    auto entry_top = [&](bool burst) {
         t0 = (dbg & 16) ? (uint32_t)__builtin_readcyclecounter() : 0u;
-        if (ew2 != ~0u && !(dbg & 1)) filler.fill((int)((dbg & 128) ? (ew2 & 7u) : ew2) * kLdsRows, lds0 + (buf ^ 1u) * BUFB);   // (128: every fill from the same 8 ranges - an L2-resident source, for the ingest-rate measurement)
+        if (burst && ew2 != ~0u && !(dbg & 1)) filler.fill((int)((dbg & 128) ? (ew2 & 7u) : ew2) * kLdsRows, lds0 + (buf ^ 1u) * BUFB);   // (128: every fill from the same 8 ranges - an L2-resident source, for the ingest-rate measurement)
         t1 = (dbg & 16) ? (uint32_t)__builtin_readcyclecounter() : 0u;
     };
     // end of an entry: wait for what was requested an entry ago, take the next entry's words, the cold remainder's step, the requests
@@ -212,10 +226,14 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
         }
         const uint32_t t3 = (dbg & 16) ? (uint32_t)__builtin_readcyclecounter() : 0u;
         if (!(dbg & 8)) __builtin_amdgcn_s_barrier();
-        if (dbg & 16) { const uint32_t t4 = (uint32_t)__builtin_readcyclecounter(); ph[0] += t1 - t0; ph[1] += t2 - t1; ph[2] += t3 - t2; ph[3] += t4 - t3; }
+        if (dbg & 16) {
+            const uint32_t t4 = (uint32_t)__builtin_readcyclecounter(), tf = LONG ? tfill : 0u;   // (ph[0]: fill issue, wherever in the entry it went out)
+            ph[0] += t1 - t0 + tf; ph[1] += t2 - t1 - tf; ph[2] += t3 - t2; ph[3] += t4 - t3;
+        }
     };
     for (; r < nr && !(ew0 >> 31); ++r) {   // ---- normal entries
-        entry_top();
+        entry_top(!spread);
+        tfill = 0u;
         const uint32_t padaddr = pad0 + (uint32_t)(r & 1) * PADB, bb = lanebase + buf * BUFB;
         if (!(dbg & 2)) {
             FlatMeta<T> m;
@@ -239,6 +257,13 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
                 if (x / TPC == MAXW - 1 && !last_valid) break;      // (the first comparison folds once unrolled; nothing is in flight here: lds_flat_step_if)
                 // (priority falls as a wavefront advances through its windows: whoever is behind on the SIMD goes first)
                 if (x % TPC == 0 && !(dbg & 32)) set_wave_priority(3 - (x / TPC) * 4 / MAXW);
+                if constexpr (LONG) {   // slice x / kSpreadStride of the next range's fill (wave-uniform tests; x is a compile-time constant)
+                    if (x % kSpreadStride == 0 && x / kSpreadStride < kSpreadSlices && spread && ew2 != ~0u && !(dbg & 1)) {
+                        const uint32_t f0 = (dbg & 16) ? (uint32_t)__builtin_readcyclecounter() : 0u;
+                        filler.fill_one(x / kSpreadStride, (int)((dbg & 128) ? (ew2 & 7u) : ew2) * kLdsRows, lds0 + (buf ^ 1u) * BUFB);
+                        if (dbg & 16) tfill += (uint32_t)__builtin_readcyclecounter() - f0;
+                    }
+                }
                 const int cs = PIPE ? (x & 1) : 0;
                 if constexpr (!PIPE) { flat_issue<NT, PLANEB>(bb + (m.idw[x] & 0xffffu), bb + (m.idw[x] >> 16), lo[0], hi[0]); flat_drain<NT>(lo[0], hi[0]); }
                 else if (x + 1 < T && (x + 1) / TPC == MAXW - 1 && x / TPC != MAXW - 1)   // the step in front of the last slot: its reads only if the slot holds a window
@@ -271,7 +296,8 @@ __global__ __launch_bounds__(kLdsWaves * 64) void TCGNN_KERNEL_NAME(TCGNN_KERNEL
         dnext = d1;
     }
     for (; __builtin_expect(r < nr, 0); ++r) {                   // ---- dense entries
-        entry_top();
+        entry_top(true);
+        tfill = 0u;
         const uint32_t padaddr = pad0 + (uint32_t)(r & 1) * PADB, bb = lanebase + buf * BUFB;
         if (!(dbg & 2)) {
             // ---- a dense entry: up to T ordinary-format tiles of this wavefront in the pad, ew1 = tiles per window slot (4 bits each)

@@ -357,7 +357,7 @@ static int launch_lds(const SpmmCall& c, const SpmmRoute& r, const StagedImage& 
             f.blocks = cs.d_flat; f.order = cs.d_order; f.x16 = im.x16; f.hdr = im.hdr; f.y = c.d_Y;
             f.N = plan->N; f.D = D; f.stride = im.dpad / 16; f.chunk0 = p.chunk0; f.xrows = plan->Nc + 1; f.nw = plan->nw_eff; f.nwg = cs.nwg;
             f.dbg = g_lds_dbg; f.relu = has_cold ? 0 : c.relu; f.rbase = cs.d_rbase; f.rl2 = cs.d_rl2; f.nent = std::max(cs.npairs, 1);
-            f.w = c.d_W; f.dout = c.D_out; f.accumulate = r.accumulate; f.fill_quota = g_lds_fill_quota; f.wcold_ptr = cs.d_wcold_ptr; f.wcold = cs.d_wcold; f.fb = fb;
+            f.w = c.d_W; f.dout = c.D_out; f.accumulate = r.accumulate; f.fill_quota = slot == kLdsLongSlot ? lds_long_fill_quota() : g_lds_fill_quota; f.wcold_ptr = cs.d_wcold_ptr; f.wcold = cs.d_wcold; f.fb = fb;
             HIP_TRY(launch_flat_any(p.maxw, p.nt, cs.flat_tpc, f, p.nchunks, stream, cs.dense_entries > 0, has_cold ? no_epi : epi, slot == kLdsLongSlot));
             if (has_cold && !(g_lds_dbg & 16)) {
                 const int cd = lds_chunk_dims(p.maxw);
