@@ -906,6 +906,48 @@ int tcgnn_gatedgcn_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_
                                int32_t num_nodes, int64_t num_edges, const float* d_G, const float* d_Z, const float* d_dY,
                                const float* d_Den, int32_t D, float eps, float* d_dq, float* d_dv, void* stream);
 
+/* ---- Fused attention (multi-head dot-product attention over a node's incoming edges: PyG's TransformerConv, DGL's DotGatConv; no
+ * counterpart in the reference) ----
+ *
+ * Scores, their softmax by row and the weighted sum of the values in ONE walk per direction, the softmax done online inside the walk:
+ * nothing of size E is written or read.  CSR row = destination i, column = source j, e = CSR position.  q, k, v, Y, dY, dq, dk, dv are
+ * fp32 [num_nodes, H F] row-major, head h in columns h F .. h F + F; L and delta are fp32 [num_nodes, H]; d_q, d_k and d_v may alias
+ * one another, outputs may alias nothing.  Planless like tcgnn_gated_sum: device pointers, the caller's stream, no allocation, no
+ * synchronisation (capturable in a HIP graph); no atomics and every order fixed: bit-identical on repetition.  Everything is read as
+ * fp32 - no fp16 image, no range guard.  Any H >= 1 and F >= 1.
+ *   the score               s[h, e] = fl32(fl32(sum_f (double)q[i, hF+f] (double)k[j, hF+f]) * scale): exact products, an fp64 sum in a
+ *                           fixed order, rounded once, then ONE fp32 product.  All three calls form the same bits.
+ *   exp                     exp2(fl32(x * log2 e)) on the hardware exponential (tcgnn_edge_softmax's).
+ *   tcgnn_attn_forward      online: a running maximum m, l = sum (double)exp(s - m) and sum (double)exp(s - m) (double)v[j, hF+f] in fp64;
+ *                           when m rises, l and the sums are multiplied by exp(m_old - m_new); partial states are merged the same way,
+ *                           each rescaled to the common maximum.  Y[i, hF+f] = fl32(sum / l);  L[i, h] = fl32((double)m + log(l)), the
+ *                           log-sum-exp of the row's scores (d_L may be NULL: nothing is computed for it, Y has the same bits).  A row
+ *                           without edges: Y = 0, L = 0.
+ *   tcgnn_attn_backward     by row.  delta[i, h] = fl32(sum_f (double)dY[i, hF+f] (double)Y[i, hF+f]);  p = exp(fl32(s - L[i, h]));
+ *                           a = sum_f (double)dY[i, hF+f] (double)v[j, hF+f] in fp64;  g = (double)p (a - (double)delta[i, h]);
+ *                           dq[i, hF+f] = fl32((double)scale * sum over e in row i of g (double)k[j, hF+f]).  d_dq may be NULL: delta
+ *                           alone is produced, by a light kernel without the walk, and d_q, d_k, d_v, d_L may then be NULL too.
+ *   tcgnn_attn_source_grad  over the rows of A^T (d_nodePointer_t, d_edgeList_t, d_perm: what tcgnn_transpose_ws wrote; d_perm is not
+ *                           read and may be NULL).  For source row j and i = edgeList_t[eT]: s, p, a and g as above from L[i, h] and
+ *                           delta[i, h];  dk[j, hF+f] = fl32((double)scale * sum g (double)q[i, hF+f]);
+ *                           dv[j, hF+f] = fl32(sum (double)p (double)dY[i, hF+f]).  A source nobody reads gets 0 in both.
+ * Rows are read with 16-byte loads when F % 4 == 0 and every [num_nodes, H F] input of the call is 16-byte aligned, with 4-byte loads
+ * otherwise: the same bits either way.  Row pointers are clamped to [0, num_edges] and a descending pair is an empty row; a column id
+ * is clamped to the nearer end of [0, num_nodes): safe reads, values of no meaning for such arrays.  Every element of every output is
+ * written and nothing outside them.  num_nodes = 0 or H = 0 returns TCGNN_OK and writes nothing; F = 0 returns TCGNN_OK with L / delta
+ * zeroed where given; num_edges = 0 returns TCGNN_OK with the outputs zeroed (by a kernel); a negative size, num_edges >= 2^31,
+ * H F >= 2^31 or a null array otherwise: TCGNN_ERR_INVALID_ARG before anything is written.  A hub row stays on one workgroup. */
+int tcgnn_attn_forward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                       const float* d_q, const float* d_k, const float* d_v, int32_t H, int32_t F, float scale, float* d_Y,
+                       float* d_L /* may be NULL */, void* stream);
+int tcgnn_attn_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                        const float* d_q, const float* d_k, const float* d_v, const float* d_Y, const float* d_dY, const float* d_L,
+                        int32_t H, int32_t F, float scale, float* d_dq /* may be NULL */, float* d_delta, void* stream);
+int tcgnn_attn_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm /* not read */,
+                           int32_t num_nodes, int64_t num_edges, const float* d_q, const float* d_k, const float* d_v,
+                           const float* d_dY, const float* d_L, const float* d_delta, int32_t H, int32_t F, float scale,
+                           float* d_dk, float* d_dv, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

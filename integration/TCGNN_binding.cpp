@@ -943,6 +943,77 @@ std::tuple<torch::Tensor, torch::Tensor> source_grad_gatedgcn(torch::Tensor G, t
   return {dq, dv};
 }
 
+// ---- not in the reference: fused sparse attention (tcgnn_attn_forward / _backward / _source_grad; the ctypes module's forward_attn,
+// backward_attn and source_grad_attn) ------------------------------------------------------------------------------------------------
+namespace {
+struct AttnArgs {
+  int32_t N;
+  int64_t E;
+  int32_t H, F;
+  float scale;
+};
+AttnArgs attn_args(const torch::Tensor& q, std::initializer_list<const torch::Tensor*> others, int64_t heads, const torch::Tensor& nodePointer,
+                   const torch::Tensor& edgeList, c10::optional<double> scale) {
+  auto [N, E, D] = gatedgcn_nodes(q, "q", others, nodePointer, edgeList);
+  TORCH_CHECK(heads >= 1 && D % heads == 0, "heads must be >= 1 and divide the width ", D, ", got ", heads);
+  const int32_t F = (int32_t)(D / heads);
+  // (scale = None: F ** -0.5 as Python forms it, a double, narrowed once)
+  return {N, E, (int32_t)heads, F, (float)(scale.has_value() ? *scale : (F ? std::pow((double)F, -0.5) : 1.0))};
+}
+void attn_nodes(const torch::Tensor& t, const char* name, const AttnArgs& a, const torch::Tensor& q) {
+  CHECK_INPUT(t);
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == a.N && t.size(1) == a.H && t.device() == q.device(), name, " must be fp32 [num_nodes, heads] on q's device");
+}
+}  // namespace
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> forward_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v, int64_t heads, torch::Tensor nodePointer,
+                                                                     torch::Tensor edgeList, c10::optional<double> scale, bool return_lse,
+                                                                     c10::optional<torch::Tensor> out) {
+  const AttnArgs a = attn_args(q, {&k, &v}, heads, nodePointer, edgeList, scale);
+  torch::Tensor Y = out_like(out, q, "q");
+  check_out_apart(out, {&q, &k, &v});
+  DeviceGuard guard(q.device());
+  c10::optional<torch::Tensor> L;
+  if (return_lse) L = torch::empty({(int64_t)a.N, (int64_t)a.H}, q.options());
+  tcgnn_check(tcgnn_attn_forward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(),
+                                 a.H, a.F, a.scale, Y.data_ptr<float>(), L.has_value() ? L->data_ptr<float>() : nullptr, current_stream(q)),
+              "tcgnn_attn_forward");
+  return {Y, L};
+}
+
+std::tuple<c10::optional<torch::Tensor>, torch::Tensor> backward_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor Y, torch::Tensor dY,
+                                                                      torch::Tensor L, int64_t heads, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                                      c10::optional<double> scale, bool need_dq) {
+  const AttnArgs a = attn_args(q, {&k, &v, &Y, &dY}, heads, nodePointer, edgeList, scale);
+  attn_nodes(L, "L", a, q);
+  DeviceGuard guard(q.device());
+  c10::optional<torch::Tensor> dq;
+  if (need_dq) dq = torch::empty_like(q);
+  torch::Tensor delta = torch::empty({(int64_t)a.N, (int64_t)a.H}, q.options());
+  tcgnn_check(tcgnn_attn_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(), k.data_ptr<float>(), v.data_ptr<float>(),
+                                  Y.data_ptr<float>(), dY.data_ptr<float>(), L.data_ptr<float>(), a.H, a.F, a.scale,
+                                  dq.has_value() ? dq->data_ptr<float>() : nullptr, delta.data_ptr<float>(), current_stream(q)),
+              "tcgnn_attn_backward");
+  return {dq, delta};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> source_grad_attn(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor dY, torch::Tensor L,
+                                                          torch::Tensor delta, int64_t heads, torch::Tensor nodePointer, torch::Tensor edgeList,
+                                                          c10::optional<double> scale) {
+  const AttnArgs a = attn_args(q, {&k, &v, &dY}, heads, nodePointer, edgeList, scale);
+  attn_nodes(L, "L", a, q);
+  attn_nodes(delta, "delta", a, q);
+  DeviceGuard guard(q.device());
+  torch::Tensor dk = torch::empty_like(q), dv = torch::empty_like(q);
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_attn_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(),
+                                     k.data_ptr<float>(), v.data_ptr<float>(), dY.data_ptr<float>(), L.data_ptr<float>(), delta.data_ptr<float>(), a.H, a.F,
+                                     a.scale, dk.data_ptr<float>(), dv.data_ptr<float>(), current_stream(q)),
+              "tcgnn_attn_source_grad");
+  return {dk, dv};
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
   CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
@@ -1359,6 +1430,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Y"), py::arg("Den"), py::arg("Z"), py::arg("v"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("eps") = 1e-6);
   m.def("source_grad_gatedgcn", &source_grad_gatedgcn, "source side of forward_gatedgcn's backward: (dq, dv) (not in the reference)", py::arg("G"),
         py::arg("Z"), py::arg("dY"), py::arg("Den"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("eps") = 1e-6);
+  m.def("forward_attn", &forward_attn, "fused multi-head dot-product attention over every node's incoming edges, the softmax done online in one "
+        "walk: (Y, L) with L the rows' log-sum-exp (not in the reference)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("heads"),
+        py::arg("nodePointer"), py::arg("edgeList"), py::arg("scale") = py::none(), py::arg("return_lse") = true, py::arg("out") = py::none());
+  m.def("backward_attn", &backward_attn, "row side of forward_attn's backward: (dq, delta) (not in the reference)", py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("Y"), py::arg("dY"), py::arg("L"), py::arg("heads"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("scale") = py::none(),
+        py::arg("need_dq") = true);
+  m.def("source_grad_attn", &source_grad_attn, "source side of forward_attn's backward: (dk, dv) (not in the reference)", py::arg("q"), py::arg("k"),
+        py::arg("v"), py::arg("dY"), py::arg("L"), py::arg("delta"), py::arg("heads"), py::arg("nodePointer"), py::arg("edgeList"),
+        py::arg("scale") = py::none());
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

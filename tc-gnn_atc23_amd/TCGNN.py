@@ -38,7 +38,7 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
            "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "forward_gated", "source_grad_gated",
-           "forward_gatedgcn", "backward_gatedgcn", "source_grad_gatedgcn", "sample_neighbors", "compact_nodes", "compact_graph",
+           "forward_gatedgcn", "backward_gatedgcn", "source_grad_gatedgcn", "forward_attn", "backward_attn", "source_grad_attn", "sample_neighbors", "compact_nodes", "compact_graph",
            "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
@@ -553,7 +553,7 @@ def plan_info(nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, tr
 
 
 def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToRow, edge_valued=False, transpose=False, attention=False, heads=1,
-            max_aggregation=False, edge_project=None, gated=False):
+            max_aggregation=False, edge_project=None, gated=False, fused_attention=False):
     """Not part of the reference API: build, now, what the hot path would otherwise build at its first call of each feature width
     in `widths` (tcgnn_plan_prepare: the cell streams of the LDS-resident kernel where the plan's time model picks it; with
     edge_valued=True also tcgnn_plan_prepare_val: the single-edge stream forward_AGNN's LDS-resident walk reads).  After it no
@@ -575,8 +575,10 @@ def prepare(widths, nodePointer, edgeList, blockPartition, edgeToColumn, edgeToR
     edge_project=K (a model with GINEConv(fuse_edge=True) layers of edge_dim K: forward_uep / backward_uep / source_grad_uep): the
     transposed CSR source_grad_uep walks and the scratch of backward_uep's dWe / dbe partials at every width, on the current stream.
     gated=True (a model with ResGatedGraphConv or GatedGCNConv layers: forward_gated / source_grad_gated, forward_gatedgcn /
-    backward_gatedgcn / source_grad_gatedgcn): the transposed CSR the source-side calls walk, built now - the calls are planless and need nothing else."""
-    if max_aggregation or gated or edge_project is not None:
+    backward_gatedgcn / source_grad_gatedgcn): the transposed CSR the source-side calls walk, built now - the calls are planless and need nothing else.
+    fused_attention=True (a model with TransformerConv(fused=True) layers: forward_attn / backward_attn / source_grad_attn): the same
+    transposed CSR, built now, for source_grad_attn - the calls are planless too."""
+    if max_aggregation or gated or fused_attention or edge_project is not None:
         transpose_graph(nodePointer, edgeList)
     if edge_project is not None:
         with torch.cuda.device(nodePointer.device):
@@ -1670,6 +1672,79 @@ def source_grad_gatedgcn(G, Z, dY, Den, nodePointer, edgeList, eps=1e-6):
     _call(_c.lib.tcgnn_gatedgcn_source_grad, dY.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, G.data_ptr(), Z.data_ptr(), dY.data_ptr(),
           Den.data_ptr(), D, float(eps), dq.data_ptr(), dv.data_ptr())
     return dq, dv
+
+
+# ---- additions (not in the reference module): fused sparse attention (TransformerConv's dot-product attention in one walk) --
+
+def _attn_args(q, others, heads, nodePointer, edgeList, scale):
+    """(N, E, H, F, scale) of a fused-attention call: q and every tensor of `others` fp32 [N, heads * F] on one device"""
+    N, E, D = _max_args(q, "q", nodePointer, edgeList)
+    for t, n in others:
+        _check_input(t, n)
+        _check_float(t, n)
+        if t.shape != q.shape or t.device != q.device:
+            raise RuntimeError("%s must have the shape and device of q, got %s" % (n, tuple(t.shape)))
+    H = int(heads)
+    if H < 1 or D % H:
+        raise RuntimeError("heads must be >= 1 and divide the width %d, got %r" % (D, heads))
+    F = D // H
+    return N, E, H, F, float((F ** -0.5 if F else 1.0) if scale is None else scale)
+
+
+def _attn_nodes(t, name, N, H, like):
+    _check_input(t, name)
+    _check_float(t, name)
+    if tuple(t.shape) != (N, H) or t.device != like.device:
+        raise RuntimeError("%s must be fp32 [num_nodes, heads] = [%d, %d] on q's device, got %s" % (name, N, H, tuple(t.shape)))
+
+
+def forward_attn(q, k, v, heads, nodePointer, edgeList, scale=None, return_lse=True, out=None):
+    """Not in the reference module: (Y, L) of multi-head dot-product attention over every node's incoming edges (tcgnn_attn_forward),
+        s[h, e] = scale * <q[row(e), head h], k[col(e), head h]>;   p[h] = softmax of s[h] over each row;
+        Y[i, head h] = the sum over the edges e of row i of p[h, e] * v[col(e), head h];   L[i, h] = log sum_e exp(s[h, e])
+    in ONE walk with the softmax done online: no [heads, E] tensor exists.  q, k, v: fp32 [N, heads * F] (head h in columns h F ..
+    h F + F); they may be one tensor.  scale=None: F ** -0.5.  Everything is read as fp32, the sums are fp64 in a fixed order, rounded
+    once (include/tcgnn.h states the roundings).  A row without edges gives Y = 0, L = 0.  return_lse=False (inference): L is None,
+    Y has the same bits.  Deterministic, no atomics."""
+    N, E, H, F, sc = _attn_args(q, ((k, "k"), (v, "v")), heads, nodePointer, edgeList, scale)
+    res = _out_like(out, q, "q")
+    _out_apart(res, out, q, k, v)
+    lse = torch.empty(N, H, dtype=torch.float32, device=q.device) if return_lse else None
+    _call(_c.lib.tcgnn_attn_forward, q.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(), H, F, sc,
+          res.data_ptr(), _ptr(lse))
+    return res, lse
+
+
+def backward_attn(q, k, v, Y, dY, L, heads, nodePointer, edgeList, scale=None, need_dq=True):
+    """Not in the reference module: (dq, delta), the row side of forward_attn's backward (tcgnn_attn_backward).
+        delta[i, h] = <dY[i, head h], Y[i, head h]>   fp32 [N, heads]: what source_grad_attn needs;
+        dq[i, head h] = scale * the sum over the edges e of row i of p[h, e] (<dY[i], v[col(e)]> - delta[i, h]) * k[col(e), head h]
+    with p recomputed from L - one walk by row, fp64 sums in a fixed order.  need_dq=False: dq is None and only delta is formed (a
+    light kernel without the walk).  scale must be the forward's."""
+    N, E, H, F, sc = _attn_args(q, ((k, "k"), (v, "v"), (Y, "Y"), (dY, "dY")), heads, nodePointer, edgeList, scale)
+    _attn_nodes(L, "L", N, H, q)
+    dq = torch.empty_like(q) if need_dq else None
+    delta = torch.empty(N, H, dtype=torch.float32, device=q.device)
+    _call(_c.lib.tcgnn_attn_backward, q.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(), Y.data_ptr(),
+          dY.data_ptr(), L.data_ptr(), H, F, sc, _ptr(dq), delta.data_ptr())
+    return dq, delta
+
+
+def source_grad_attn(q, k, v, dY, L, delta, heads, nodePointer, edgeList, scale=None):
+    """Not in the reference module: (dk, dv), the source side of forward_attn's backward (tcgnn_attn_source_grad), fp32 [N, heads * F]
+    each: over the edges (i <- j) that read node j,
+        dv[j, head h] = the sum of p[h, e] * dY[i, head h];   dk[j, head h] = scale * the sum of p[h, e] (<dY[i], v[j]> - delta[i, h]) * q[i, head h]
+    - ONE walk over the rows of A^T gathers q[i] and dY[i] once per edge for both; the score is the forward's, bit for bit, and p comes
+    from L (forward_attn) and delta (backward_attn).  A node nobody reads gets 0.  The transposed CSR is the module's cached one
+    (transpose_graph): built at the first call for a graph, or by prepare(..., fused_attention=True)."""
+    N, E, H, F, sc = _attn_args(q, ((k, "k"), (v, "v"), (dY, "dY")), heads, nodePointer, edgeList, scale)
+    _attn_nodes(L, "L", N, H, q)
+    _attn_nodes(delta, "delta", N, H, q)
+    dk, dv = torch.empty_like(q), torch.empty_like(q)
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_attn_source_grad, q.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+          dY.data_ptr(), L.data_ptr(), delta.data_ptr(), H, F, sc, dk.data_ptr(), dv.data_ptr())
+    return dk, dv
 
 
 # ---- additions (not in the reference module): the two products of an AGNN layer in one pass ------------

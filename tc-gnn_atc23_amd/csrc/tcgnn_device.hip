@@ -64,6 +64,9 @@
 //   tcgnn_gatedgcn.inc        GatedGCN with edge features: that gate with a per-edge term, Z[e] = k[row] + q[col] + c[e] as a new [E, D] edge feature, the
 //                             gated mean sum(eta v) / (sum(eta) + eps), its row-side (G = dc, dk) and source-side (dq, dv) backward - one walk in four
 //                             modes, gathered [N, D] rows and non-temporal [E, D] streams interleaved (segment_max's scheduling)
+//   tcgnn_attn.inc            fused sparse attention: multi-head dot-product scores, their softmax done online and the weighted sum of the values in
+//                             one walk, the row-side (dq, delta) and source-side (dk, dv) backward one walk each - nothing of size E exists
+//                             (segment_max's scheduling, gatv2's head-wise lane layout)
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells (a cell stream in named steps over a
 //                             CellBuild; flat_entries, the entry records, is a pure host function; cells_publish cannot fail), build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
@@ -336,6 +339,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_edge_project.inc"
 #include "tcgnn_gated.inc"
 #include "tcgnn_gatedgcn.inc"
+#include "tcgnn_attn.inc"
 
 // ---- run-time switches.  Product: TCGNN_SPMM_MODE / TCGNN_RANGE_GUARD (initial values of tcgnn_set_spmm_mode / tcgnn_set_range_guard,
 // include/tcgnn.h) and TCGNN_VERBOSE (plan statistics on stderr).  TEST AIDS, read through test_knob() only - tests/ forces every walk

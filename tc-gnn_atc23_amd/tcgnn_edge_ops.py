@@ -19,6 +19,7 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     edge_sum(M, rowptr, col)      Y[i, d] = sum over row i of M[e, d], M [E, D] (copy_e)                        bwd: dM[e] = dY[row e]
     aggregate_gated(k, q, v, rowptr, col)  Y[i, d] = sum over row i of sigmoid(k[i, d] + q[col e, d]) v[col e, d] (ResGatedGraphConv)   bwd: dk = dY * S (S: the forward's second output), (dq, dv) from one walk over A^T
     aggregate_gatedgcn(k, q, v, c, rowptr, col, eps)  Z[e] = k[row e] + q[col e] + c[e] and Y[i] = sum of sigmoid(Z[e]) v[col e] / (sum of sigmoid(Z[e]) + eps), c and Z [E, D] (GatedGCN)   bwd: (dc, dk) from one walk by row, (dq, dv) from one over A^T
+    aggregate_attention(q, k, v, H, rowptr, col, scale)  Y[i, head h] = sum over row i of softmax_row(scale <q[i, head h], k[col e, head h]>) v[col e, head h] (TransformerConv, fused)   bwd: (dq, delta) from one walk by row, (dk, dv) from one over A^T; no [H, E] tensor either way
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
@@ -433,6 +434,43 @@ def aggregate_gatedgcn(k, q, v, c, row_pointers, column_index, eps=1e-6):
         raise RuntimeError("k, q and v must be [N, D] tensors of one shape and c [E, D], got %s, %s, %s and %s"
                            % (tuple(k.shape), tuple(q.shape), tuple(v.shape), tuple(c.shape)))
     return _AggregateGatedGCN.apply(k, q, v, c, row_pointers, column_index, float(eps))
+
+
+class _AggregateAttention(torch.autograd.Function):
+    """(Y, L) = forward_attn(q, k, v); backward: (dq, delta) = backward_attn - one walk by row, p recomputed from L -, then
+    (dk, dv) = source_grad_attn - one walk over A^T.  Saved: q, k, v, Y and L ([N, heads]) - nothing of size E.  The source side is
+    skipped when neither dk nor dv is wanted; without dq the row side forms delta alone."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, row_pointers, column_index, scale):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        ctx.graph, ctx.heads, ctx.scale = (row_pointers, column_index), heads, scale
+        Y, L = _L.backend().forward_attn(q, k, v, heads, row_pointers, column_index, scale)
+        ctx.save_for_backward(q, k, v, Y, L)
+        return Y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        q, k, v, Y, L = ctx.saved_tensors
+        d_y = d_y.contiguous()
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        d_q = d_k = d_v = None
+        if need_q or need_k or need_v:
+            d_q, delta = _L.backend().backward_attn(q, k, v, Y, d_y, L, ctx.heads, *ctx.graph, ctx.scale, need_q)
+            if need_k or need_v:
+                d_k, d_v = _L.backend().source_grad_attn(q, k, v, d_y, L, delta, ctx.heads, *ctx.graph, ctx.scale)
+        return d_q, (d_k if need_k else None), (d_v if need_v else None), None, None, None, None
+
+
+def aggregate_attention(q, k, v, heads, row_pointers, column_index, scale=None):
+    """Y[i, head h] = the sum over the edges e of CSR row i of p[h, e] v[col e, head h], p[h] = softmax by row of
+    scale <q[row e, head h], k[col e, head h]>: multi-head dot-product attention (TransformerConv) as ONE fused walk forward - the
+    softmax online - and two back.  q, k, v: [N, heads * F]; scale=None: F ** -0.5.  No [heads, E] tensor in either direction;
+    everything read as fp32, fp64 sums in a fixed order, no atomics; exact on any graph."""
+    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape or int(heads) < 1 or q.shape[1] % int(heads):
+        raise RuntimeError("q, k and v must be [N, heads * F] tensors of one shape, got %s, %s and %s with heads = %r"
+                           % (tuple(q.shape), tuple(k.shape), tuple(v.shape), heads))
+    return _AggregateAttention.apply(q, k, v, int(heads), row_pointers, column_index, None if scale is None else float(scale))
 
 
 class _EdgeSum(torch.autograd.Function):

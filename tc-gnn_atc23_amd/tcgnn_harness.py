@@ -59,6 +59,9 @@ def build_parser():
                    "features ('max') or of a learned projection of them ('pool') (not in the reference)")
     p.add_argument("--fuse-edge", dest="fuse_edge", action="store_true",
                    help="GINE only: form the edge projection inside the message walk (GINEConv(fuse_edge=True): no [E, hidden] tensor; not in the reference)")
+    p.add_argument("--fused-attention", dest="fused_attention", action="store_true",
+                   help="transformer only: every layer runs its attention as one fused walk with the softmax done online "
+                   "(TransformerConv(fused=True): no [heads, E] tensor, everything read as fp32; not in the reference)")
     p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
                    help="GINE and GatedGCN only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
     p.add_argument("--fanout", type=str, default=None,
@@ -244,7 +247,7 @@ def make_adam(params, lr=0.01):
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
                   norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fuse_edge=False, fanout=None,
-                  batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0):
+                  batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0, fused_attention=False):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -263,6 +266,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     graph the edge features flow from layer to layer, on sampled graphs (fanout, batch_size, the subgraph samplers) every layer takes its graph's edge_attr[eid];
     the transposed CSR is prepared as for 'resgated'.
     fuse_edge (GINE only): GINEConv(fuse_edge=True) - the edge projection formed inside the walk; the scratch of its backward is prepared with the transposed CSR.
+    fused_attention (transformer only): TransformerConv(fused=True) - the attention as one fused walk forward and two back; planless: only the transposed
+    CSR is prepared (prepare(..., fused_attention=True)).
     fanout (not in the reference; None: the path above, unchanged): a list of one fan-out per layer.  Every epoch, dry ones included, draws
     tcgnn_layers.sample_meta(meta, k, seed + epoch) per distinct k, builds what the model's operators need on it (the plan at every width and,
     for the layers with a `directed` switch, A^T's - a sampled graph is not symmetric, so those layers are built with directed=True - or, for
@@ -320,8 +325,10 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         out_cls = L.GATv2Conv
     elif model_name == "transformer":
         def conv_cls(a, b):
-            return L.TransformerConv(a, b // heads, heads=heads)
-        out_cls = L.TransformerConv
+            return L.TransformerConv(a, b // heads, heads=heads, fused=bool(fused_attention))
+
+        def out_cls(a, b):
+            return L.TransformerConv(a, b, fused=bool(fused_attention))
     elif model_name == "sage":
         def conv_cls(a, b, **kw):
             return L.SAGEConv(a, b, aggregator=aggregator, **kw)
@@ -341,6 +348,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         if aggregator != "mean":
             raise ValueError("aggregator applies to the SAGE model only")
         conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv, "resgated": L.ResGatedGraphConv}[model_name]
+    if fused_attention and model_name != "transformer":
+        raise ValueError("fused_attention applies to the transformer model only")
     if fuse_edge and model_name != "gine":
         raise ValueError("fuse_edge applies to the GINE model only")
     sampled_attr = {}
@@ -372,7 +381,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         return loss
 
     prep = getattr(L.backend(), "prepare", None)
-    planless = model_name in ("pna", "gine", "resgated", "gatedgcn") or (model_name == "sage" and aggregator != "mean")
+    planless = model_name in ("pna", "gine", "resgated", "gatedgcn") or (model_name == "sage" and aggregator != "mean") or bool(fused_attention)
 
     def prepare(meta):
         """what this model's operators need on the graph `meta`, built now: nothing is built (or synchronised) inside a step"""
@@ -388,6 +397,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
             prep([in_dim] + [hidden] * max(1, num_layers - 1), *meta, max_aggregation=True, edge_project=int(edge_dim))
         elif prep is not None and meta[0].is_cuda and model_name in ("resgated", "gatedgcn"):
             prep([], *meta, gated=True)   # (the gated calls are planless: the transposed CSR is all they need)
+        elif prep is not None and meta[0].is_cuda and fused_attention:
+            prep([], *meta, fused_attention=True)   # (the fused attention calls are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda and model_name in ("pna", "gine"):
             prep([], *meta, max_aggregation=True)   # (forward_stats / backward_stats, forward_ue / edge_sum are planless: the transposed CSR is all they need)
         elif prep is not None and meta[0].is_cuda:   # every width this model aggregates at
@@ -667,7 +678,8 @@ def run(args, quiet=False):
                       attention=getattr(args, "attention", "reference"), heads=getattr(args, "heads", 1),
                       aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fuse_edge=getattr(args, "fuse_edge", False), fanout=getattr(args, "fanout", None),
                       batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None),
-                      sampler=getattr(args, "sampler", "dense"), walk_length=getattr(args, "walk_length", 2), saint_norm=getattr(args, "saint_norm", 0))
+                      sampler=getattr(args, "sampler", "dense"), walk_length=getattr(args, "walk_length", 2), saint_norm=getattr(args, "saint_norm", 0),
+                      fused_attention=getattr(args, "fused_attention", False))
     if "sample_ms" in r:
         say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
     if "compact_ms" in r:

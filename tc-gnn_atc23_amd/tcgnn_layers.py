@@ -707,13 +707,16 @@ class TransformerConv(torch.nn.Module):
     (tcgnn_edge_ops.sddmm_heads - one multi-head SDDMM call -, edge_softmax_heads and aggregate_heads; gradients exact on any graph).
     The heads are concatenated ([N, heads * output_dim]) or, with concat=False, averaged ([N, output_dim]); with root_weight X W_root is
     added, then the output bias: a node without incoming edges gets the root term and the bias only.  bias=False drops b_q, b_k, b_v
-    and the output bias.  Glorot-uniform weights, zero biases.  No attention dropout."""
+    and the output bias.  Glorot-uniform weights, zero biases.  No attention dropout.
+    fused=True replaces the three operators by tcgnn_edge_ops.aggregate_attention: one fused walk forward with the softmax done online
+    and two back, everything read as fp32 and no [heads, E] tensor kept (the blockPartition / edgeToColumn / edgeToRow arguments are
+    then unused).  The default is the composition."""
 
-    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, bias=True):
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, bias=True, fused=False):
         super().__init__()
         if heads < 1:
             raise ValueError("heads must be >= 1, got %r" % (heads,))
-        self.heads, self.output_dim, self.concat = int(heads), int(output_dim), bool(concat)
+        self.heads, self.output_dim, self.concat, self.fused = int(heads), int(output_dim), bool(concat), bool(fused)
         wide = self.heads * self.output_dim
         out = wide if self.concat else self.output_dim
         for name in ("q", "k", "v"):
@@ -752,9 +755,12 @@ class TransformerConv(torch.nn.Module):
         Q = self._project(X, self.weights_q, self.bias_q)
         K = self._project(X, self.weights_k, self.bias_k)
         V = self._project(X, self.weights_v, self.bias_v)
-        S = E.sddmm_heads(Q, K, meta, self.heads)
-        P = E.edge_softmax_heads(S, row_pointers, self.scale.to(S.dtype))
-        Y = E.aggregate_heads(P, V, meta)
+        if self.fused:
+            Y = E.aggregate_attention(Q, K, V, self.heads, row_pointers, column_index, self.output_dim ** -0.5)
+        else:
+            S = E.sddmm_heads(Q, K, meta, self.heads)
+            P = E.edge_softmax_heads(S, row_pointers, self.scale.to(S.dtype))
+            Y = E.aggregate_heads(P, V, meta)
         if not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
         if self.weights_root is not None:
