@@ -948,6 +948,48 @@ int tcgnn_attn_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edge
                            const float* d_dY, const float* d_L, const float* d_delta, int32_t H, int32_t F, float scale,
                            float* d_dk, float* d_dv, void* stream);
 
+/* ---- Fused attention with edge features (PyG's TransformerConv(edge_dim=...): the projected edge vector joins the key in the score and
+ * the value in the message; no counterpart in the reference) ----
+ *
+ * The calls above with one more operand: ee, fp32 [num_edges, H F] in the CSR order of A (ee[e] belongs to the edge at CSR position e),
+ * the already projected edge vector.  Everything said above holds (layouts, aliasing, planless, capturable, no atomics, bit-identical on
+ * repetition, clamped row pointers and column ids); dee is fp32 [num_edges, H F] like ee, pg is fp32 [num_edges, H, 2].
+ *   the score                    s[h, e] = fl32(fl32(t) * scale),  t = (sum_f (double)q[i, hF+f] (double)k[j, hF+f]) + (sum_f (double)q[i, hF+f]
+ *                                (double)ee[e, hF+f]): two sums of exact products, each in tcgnn_attn_forward's order, the second added to
+ *                                the first in fp64.  With ee = 0 the score has tcgnn_attn_forward's bits.
+ *   tcgnn_attn_edge_forward      tcgnn_attn_forward's online softmax, state and merge order, with the message (double)v[j, hF+f] +
+ *                                (double)ee[e, hF+f] (added before the multiplication by the weight) in place of v:
+ *                                Y[i] = sum_e p (v[j] + ee[e]);  L[i, h] as above (d_L may be NULL).  A row without edges: Y = 0, L = 0.
+ *   tcgnn_attn_edge_backward     by row.  delta[i, h] = fl32(sum_f (double)dY[i, hF+f] (double)Y[i, hF+f]), always written;
+ *                                p = exp(fl32(s - L[i, h]));  a = (sum_f dY[i] v[j]) + (sum_f dY[i] ee[e]), two fp64 sums as in the score;
+ *                                g = (double)p (a - (double)delta[i, h]);
+ *                                dq[i, hF+f] = fl32((double)scale * sum over e in row i of g ((double)k[j, hF+f] + (double)ee[e, hF+f]));
+ *                                dee[e, hF+f] = fl32(((double)scale g) (double)q[i, hF+f] + (double)p (double)dY[i, hF+f]), written once,
+ *                                by the row that owns e;  pg[e, h] = (fl32(p), fl32(g)).  d_dq, d_dee and d_pg may each be NULL: that
+ *                                output is not formed.  With all three NULL delta alone is produced, by a light kernel without the
+ *                                walk, and d_q, d_k, d_v, d_ee, d_L may then be NULL too.
+ *   tcgnn_attn_edge_source_grad  over the rows of A^T (d_nodePointer_t, d_edgeList_t, d_perm: what tcgnn_transpose_ws wrote; d_perm IS
+ *                                read here).  For source row j, i = edgeList_t[eT] and (p, g) = pg[perm[eT], h], as the backward call
+ *                                wrote them:  dk[j, hF+f] = fl32((double)scale * sum (double)g (double)q[i, hF+f]);
+ *                                dv[j, hF+f] = fl32(sum (double)p (double)dY[i, hF+f]).  No score is formed again: ee is not read.  A
+ *                                perm entry outside [0, num_edges) reads position 0.  A source nobody reads gets 0 in both.
+ * 16-byte loads and stores are used when F % 4 == 0 and every [num_nodes, H F] and [num_edges, H F] array of the call (d_dee included
+ * where given) is 16-byte aligned, 4-byte ones otherwise: the same bits either way.  pg needs a float's alignment only.  Every element
+ * of every output given is written and nothing outside them.  num_nodes = 0 or H = 0 returns TCGNN_OK and writes nothing; F = 0 returns
+ * TCGNN_OK with L / delta zeroed where given; num_edges = 0 returns TCGNN_OK with Y, L, dq, delta, dk, dv zeroed where given (dee and pg
+ * have no elements); a negative size, num_edges >= 2^31, H F >= 2^31, more than 65535 column passes (heads beyond a lane group times
+ * chunks of F > 256) or a null array otherwise: TCGNN_ERR_INVALID_ARG before anything is written.  A hub row stays on one workgroup. */
+int tcgnn_attn_edge_forward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                            const float* d_q, const float* d_k, const float* d_v, const float* d_ee, int32_t H, int32_t F,
+                            float scale, float* d_Y, float* d_L /* may be NULL */, void* stream);
+int tcgnn_attn_edge_backward(const int32_t* d_nodePointer, const int32_t* d_edgeList, int32_t num_nodes, int64_t num_edges,
+                             const float* d_q, const float* d_k, const float* d_v, const float* d_ee, const float* d_Y,
+                             const float* d_dY, const float* d_L, int32_t H, int32_t F, float scale, float* d_dq /* may be NULL */,
+                             float* d_delta, float* d_dee /* may be NULL */, float* d_pg /* may be NULL */, void* stream);
+int tcgnn_attn_edge_source_grad(const int32_t* d_nodePointer_t, const int32_t* d_edgeList_t, const int32_t* d_perm,
+                                int32_t num_nodes, int64_t num_edges, const float* d_q, const float* d_dY, const float* d_pg,
+                                int32_t H, int32_t F, float scale, float* d_dk, float* d_dv, void* stream);
+
 /* ---- fused AGNN layer products (one gather of the neighbour rows feeds both) ----------------
  *
  * The reference's AGNN layer (gnn_conv.py:115-158) calls forward_ef and forward_AGNN back to back on

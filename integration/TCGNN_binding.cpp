@@ -1014,6 +1014,72 @@ std::tuple<torch::Tensor, torch::Tensor> source_grad_attn(torch::Tensor q, torch
   return {dk, dv};
 }
 
+// ---- not in the reference: fused sparse attention with edge features (tcgnn_attn_edge_forward / _backward / _source_grad; the ctypes
+// module's forward_attn_edge, backward_attn_edge and source_grad_attn_edge) ---------------------------------------------------------
+namespace {
+void attn_edges(const torch::Tensor& ee, const AttnArgs& a, const torch::Tensor& q) {
+  CHECK_INPUT(ee);
+  TORCH_CHECK(ee.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(ee.dim() == 2 && ee.size(0) == a.E && ee.size(1) == q.size(1) && ee.device() == q.device(),
+              "ee must be fp32 [num_edges, heads * F] on q's device");
+}
+}  // namespace
+
+std::tuple<torch::Tensor, c10::optional<torch::Tensor>> forward_attn_edge(torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor ee, int64_t heads,
+                                                                          torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<double> scale,
+                                                                          bool return_lse, c10::optional<torch::Tensor> out) {
+  const AttnArgs a = attn_args(q, {&k, &v}, heads, nodePointer, edgeList, scale);
+  attn_edges(ee, a, q);
+  torch::Tensor Y = out_like(out, q, "q");
+  check_out_apart(out, {&q, &k, &v, &ee});
+  DeviceGuard guard(q.device());
+  c10::optional<torch::Tensor> L;
+  if (return_lse) L = torch::empty({(int64_t)a.N, (int64_t)a.H}, q.options());
+  tcgnn_check(tcgnn_attn_edge_forward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(), k.data_ptr<float>(),
+                                      v.data_ptr<float>(), ee.data_ptr<float>(), a.H, a.F, a.scale, Y.data_ptr<float>(),
+                                      L.has_value() ? L->data_ptr<float>() : nullptr, current_stream(q)),
+              "tcgnn_attn_edge_forward");
+  return {Y, L};
+}
+
+std::tuple<c10::optional<torch::Tensor>, torch::Tensor, c10::optional<torch::Tensor>, c10::optional<torch::Tensor>> backward_attn_edge(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor ee, torch::Tensor Y, torch::Tensor dY, torch::Tensor L, int64_t heads,
+    torch::Tensor nodePointer, torch::Tensor edgeList, c10::optional<double> scale, bool need_dq, bool need_dee, bool need_pg) {
+  const AttnArgs a = attn_args(q, {&k, &v, &Y, &dY}, heads, nodePointer, edgeList, scale);
+  attn_edges(ee, a, q);
+  attn_nodes(L, "L", a, q);
+  DeviceGuard guard(q.device());
+  c10::optional<torch::Tensor> dq, dee, pg;
+  if (need_dq) dq = torch::empty_like(q);
+  if (need_dee) dee = torch::empty_like(ee);
+  if (need_pg) pg = torch::empty({a.E, (int64_t)a.H, (int64_t)2}, q.options());
+  torch::Tensor delta = torch::empty({(int64_t)a.N, (int64_t)a.H}, q.options());
+  tcgnn_check(tcgnn_attn_edge_backward(nodePointer.data_ptr<int>(), edgeList.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(), k.data_ptr<float>(),
+                                       v.data_ptr<float>(), ee.data_ptr<float>(), Y.data_ptr<float>(), dY.data_ptr<float>(), L.data_ptr<float>(), a.H, a.F,
+                                       a.scale, dq.has_value() ? dq->data_ptr<float>() : nullptr, delta.data_ptr<float>(),
+                                       dee.has_value() ? dee->data_ptr<float>() : nullptr, pg.has_value() ? pg->data_ptr<float>() : nullptr,
+                                       current_stream(q)),
+              "tcgnn_attn_edge_backward");
+  return {dq, delta, dee, pg};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> source_grad_attn_edge(torch::Tensor q, torch::Tensor dY, torch::Tensor pg, int64_t heads, torch::Tensor nodePointer,
+                                                               torch::Tensor edgeList, c10::optional<double> scale) {
+  const AttnArgs a = attn_args(q, {&dY}, heads, nodePointer, edgeList, scale);
+  CHECK_INPUT(pg);
+  TORCH_CHECK(pg.scalar_type() == torch::kFloat32, "expected scalar type Float");
+  TORCH_CHECK(pg.dim() == 3 && pg.size(0) == a.E && pg.size(1) == a.H && pg.size(2) == 2 && pg.device() == q.device(),
+              "pg must be fp32 [num_edges, heads, 2] on q's device");
+  DeviceGuard guard(q.device());
+  torch::Tensor dk = torch::empty_like(q), dv = torch::empty_like(q);
+  TransposedCsr& t = transposed_csr(nodePointer, edgeList);
+  tcgnn_check(tcgnn_attn_edge_source_grad(t.rp_t.data_ptr<int>(), t.col_t.data_ptr<int>(), t.perm.data_ptr<int>(), a.N, a.E, q.data_ptr<float>(),
+                                          dY.data_ptr<float>(), pg.data_ptr<float>(), a.H, a.F, a.scale, dk.data_ptr<float>(), dv.data_ptr<float>(),
+                                          current_stream(q)),
+              "tcgnn_attn_edge_source_grad");
+  return {dk, dv};
+}
+
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, bool> transpose_graph(torch::Tensor nodePointer, torch::Tensor edgeList) {
   CHECK_INPUT(nodePointer); CHECK_INPUT(edgeList);
   TORCH_CHECK(nodePointer.scalar_type() == torch::kInt32 && edgeList.scalar_type() == torch::kInt32, "expected scalar type Int");
@@ -1439,6 +1505,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("source_grad_attn", &source_grad_attn, "source side of forward_attn's backward: (dk, dv) (not in the reference)", py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("dY"), py::arg("L"), py::arg("delta"), py::arg("heads"), py::arg("nodePointer"), py::arg("edgeList"),
         py::arg("scale") = py::none());
+  m.def("forward_attn_edge", &forward_attn_edge, "forward_attn with a projected edge vector ee [E, heads * F] in the score (k + ee) and the message "
+        "(v + ee): (Y, L) (not in the reference)", py::arg("q"), py::arg("k"), py::arg("v"), py::arg("ee"), py::arg("heads"), py::arg("nodePointer"),
+        py::arg("edgeList"), py::arg("scale") = py::none(), py::arg("return_lse") = true, py::arg("out") = py::none());
+  m.def("backward_attn_edge", &backward_attn_edge, "row side of forward_attn_edge's backward: (dq, delta, dee, pg) (not in the reference)", py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("ee"), py::arg("Y"), py::arg("dY"), py::arg("L"), py::arg("heads"), py::arg("nodePointer"), py::arg("edgeList"),
+        py::arg("scale") = py::none(), py::arg("need_dq") = true, py::arg("need_dee") = true, py::arg("need_pg") = true);
+  m.def("source_grad_attn_edge", &source_grad_attn_edge, "source side of forward_attn_edge's backward from the row side's pg: (dk, dv) (not in the "
+        "reference)", py::arg("q"), py::arg("dY"), py::arg("pg"), py::arg("heads"), py::arg("nodePointer"), py::arg("edgeList"), py::arg("scale") = py::none());
   m.def("transpose_graph", &transpose_graph, "the cached CSR of A^T: (nodePointer_t, edgeList_t, perm, symmetric) (not in the reference)",
         py::arg("nodePointer"), py::arg("edgeList"));
 }

@@ -38,7 +38,8 @@ __all__ = ["preprocess", "preprocess_gpu", "forward", "forward_ef", "forward_AGN
            "forward_ef2", "edge_softmax", "edge_softmax_backward", "gat_softmax", "gat_softmax_backward", "edge_colsum", "forward_heads", "forward_ef_heads",
            "forward_max", "backward_max", "forward_stats", "backward_stats", "cache_stats", "drop_scales", "gatv2_softmax", "gatv2_softmax_backward", "gatv2_source_grad",
            "forward_ue", "backward_ue", "edge_sum", "forward_uep", "backward_uep", "source_grad_uep", "forward_gated", "source_grad_gated",
-           "forward_gatedgcn", "backward_gatedgcn", "source_grad_gatedgcn", "forward_attn", "backward_attn", "source_grad_attn", "sample_neighbors", "compact_nodes", "compact_graph",
+           "forward_gatedgcn", "backward_gatedgcn", "source_grad_gatedgcn", "forward_attn", "backward_attn", "source_grad_attn",
+           "forward_attn_edge", "backward_attn_edge", "source_grad_attn_edge", "sample_neighbors", "compact_nodes", "compact_graph",
            "sample_rows", "extend_nodes", "compact_rows_graph", "random_walk", "induce_subgraph"]
 
 
@@ -1744,6 +1745,71 @@ def source_grad_attn(q, k, v, dY, L, delta, heads, nodePointer, edgeList, scale=
     rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
     _call(_c.lib.tcgnn_attn_source_grad, q.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(),
           dY.data_ptr(), L.data_ptr(), delta.data_ptr(), H, F, sc, dk.data_ptr(), dv.data_ptr())
+    return dk, dv
+
+
+# ---- additions (not in the reference module): fused sparse attention with edge features (TransformerConv(edge_dim=...)) --
+
+def _attn_edges(ee, name, E, q):
+    _check_input(ee, name)
+    _check_float(ee, name)
+    if tuple(ee.shape) != (E, q.shape[1]) or ee.device != q.device:
+        raise RuntimeError("%s must be fp32 [num_edges, heads * F] = [%d, %d] on q's device, got %s" % (name, E, q.shape[1], tuple(ee.shape)))
+
+
+def forward_attn_edge(q, k, v, ee, heads, nodePointer, edgeList, scale=None, return_lse=True, out=None):
+    """Not in the reference module: forward_attn with a vector per edge (tcgnn_attn_edge_forward) - ee, fp32 [E, heads * F] in CSR order,
+    the already projected edge feature, joins the key in the score and the value in the message:
+        s[h, e] = scale * <q[row(e), head h], k[col(e), head h] + ee[e, head h]>;   p[h] = softmax of s[h] over each row;
+        Y[i, head h] = the sum over the edges e of row i of p[h, e] * (v[col(e), head h] + ee[e, head h])
+    in ONE walk that streams ee beside its two gathered rows; (Y, L) as forward_attn returns them, and with ee = 0 its bits.
+    return_lse=False: L is None.  Deterministic, no atomics."""
+    N, E, H, F, sc = _attn_args(q, ((k, "k"), (v, "v")), heads, nodePointer, edgeList, scale)
+    _attn_edges(ee, "ee", E, q)
+    res = _out_like(out, q, "q")
+    _out_apart(res, out, q, k, v, ee)
+    lse = torch.empty(N, H, dtype=torch.float32, device=q.device) if return_lse else None
+    _call(_c.lib.tcgnn_attn_edge_forward, q.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(), ee.data_ptr(),
+          H, F, sc, res.data_ptr(), _ptr(lse))
+    return res, lse
+
+
+def backward_attn_edge(q, k, v, ee, Y, dY, L, heads, nodePointer, edgeList, scale=None, need_dq=True, need_dee=True, need_pg=True):
+    """Not in the reference module: (dq, delta, dee, pg), the row side of forward_attn_edge's backward (tcgnn_attn_edge_backward), one
+    walk by row with p recomputed from L and g = p (<dY[i], v[col(e)] + ee[e]> - delta[i, h]):
+        delta[i, h] = <dY[i, head h], Y[i, head h]>   fp32 [N, heads];
+        dq[i, head h] = scale * the sum over the edges e of row i of g[h, e] * (k[col(e), head h] + ee[e, head h]);
+        dee[e, head h] = scale * g[h, e] * q[row(e), head h] + p[h, e] * dY[row(e), head h]   fp32 [E, heads * F], written along the row;
+        pg[e, h] = (p, g)   fp32 [E, heads, 2]: what source_grad_attn_edge reads instead of forming the scores again.
+    need_dq / need_dee / need_pg = False: that output is None and is not formed; with all three off only delta is (a light kernel
+    without the walk).  scale must be the forward's."""
+    N, E, H, F, sc = _attn_args(q, ((k, "k"), (v, "v"), (Y, "Y"), (dY, "dY")), heads, nodePointer, edgeList, scale)
+    _attn_edges(ee, "ee", E, q)
+    _attn_nodes(L, "L", N, H, q)
+    dq = torch.empty_like(q) if need_dq else None
+    delta = torch.empty(N, H, dtype=torch.float32, device=q.device)
+    dee = torch.empty_like(ee) if need_dee else None
+    pg = torch.empty(E, H, 2, dtype=torch.float32, device=q.device) if need_pg else None
+    _call(_c.lib.tcgnn_attn_edge_backward, q.device, nodePointer.data_ptr(), edgeList.data_ptr(), N, E, q.data_ptr(), k.data_ptr(), v.data_ptr(),
+          ee.data_ptr(), Y.data_ptr(), dY.data_ptr(), L.data_ptr(), H, F, sc, _ptr(dq), delta.data_ptr(), _ptr(dee), _ptr(pg))
+    return dq, delta, dee, pg
+
+
+def source_grad_attn_edge(q, dY, pg, heads, nodePointer, edgeList, scale=None):
+    """Not in the reference module: (dk, dv), the source side of forward_attn_edge's backward (tcgnn_attn_edge_source_grad), fp32
+    [N, heads * F] each: over the edges (i <- j) that read node j, with (p, g) = pg[e] as backward_attn_edge wrote them,
+        dv[j, head h] = the sum of p[h, e] * dY[i, head h];   dk[j, head h] = scale * the sum of g[h, e] * q[i, head h]
+    - a plain weighted gather-sum over the rows of A^T: no score is formed again and ee is not read.  A node nobody reads gets 0.  The
+    transposed CSR is the module's cached one (transpose_graph)."""
+    N, E, H, F, sc = _attn_args(q, ((dY, "dY"),), heads, nodePointer, edgeList, scale)
+    _check_input(pg, "pg")
+    _check_float(pg, "pg")
+    if tuple(pg.shape) != (E, H, 2) or pg.device != q.device:
+        raise RuntimeError("pg must be fp32 [num_edges, heads, 2] = [%d, %d, 2] on q's device, got %s" % (E, H, tuple(pg.shape)))
+    dk, dv = torch.empty_like(q), torch.empty_like(q)
+    rp_t, col_t, perm, _ = transpose_graph(nodePointer, edgeList)
+    _call(_c.lib.tcgnn_attn_edge_source_grad, q.device, rp_t.data_ptr(), col_t.data_ptr(), perm.data_ptr(), N, E, q.data_ptr(), dY.data_ptr(), pg.data_ptr(),
+          H, F, sc, dk.data_ptr(), dv.data_ptr())
     return dk, dv
 
 

@@ -67,6 +67,9 @@
 //   tcgnn_attn.inc            fused sparse attention: multi-head dot-product scores, their softmax done online and the weighted sum of the values in
 //                             one walk, the row-side (dq, delta) and source-side (dk, dv) backward one walk each - nothing of size E exists
 //                             (segment_max's scheduling, gatv2's head-wise lane layout)
+//   tcgnn_attn_edge.inc       that attention with a projected edge vector ee[e] in the score (q . (k + ee)) and in the message (v + ee): the forward
+//                             and the row side (dq, delta, dee, pg) stream [E, H F] beside their gathers; the source side (dk, dv) reads the row
+//                             side's (p, g) per edge and head instead of forming scores again - a plain weighted gather-sum over A^T
 //   tcgnn_lds_plan.inc        host side of the LDS-resident walks: time models, placement, build_lds_cells (a cell stream in named steps over a
 //                             CellBuild; flat_entries, the entry records, is a pure host function; cells_publish cannot fail), build_val_stream
 //   tcgnn_edge_dispatch.inc   host side of an SDDMM / fused-AGNN call: SddmmCall, route_sddmm, AgnnCall, route_agnn, launchers, run_sddmm, run_agnn
@@ -340,6 +343,7 @@ __device__ __forceinline__ half4 lds_read_tr16(const char* p) {
 #include "tcgnn_gated.inc"
 #include "tcgnn_gatedgcn.inc"
 #include "tcgnn_attn.inc"
+#include "tcgnn_attn_edge.inc"
 
 // ---- run-time switches.  Product: TCGNN_SPMM_MODE / TCGNN_RANGE_GUARD (initial values of tcgnn_set_spmm_mode / tcgnn_set_range_guard,
 // include/tcgnn.h) and TCGNN_VERBOSE (plan statistics on stderr).  TEST AIDS, read through test_knob() only - tests/ forces every walk

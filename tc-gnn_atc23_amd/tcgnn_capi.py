@@ -131,6 +131,9 @@ SIGNATURES = {
     "tcgnn_attn_forward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp]),
     "tcgnn_attn_backward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp]),
     "tcgnn_attn_source_grad": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp]),
+    "tcgnn_attn_edge_forward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp]),
+    "tcgnn_attn_edge_backward": (ctypes.c_int, [_i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "tcgnn_attn_edge_source_grad": (ctypes.c_int, [_i32p, _i32p, _i32p, _i32, _i64, _vp, _vp, _vp, _i32, _i32, ctypes.c_float, _vp, _vp, _vp]),
     "tcgnn_agnn_supported": (ctypes.c_int, [_vp, _i32]),
     "tcgnn_agnn_pair_forward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp]),
     "tcgnn_agnn_pair_backward": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _vp, _sz, _vp]),

@@ -20,6 +20,7 @@ unnormalised scores and does not propagate through them).  Every gradient is exa
     aggregate_gated(k, q, v, rowptr, col)  Y[i, d] = sum over row i of sigmoid(k[i, d] + q[col e, d]) v[col e, d] (ResGatedGraphConv)   bwd: dk = dY * S (S: the forward's second output), (dq, dv) from one walk over A^T
     aggregate_gatedgcn(k, q, v, c, rowptr, col, eps)  Z[e] = k[row e] + q[col e] + c[e] and Y[i] = sum of sigmoid(Z[e]) v[col e] / (sum of sigmoid(Z[e]) + eps), c and Z [E, D] (GatedGCN)   bwd: (dc, dk) from one walk by row, (dq, dv) from one over A^T
     aggregate_attention(q, k, v, H, rowptr, col, scale)  Y[i, head h] = sum over row i of softmax_row(scale <q[i, head h], k[col e, head h]>) v[col e, head h] (TransformerConv, fused)   bwd: (dq, delta) from one walk by row, (dk, dv) from one over A^T; no [H, E] tensor either way
+    aggregate_attention(..., edge=ee)   the same with ee[e] ([E, H F], CSR order) added to k[col e] in the score and to v[col e] in the message (TransformerConv's edge_dim)   bwd: (dq, delta, d_ee, pg) from one walk by row, (dk, dv) from pg by a gather-sum over A^T
 
 `meta` is the five metadata tensors every operator of the API takes (row_pointers, column_index, blockPartition, edgeToColumn,
 edgeToRow).  aggregate ALWAYS back-propagates through the transposed matrix, also on a structurally symmetric graph: softmax
@@ -462,15 +463,50 @@ class _AggregateAttention(torch.autograd.Function):
         return d_q, (d_k if need_k else None), (d_v if need_v else None), None, None, None, None
 
 
-def aggregate_attention(q, k, v, heads, row_pointers, column_index, scale=None):
+class _AggregateAttentionEdge(torch.autograd.Function):
+    """(Y, L) = forward_attn_edge(q, k, v, edge); backward: (dq, delta, dee, pg) = backward_attn_edge - one walk by row that also writes
+    the edge gradient along the row and parks (p, g) per edge and head -, then (dk, dv) = source_grad_attn_edge from pg - a plain
+    gather-sum over A^T.  Saved: q, k, v, edge, Y and L.  The source side is skipped when neither dk nor dv is wanted, and pg is not
+    requested then; dq and dee are formed only where wanted."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, edge, heads, row_pointers, column_index, scale):
+        q, k, v, edge = q.contiguous(), k.contiguous(), v.contiguous(), edge.contiguous()
+        ctx.graph, ctx.heads, ctx.scale = (row_pointers, column_index), heads, scale
+        Y, L = _L.backend().forward_attn_edge(q, k, v, edge, heads, row_pointers, column_index, scale)
+        ctx.save_for_backward(q, k, v, edge, Y, L)
+        return Y
+
+    @staticmethod
+    def backward(ctx, d_y):
+        q, k, v, edge, Y, L = ctx.saved_tensors
+        d_y = d_y.contiguous()
+        need_q, need_k, need_v, need_e = ctx.needs_input_grad[:4]
+        d_q = d_k = d_v = d_e = None
+        if need_q or need_k or need_v or need_e:
+            src = need_k or need_v
+            d_q, _, d_e, pg = _L.backend().backward_attn_edge(q, k, v, edge, Y, d_y, L, ctx.heads, *ctx.graph, ctx.scale, need_dq=need_q, need_dee=need_e,
+                                                              need_pg=src)
+            if src:
+                d_k, d_v = _L.backend().source_grad_attn_edge(q, d_y, pg, ctx.heads, *ctx.graph, ctx.scale)
+        return d_q, (d_k if need_k else None), (d_v if need_v else None), d_e, None, None, None, None
+
+
+def aggregate_attention(q, k, v, heads, row_pointers, column_index, scale=None, edge=None):
     """Y[i, head h] = the sum over the edges e of CSR row i of p[h, e] v[col e, head h], p[h] = softmax by row of
     scale <q[row e, head h], k[col e, head h]>: multi-head dot-product attention (TransformerConv) as ONE fused walk forward - the
     softmax online - and two back.  q, k, v: [N, heads * F]; scale=None: F ** -0.5.  No [heads, E] tensor in either direction;
-    everything read as fp32, fp64 sums in a fixed order, no atomics; exact on any graph."""
+    everything read as fp32, fp64 sums in a fixed order, no atomics; exact on any graph.
+    edge: [E, heads * F] in CSR order, a vector per edge that joins the key in the score and the value in the message (TransformerConv's
+    edge_dim, already projected): scale <q[row e], k[col e] + edge[e]> and p (v[col e] + edge[e]).  It gets a gradient like q, k, v."""
     if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape or int(heads) < 1 or q.shape[1] % int(heads):
         raise RuntimeError("q, k and v must be [N, heads * F] tensors of one shape, got %s, %s and %s with heads = %r"
                            % (tuple(q.shape), tuple(k.shape), tuple(v.shape), heads))
-    return _AggregateAttention.apply(q, k, v, int(heads), row_pointers, column_index, None if scale is None else float(scale))
+    if edge is None:
+        return _AggregateAttention.apply(q, k, v, int(heads), row_pointers, column_index, None if scale is None else float(scale))
+    if edge.dim() != 2 or tuple(edge.shape) != (column_index.numel(), q.shape[1]):
+        raise RuntimeError("edge must be [E, heads * F] = [%d, %d], got %s" % (column_index.numel(), q.shape[1], tuple(edge.shape)))
+    return _AggregateAttentionEdge.apply(q, k, v, edge, int(heads), row_pointers, column_index, None if scale is None else float(scale))
 
 
 class _EdgeSum(torch.autograd.Function):

@@ -62,8 +62,11 @@ def build_parser():
     p.add_argument("--fused-attention", dest="fused_attention", action="store_true",
                    help="transformer only: every layer runs its attention as one fused walk with the softmax done online "
                    "(TransformerConv(fused=True): no [heads, E] tensor, everything read as fp32; not in the reference)")
+    p.add_argument("--attention-edges", dest="attention_edges", action="store_true",
+                   help="transformer with --fused-attention only, on the full graph: every layer is TransformerConv(edge_dim=--edge-dim) and reads a drawn "
+                   "edge_attr [E, --edge-dim] - the projected edge vector joins the key in the score and the value in the message (not in the reference)")
     p.add_argument("--edge-dim", dest="edge_dim", type=int, default=16,
-                   help="GINE and GatedGCN only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
+                   help="GINE, GatedGCN and --attention-edges only: width of the edge features; the datasets here carry none, so they are drawn once on the device from --seed (not in the reference)")
     p.add_argument("--fanout", type=str, default=None,
                    help="K[,K...]: train every epoch on a freshly sampled graph that keeps at most K in-edges per node (TCGNN.sample_neighbors, seed + epoch); "
                    "several values give one fan-out per layer, input layer first; the final loss is evaluated on the full graph (not in the reference)")
@@ -247,7 +250,7 @@ def make_adam(params, lr=0.01):
 
 def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, epochs, seed=0, warmup=9, hip_graph=False, tune=True,
                   norm="none", bias=False, directed=False, attention="reference", heads=1, aggregator="mean", edge_dim=16, fuse_edge=False, fanout=None,
-                  batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0, fused_attention=False):
+                  batch_size=None, batch_hook=None, sampler="dense", walk_length=2, saint_norm=0, fused_attention=False, attention_edges=False):
     """The timed part of main_tcgnn.py (:141-181) on tensors that already live on the GPU:
     Adam(lr=0.01), nll_loss over all nodes, `warmup` dry epochs then `epochs` timed ones.
     hip_graph: capture one whole epoch (forward, loss, backward, Adam step - the reference already asks for a capturable
@@ -268,6 +271,7 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
     fuse_edge (GINE only): GINEConv(fuse_edge=True) - the edge projection formed inside the walk; the scratch of its backward is prepared with the transposed CSR.
     fused_attention (transformer only): TransformerConv(fused=True) - the attention as one fused walk forward and two back; planless: only the transposed
     CSR is prepared (prepare(..., fused_attention=True)).
+    attention_edges (transformer with fused_attention only, full graph only): TransformerConv(edge_dim=edge_dim) layers on an edge_attr drawn as for 'gine'.
     fanout (not in the reference; None: the path above, unchanged): a list of one fan-out per layer.  Every epoch, dry ones included, draws
     tcgnn_layers.sample_meta(meta, k, seed + epoch) per distinct k, builds what the model's operators need on it (the plan at every width and,
     for the layers with a `directed` switch, A^T's - a sampled graph is not symmetric, so those layers are built with directed=True - or, for
@@ -323,6 +327,20 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         def conv_cls(a, b):
             return L.GATv2Conv(a, b // heads, heads=heads)
         out_cls = L.GATv2Conv
+    elif model_name == "transformer" and attention_edges:
+        if not fused_attention or fanout is not None or batch_size is not None:
+            raise ValueError("--attention-edges needs --fused-attention (the composition has no edge path) and the full graph (no --fanout / --batch-size)")
+        edge_attr = torch.randn(meta[1].numel(), int(edge_dim), device=x.device, generator=torch.Generator(device=x.device).manual_seed(seed))
+
+        class EdgeTransformerConv(L.TransformerConv):
+            def forward(self, X, *graph):
+                return super().forward(X, *graph, edge_attr=edge_attr)
+
+        def conv_cls(a, b):
+            return EdgeTransformerConv(a, b // heads, heads=heads, fused=True, edge_dim=int(edge_dim))
+
+        def out_cls(a, b):
+            return EdgeTransformerConv(a, b, fused=True, edge_dim=int(edge_dim))
     elif model_name == "transformer":
         def conv_cls(a, b):
             return L.TransformerConv(a, b // heads, heads=heads, fused=bool(fused_attention))
@@ -350,6 +368,8 @@ def time_training(model_name, meta, x, y, in_dim, hidden, classes, num_layers, e
         conv_cls = {"gcn": L.GCNConv, "gin": L.GINConv, "agnn": L.AGNNConv, "pna": L.PNAConv, "resgated": L.ResGatedGraphConv}[model_name]
     if fused_attention and model_name != "transformer":
         raise ValueError("fused_attention applies to the transformer model only")
+    if attention_edges and model_name != "transformer":
+        raise ValueError("--attention-edges applies to the transformer model with --fused-attention only")
     if fuse_edge and model_name != "gine":
         raise ValueError("fuse_edge applies to the GINE model only")
     sampled_attr = {}
@@ -669,7 +689,7 @@ def run(args, quiet=False):
         result["sag_ms"] = L.SAG(*meta).profile(x)
         return result
 
-    if args.model in ("gine", "gatedgcn"):
+    if args.model in ("gine", "gatedgcn") or getattr(args, "attention_edges", False):
         say("edge_attr:\t[%d, %d] standard normal, drawn once on the device from seed %d (the dataset carries no edge features)"
             % (meta[1].numel(), getattr(args, "edge_dim", 16), args.seed))
     r = time_training(args.model, meta, x, y, ds.num_features, args.hidden, ds.num_classes, args.num_layers, args.epochs,
@@ -679,7 +699,7 @@ def run(args, quiet=False):
                       aggregator=getattr(args, "aggregator", "mean"), edge_dim=getattr(args, "edge_dim", 16), fuse_edge=getattr(args, "fuse_edge", False), fanout=getattr(args, "fanout", None),
                       batch_size=getattr(args, "batch_size", None), batch_hook=getattr(args, "batch_hook", None),
                       sampler=getattr(args, "sampler", "dense"), walk_length=getattr(args, "walk_length", 2), saint_norm=getattr(args, "saint_norm", 0),
-                      fused_attention=getattr(args, "fused_attention", False))
+                      fused_attention=getattr(args, "fused_attention", False), attention_edges=getattr(args, "attention_edges", False))
     if "sample_ms" in r:
         say("Sample (ms):\t{:6.3f}\nPlan (ms):\t{:6.3f}".format(r["sample_ms"], r["plan_ms"]))
     if "compact_ms" in r:

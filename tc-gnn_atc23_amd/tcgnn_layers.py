@@ -700,8 +700,8 @@ class GATv2Conv(torch.nn.Module):
 
 
 class TransformerConv(torch.nn.Module):
-    """Not in the reference: multi-head dot-product attention after PyG's TransformerConv (DGL's DotGatConv), without edge features
-    and without the beta gate:
+    """Not in the reference: multi-head dot-product attention after PyG's TransformerConv (DGL's DotGatConv); edge features (edge_dim)
+    and the beta gate are options of the fused path and of the root term, below:
         Q = X W_q + b_q,  K = X W_k + b_k,  V = X W_v + b_v   [N, heads * output_dim] each;
         S[h, e] = <Q[row e, head h], K[col e, head h]>;   P[h] = softmax by row of S[h] / sqrt(output_dim);   Y_h = A_val(P[h]) V_h
     (tcgnn_edge_ops.sddmm_heads - one multi-head SDDMM call -, edge_softmax_heads and aggregate_heads; gradients exact on any graph).
@@ -710,15 +710,35 @@ class TransformerConv(torch.nn.Module):
     and the output bias.  Glorot-uniform weights, zero biases.  No attention dropout.
     fused=True replaces the three operators by tcgnn_edge_ops.aggregate_attention: one fused walk forward with the softmax done online
     and two back, everything read as fp32 and no [heads, E] tensor kept (the blockPartition / edgeToColumn / edgeToRow arguments are
-    then unused).  The default is the composition."""
+    then unused).  The default is the composition.
+    edge_dim (fused=True only - the composition has no edge path): forward takes edge_attr [E, edge_dim] in CSR position order;
+    Ee = edge_attr W_e (weights_edge [edge_dim, heads * output_dim], no bias, as in PyG) joins the key in the score and the value in the
+    message, S = <Q[row e], K[col e] + Ee[e]>, Y_h = sum P (V[col e] + Ee[e]) (aggregate_attention(..., edge=Ee)).
+    beta=True (needs root_weight): Y = b X_r + (1 - b) Y with X_r = X W_root and b = sigmoid([Y, X_r, Y - X_r] weights_beta), weights_beta
+    [3 out, 1], in plain torch operators, before the output bias."""
 
-    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, bias=True, fused=False):
+    def __init__(self, input_dim, output_dim, heads=1, concat=True, root_weight=True, bias=True, fused=False, edge_dim=None, beta=False):
         super().__init__()
         if heads < 1:
             raise ValueError("heads must be >= 1, got %r" % (heads,))
+        if edge_dim is not None and not fused:
+            raise ValueError("edge_dim needs fused=True: the composition of sddmm_heads, edge_softmax_heads and aggregate_heads has no edge path")
+        if edge_dim is not None and int(edge_dim) < 1:
+            raise ValueError("edge_dim must be >= 1, got %r" % (edge_dim,))
+        if beta and not root_weight:
+            raise ValueError("beta=True gates between the attention and the root term: it needs root_weight=True")
         self.heads, self.output_dim, self.concat, self.fused = int(heads), int(output_dim), bool(concat), bool(fused)
+        self.edge_dim = None if edge_dim is None else int(edge_dim)
         wide = self.heads * self.output_dim
         out = wide if self.concat else self.output_dim
+        if self.edge_dim is not None:
+            self.weights_edge = torch.nn.Parameter(torch.empty(self.edge_dim, wide))
+        else:
+            self.register_parameter("weights_edge", None)
+        if beta:
+            self.weights_beta = torch.nn.Parameter(torch.empty(3 * out, 1))
+        else:
+            self.register_parameter("weights_beta", None)
         for name in ("q", "k", "v"):
             setattr(self, "weights_" + name, torch.nn.Parameter(torch.empty(input_dim, wide)))
             if bias:
@@ -738,7 +758,7 @@ class TransformerConv(torch.nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        for p in (self.weights_q, self.weights_k, self.weights_v, self.weights_root):
+        for p in (self.weights_q, self.weights_k, self.weights_v, self.weights_root, self.weights_edge, self.weights_beta):
             if p is not None:
                 torch.nn.init.xavier_uniform_(p)
         for b in (self.bias_q, self.bias_k, self.bias_v, self.bias):
@@ -749,21 +769,32 @@ class TransformerConv(torch.nn.Module):
         Y = dense_update(X, W)
         return Y + b if b is not None else Y
 
-    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow):
+    def forward(self, X, row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow, edge_attr=None):
         import tcgnn_edge_ops as E   # (it imports this module)
         meta = (row_pointers, column_index, blockPartition, edgeToColumn, edgeToRow)
+        if self.edge_dim is None:
+            if edge_attr is not None:
+                raise ValueError("this TransformerConv was built without edge_dim and takes no edge_attr")
+        elif edge_attr is None or edge_attr.dim() != 2 or tuple(edge_attr.shape) != (column_index.numel(), self.edge_dim):
+            raise ValueError("TransformerConv(edge_dim=%d) needs edge_attr [num_edges, edge_dim] = [%d, %d] in CSR position order, got %s"
+                             % (self.edge_dim, column_index.numel(), self.edge_dim, None if edge_attr is None else tuple(edge_attr.shape)))
         Q = self._project(X, self.weights_q, self.bias_q)
         K = self._project(X, self.weights_k, self.bias_k)
         V = self._project(X, self.weights_v, self.bias_v)
         if self.fused:
-            Y = E.aggregate_attention(Q, K, V, self.heads, row_pointers, column_index, self.output_dim ** -0.5)
+            Ee = dense_update(edge_attr, self.weights_edge) if self.edge_dim is not None else None
+            Y = E.aggregate_attention(Q, K, V, self.heads, row_pointers, column_index, self.output_dim ** -0.5, edge=Ee)
         else:
             S = E.sddmm_heads(Q, K, meta, self.heads)
             P = E.edge_softmax_heads(S, row_pointers, self.scale.to(S.dtype))
             Y = E.aggregate_heads(P, V, meta)
         if not self.concat:
             Y = Y.view(Y.shape[0], self.heads, self.output_dim).mean(1)
-        if self.weights_root is not None:
+        if self.weights_beta is not None:
+            Xr = dense_update(X, self.weights_root)
+            b = torch.sigmoid(torch.cat([Y, Xr, Y - Xr], dim=1) @ self.weights_beta)
+            Y = b * Xr + (1 - b) * Y
+        elif self.weights_root is not None:
             Y = Y + dense_update(X, self.weights_root)
         return Y + self.bias if self.bias is not None else Y
 
